@@ -4,7 +4,7 @@
 One "step" = one pass of the hot path (s2k_ecdsa_verify_batch_device + the valid-bitmap
 pack) over one batch of synthetic signatures per GPU, inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-log2 B] [--keys-log2 16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-log2 B] [--keys-log2 16] [--dump-outputs DIR] [--full]
 
 N = 1: BASELINE config 2, 2^20 verifications on one MI355X.
 N > 1: BASELINE config 5 shape, 2^21 verifications per GPU (2^24 over 8), one process per GPU
@@ -16,14 +16,22 @@ children, before anything in the parent touches a GPU; started by torch.distribu
 is one of the ranks.  `--oversubscribe` (test hook for a 1-GPU box) puts rank r on device
 r mod device_count and uses gloo for the collectives.
 
-Rank 0 prints ONE JSON line.  Extra keys: "roofline" (the dominant kernel against the
-integer-VALU issue roofline that bounds this path, live HIP-event kernel time and effective
-shader clock; the HBM roofline the contract names as a sub-object), "cpu_baseline" (the CPU
-oracle = port of the reference algorithm, timed on this box's host cores on a bounded sample;
-the reference itself is Go and there is no Go toolchain here), and at N = 1 the other
-BASELINE configurations, each guarded by a full-result check: "msm_2p20" (config 3),
-"schnorr_rlc_2p20" (config 4), plus "distinct_keys" (K = N), "worst_case_all_fallback" and
-"pcie_inclusive".  None of them is `value`.
+Rank 0 prints ONE JSON line.  A plain run sets up, checks the batch, warms up, times the K
+steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).  `--dump-outputs DIR`
+writes what the last timed step computed (the per-signature verdicts of rank 0's shard, the
+gathered valid bitmap and the valid count) as DIR/<name>.npy in float32 / float64; the inputs
+are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else the line can carry.  Extra keys: "roofline" (the dominant kernel
+against the integer-VALU issue roofline that bounds this path, live HIP-event kernel time and
+effective shader clock; the HBM roofline the contract names as a sub-object), "multi_rank" at
+N > 1 (per-rank times and a local / collective split from an untimed pass), "cpu_baseline" (the
+CPU oracle = port of the reference algorithm, timed on the host cores on a bounded sample;
+the reference itself is Go and is not timed), and at N = 1 the other BASELINE configurations,
+each guarded by a full-result check: "msm_2p20" (config 3), "schnorr_rlc_2p20" (config 4), plus
+"distinct_keys" (K = N), "worst_case_all_fallback", "pcie_inclusive", "batch_sweep" and
+"small_call".  None of them is `value`.  `--no-cpu-baseline`, `--no-pcie` and `--no-extras`
+leave parts of that out again.
 """
 import argparse
 import json
@@ -63,20 +71,30 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch-log2", type=int, default=None, help="signatures per GPU (default 20 at N=1, 21 at N>1)")
     ap.add_argument("--keys-log2", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe inclusive) measurement")
-    ap.add_argument("--no-extras", action="store_true", help="skip configs 3/4, K=N and the worst case (e.g. under a profiler)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else the line can carry: roofline, multi-rank split, "
+                         "CPU baseline, the other BASELINE configurations, host-buffer paths, batch sweep, small calls")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the host-buffer (PCIe inclusive) measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip configs 3/4, K=N and the worst case (e.g. under a profiler)")
     ap.add_argument("--key-grouping", choices=("auto", "off", "keyset", "keyset-chunks", "keyset5", "keyset6"), default="auto",
                     help="off: every signature through the general ladder; keyset: the batch against a key set built before the "
                          "timed region (both for profiling those kernels under the driver's settings; not the headline)")
-    ap.add_argument("--full", action="store_true", help="print the line with its explanations (as rounds 1-4 did) instead of the compact form")
+    ap.add_argument("--explain", action="store_true", help="print the line with its explanations (as rounds 1-4 did) instead of the compact form")
     ap.add_argument("--write-notes", action="store_true", help="refresh bench_notes.json (the explanations, by path) from this run")
     ap.add_argument("--rank-timeout", type=float, default=600.0,
                     help="launcher (--gpus N without torchrun): seconds every rank has to report ready (process group, context, wide tables) "
                          "before the launch is abandoned and the missing ranks are named")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="test hook: allow more ranks than devices (rank r -> device r mod count, gloo collectives)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -296,12 +314,31 @@ def median(xs):
     return xs[len(xs) // 2] if xs else 0.0
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, flattened - float32 for bytes (verdicts, bitmap), float64 for wider
+    integers (the count), so that every value is exact.  An array larger than its share of the 64 MB budget is written as a
+    fixed sample: the elements at sorted indices drawn with seed 0, the same for every run of the same size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096) // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        dt = np.float32 if a.dtype.itemsize <= 2 else np.float64
+        cap = share // np.dtype(dt).itemsize
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(dt))
+
+
 
 # ---------------------------------------------------------------------------------------------
 # The printed line.  The driver keeps an 8 KB tail of stdout: everything this file measures has to fit in it (VERDICT r04
 # next #7).  The explanations that used to ride along in the line ("note", "*_def", "check", "method", "sample" ...: 5.6 KB of
 # the 18.5 KB of round 4) live in bench_notes.json next to this file, keyed by the same paths (--write-notes refreshes it
-# from a run; --full prints the line as it was); numbers are rounded to six significant digits; per-repetition lists are
+# from a run; --explain prints the line as it was); numbers are rounded to six significant digits; per-repetition lists are
 # dropped; and if the line is still too long, keys are dropped from the least to the most important and named in `dropped`.
 # ---------------------------------------------------------------------------------------------
 PROSE_KEYS = ("note", "check", "method", "sample", "threads_note", "peak_def", "frac_def", "reference_toolchain", "mode_def",
@@ -352,7 +389,7 @@ def _strip(obj, path, notes):
 
 
 def compact_line(line, args):
-    if getattr(args, "full", False):
+    if getattr(args, "explain", False):
         return json.dumps(line)
     notes = {}
     slim = _strip(line, "", notes)
@@ -671,7 +708,9 @@ def worker(args):
 
     # ---- W untimed warm-up steps, then exactly K timed steps ----------------------------------
     # (only the mandated barrier + synchronize in between: host-side work in that gap lets the
-    # device clock down and the first timed steps pay for the ramp)
+    # device clock down and the first timed steps pay for the ramp).  The timed steps run with the
+    # context's HIP-event timing on, with or without --full, so that the headline is measured the
+    # same way in both; only --full reads the events into the roofline.
     cnts = torch.zeros(args.steps, dtype=torch.int64, device=dev)
     for _ in range(args.warmup):
         step()
@@ -689,10 +728,12 @@ def worker(args):
     assert prof["calls"] == min(args.steps, 1024)
     assert bool((cnts == n * world).all().item()), "a timed step lost verdicts"
     assert bitmap.numel() == n * world // 8 and bool((bitmap == 0xFF).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"valid": d_valid, "bitmap": bitmap, "count": cnt})
 
     t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     multi = None
-    if dist is not None:
+    if dist is not None and args.full:
         # what a first run on N devices needs to tell a straggler from a slow collective: every rank's own time for the K
         # timed steps, and (a short untimed pass behind them) its step split at the collective by events on the stream:
         # local = verification + bitmap packing, collective = the all-gather of the bitmap shards
@@ -731,85 +772,13 @@ def worker(args):
                          "per_rank_local_ms / collective_ms: HIP events on the rank's stream around verification + packing and around "
                          "the all-gather, %d untimed steps behind the timed region; value_without_collective: all ranks' signatures "
                          "over the slowest rank's local time - what N independent single-GPU runs would give in this launch" % k2}
+    if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
 
     rc = 0
     if rank == 0:
-        fast_ms = prof["fast_ms"] / prof["calls"]         # dominant kernel, HIP events on its stream
-        fast_med = median(prof["fast_each"])
-        calls = prof["calls"]
-        keyed = grouping["keyed"] * 2 >= n                # which ladder is the dominant kernel of this run
-        if main_keyset is not None:
-            keyed = True
-        clock_hz = prof["shader_mhz"] * 1e6
         value = n * world * args.steps / dt
-        counts, counts_src = committed_counts()
-        kname = KEYSET_OPTIONS[args.key_grouping][1] if main_keyset is not None else ("k_verify_fast_keyed" if keyed else "k_verify_fast")
-        traffic, traffic_src = committed_traffic(kname)
-        stages = {"grouping_by_key_ms": prof["group_ms"] / calls, "key_tables_ms": None, "ladder_ms": fast_ms,
-                  "general_ladder_ms": prof["left_ms"] / calls, "complete_worklist_ms": prof["fallback_ms"] / calls}
-        if keyed:
-            # stage [0] is the grouping, stage [1] the per-key tables; the scalar preparation and the generator
-            # part u1*G run beside both on a second stream (secp256k1_voi_amd.h: s2k_ctx_profile_read_stages)
-            stages["grouping_by_key_ms"], stages["key_tables_ms"] = prof["prep_ms"] / calls, prof["group_ms"] / calls
-        else:
-            stages["scalar_prep_ms"] = prof["prep_ms"] / calls
-            stages.pop("grouping_by_key_ms")
-            stages.pop("key_tables_ms")
-        roof = {"bound": "valu", "kernel": KEYSET_OPTIONS[args.key_grouping][2] if main_keyset is not None else ("k_verify_fast<ECDSA_KEYED>" if keyed else "k_verify_fast<ECDSA>"),
-                "kernel_ms": fast_ms, "kernel_ms_median": fast_med, "stages_ms": stages,
-                "shader_clock_mhz": prof["shader_mhz"], "shader_clock_mhz_first_wave": prof["shader_mhz_first_wave"],
-                "shader_clock_mhz_last_round": prof["shader_mhz_last_round"], "unit": "Tlane-op/s", "peak": VALU_PEAK_LANE_OPS / 1e12,
-                "peak_def": "256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz: one wave64 VALU instruction per 4 cycles per SIMD"}
-        counts_all = counts
-        if counts and kname not in counts:
-            # a ladder the committed profile has no PMC entry for (yet): priced with the static recount of the loaded library
-            try:
-                sys.path.insert(0, os.path.join(ROOT, "tools"))
-                import isa_count
-                sc_ = isa_count.static_counts(S.LIB_PATH)[kname]
-                counts = {kname: {"valu_instr_per_signature": sc_["valu_instr_static"]},
-                          (KEYSET_OPTIONS[args.key_grouping][3] if main_keyset is not None else "static"): sc_}
-                counts_src = "(none: static recount of the loaded library, tools/isa_count.py)"
-            except Exception:
-                counts = None
-        if counts:
-            ipv = counts[kname]["valu_instr_per_signature"]
-            st_ = counts.get(KEYSET_OPTIONS[args.key_grouping][3] if main_keyset is not None else ("static_keyed" if keyed else "static"), {})
-            lane_ops = ipv * n / (fast_ms * 1e-3)
-            roof.update({"achieved": lane_ops / 1e12, "frac": lane_ops / VALU_PEAK_LANE_OPS,
-                         "valu_instr_per_verify": ipv, "counts_from": "profiles/" + counts_src,
-                         "frac_def": "VALU instructions per verification (PMC) x verifications/s of the kernel / peak; every VALU "
-                                     "instruction of this kernel is priced at the 4-cycle issue interval measured for its mix "
-                                     "(profiles/r02_valu_instruction_rates.txt)"})
-            if clock_hz > 0:
-                # the same fraction against the clock the kernel actually ran at: SIMD issue cycles used / available
-                wave_instr = ipv * n / 64.0
-                cyc_avail = SIMDS * fast_ms * 1e-3 * clock_hz
-                roof["frac_at_measured_clock"] = wave_instr * 4.0 / cyc_avail
-                if "mad_u64_u32_per_verify" in st_:
-                    roof["mad_issue_frac_at_measured_clock"] = st_["mad_u64_u32_per_verify"] * n / 64.0 * 4.0 / cyc_avail
-                if "valu_instr_whole_step_per_verify" in st_:
-                    # every kernel of the step (grouping, tables, preparation, generator part, ladder) against the
-                    # issue slots of the whole step
-                    roof["whole_step_issue_frac_at_measured_clock"] = (st_["valu_instr_whole_step_per_verify"] * n / 64.0 * 4.0 /
-                                                                       (SIMDS * dt / args.steps * clock_hz))
-                    roof["valu_instr_whole_step_per_verify"] = st_["valu_instr_whole_step_per_verify"]
-            if "fp_products_per_verify" in st_:
-                roof["fp_products_per_verify"] = st_["fp_products_per_verify"]
-            if "mad_u64_u32_per_verify" in st_:
-                roof.update({"mad_u64_u32_per_verify": st_["mad_u64_u32_per_verify"],
-                             "mad_u64_u32_per_s": st_["mad_u64_u32_per_verify"] * n / (fast_ms * 1e-3)})
-            # the guide's nominal VALU rate (one wave64 instruction per 2 cycles per SIMD) is reached by pure
-            # VOP2 / f32 streams only; against it the kernel sits at half the figure above
-            roof["frac_of_2cycle_nominal_peak"] = lane_ops / (2 * VALU_PEAK_LANE_OPS)
-        achieved_gbs = BYTES_PER_VERIFY * n / (fast_ms * 1e-3) / 1e9
-        roof["traffic"] = traffic
-        roof["hbm"] = {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": achieved_gbs / HBM_PEAK_GBS, "bytes_per_verify": BYTES_PER_VERIFY,
-                       "traffic_from": ("profiles/" + traffic_src) if traffic_src else None,
-                       "note": "algorithmic bytes / kernel time; the path is VALU-bound, this fraction is ~1e-3 by construction"}
         line = {
             "metric": "secp256k1 ECDSA verifications/sec at batch=2^%d per GPU" % batch_log2,
             "value": value, "unit": "verifications/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -824,16 +793,16 @@ def worker(args):
                        "build": eng._lib.s2k_build_config().decode(),
                        "gt_bits": gt_now["bits"], "gt_bits_at_first_call": gt_first["bits"], "ctx_create_s": ctx_create_s,
                        "wide_tables_ready_s": gt_wait_s, "gt_bytes": gt_now["bytes"], "numa_node": numa_node, "cpus_bound": numa_cpus},
-            "roofline": roof,
             "key_grouping": {"mode": "adaptive (s2k_ctx_set_key_grouping default: looks for repeated keys until two large batches in a row have none)" if args.key_grouping == "auto" else "%s (--key-grouping %s)" % (args.key_grouping, args.key_grouping), "signatures_on_key_tables": grouping["keyed"],
                              "tables_built_per_step": grouping["tables"], "signatures_on_general_ladder": grouping["general"],
                              "note": "signatures are grouped by public key inside every step; keys with >= 4 signatures get a "
                                      "precomputed table (built inside the step) and their signatures a 12-doubling ladder"},
         }
+        if args.full:
+            line["roofline"] = headline_roofline(S, args, prof, grouping, n, dt, main_keyset)
         if multi is not None:
             line["multi_rank"] = multi
-        roof.update(recount_shipped_binary(S.LIB_PATH, counts_all))
-        extras = world == 1 and not args.no_extras
+        extras = args.full and world == 1 and not args.no_extras
         if extras:
             try:
                 line.update(extra_measurements(eng, dev, n, n_keys, step, sync, st, args, host_pub=pub, resident=(d_dig, d_r, d_s)))
@@ -845,7 +814,7 @@ def worker(args):
                 rc = 1
         # host-buffer entry point (chunked H2D overlapped with the kernels, D2H); reported, never `value`.
         # One untimed call first: it creates the context's staging buffers and streams.
-        if not args.no_pcie and world == 1:
+        if args.full and not args.no_pcie and world == 1:
             try:
                 eng.ecdsa_verify_batch(pub, digest, r, s)
                 host_ms = []
@@ -948,13 +917,13 @@ def worker(args):
             except Exception as e:          # an infrastructure error there: the line is printed all the same
                 line["pcie_inclusive_error"] = "%s: %s" % (type(e).__name__, e)
                 rc = 1
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(pub, digest, r, s)
             except Exception as e:          # (the checker could not be built or run on this box: the line is printed all the same)
                 line["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, e)}
                 rc = 1
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             try:
                 line["batch_sweep"] = batch_sweep(eng, pub, digest, r, s, line.get("cpu_baseline"))
             except AssertionError as e:
@@ -963,7 +932,7 @@ def worker(args):
             except Exception as e:
                 line["batch_sweep"] = {"error": "%s: %s" % (type(e).__name__, e)}
                 rc = 1
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             try:
                 line["small_call"] = small_call(eng, S, torch, d_pub, d_dig, d_r, d_s, line.get("batch_sweep"))
                 if line["small_call"].get("crossovers_off_by_more_than_2x"):
@@ -978,6 +947,87 @@ def worker(args):
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def headline_roofline(S, args, prof, grouping, n, dt, main_keyset):
+    """--full: the dominant kernel of the timed steps against the VALU issue roofline (HIP-event times of the timed steps,
+    instruction counts from the committed PMC profile, checked against a static recount of the loaded library) and the
+    HBM roofline as a sub-object."""
+    fast_ms = prof["fast_ms"] / prof["calls"]         # dominant kernel, HIP events on its stream
+    fast_med = median(prof["fast_each"])
+    calls = prof["calls"]
+    keyed = grouping["keyed"] * 2 >= n                # which ladder is the dominant kernel of this run
+    if main_keyset is not None:
+        keyed = True
+    clock_hz = prof["shader_mhz"] * 1e6
+    counts, counts_src = committed_counts()
+    kname = KEYSET_OPTIONS[args.key_grouping][1] if main_keyset is not None else ("k_verify_fast_keyed" if keyed else "k_verify_fast")
+    traffic, traffic_src = committed_traffic(kname)
+    stages = {"grouping_by_key_ms": prof["group_ms"] / calls, "key_tables_ms": None, "ladder_ms": fast_ms,
+              "general_ladder_ms": prof["left_ms"] / calls, "complete_worklist_ms": prof["fallback_ms"] / calls}
+    if keyed:
+        # stage [0] is the grouping, stage [1] the per-key tables; the scalar preparation and the generator
+        # part u1*G run beside both on a second stream (secp256k1_voi_amd.h: s2k_ctx_profile_read_stages)
+        stages["grouping_by_key_ms"], stages["key_tables_ms"] = prof["prep_ms"] / calls, prof["group_ms"] / calls
+    else:
+        stages["scalar_prep_ms"] = prof["prep_ms"] / calls
+        stages.pop("grouping_by_key_ms")
+        stages.pop("key_tables_ms")
+    roof = {"bound": "valu", "kernel": KEYSET_OPTIONS[args.key_grouping][2] if main_keyset is not None else ("k_verify_fast<ECDSA_KEYED>" if keyed else "k_verify_fast<ECDSA>"),
+            "kernel_ms": fast_ms, "kernel_ms_median": fast_med, "stages_ms": stages,
+            "shader_clock_mhz": prof["shader_mhz"], "shader_clock_mhz_first_wave": prof["shader_mhz_first_wave"],
+            "shader_clock_mhz_last_round": prof["shader_mhz_last_round"], "unit": "Tlane-op/s", "peak": VALU_PEAK_LANE_OPS / 1e12,
+            "peak_def": "256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz: one wave64 VALU instruction per 4 cycles per SIMD"}
+    counts_all = counts
+    if counts and kname not in counts:
+        # a ladder the committed profile has no PMC entry for (yet): priced with the static recount of the loaded library
+        try:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import isa_count
+            sc_ = isa_count.static_counts(S.LIB_PATH)[kname]
+            counts = {kname: {"valu_instr_per_signature": sc_["valu_instr_static"]},
+                      (KEYSET_OPTIONS[args.key_grouping][3] if main_keyset is not None else "static"): sc_}
+            counts_src = "(none: static recount of the loaded library, tools/isa_count.py)"
+        except Exception:
+            counts = None
+    if counts:
+        ipv = counts[kname]["valu_instr_per_signature"]
+        st_ = counts.get(KEYSET_OPTIONS[args.key_grouping][3] if main_keyset is not None else ("static_keyed" if keyed else "static"), {})
+        lane_ops = ipv * n / (fast_ms * 1e-3)
+        roof.update({"achieved": lane_ops / 1e12, "frac": lane_ops / VALU_PEAK_LANE_OPS,
+                     "valu_instr_per_verify": ipv, "counts_from": "profiles/" + counts_src,
+                     "frac_def": "VALU instructions per verification (PMC) x verifications/s of the kernel / peak; every VALU "
+                                 "instruction of this kernel is priced at the 4-cycle issue interval measured for its mix "
+                                 "(profiles/r02_valu_instruction_rates.txt)"})
+        if clock_hz > 0:
+            # the same fraction against the clock the kernel actually ran at: SIMD issue cycles used / available
+            wave_instr = ipv * n / 64.0
+            cyc_avail = SIMDS * fast_ms * 1e-3 * clock_hz
+            roof["frac_at_measured_clock"] = wave_instr * 4.0 / cyc_avail
+            if "mad_u64_u32_per_verify" in st_:
+                roof["mad_issue_frac_at_measured_clock"] = st_["mad_u64_u32_per_verify"] * n / 64.0 * 4.0 / cyc_avail
+            if "valu_instr_whole_step_per_verify" in st_:
+                # every kernel of the step (grouping, tables, preparation, generator part, ladder) against the
+                # issue slots of the whole step
+                roof["whole_step_issue_frac_at_measured_clock"] = (st_["valu_instr_whole_step_per_verify"] * n / 64.0 * 4.0 /
+                                                                   (SIMDS * dt / args.steps * clock_hz))
+                roof["valu_instr_whole_step_per_verify"] = st_["valu_instr_whole_step_per_verify"]
+        if "fp_products_per_verify" in st_:
+            roof["fp_products_per_verify"] = st_["fp_products_per_verify"]
+        if "mad_u64_u32_per_verify" in st_:
+            roof.update({"mad_u64_u32_per_verify": st_["mad_u64_u32_per_verify"],
+                         "mad_u64_u32_per_s": st_["mad_u64_u32_per_verify"] * n / (fast_ms * 1e-3)})
+        # the guide's nominal VALU rate (one wave64 instruction per 2 cycles per SIMD) is reached by pure
+        # VOP2 / f32 streams only; against it the kernel sits at half the figure above
+        roof["frac_of_2cycle_nominal_peak"] = lane_ops / (2 * VALU_PEAK_LANE_OPS)
+    achieved_gbs = BYTES_PER_VERIFY * n / (fast_ms * 1e-3) / 1e9
+    roof["traffic"] = traffic
+    roof["hbm"] = {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                   "frac": achieved_gbs / HBM_PEAK_GBS, "bytes_per_verify": BYTES_PER_VERIFY,
+                   "traffic_from": ("profiles/" + traffic_src) if traffic_src else None,
+                   "note": "algorithmic bytes / kernel time; the path is VALU-bound, this fraction is ~1e-3 by construction"}
+    roof.update(recount_shipped_binary(S.LIB_PATH, counts_all))
+    return roof
 
 
 def encoded_measurement(eng, pub, digest, r, s, reps=3):

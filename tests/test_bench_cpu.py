@@ -48,6 +48,30 @@ def test_bench_launcher_times_out_on_ranks_that_never_get_ready():
     assert "have not reported ready" in p.stderr and "[0, 1]" in p.stderr, p.stderr[-1500:]
 
 
+def test_dump_outputs_exact_and_within_budget(tmp_path):
+    """--dump-outputs: bytes as float32 and wider integers as float64, every value exact; an array beyond its share of the
+    64 MB budget is written as the same seeded sample every time."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = {"valid": torch.arange(1000, dtype=torch.int64).remainder(2).to(torch.uint8), "count": torch.tensor([(1 << 40) + 3])}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    valid, count = np.load(tmp_path / "a" / "valid.npy"), np.load(tmp_path / "a" / "count.npy")
+    assert valid.dtype == np.float32 and valid.tolist() == [float(i % 2) for i in range(1000)]
+    assert count.dtype == np.float64 and count.tolist() == [float((1 << 40) + 3)]
+    big = {"valid": torch.arange(1 << 25, dtype=torch.int64).remainder(251).to(torch.uint8), "count": torch.tensor([7])}
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), big)
+    files = [tmp_path / sub / name for sub in ("b", "c") for name in ("valid.npy", "count.npy")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= bench.DUMP_BUDGET_BYTES
+    b, c = np.load(files[0]), np.load(files[2])
+    assert 0 < b.size < (1 << 25) and np.array_equal(b, c)
+
+
 def test_bench_line_fits_the_drivers_record():
     """The driver keeps an 8 KB tail of stdout: bench.py's compact form carries numbers only - the prose
     goes to bench_notes.json by path -, puts what must survive LAST, rounds to six digits, and names what it had to drop.
@@ -64,7 +88,7 @@ def test_bench_line_fits_the_drivers_record():
     line["recover_2p20"] = {"sigs": 1 << 20, "ms": 8.123456789, "roofline": {"kernel": "k_verify_fast<RECOVER>", "kernel_ms": 7.1, "frac": 0.9,
                                                                              "valu_instr_per_item": 260000.123, "frac_def": "x" * 300}, "note": "y" * 200}
     line["batch_sweep"] = {"log2_n": list(range(10, 23)), "ms": [0.123456789 * k for k in range(10, 23)], "note": "z" * 300}
-    args = argparse.Namespace(full=False, write_notes=False)
+    args = argparse.Namespace(explain=False, write_notes=False)
     text = bench.compact_line(line, args)
     assert len(text) <= 7800, len(text)
     d = json.loads(text)
@@ -81,4 +105,4 @@ def test_bench_line_fits_the_drivers_record():
     for k in ("distinct_keys", "general_path_same_batch", "keyset_resident", "pcie_inclusive", "batch_sweep", "msm_2p20", "schnorr_rlc_2p20",
               "recover_2p20"):
         assert k in d, k                                   # what the judge asked to see in the record survives the cut
-    assert json.loads(bench.compact_line(line, argparse.Namespace(full=True, write_notes=False))) == line
+    assert json.loads(bench.compact_line(line, argparse.Namespace(explain=True, write_notes=False))) == line

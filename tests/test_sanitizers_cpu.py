@@ -1,6 +1,5 @@
-"""Sanitizer runs of the CPU half (host builds only; the GPU pool has no sanitizers, and this file is listed in
-.gpurunignore so that it does not travel to the GPU box): csrc/ct_cpu.cpp and the csrc/der.h parsers under
-AddressSanitizer + UndefinedBehaviorSanitizer."""
+"""Sanitizer runs of the CPU half (host builds only: no device code is sanitized, and the hipcc line says so with
+-fno-gpu-sanitize): csrc/ct_cpu.cpp and the csrc/der.h parsers under AddressSanitizer + UndefinedBehaviorSanitizer."""
 import os
 
 import pytest
@@ -37,7 +36,7 @@ def test_der_parsers_under_sanitizers(tmp_path):
         pytest.skip("no hipcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "der_san")
-    subprocess.check_call([hipcc, "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
+    subprocess.check_call([hipcc, "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
                            "-fno-sanitize-recover=all", "-I", os.path.join(root, "secp256k1_voi_amd", "csrc"),
                            "-I", os.path.join(root, "include"), os.path.join(root, "tests", "c", "der_sanitize_main.cpp"), "-o", exe],
                           stderr=subprocess.DEVNULL)
@@ -61,6 +60,20 @@ def _build_group_driver(tmp_path, sanitize, name):
     return exe
 
 
+def _without_aslr(cmd):
+    """gcc's ThreadSanitizer runtime expects the program and its libraries where a kernel with the usual ASLR entropy maps
+    them; with more entropy (vm.mmap_rnd_bits = 32) they land elsewhere and the runtime stops at start-up ("unexpected memory
+    mapping").  So the driver runs with address randomisation off for its own process only (setarch -R sets the personality
+    of that one process), as newer sanitizer runtimes re-execute themselves; where setarch cannot do so, it runs as it is."""
+    import platform
+    import shutil
+    import subprocess
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        return [setarch, platform.machine(), "-R"] + cmd
+    return cmd
+
+
 def test_group_threads_under_thread_sanitizer(tmp_path):
     """csrc/group.cpp (member threads, job queues, tickets, the failure ring, host blocks) and
     csrc/topology.cpp reach the GPU only through the C-ABI, so they are linked against tests/c/stub_ctx.cpp - contexts whose
@@ -71,7 +84,7 @@ def test_group_threads_under_thread_sanitizer(tmp_path):
     import subprocess
     exe = _build_group_driver(tmp_path, "thread", "group_tsan")
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    p = subprocess.run([exe, "40"], capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run(_without_aslr([exe, "40"]), capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok") and "ThreadSanitizer" not in p.stderr, p.stdout + p.stderr[-3000:]
 
 

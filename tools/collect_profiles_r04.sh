@@ -11,7 +11,7 @@ O=$REPO/gpurun_out
 P=$O/profiles_$TAG
 mkdir -p $P
 cd $REPO
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pcie --no-extras"
+B="python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-pcie --no-extras"
 PMC="SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE SQ_INSTS_VMEM"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o run -- $B > $P/bench_under_kernel_trace.json 2> $O/prof_${TAG}.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$TAG -o run -- $B > /dev/null 2>&1

@@ -2,7 +2,7 @@
 # Run on the GPU box (gpurun -- bash tools/gpu_check.sh): every GPU test, then the bench at the driver's settings with a short digest.
 O=gpurun_out/check; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -6 $O/pytest.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -3 $O/bench_n1.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -3 $O/bench_n1.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/check/bench_n1.json"))

@@ -4,7 +4,7 @@ O=gpurun_out/two_rank; mkdir -p $O
 one() {  # tag, env..., -- args
   local tag=$1; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout 600 python bench.py --gpus 2 --oversubscribe --steps 5 --warmup 2 "$@" > $O/$tag.json 2> $O/$tag.err
+  env "${envs[@]}" timeout 600 python bench.py --gpus 2 --oversubscribe --steps 5 --warmup 2 --full "$@" > $O/$tag.json 2> $O/$tag.err
   echo "$tag rc=$? $(grep '^{' $O/$tag.json | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); m=d['multi_rank']
