@@ -715,7 +715,16 @@ enum {
    * the rows agree.  PT29R_DBL / PT29R_ADD: inputs, outputs and chaining (bits 20.. of `lazy`) as PT29Q_*; bit 0 of `lazy`:
    * P's y with two units; flag 2 = the rows disagree.  FER_SWAPS (n >= 8): out[0..255] = the lane numbers after
    * v_permlane16_swap (even | odd rows) and v_permlane32_swap (low | high half). */
-  S2K_HP_FER_MUL, S2K_HP_FER_MUL_PLUS, S2K_HP_FER_MUL_ADD_MUL, S2K_HP_FER_SMALL, S2K_HP_PT29R_DBL, S2K_HP_PT29R_ADD, S2K_HP_FER_SWAPS
+  S2K_HP_FER_MUL, S2K_HP_FER_MUL_PLUS, S2K_HP_FER_MUL_ADD_MUL, S2K_HP_FER_SMALL, S2K_HP_PT29R_DBL, S2K_HP_PT29R_ADD, S2K_HP_FER_SWAPS,
+  /* arithmetic mod n.  sc26.h (the lazy 10 x 26 Montgomery form of the scalar preparation, R = 2^260; bit 0 of an operand's
+   * code in `lazy` adds n to it): SC26_MUL a*b/R | SC26_SQR a^2/R | SC26_TO_MONT a*R | SC26_TO_SC a (a < 2n) | SC26_INV
+   * a^-1 R^2 (Montgomery inverse, a < 2n, 0 -> 0) | SC26_CHAIN acc = a, acc = acc*b/R as often as bits 20.. of `lazy` say (0: once).  out =
+   * the raw lazy result mod 2^256, flag bit 0 = its bit 256, flag bit 1 = its limbs are in bounds, out2 = it reduced mod n.
+   * sc.h (8 x 32, canonical operands taken as they are): SC_MONTMUL a*b/2^256 | SC_TO_MONT a*2^256 | SC_MONT_INV (the
+   * Fermat chain) | SC_ADD a+b | SC_NEG -a | SC_REDUCE_ONCE (a < 2n) | SC_GT_HALF_N (flag = a > (n-1)/2) */
+  S2K_HP_SC26_MUL, S2K_HP_SC26_SQR, S2K_HP_SC26_TO_MONT, S2K_HP_SC26_TO_SC, S2K_HP_SC26_INV, S2K_HP_SC26_CHAIN,
+  S2K_HP_SC_MONTMUL, S2K_HP_SC_TO_MONT, S2K_HP_SC_MONT_INV, S2K_HP_SC_ADD, S2K_HP_SC_NEG, S2K_HP_SC_REDUCE_ONCE,
+  S2K_HP_SC_GT_HALF_N
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);

@@ -567,6 +567,79 @@ k_pt29r_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
   if (flag) flag[idx] = f;
 }
 
+// Arithmetic mod n as the scalar preparation runs it: the lazy 10x26 Montgomery form of sc26.h (k_scalar_prep,
+// scalar_prep_one) and the canonical 8x32 form of sc.h (the BIP-340 coefficients, the complete-formula kernels).  10x26
+// operands: bit 0 of an operand's 4-bit code in `lazy` adds n to it (a canonical input lands in [n, 2n), [2^256, 2n)
+// included); results come back raw (out = value mod 2^256, flag bit 0 = bit 256, flag bit 1 = limbs 0..8 < 2^26 and limb
+// 9 < 2^23) and canonical (out2 = sc26_to_sc).  8x32 operands are taken as they are; flag = 1 (GT_HALF_N: the answer).
+S2K_DEV sc26 sc26_lazy_form(sc26 v, uint32_t code) {
+  if (code & 1u) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      const uint32_t t = v.n[i] + SC26_N[i] + c;
+      v.n[i] = i < 9 ? t & F26_M : t;
+      c = t >> 26;
+    }
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(256)
+k_sc_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
+        uint8_t* __restrict__ flag) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  sc x[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    x[j] = sc_zero();
+    if (args.in[j]) load_be32(x[j].v, args.in[j] + idx * 32);
+  }
+  if (op >= S2K_HP_SC_MONTMUL) {
+    sc r = sc_zero();
+    uint8_t f = 1;
+    switch (op) {
+      case S2K_HP_SC_MONTMUL: r = sc_montmul(x[0], x[1]); break;
+      case S2K_HP_SC_TO_MONT: r = sc_to_mont(x[0]); break;
+      case S2K_HP_SC_MONT_INV: r = sc_mont_inv(x[0]); break;
+      case S2K_HP_SC_ADD: r = sc_add(x[0], x[1]); break;
+      case S2K_HP_SC_NEG: r = sc_neg(x[0]); break;
+      case S2K_HP_SC_REDUCE_ONCE: r = sc_reduce_once(x[0].v); break;
+      default: f = sc_is_gt_half_n(x[0]) ? 1 : 0; break;    // S2K_HP_SC_GT_HALF_N
+    }
+    store_be32(out + idx * 32, r.v);
+    if (flag) flag[idx] = f;
+    return;
+  }
+  const sc26 a = sc26_lazy_form(sc26_from_sc(x[0]), lazy & 15u), b = sc26_lazy_form(sc26_from_sc(x[1]), (lazy >> 4) & 15u);
+  sc26 r = a;
+  switch (op) {
+    case S2K_HP_SC26_MUL: r = sc26_mm(a, b); break;
+    case S2K_HP_SC26_SQR: r = sc26_montsqr(a); break;
+    case S2K_HP_SC26_TO_MONT: r = sc26_to_mont(a); break;
+    case S2K_HP_SC26_TO_SC: break;                          // out2 is the answer, out the input as it went in
+    case S2K_HP_SC26_INV: r = sc26_mont_inv(a); break;
+    default:                                                // S2K_HP_SC26_CHAIN: acc <- acc * b, `reps` times
+#pragma unroll 1
+      for (uint32_t i = 0; i < reps; ++i) r = sc26_mm(r, b);
+      break;
+  }
+  bool in_bounds = r.n[9] < (1u << 23);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) in_bounds = in_bounds && r.n[i] <= F26_M;
+  fe26 t;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) t.n[i] = r.n[i];
+  const uint32_t top = (t.n[9] >> 22) & 1u;              // bit 256
+  t.n[9] &= 0x3FFFFFu;
+  uint32_t w[8];
+  fe26_to_words(w, t);
+  store_be32(out + idx * 32, w);
+  if (out2) store_be32(out2 + idx * 32, sc26_to_sc(r).v);
+  if (flag) flag[idx] = (uint8_t)(top | (in_bounds ? 2u : 0u));
+}
+
 // odd GLV split of the hot path (sc_split_glv_odd): magnitudes (129 bits) and sign bits
 __global__ void __launch_bounds__(256)
 k_split_glv_odd(uint32_t n, const uint8_t* __restrict__ k, uint8_t* __restrict__ k1o, uint8_t* __restrict__ k2o,
@@ -736,9 +809,9 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
                        uint8_t* out, uint8_t* out2, uint8_t* flag) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex serves S2K_IMPL_FAST only (8x32: s2k_fp_op_batch)");
-  const uint32_t reps = lazy >> 20;           // quad operations: bits 20.. of `lazy` = how often the operation is chained (0: once)
+  const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN: bits 20.. of `lazy` = how often the operation is chained (0: once)
   lazy &= 0xfffffu;
-  if (op < 0 || op > S2K_HP_FER_SWAPS) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (op < 0 || op > S2K_HP_SC_GT_HALF_N) return fail(ctx, S2K_ERR_ARG, "bad op");
   if (op == S2K_HP_FER_SWAPS && n < 8) return fail(ctx, S2K_ERR_ARG, "S2K_HP_FER_SWAPS writes 256 bytes: n >= 8");
   if (n == 0) return S2K_OK;
   if (!in || !in[0] || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
@@ -759,6 +832,8 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   if (flag) HIP_TRY(ctx, dflag.alloc(n));
   if (op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS)
     k_pt29r_op<<<blocks_for(64 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
+  else if (op >= S2K_HP_SC26_MUL)
+    k_sc_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_PT29Q_DBL || op == S2K_HP_PT29Q_ADD)
     k_pt29q_op<<<blocks_for(4 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else
