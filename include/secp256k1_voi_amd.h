@@ -724,7 +724,11 @@ enum {
    * Fermat chain) | SC_ADD a+b | SC_NEG -a | SC_REDUCE_ONCE (a < 2n) | SC_GT_HALF_N (flag = a > (n-1)/2) */
   S2K_HP_SC26_MUL, S2K_HP_SC26_SQR, S2K_HP_SC26_TO_MONT, S2K_HP_SC26_TO_SC, S2K_HP_SC26_INV, S2K_HP_SC26_CHAIN,
   S2K_HP_SC_MONTMUL, S2K_HP_SC_TO_MONT, S2K_HP_SC_MONT_INV, S2K_HP_SC_ADD, S2K_HP_SC_NEG, S2K_HP_SC_REDUCE_ONCE,
-  S2K_HP_SC_GT_HALF_N
+  S2K_HP_SC_GT_HALF_N,
+  /* aff29.h, the affine formulas of the wide joint tables (one safegcd inversion each; no curve constant, so any curve
+   * y^2 = x^3 + b): AFF_DBL (a, b) -> 2 (a, b) | AFF_ADD (a, b) + (c, d), x1 != x2.  Operands in their lazy forms; bits 20..
+   * of `lazy` chain the operation on its own result (2^k P; P + k Q), 0 means once; out, out2 = x, y canonical. */
+  S2K_HP_AFF_DBL, S2K_HP_AFF_ADD
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "aff29.h"
 #include "complete_path.h"
 #include "engine_internal.h"
 #include "fe29_inv.h"
@@ -383,6 +384,45 @@ k_fp29_op(int op, uint32_t lazy, uint32_t n, hp_args args, uint8_t* __restrict__
     store_be32(out2 + idx * 32, w);
   }
   if (flag) flag[idx] = f;
+}
+
+// The affine formulas of aff29.h (the wide joint tables of keyed.hip): P = (a, b), Q = (c, d), in their lazy forms; `reps`
+// chains the operation on its own result as k_ksw_odd / k_ksw_lead do (AFF_DBL: 2^reps P; AFF_ADD: P + reps Q, Q fixed)
+__global__ void __launch_bounds__(256)
+k_aff_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
+         uint8_t* __restrict__ flag) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  fe29 v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = fe29_zero();
+    if (args.in[j]) {
+      uint32_t w[8];
+      load_be32(w, args.in[j] + idx * 32);
+      v[j] = fe29_lazy_form(fe29_from_words(w), (lazy >> (4 * j)) & 15u);
+    }
+  }
+  fe29 x = v[0], y = v[1];
+#pragma unroll 1
+  for (uint32_t i = 0; i < reps; ++i) {
+    if (op == S2K_HP_AFF_DBL) {
+      aff_double(x, y);
+    } else {
+      fe29 nx, ny;
+      aff_add(x, y, v[2], v[3], nx, ny);
+      x = nx;
+      y = ny;
+    }
+  }
+  uint32_t w[8];
+  fe29_to_words(w, fe29_normalize(x));
+  store_be32(out + idx * 32, w);
+  if (out2) {
+    fe29_to_words(w, fe29_normalize(y));
+    store_be32(out2 + idx * 32, w);
+  }
+  if (flag) flag[idx] = 1;
 }
 
 // The quad-spread group law of pt29q.h, four lanes per item: inputs as for PT29_DBL / PT29_ADD above (P = (a : b : 1)
@@ -809,9 +849,9 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
                        uint8_t* out, uint8_t* out2, uint8_t* flag) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex serves S2K_IMPL_FAST only (8x32: s2k_fp_op_batch)");
-  const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN: bits 20.. of `lazy` = how often the operation is chained (0: once)
+  const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN, AFF_*: bits 20.. of `lazy` = how often the operation is chained (0: once)
   lazy &= 0xfffffu;
-  if (op < 0 || op > S2K_HP_SC_GT_HALF_N) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (op < 0 || op > S2K_HP_AFF_ADD) return fail(ctx, S2K_ERR_ARG, "bad op");
   if (op == S2K_HP_FER_SWAPS && n < 8) return fail(ctx, S2K_ERR_ARG, "S2K_HP_FER_SWAPS writes 256 bytes: n >= 8");
   if (n == 0) return S2K_OK;
   if (!in || !in[0] || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
@@ -832,6 +872,8 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   if (flag) HIP_TRY(ctx, dflag.alloc(n));
   if (op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS)
     k_pt29r_op<<<blocks_for(64 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
+  else if (op == S2K_HP_AFF_DBL || op == S2K_HP_AFF_ADD)
+    k_aff_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op >= S2K_HP_SC26_MUL)
     k_sc_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_PT29Q_DBL || op == S2K_HP_PT29Q_ADD)

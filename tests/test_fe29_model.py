@@ -183,6 +183,70 @@ def test_linear_ops_match_arithmetic():
 
 
 # ---- interval layer ------------------------------------------------------------------------------
+# Every model function that restates a C++ function carries that function's name (@cpp).  While a drift guard
+# records (test_fe29_formulas_model.py), a call made from the recorded body itself - not from inside another
+# modelled call - appends its C++ name to TRACE: the list is compared with the calls of the C++ body.  MUTATE
+# (name, k, change[, deep]) alters the k-th such call (0-based) before it runs: `change` maps its argument tuple to a
+# new one, is None to drop the call (the call returns its first argument, as if `fe29_f(x)` read `x`), or is a pair
+# (other modelled function, argument map) for a call of another function in its place.  `deep`: calls made inside
+# other modelled calls count as well (a mutation of a callee's source).
+TRACE = None
+MUTATE = None
+_depth = [0]
+
+
+def cpp(name):
+    def wrap(fn):
+        def f(*args):
+            global MUTATE
+            if _depth[0] == 0 and TRACE is not None:
+                TRACE.append(name)
+            if MUTATE is not None and MUTATE[0] == name and (_depth[0] == 0 or MUTATE[3:] == (True,)):
+                k, change = MUTATE[1], MUTATE[2]
+                MUTATE = (name, k - 1) + MUTATE[2:]
+                if k == 0:
+                    if change is None:
+                        return args[0]
+                    if isinstance(change, tuple):
+                        other, argmap = change
+                        _depth[0] += 1
+                        try:
+                            return other.body(*argmap(args))
+                        finally:
+                            _depth[0] -= 1
+                    args = change(args)
+            _depth[0] += 1
+            try:
+                return fn(*args)
+            finally:
+                _depth[0] -= 1
+        f.cpp_name = name
+        f.body = fn
+        return f
+    return wrap
+
+
+def record(fn, *args):
+    """the C++ names of the modelled calls that one run of `fn`'s own body makes, in evaluation order"""
+    global TRACE
+    TRACE = []
+    try:
+        getattr(fn, "body", fn)(*args)
+        return TRACE
+    finally:
+        TRACE = None
+
+
+def mutated(fn, mutation, *args):
+    """one run of `fn`'s body with `mutation` (see MUTATE) applied"""
+    global MUTATE
+    MUTATE = mutation
+    try:
+        return getattr(fn, "body", fn)(*args)
+    finally:
+        MUTATE = None
+
+
 class B:
     """upper bounds of the limbs (lower bound 0)"""
 
@@ -198,26 +262,31 @@ class B:
         return all(a <= b for a, b in zip(self.hi, B.units(w).hi))
 
 
+@cpp("fe29_add")
 def add(a, b):
     return B([x + y for x, y in zip(a.hi, b.hi)])
 
 
+@cpp("fe29_negate")
 def negate(a, w):
     bias = [p * (w + 1) for p in P_LIMBS]
     assert all(x <= b for x, b in zip(a.hi, bias)), "negate bias too small"
     return B(bias)
 
 
+@cpp("fe29_mul_int")
 def mul_int(a, k):
     return B([x * k for x in a.hi])
 
 
+@cpp("fe29_half")
 def half(a):
     t = [a.hi[i] + P_LIMBS[i] for i in range(L)]
     assert all(x < U32 for x in t)
     return B([(t[i] >> 1) + (1 << 28) for i in range(L - 1)] + [t[8] >> 1])
 
 
+@cpp("fe29_normalize_weak")
 def normalize_weak(a):
     x = a.hi[8] >> 24
     assert a.hi[0] + x * 0x3D1 < U32 and a.hi[1] + (x << 3) + 8 < U32
@@ -263,41 +332,65 @@ def mulsum(pairs, addend=None):
     return out
 
 
+@cpp("fe29_mul")
 def mul(a, b):
     return mulsum([(a, b)])
 
 
+@cpp("fe29_sqr")
 def sqr(a):
     return mulsum([(a, a)])
+
+
+@cpp("fe29_mul_plus")
+def mul_plus(a, b, e):
+    return mulsum([(a, b)], e)
+
+
+@cpp("fe29_sqr_plus")
+def sqr_plus(a, e):
+    return mulsum([(a, a)], e)
+
+
+@cpp("fe29_mul_add_mul")
+def mul_add_mul(a, b, c, d):
+    return mulsum([(a, b), (c, d)])
+
+
+@cpp("fe29_mul_add_sqr")
+def mul_add_sqr(a, b, c):
+    return mulsum([(a, b), (c, c)])
 
 
 ONE_UNIT = mulsum([(B.units(1), B.units(1))])   # what a product looks like
 
 
+@cpp("jpt29_double")
 def jpt_double(x, y, z):
     z3 = mul(y, z)
     s = sqr(y)
     l = half(mul_int(sqr(x), 3))
     t = mul(negate(s, 1), x)
-    x3 = mulsum([(l, l)], add(t, t))
+    x3 = sqr_plus(l, add(t, t))
     t = add(t, x3)
-    y3 = negate(mulsum([(t, l), (s, s)]), 1)
+    y3 = negate(mul_add_sqr(t, l, s), 1)
     return x3, y3, z3
 
 
+@cpp("jpt29_add_affine")
 def jpt_add_affine(x, y, z, bx, by):
     zz = sqr(z)
     nx = negate(x, 1)
-    h = mulsum([(bx, zz)], nx)
+    h = mul_plus(bx, zz, nx)
     ns = negate(mul(by, zz), 1)
-    i = mulsum([(ns, z)], y)
+    i = mul_plus(ns, z, y)
     z3 = mul(z, h)
     h2 = sqr(h)
     h3 = mul(h2, negate(h, 1))
     t = mul(nx, h2)
-    x3 = mulsum([(i, i)], add(add(h3, t), t))
+    x3 = sqr_plus(i, add(add(h3, t), t))
     t = add(t, x3)
-    y3 = mulsum([(t, i), (h3, y)])
+    y3 = mul_add_mul(t, i, h3, y)
     return x3, y3, z3, h
 
 
@@ -336,6 +429,7 @@ def test_table_build_bounds():
 
 
 # ---- pt29.h --------------------------------------------------------------------------------------
+@cpp("fe29_mul_small_norm")
 def mul_small_norm(a, k):
     c = 0
     for i in range(8):
@@ -350,36 +444,41 @@ def mul_small_norm(a, k):
     return out
 
 
+@cpp("fe29_triple_norm")
 def triple_norm(a):
     return normalize_weak(mul_int(a, 3))
 
 
+@cpp("pt29_add_tail")
 def pt_add_tail(t0, t1, t2, t3, t4, y3):
     t0n = triple_norm(t0)
     z3 = add(t1, t2)
     t1m = add(t1, negate(t2, 1))
-    return (mulsum([(t3, t1m), (negate(t4, 1), y3)]), mulsum([(t1m, z3), (y3, t0n)]), mulsum([(z3, t4), (t0n, t3)]))
+    return (mul_add_mul(t3, t1m, negate(t4, 1), y3), mul_add_mul(t1m, z3, y3, t0n), mul_add_mul(z3, t4, t0n, t3))
 
 
+@cpp("pt29_add_mixed")
 def pt_add_mixed(p, qx, qy):
     px, py, pz = p
     t0, t1 = mul(px, qx), mul(py, qy)
-    t3 = mulsum([(add(qx, qy), add(px, py))], negate(add(t0, t1), 2))
-    t4 = mulsum([(qy, pz)], py)
-    y3 = mul_small_norm(mulsum([(qx, pz)], px), 21)
+    t3 = mul_plus(add(qx, qy), add(px, py), negate(add(t0, t1), 2))
+    t4 = mul_plus(qy, pz, py)
+    y3 = mul_small_norm(mul_plus(qx, pz, px), 21)
     t2 = mul_small_norm(pz, 21)
     return pt_add_tail(t0, t1, t2, t3, t4, y3)
 
 
+@cpp("pt29_add")
 def pt_add(p, q):
     (px, py, pz), (qx, qy, qz) = p, q
     t0, t1, t2 = mul(px, qx), mul(py, qy), mul(pz, qz)
-    t3 = mulsum([(add(px, py), add(qx, qy))], negate(add(t0, t1), 2))
-    t4 = mulsum([(add(py, pz), add(qy, qz))], negate(add(t1, t2), 2))
-    y3 = mulsum([(add(px, pz), add(qx, qz))], negate(add(t0, t2), 2))
+    t3 = mul_plus(add(px, py), add(qx, qy), negate(add(t0, t1), 2))
+    t4 = mul_plus(add(py, pz), add(qy, qz), negate(add(t1, t2), 2))
+    y3 = mul_plus(add(px, pz), add(qx, qz), negate(add(t0, t2), 2))
     return pt_add_tail(t0, t1, mul_small_norm(t2, 21), t3, t4, mul_small_norm(y3, 21))
 
 
+@cpp("pt29_double")
 def pt_double(p):
     px, py, pz = p
     t0 = sqr(py)
@@ -389,7 +488,10 @@ def pt_double(p):
     t2 = mul_small_norm(zz, 21)
     y3 = add(t0, t2)
     t0m = normalize_weak(add(t0, negate(mul_small_norm(zz, 63), 1)))
-    return mul(mul_int(t0m, 2), mul(px, py)), mulsum([(t2, z3), (t0m, y3)]), mul(t1, z3)
+    ry = mul_add_mul(t2, z3, t0m, y3)
+    rz = mul(t1, z3)
+    rx = mul(mul_int(t0m, 2), mul(px, py))
+    return rx, ry, rz
 
 
 def test_projective_invariant_closed():
