@@ -590,6 +590,35 @@ int s2k_multi_scalar_mult(s2k_ctx *ctx, size_t n, const uint8_t *k /* n*32 */, c
                           uint8_t *out /* 65 */);
 int s2k_multi_scalar_mult_device(s2k_ctx *ctx, size_t n, const void *d_k, const void *d_points, void *d_out65,
                                  void *hip_stream);
+/* Many independent sums in one call: out[j] = sum of k[i] * P[i] over i in [seg_offsets[j], seg_offsets[j+1]) — for every j
+ * the record Point.MultiScalarMultVartime(scalars[a:b], points[a:b]) gives (point_mul_multi.go:73-117), so exactly what
+ * s2k_multi_scalar_mult returns for that slice.  ONLY the Vartime form: variable time (data-dependent digit additions and
+ * bucket sorts), public scalars only.  The constant-time Point.MultiScalarMult (:25-67) binds to s2k_ct_multi_scalar_mult
+ * below, never to this.  seg_offsets is HOST memory in both forms (n_seg + 1 entries, seg_offsets[0] == 0, non-decreasing,
+ * seg_offsets[n_seg] == n; anything else is S2K_ERR_ARG before any launch).  An empty segment gives the identity record
+ * (65 zero bytes, :37); n_seg == 0 writes nothing.  Segments of at most S2K_MSM_SEG_CROSSOVER (16384) terms run Straus in
+ * pieces of S2K_MSM_SEG_T (8) terms, one lane and one shared chain of doublings per piece, complete additions, all pieces of
+ * all segments side by side; longer ones take the bucket method of s2k_multi_scalar_mult one after the other (one such
+ * segment alone IS that call).  The two environment variables are read at every call: do not change them while another
+ * thread is inside the library.  Workspace: 578 bytes per term on the Straus path and 108 per piece, a block of the context
+ * allocated at the first call and kept until s2k_ctx_destroy (s2k_ctx_device_bytes counts no multiscalar workspace).  A malformed point record anywhere is
+ * S2K_ERR_ARG for the call.  The device form takes device pointers and synchronises the stream once, at the end (it has
+ * to read back the status word). */
+int s2k_multi_scalar_mult_segments(s2k_ctx *ctx, size_t n, const uint8_t *k /* n*32 */, const uint8_t *points /* n*65 */,
+                                   size_t n_seg, const uint64_t *seg_offsets /* n_seg+1 */, uint8_t *out /* n_seg*65 */);
+int s2k_multi_scalar_mult_segments_device(s2k_ctx *ctx, size_t n, const void *d_k, const void *d_points,
+                                          size_t n_seg, const uint64_t *seg_offsets /* host */, void *d_out /* n_seg*65 */,
+                                          void *hip_stream);
+/* The host-side plan of the segmented call as a pure function (no device, no context), for the tests.  piece_terms == 0 /
+ * crossover == 0: the defaults the call uses (S2K_MSM_SEG_T, S2K_MSM_SEG_CROSSOVER).  summary: pieces, segments on the bucket
+ * method, terms on the Straus path, workspace bytes the call reserves, longest bucket-method segment, piece_terms and
+ * crossover used, runs of consecutive Straus terms (one front-end launch each).  The arrays may be NULL (counts only); else
+ * piece i of the launch order (longest first) covers the terms [piece_first[i], piece_first[i] + piece_len[i]) and is
+ * piece number piece_dest[i] in segment order; seg_desc[2j] is the first piece of segment j, seg_desc[2j+1] its piece
+ * count, or 0x80000000 when it takes the bucket method.  Bad offsets or sizes: S2K_ERR_ARG, as the call. */
+int s2k_debug_msm_segments_plan(size_t n, size_t n_seg, const uint64_t *seg_offsets, uint32_t piece_terms, uint64_t crossover,
+                                uint64_t summary[8], size_t piece_cap, uint32_t *piece_first, uint32_t *piece_len,
+                                uint32_t *piece_dest, uint32_t *seg_desc);
 /* SEC1 decode of n fixed-size encodings (enc_len = 33: SetCompressedBytes point_s11n.go:140;
  * enc_len = 65: SetUncompressedBytes :178).  ok[i] = 1 and out[i] = point on success,
  * ok[i] = 0 and out[i] = zeros otherwise. */

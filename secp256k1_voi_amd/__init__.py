@@ -313,6 +313,9 @@ def load_library() -> C.CDLL:
     lib.s2k_point_decode_batch.argtypes = [vp, sz, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult_device.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.s2k_multi_scalar_mult_segments.argtypes = [vp, sz, vp, vp, sz, vp, vp]
+    lib.s2k_multi_scalar_mult_segments_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
+    lib.s2k_debug_msm_segments_plan.argtypes = [sz, sz, vp, u32, C.c_uint64, vp, sz, vp, vp, vp, vp]
     lib.s2k_fp_op_batch.argtypes = [vp, ci, sz, vp, vp, vp, vp]
     lib.s2k_fn_op_batch.argtypes = [vp, ci, sz, vp, vp, vp, vp]
     lib.s2k_fn_split_glv_batch.argtypes = [vp, sz, vp, vp, vp]
@@ -395,6 +398,7 @@ EXPORTED_SYMBOLS = [
     "s2k_scalar_base_mult_batch", "s2k_scalar_mult_batch", "s2k_double_scalar_mult_basepoint_batch",
     "s2k_point_add_batch", "s2k_point_double_batch", "s2k_point_decode_batch",
     "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device",
+    "s2k_multi_scalar_mult_segments", "s2k_multi_scalar_mult_segments_device", "s2k_debug_msm_segments_plan",
     "s2k_fp_op_batch", "s2k_fn_op_batch", "s2k_fn_split_glv_batch", "s2k_debug_gtable_entry", "s2k_generator_window_bits",
     "s2k_double_scalar_mult_basepoint_batch_ex", "s2k_fp_op_batch_ex", "s2k_fn_split_glv_batch_ex",
     "s2k_ct_scalar_mult", "s2k_ct_scalar_base_mult", "s2k_ct_ecdh", "s2k_ct_ecdsa_sign_raw", "s2k_ct_debug_fe_mul_count",
@@ -452,6 +456,49 @@ def ct_scalar_mult(k: bytes, point65: bytes):
     for a malformed point."""
     out = C.create_string_buffer(65)
     return out.raw if load_library().s2k_ct_scalar_mult(bytes(k), bytes(point65), out) == 0 else None
+
+
+def check_segment_offsets(offsets, n: int) -> np.ndarray:
+    """Segment offsets as the contiguous uint64 array the C-ABI takes; ValueError unless they start at 0, never decrease
+    and end at n (what s2k_multi_scalar_mult_segments would refuse with S2K_ERR_ARG)."""
+    raw = np.asarray(offsets)
+    if raw.ndim != 1 or raw.shape[0] < 1:
+        raise ValueError("offsets must be a one-dimensional array of n_seg + 1 entries")
+    if raw.dtype.kind not in "iu" or (raw.dtype.kind == "i" and raw.size and int(raw.min()) < 0):
+        raise ValueError("offsets must be non-negative integers")
+    off = np.ascontiguousarray(raw, dtype=np.uint64)
+    if int(off[0]) != 0:
+        raise ValueError("offsets must start at 0")
+    if off.shape[0] > 1 and bool(np.any(off[1:] < off[:-1])):
+        raise ValueError("offsets must not decrease")
+    if int(off[-1]) != int(n):
+        raise ValueError(f"offsets must end at the number of terms ({int(off[-1])} != {int(n)})")
+    return off
+
+
+def msm_segments_plan(n: int, offsets, piece_terms: int = 0, crossover: int = 0, arrays: bool = True) -> dict:
+    """The host-side plan of multi_scalar_mult_segments (s2k_debug_msm_segments_plan; no device).  `offsets` goes to the library
+    as it is (a uint64 array): its argument checks are part of what this exposes.  EngineError on refused arguments."""
+    lib = load_library()
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n_seg = max(off.shape[0] - 1, 0)
+    summary = np.zeros(8, dtype=np.uint64)
+    optr = off.ctypes.data if off.shape[0] else None
+    rc = lib.s2k_debug_msm_segments_plan(int(n), n_seg, optr, int(piece_terms), int(crossover), summary.ctypes.data, 0, None, None, None, None)
+    if rc:
+        raise EngineError(f"s2k_debug_msm_segments_plan: {rc}")
+    keys = ("pieces", "long_segments", "short_terms", "workspace_bytes", "max_long", "piece_terms", "crossover", "runs")
+    plan = {k: int(v) for k, v in zip(keys, summary)}
+    if arrays:
+        npc = plan["pieces"]
+        first, ln, dest = (np.zeros(max(npc, 1), dtype=np.uint32) for _ in range(3))
+        desc = np.zeros(max(2 * n_seg, 1), dtype=np.uint32)
+        rc = lib.s2k_debug_msm_segments_plan(int(n), n_seg, optr, int(piece_terms), int(crossover), summary.ctypes.data, npc,
+                                             first.ctypes.data, ln.ctypes.data, dest.ctypes.data, desc.ctypes.data)
+        if rc:
+            raise EngineError(f"s2k_debug_msm_segments_plan: {rc}")
+        plan.update(piece_first=first[:npc], piece_len=ln[:npc], piece_dest=dest[:npc], seg_desc=desc[:2 * n_seg].reshape(n_seg, 2))
+    return plan
 
 
 def ct_multi_scalar_mult(scalars, points):
@@ -1081,6 +1128,26 @@ class Engine(_TicketOwner):
 
     def multi_scalar_mult_device(self, n, d_scalars, d_points, d_out65, stream=0):
         self._check(self._lib.s2k_multi_scalar_mult_device(self._h, int(n), d_scalars, d_points, d_out65, stream))
+
+    def multi_scalar_mult_segments(self, scalars, points, offsets) -> np.ndarray:
+        """out[j] = sum of scalars[i] * points[i] over offsets[j] <= i < offsets[j + 1] (MultiScalarMultVartime per segment):
+        (n_seg, 65) records, an empty segment gives the identity record.  Public scalars only."""
+        scalars = _arr(scalars, 32)
+        n = scalars.shape[0]
+        points = _arr(points, 65, n)            # length mismatch raises, like the reference panics
+        off = check_segment_offsets(offsets, n)
+        n_seg = off.shape[0] - 1
+        out = np.zeros((n_seg, 65), dtype=np.uint8)
+        self._check(self._lib.s2k_multi_scalar_mult_segments(self._h, n, scalars.ctypes.data if n else None,
+                                                             points.ctypes.data if n else None, n_seg, off.ctypes.data,
+                                                             out.ctypes.data if n_seg else None))
+        return out
+
+    def multi_scalar_mult_segments_device(self, n, d_scalars, d_points, offsets, d_out, stream=0):
+        """The same on device buffers (d_out: n_seg * 65 bytes); `offsets` stays host memory.  Synchronises `stream` once."""
+        off = check_segment_offsets(offsets, int(n))
+        self._check(self._lib.s2k_multi_scalar_mult_segments_device(self._h, int(n), d_scalars, d_points, off.shape[0] - 1,
+                                                                    off.ctypes.data, d_out, stream))
 
     def point_decode_batch(self, enc, enc_len):
         enc = _arr(enc, enc_len)

@@ -110,6 +110,10 @@ struct s2k_ctx {
   size_t ws_bytes = 0;
   void* msm_ws = nullptr;       // workspace of the multi-scalar multiplication
   size_t msm_ws_bytes = 0;
+  void* seg_ws = nullptr;       // workspace of the segmented multi-scalar multiplication (msm_seg.hip), allocated on its first call
+  size_t seg_ws_bytes = 0;
+  void* seg_host = nullptr;     // pinned host block its plan is uploaded from (one copy per call)
+  size_t seg_host_bytes = 0;
   void* rlc_save = nullptr;     // kept terms of a rejected BIP-340 batch while its failing signatures are located
   size_t rlc_save_bytes = 0;
   // host-buffer entry point: device staging for inputs / verdicts, a copy stream and a compute
@@ -320,6 +324,14 @@ inline void msm_prof_mark(s2k_ctx* ctx, hipStream_t st, int slot) {
   (void)hipEventRecord(ctx->msm_prof_ev[ctx->msm_prof_used + slot], st);
   if (slot == MSM_PROF_EV - 1) ctx->msm_prof_used += MSM_PROF_EV;
 }
+
+// msm.hip, for msm_seg.hip: one bucket-method sum enqueued on `st` without a synchronisation.  *d_status receives the address
+// of the call's status word (non-zero after the launches: a malformed record), valid until the next multiscalar call of the
+// context.  s2k_internal_msm_reserve grows the workspace to what a sum of n inputs needs, so that no later enqueue has to with
+// work in flight (the carve is not monotonic in n - the window width changes it - so a caller reserves for every size it will run).
+int s2k_internal_msm_enqueue(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_scalars, const void* d_points, void* d_out65,
+                             uint32_t** d_status);
+int s2k_internal_msm_reserve(s2k_ctx* ctx, size_t n);
 
 // submit / wait plumbing (engine.hip), shared with the encoded entry point (ingest.hip)
 int s2k_internal_pipe_slot(s2k_ctx* ctx, size_t n, uint8_t* valid, s2k_ctx::pipe_slot** out);   // free slot for the next ticket

@@ -1576,6 +1576,27 @@ k_rlc_mark_valid(uint32_t lo, uint32_t m, const uint8_t* __restrict__ s_flag, ui
 
 }  // namespace
 
+// (engine_internal.h) the launches of one sum, n > 0 inputs; the caller has entered the context and synchronises
+__attribute__((visibility("hidden"))) int s2k_internal_msm_enqueue(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_scalars, const void* d_points, void* d_out65,
+                             uint32_t** d_status) {
+  msm_ws m;
+  int rc = msm_setup(ctx, 2 * n, 0, m);   // every input is two terms (endomorphism split)
+  if (rc) return rc;
+  msm_prof_mark(ctx, st, 0);
+  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
+  // (the front end moves 275 MB in 0.075 ms - it is bound by that, not by its arithmetic: splitting it into a scalar kernel in
+  // front of the sort and a point kernel beside it on a second stream was measured 0.03 ms SLOWER, profiles/r06_msm_attempts.txt)
+  k_msm_parse<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, (const uint8_t*)d_scalars, (const uint8_t*)d_points, m.scw,
+                                             m.ptw, m.flag, m.status);
+  HIP_TRY(ctx, hipGetLastError());
+  *d_status = m.status;
+  return msm_core(ctx, st, 2 * n, m, (uint8_t*)d_out65);
+}
+__attribute__((visibility("hidden"))) int s2k_internal_msm_reserve(s2k_ctx* ctx, size_t n) {
+  msm_ws m;
+  return msm_setup(ctx, 2 * n, 0, m);
+}
+
 extern "C" {
 
 int s2k_ctx_profile_msm(s2k_ctx* ctx, int enable) {
@@ -1631,21 +1652,12 @@ int s2k_multi_scalar_mult_device(s2k_ctx* ctx, size_t n, const void* d_scalars, 
   }
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
-  msm_ws m;
-  rc = msm_setup(ctx, 2 * n, 0, m);   // every input is two terms (endomorphism split)
-  if (rc) return rc;
-  msm_prof_mark(ctx, st, 0);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
-  // (the front end moves 275 MB in 0.075 ms - it is bound by that, not by its arithmetic: splitting it into a scalar kernel in
-  // front of the sort and a point kernel beside it on a second stream was measured 0.03 ms SLOWER, profiles/r06_msm_attempts.txt)
-  k_msm_parse<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, (const uint8_t*)d_scalars, (const uint8_t*)d_points, m.scw,
-                                             m.ptw, m.flag, m.status);
-  HIP_TRY(ctx, hipGetLastError());
-  rc = msm_core(ctx, st, 2 * n, m, (uint8_t*)d_out65);
+  uint32_t* d_status = nullptr;
+  rc = s2k_internal_msm_enqueue(ctx, st, n, d_scalars, d_points, d_out65, &d_status);
   if (rc) return rc;
   // malformed point records are a caller error (the reference cannot even construct such Points)
   uint32_t h_status = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&h_status, m.status, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&h_status, d_status, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   ctx->have_last = false;   // the stream has been synchronised: nothing of this context is in flight
   if (h_status) return fail(ctx, S2K_ERR_ARG, "malformed point record in multi-scalar multiplication input");
