@@ -624,6 +624,45 @@ int s2k_debug_msm_segments_plan(size_t n, size_t n_seg, const uint64_t *seg_offs
  * ok[i] = 0 and out[i] = zeros otherwise. */
 int s2k_point_decode_batch(s2k_ctx *ctx, size_t n, size_t enc_len, const uint8_t *enc, uint8_t *out, uint8_t *ok);
 
+/* ---- hashing to the curve (RFC 9380, secp256k1_XMD:SHA-256_SSWU_RO_ / _NU_; batched) --------
+ * Public data, one independent item per message, VARIABLE TIME like everything on the GPU here.  The output is the 65-byte
+ * point record the multiscalar entry points take (65 zero bytes for the identity).  Messages follow the convention of
+ * s2k_schnorr_verify_batch: n strings of msg_len bytes each (msg_offsets == NULL), or concatenated with msg_offsets[n+1]
+ * byte offsets (msg_offsets[0] == 0, non-decreasing; any lengths).  The domain separation tag is common to a call and is
+ * HOST memory in every form.  Refused with S2K_ERR_ARG before any launch, the output untouched: a null context, a null
+ * buffer with n > 0, n > 2^31 - 1, dst_len == 0 (h2c_expand_message.go:50-53), offsets that do not start at 0 or that
+ * decrease.  n == 0 writes nothing and succeeds. */
+#define S2K_H2C_SSWU_RO 0 /* hash_to_curve: two field elements, two mapped points, their sum */
+#define S2K_H2C_SSWU_NU 1 /* encode_to_curve: one field element, one mapped point */
+/* DST_prime of expand_message_xmd (h2c_expand_message.go:46-63,79-80): dst || I2OSP(dst_len, 1), and for a tag of more than
+ * 255 bytes SHA-256("H2C-OVERSIZE-DST-" || dst) || 0x20.  Host function: no context, no device.  out holds up to 256 bytes;
+ * *out_len receives the length.  dst_len == 0 (or a null pointer): S2K_ERR_ARG (:50-53). */
+int s2k_h2c_dst_prime(const uint8_t *dst, size_t dst_len, uint8_t out[256], size_t *out_len);
+/* out[i] = len_in_bytes uniform bytes for message i — expandMessageXMD with SHA-256 (h2c_expand_message.go:27-139).
+ * len_in_bytes must be in 1..8160 (ell = ceil(len_in_bytes / 32) <= 255, :42-44,71-73). */
+int s2k_expand_message_xmd_batch(s2k_ctx *ctx, size_t n, const uint8_t *dst, size_t dst_len, const uint8_t *msgs,
+                                 const uint64_t *msg_offsets, size_t msg_len, size_t len_in_bytes,
+                                 uint8_t *out /* n*len_in_bytes */);
+/* out[i] = sum over j < count of Point.SetUniformBytes(uniform[(i*count + j)*len ...]) (point_h2c.go:23-55): the wide
+ * reduction mod p (field.Element.SetWideBytes, internal/field/field_reduce.go:24-64; a 32-byte value >= p is reduced, not
+ * refused), swu.MapToCurveSimpleSWU and swu.IsoMap (internal/swu/swu.go:70-199).  count is 1 or 2 — count = 2 is exactly
+ * steps 2-5 of the RO suite (h2c.go:32-44) —, len in [32, 64]; anything else is S2K_ERR_ARG (the reference panics). */
+int s2k_map_to_curve_batch(s2k_ctx *ctx, size_t n, size_t count, size_t len, const uint8_t *uniform /* n*count*len */,
+                           uint8_t *out /* n*65 */);
+/* out[i] = Secp256k1_XMD_SHA256_SSWU_RO(dst, msg_i) (suite S2K_H2C_SSWU_RO, h2c.go:25-45) or
+ * Secp256k1_XMD_SHA256_SSWU_NU(dst, msg_i) (S2K_H2C_SSWU_NU, h2c.go:49-63), one kernel from message bytes to record. */
+int s2k_hash_to_curve_batch(s2k_ctx *ctx, int suite, size_t n, const uint8_t *dst, size_t dst_len, const uint8_t *msgs,
+                            const uint64_t *msg_offsets, size_t msg_len, uint8_t *out /* n*65 */);
+/* The same on device pointers and the caller's stream (the tag stays host memory), chained behind the context's earlier
+ * calls like the other *_device forms; it synchronises the stream once, at the end, to read back its status word.  The
+ * offsets are device memory here, so the caller states the size of the message buffer: total_msg_bytes.  No lane reads
+ * outside [0, total_msg_bytes): an item whose range is not inside it, or whose offsets decrease (or do not start at 0),
+ * gets the identity record and the call returns S2K_ERR_ARG; the other records are written.  With msg_offsets == NULL,
+ * n * msg_len > total_msg_bytes is refused before any launch. */
+int s2k_hash_to_curve_batch_device(s2k_ctx *ctx, int suite, size_t n, const uint8_t *dst /* host */, size_t dst_len,
+                                   const void *d_msgs, const void *d_msg_offsets, size_t msg_len, size_t total_msg_bytes,
+                                   void *d_out /* n*65 */, void *hip_stream);
+
 /* ---- constant-time twins, host CPU (no GPU, no context) ------------------------------------
  * What the reference's secret-handling code calls.  No branch, address or
  * loop count depends on the scalar, the private key or the nonce: masked full-table scans

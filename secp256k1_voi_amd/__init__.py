@@ -55,6 +55,7 @@ KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 = 0, 1, 2
  HP_SC26_MUL, HP_SC26_SQR, HP_SC26_TO_MONT, HP_SC26_TO_SC, HP_SC26_INV, HP_SC26_CHAIN,
  HP_SC_MONTMUL, HP_SC_TO_MONT, HP_SC_MONT_INV, HP_SC_ADD, HP_SC_NEG, HP_SC_REDUCE_ONCE, HP_SC_GT_HALF_N,
  HP_AFF_DBL, HP_AFF_ADD) = range(49)
+H2C_SSWU_RO, H2C_SSWU_NU = 0, 1        # s2k_hash_to_curve_batch: hash_to_curve (random oracle) / encode_to_curve (non-uniform)
 
 IDENTITY = bytes(65)
 
@@ -316,6 +317,11 @@ def load_library() -> C.CDLL:
     lib.s2k_multi_scalar_mult_segments.argtypes = [vp, sz, vp, vp, sz, vp, vp]
     lib.s2k_multi_scalar_mult_segments_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
     lib.s2k_debug_msm_segments_plan.argtypes = [sz, sz, vp, u32, C.c_uint64, vp, sz, vp, vp, vp, vp]
+    lib.s2k_h2c_dst_prime.argtypes = [C.c_char_p, sz, C.c_char_p, C.POINTER(sz)]
+    lib.s2k_expand_message_xmd_batch.argtypes = [vp, sz, C.c_char_p, sz, vp, vp, sz, sz, vp]
+    lib.s2k_map_to_curve_batch.argtypes = [vp, sz, sz, sz, vp, vp]
+    lib.s2k_hash_to_curve_batch.argtypes = [vp, ci, sz, C.c_char_p, sz, vp, vp, sz, vp]
+    lib.s2k_hash_to_curve_batch_device.argtypes = [vp, ci, sz, C.c_char_p, sz, vp, vp, sz, sz, vp, vp]
     lib.s2k_fp_op_batch.argtypes = [vp, ci, sz, vp, vp, vp, vp]
     lib.s2k_fn_op_batch.argtypes = [vp, ci, sz, vp, vp, vp, vp]
     lib.s2k_fn_split_glv_batch.argtypes = [vp, sz, vp, vp, vp]
@@ -399,6 +405,7 @@ EXPORTED_SYMBOLS = [
     "s2k_point_add_batch", "s2k_point_double_batch", "s2k_point_decode_batch",
     "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device",
     "s2k_multi_scalar_mult_segments", "s2k_multi_scalar_mult_segments_device", "s2k_debug_msm_segments_plan",
+    "s2k_h2c_dst_prime", "s2k_expand_message_xmd_batch", "s2k_map_to_curve_batch", "s2k_hash_to_curve_batch", "s2k_hash_to_curve_batch_device",
     "s2k_fp_op_batch", "s2k_fn_op_batch", "s2k_fn_split_glv_batch", "s2k_debug_gtable_entry", "s2k_generator_window_bits",
     "s2k_double_scalar_mult_basepoint_batch_ex", "s2k_fp_op_batch_ex", "s2k_fn_split_glv_batch_ex",
     "s2k_ct_scalar_mult", "s2k_ct_scalar_base_mult", "s2k_ct_ecdh", "s2k_ct_ecdsa_sign_raw", "s2k_ct_debug_fe_mul_count",
@@ -456,6 +463,46 @@ def ct_scalar_mult(k: bytes, point65: bytes):
     for a malformed point."""
     out = C.create_string_buffer(65)
     return out.raw if load_library().s2k_ct_scalar_mult(bytes(k), bytes(point65), out) == 0 else None
+
+
+def h2c_dst_prime(dst: bytes) -> bytes:
+    """DST_prime of expand_message_xmd (s2k_h2c_dst_prime; h2c_expand_message.go:46-63): dst || len(dst), a tag of more than
+    255 bytes hashed first.  Host only.  An empty tag raises ValueError (the reference returns errInvalidDomainSep)."""
+    dst = bytes(dst)
+    if len(dst) == 0:
+        raise ValueError("secp256k1/secec/h2c: invalid domain separator")
+    out, n = C.create_string_buffer(256), C.c_size_t(0)
+    rc = load_library().s2k_h2c_dst_prime(dst, len(dst), out, C.byref(n))
+    if rc != 0:
+        raise EngineError(f"s2k_h2c_dst_prime failed ({rc})")
+    return out.raw[:n.value]
+
+
+def _h2c_messages(msgs):
+    """A list of byte strings or a (blob, offsets) pair -> (n, contiguous uint8 blob, uint64 offsets); ValueError for offsets
+    that do not start at 0, decrease or leave the blob (what the C-ABI would refuse, or could not check)."""
+    if isinstance(msgs, tuple) and len(msgs) == 2 and not isinstance(msgs[0], (bytes, bytearray)):
+        blob = np.ascontiguousarray(msgs[0], dtype=np.uint8).reshape(-1)
+        raw = np.asarray(msgs[1])
+        if raw.ndim != 1 or raw.shape[0] < 1 or raw.dtype.kind not in "iu" or (raw.dtype.kind == "i" and int(raw.min()) < 0):
+            raise ValueError("offsets must be a one-dimensional array of n + 1 non-negative integers")
+        offs = np.ascontiguousarray(raw, dtype=np.uint64)
+        if int(offs[0]) != 0 or bool(np.any(offs[1:] < offs[:-1])):
+            raise ValueError("offsets must start at 0 and must not decrease")
+        if int(offs[-1]) > blob.size:
+            raise ValueError(f"offsets end at {int(offs[-1])}, the message buffer holds {blob.size} bytes")
+        if blob.size == 0:
+            blob = np.zeros(1, dtype=np.uint8)
+        return offs.shape[0] - 1, blob, offs
+    blob, offs = _concat([bytes(m) for m in msgs])
+    return len(offs) - 1, blob, offs
+
+
+def _h2c_dst(dst) -> bytes:
+    dst = bytes(dst)
+    if len(dst) == 0:
+        raise ValueError("secp256k1/secec/h2c: invalid domain separator")
+    return dst
 
 
 def check_segment_offsets(offsets, n: int) -> np.ndarray:
@@ -1148,6 +1195,57 @@ class Engine(_TicketOwner):
         off = check_segment_offsets(offsets, int(n))
         self._check(self._lib.s2k_multi_scalar_mult_segments_device(self._h, int(n), d_scalars, d_points, off.shape[0] - 1,
                                                                     off.ctypes.data, d_out, stream))
+
+    # ---- hashing to the curve (RFC 9380; h2c.hip) -------------------------------------
+    def expand_message_xmd(self, msgs, dst, len_in_bytes: int) -> np.ndarray:
+        """expand_message_xmd with SHA-256 for every message (s2k_expand_message_xmd_batch): (n, len_in_bytes) uniform bytes.
+        `msgs`: a list of byte strings or a (blob, offsets) pair; `dst`: the domain separation tag, common to the call."""
+        dst, len_in_bytes = _h2c_dst(dst), int(len_in_bytes)
+        if not 1 <= len_in_bytes <= 8160:
+            raise ValueError("secp256k1/secec/h2c: len_in_bytes out of range")
+        n, blob, offs = _h2c_messages(msgs)
+        out = np.zeros((n, len_in_bytes), dtype=np.uint8)
+        self._check(self._lib.s2k_expand_message_xmd_batch(self._h, n, dst, len(dst), blob.ctypes.data, offs.ctypes.data, 0,
+                                                           len_in_bytes, out.ctypes.data if n else None))
+        return out
+
+    def map_to_curve(self, uniform, length: int, count: int = 1) -> np.ndarray:
+        """out[i] = sum of `count` (1 or 2) points Point.SetUniformBytes(uniform[(i * count + j) * length ...]), 32 <= length
+        <= 64 (s2k_map_to_curve_batch): (n, 65) records.  `uniform`: bytes, a list of byte strings or an array, n * count *
+        length bytes in all."""
+        length, count = int(length), int(count)
+        if count not in (1, 2):
+            raise ValueError("count must be 1 or 2")
+        if not 32 <= length <= 64:
+            raise ValueError("secp256k1: uniform bytes must be 32 to 64 bytes long")
+        u = _arr(uniform, count * length)
+        n = u.shape[0]
+        out = self._points_out(n)
+        self._check(self._lib.s2k_map_to_curve_batch(self._h, n, count, length, u.ctypes.data if n else None, out.ctypes.data if n else None))
+        return out
+
+    def _hash_to_curve(self, suite, msgs, dst):
+        dst = _h2c_dst(dst)
+        n, blob, offs = _h2c_messages(msgs)
+        out = self._points_out(n)
+        self._check(self._lib.s2k_hash_to_curve_batch(self._h, suite, n, dst, len(dst), blob.ctypes.data, offs.ctypes.data, 0,
+                                                      out.ctypes.data if n else None))
+        return out
+
+    def hash_to_curve(self, msgs, dst) -> np.ndarray:
+        """Secp256k1_XMD_SHA256_SSWU_RO(dst, msg) for every message (h2c.go:25-45): (n, 65) records."""
+        return self._hash_to_curve(H2C_SSWU_RO, msgs, dst)
+
+    def encode_to_curve(self, msgs, dst) -> np.ndarray:
+        """Secp256k1_XMD_SHA256_SSWU_NU(dst, msg) for every message (h2c.go:49-63): (n, 65) records."""
+        return self._hash_to_curve(H2C_SSWU_NU, msgs, dst)
+
+    def hash_to_curve_device(self, suite, n, dst, d_msgs, d_msg_offsets, msg_len, total_msg_bytes, d_out, stream=0):
+        """s2k_hash_to_curve_batch_device: device pointers (d_msg_offsets None: n messages of msg_len bytes), the tag on the
+        host; d_out: n * 65 bytes.  Synchronises `stream` once."""
+        dst = _h2c_dst(dst)
+        self._check(self._lib.s2k_hash_to_curve_batch_device(self._h, int(suite), int(n), dst, len(dst), d_msgs, d_msg_offsets,
+                                                             int(msg_len), int(total_msg_bytes), d_out, stream))
 
     def point_decode_batch(self, enc, enc_len):
         enc = _arr(enc, enc_len)

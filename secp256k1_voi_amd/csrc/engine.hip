@@ -2725,6 +2725,8 @@ void s2k_ctx_destroy(s2k_ctx* ctx) {
   if (ctx->msm_ws) (void)hipFree(ctx->msm_ws);
   if (ctx->seg_ws) (void)hipFree(ctx->seg_ws);
   if (ctx->seg_host) (void)hipHostFree(ctx->seg_host);
+  if (ctx->h2c_dev) (void)hipFree(ctx->h2c_dev);
+  if (ctx->h2c_host) (void)hipHostFree(ctx->h2c_host);
   if (ctx->rlc_save) (void)hipFree(ctx->rlc_save);
   if (ctx->io) (void)hipFree(ctx->io);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);

@@ -114,6 +114,8 @@ struct s2k_ctx {
   size_t seg_ws_bytes = 0;
   void* seg_host = nullptr;     // pinned host block its plan is uploaded from (one copy per call)
   size_t seg_host_bytes = 0;
+  void* h2c_dev = nullptr;      // hashing to the curve (h2c.hip): status word and DST_prime on the device, allocated on its first call
+  void* h2c_host = nullptr;     // ... and the pinned host block both travel through
   void* rlc_save = nullptr;     // kept terms of a rejected BIP-340 batch while its failing signatures are located
   size_t rlc_save_bytes = 0;
   // host-buffer entry point: device staging for inputs / verdicts, a copy stream and a compute

@@ -219,6 +219,15 @@ __device__ __noinline__ fe29 fe29_inv(fe29 a) {
   t = fe29_mul(fe29_sqr_n(t, 3), x2);
   return fe29_mul(fe29_sqr_n(t, 2), a);
 }
+// a^((p-3)/4), the one exponentiation of sqrt_ratio for p = 3 mod 4 (RFC 9380 F.2.1.2; h2c.hip): the bits of p - 2 without
+// the last two, so fe29_inv's chain less its final step; a of 1 unit, 1 unit out
+__device__ __noinline__ fe29 fe29_pow_p34(fe29 a) {
+  fe29 x22, x2;
+  fe29 x223 = fe29_pow_x223(a, x22, x2);
+  fe29 t = fe29_mul(fe29_sqr_n(x223, 23), x22);
+  t = fe29_mul(fe29_sqr_n(t, 5), a);
+  return fe29_mul(fe29_sqr_n(t, 3), x2);
+}
 // a^((p+1)/4), checked by squaring (Sqrt, internal/field/field_sqrt_ratio.go:14); a of 1 unit
 __device__ __noinline__ bool fe29_sqrt(fe29& out, fe29 a) {
   fe29 x22, x2;

@@ -25,8 +25,10 @@ S2K_DEV pt29 pt29_identity() {   // (0 : 1 : 0), point.go:42
   return r;
 }
 
-// a * k for a small constant k (k < 2^6), up to 7 units in, 1 unit out: 64-bit product per limb
-// with the carry folded along, the top folded with 2^256 = 0x3D1 + 8 * 2^29.
+// a * k for a small constant k, 1 unit out: 64-bit product per limb with the carry folded along,
+// the top folded with 2^256 = 0x3D1 + 8 * 2^29.  In: w units with w * k < 2^12, that is k < 2^6 for
+// up to 7 units (the point formulas: 21, 63) or k < 2^11 for about one unit (h2c.hip: 11, 1771).
+// Then every carry is < 2^12 + 1, nothing nears 64 bits, and the fold adds < 2^23 to limb 0.
 // The products go through mad64s (inline asm) on purpose: written as `c += (uint64_t)a.n[8] * k`,
 // hipcc 7.2 (inlined after fe29_mul_tail, where limb 8 is known to be 24 bits wide) first
 // narrows the product to a 24-bit multiply, drops the `& F29_M8` that produced the limb, and then
