@@ -796,7 +796,10 @@ enum {
   /* aff29.h, the affine formulas of the wide joint tables (one safegcd inversion each; no curve constant, so any curve
    * y^2 = x^3 + b): AFF_DBL (a, b) -> 2 (a, b) | AFF_ADD (a, b) + (c, d), x1 != x2.  Operands in their lazy forms; bits 20..
    * of `lazy` chain the operation on its own result (2^k P; P + k Q), 0 means once; out, out2 = x, y canonical. */
-  S2K_HP_AFF_DBL, S2K_HP_AFF_ADD
+  S2K_HP_AFF_DBL, S2K_HP_AFF_ADD,
+  /* xyzz29_add_affine_first (xyzz29.h: the first addition of k_generator_part, both points affine): P = (a, b), Q = (d, e) in
+   * their lazy forms; out, out2 as XYZZ_ADD; flag = 0 when P and Q share their x (ZZ3 = ZZZ3 = 0) */
+  S2K_HP_XYZZ_ADD_FIRST
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);

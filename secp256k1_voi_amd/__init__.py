@@ -54,7 +54,7 @@ KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 = 0, 1, 2
  HP_FER_MUL, HP_FER_MUL_PLUS, HP_FER_MUL_ADD_MUL, HP_FER_SMALL, HP_PT29R_DBL, HP_PT29R_ADD, HP_FER_SWAPS,
  HP_SC26_MUL, HP_SC26_SQR, HP_SC26_TO_MONT, HP_SC26_TO_SC, HP_SC26_INV, HP_SC26_CHAIN,
  HP_SC_MONTMUL, HP_SC_TO_MONT, HP_SC_MONT_INV, HP_SC_ADD, HP_SC_NEG, HP_SC_REDUCE_ONCE, HP_SC_GT_HALF_N,
- HP_AFF_DBL, HP_AFF_ADD) = range(49)
+ HP_AFF_DBL, HP_AFF_ADD, HP_XYZZ_ADD_FIRST) = range(50)
 H2C_SSWU_RO, H2C_SSWU_NU = 0, 1        # s2k_hash_to_curve_batch: hash_to_curve (random oracle) / encode_to_curve (non-uniform)
 
 IDENTITY = bytes(65)

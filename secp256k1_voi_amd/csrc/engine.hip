@@ -617,10 +617,16 @@ k_generator_part(uint32_t first, uint32_t n, const uint32_t* __restrict__ prep, 
 #pragma unroll
   for (int w = 0; w < 8; ++w) u[w] = prep[(size_t)w * stride + idx];
   apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-  xyzz29 xa = xyzz29_from_affine(fe29_from_words(g.x.v), fe29_from_words(g.y.v));   // XYZZ additions, as in the keyed ladder
+  const fe29 ax = fe29_from_words(g.x.v), ay = fe29_from_words(g.y.v);
+  xyzz29 xa = xyzz29_from_affine(ax, ay);                                            // XYZZ additions, as in the keyed ladder
   g = gt_load(gt, 1, gt_next_digit(u, gt.bits));
+  if (gt.windows > 1) {   // the first addition: both points affine
+    const fe29 gx = fe29_from_words(g.x.v), gy = fe29_from_words(g.y.v);
+    if (gt.windows > 2) g = gt_load(gt, 2, gt_next_digit(u, gt.bits));
+    xa = xyzz29_add_affine_first(ax, ay, gx, gy);
+  }
 #pragma unroll 1
-  for (uint32_t w = 1; w < gt.windows; ++w) {
+  for (uint32_t w = 2; w < gt.windows; ++w) {
     const fe29 gx = fe29_from_words(g.x.v), gy = fe29_from_words(g.y.v);
     if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));   // in flight during this addition
     xa = xyzz29_add_affine(xa, gx, gy);
@@ -2052,8 +2058,10 @@ static inline void prof_mark(s2k_ctx* ctx, hipStream_t st, int slot) {
 // Second stream: the scalar preparation (`launch_prep`), then the generator part u1*G in two pieces.  These
 // have nothing to do with the keys and the grouping / table kernels are short of work for the multipliers
 // on their own (the doubling chain of the tables is one lane per KEY, the scaling pass is memory bound).
-// The first piece of the generator part runs beside the chain, the second once k_key_odd (which does keep
-// the multipliers busy) is through.  Returns with the caller's stream waiting for the second.
+// The first piece of the generator part runs beside the chain, the second beside k_key_finish (its event sits in
+// front of that kernel; between k_key_odd and k_key_cofactors where the three older kernels build the tables).  The
+// share of the first piece (S2K_GP_FIRST_PERCENT, 60) is flat between 30 and 100 and costs 0.3 ms at 0
+// (profiles/r07_key_finish_ab.txt).  Returns with the caller's stream waiting for the second.
 // Stage times (s2k_ctx_profile_read_stages): [0] grouping, [1] tables and whatever is left of the second
 // stream's work.
 // S2K_KEYS_ADAPTIVE (engine_internal.h: kga_*): takes in the notes that have arrived, decides whether this call looks for

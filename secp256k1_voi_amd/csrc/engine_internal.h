@@ -165,7 +165,7 @@ struct s2k_ctx {
   hipStream_t s_aux2 = nullptr;      // two-part flow: the second half of the tables is built here, beside the first half's ladder
   hipStream_t s_msm_tail = nullptr;  // multi-scalar multiplication in two parts (msm.hip): the upper windows' tail, beside the lower windows' bucket pass
   uint32_t kg_parts = 1;             // 1: all tables, then all ladders; 2: the two-part flow (S2K_KEYED_PARTS; measured slower)
-  uint32_t gp_first_percent = 60;    // share of k_generator_part launched beside k_key_chain (the rest: after k_key_odd)
+  uint32_t gp_first_percent = 60;    // share of k_generator_part launched beside k_key_chain (the rest: beside k_key_finish)
   void* kg = nullptr;
   size_t kg_bytes = 0;
   void* ktab = nullptr;
@@ -491,9 +491,10 @@ int s2k_internal_key_group(s2k_ctx* ctx, size_t n, const uint8_t* d_pub, int key
 int s2k_internal_key_reserve(s2k_ctx* ctx, size_t n, int key_bytes);   // grow the grouping arrays / table buffer (before any fork)
 size_t s2k_internal_key_bytes(const s2k_ctx* ctx, size_t n);            // what those hold for a batch of n
 int s2k_internal_key_chains(s2k_ctx* ctx, const uint8_t* d_pub, hipStream_t st, const key_groups* g);
-// (ev_after_odd, if any, is recorded on st between k_key_odd and k_key_cofactors)
+// (ev_mid, if any, is recorded on st where the rest of the generator part may start beside the tables: in front of
+// k_key_finish; with the three kernels of S2K_KEY_TABLES_SPLIT and for a key set between k_key_odd and k_key_cofactors)
 int s2k_internal_key_tables(s2k_ctx* ctx, hipStream_t st, const key_groups* g, uint32_t part, uint32_t nparts,
-                            hipEvent_t ev_after_odd);
+                            hipEvent_t ev_mid);
 
 // grouping of x-only keys for the BIP-340 whole-batch check (msm.hip): every key a group, long groups cut
 // into virtual groups of KG_VGROUP signatures

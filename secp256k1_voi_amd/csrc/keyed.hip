@@ -282,11 +282,15 @@ k_key_place(uint32_t n, const uint32_t* __restrict__ slot_of, const uint32_t* __
 
 // ---- per-key tables ----
 // Entry layout: lane_tables.h (x, y, beta*x in eight quads).  Entries 8c + j (c < 8, j < 8) hold
-// (2j + 1) * 2^(16c) Q, entries 64 and 65 hold L + phi(L) and L - phi(L) for L = 2^116 Q.  Four launches (only the first is a serial chain per key;
-// one lane doing everything took 1.5 ms for 2^16 keys, latency bound at one wave per SIMD):
+// (2j + 1) * 2^(16c) Q, entries 64 and 65 hold L + phi(L) and L - phi(L) for L = 2^116 Q.  Two launches for the tables of a
+// call (one lane doing everything took 1.5 ms for 2^16 keys, latency bound at one wave per SIMD):
 //   k_key_chain  lane per key: key validation, doubling chain from Q; the Jacobian 2^(16c) Q (c = 1..7)
 //                are parked in the entries 8c (X, Y, and Z in the beta*x slot), the two lead points (one co-Z
 //                addition of L and phi(L), common Z) in the entries 64 and 65
+//   k_key_finish lane per (key, chunk), CHUNKS == 8 only: the odd multiples by co-Z additions (below), the cofactors
+//                W / Z_total from the eight lanes of the key, the scaling walk; one lane of the key stores W and finishes
+//                the lead pair.  It is the three kernels below in one: they still build the tables of a key set
+//                (CHUNKS == 32, once per set) and, with S2K_KEY_TABLES_SPLIT set, those of a call:
 //   k_key_odd    lane per (key, chunk): the common-Z table of odd multiples exactly as k_verify_fast
 //                builds its per-signature table, started from the base's JACOBIAN X, Y as if they were
 //                affine: neither the doubling nor the addition formula contains the curve constant b,
@@ -301,7 +305,9 @@ k_key_place(uint32_t n, const uint32_t* __restrict__ slot_of, const uint32_t* __
 //                that (x, y) -> (W^2 x, W^3 y) maps secp256k1 onto; beta*x column (beta commutes with the map).
 //                The ladder's formulas (a = 0, no curve constant) run on that curve unchanged and its result
 //                (X, Y, Z) is the secp256k1 point (X, Y, Z W): one product per signature.
-// Cost per key: 116 doublings, 8 * (1 doubling + 7 additions), 23 products, ~7 products per point.
+// Cost per key: 116 doublings; per chunk 1 doubling + 7 co-Z additions (5 M + 2 S with the running Z; the mixed addition
+// of k_key_odd: 8 M + 3 S), 7 products per lane for the cofactors, 6 per point for the scaling: ~1700 products (three
+// kernels: ~1950).
 template <int CHUNKS>
 S2K_DEV uint4* kt_scratch(uint4* kt, int slot, int& which) {   // field elements in the scratch entries, three per entry
   which = slot % 3;
@@ -634,6 +640,171 @@ k_key_scale_wide(const uint32_t* __restrict__ counters, uint32_t max_tables, uin
   }
 }
 
+// ---- the per-call tables in one pass (k_key_finish) ----
+// k_key_odd, k_key_cofactors and k_key_scale as ONE kernel, lane per (key, chunk): the chunk's table in its intermediate
+// form (x, y over Z_j; H_j) no longer crosses a kernel boundary, and the nine cofactors of a key come from its eight
+// lanes instead of from a launch of one lane per key.
+//
+// The odd multiples by co-Z additions with update (Meloni).  After D = 2 A0 is made affine on the curve isomorphic by
+// D.z, the base (x c2, y c3) and D share Z = 1; with P the running copy of D and Q the current multiple, both over the
+// same Z:  h = X_Q - X_P,  A = h^2,  B = X_P A,  C = X_Q A,
+//   X_R = (Y_Q - Y_P)^2 - B - C,   Y_R = (Y_Q - Y_P)(B - X_R) - Y_P (C - B),   Z_R = Z h,
+// and P <- (B, Y_P (C - B)) is the same point D over Z_R.  4 M + 2 S (and one product for the running Z) against the
+// 8 M + 3 S of the mixed addition.  h = 0 needs Q = +-D, a point of order <= 15: the standing assumption of k_key_odd.
+// Units as in jacobian29.h; invariant of a coz29: all four coordinates [1]; py may also be what jpt29_double leaves
+// (2p - a product limb by limb, which fe29_negate(py, 1) takes: [<= 2], 6 units in the product with C - B).
+struct coz29 {
+  fe29 px, py, qx, qy;
+};
+S2K_DEV fe29 coz29_add_update(coz29& s) {                      // Q <- Q + P, P <- P over the new Z; returns h [1]
+  const fe29 h = fe29_normalize_weak(fe29_add(s.qx, fe29_negate(s.px, 1)));               // [1] + [2] -> [1]   X_Q - X_P
+  const fe29 a = fe29_sqr(h);                                                             // [1]
+  const fe29 b = fe29_mul(s.px, a);                                                       // [1]   B
+  const fe29 c = fe29_mul(s.qx, a);                                                       // [1]   C
+  const fe29 dy = fe29_normalize_weak(fe29_add(s.qy, fe29_negate(s.py, 1)));              // [1] + [2] -> [1]   Y_Q - Y_P
+  const fe29 xr = fe29_sqr_plus(dy, fe29_negate(fe29_add(b, c), 2));                      // [1]^2 + [3] -> [1]
+  const fe29 e = fe29_mul(s.py, fe29_add(c, fe29_negate(b, 1)));                          // [<= 2]*[3] -> [1]   Y_P (C - B)
+  const fe29 yr = fe29_mul_plus(dy, fe29_add(b, fe29_negate(xr, 1)), fe29_negate(e, 1));  // [1]*[3] + [2] -> [1]
+  s.px = b;
+  s.py = e;
+  s.qx = xr;
+  s.qy = yr;
+  return h;
+}
+template <int N>
+S2K_DEV fe29 fe29_group_shr(const fe29& a, bool keep) {     // lane j of a group of eight reads lane j - N; `keep` false: one
+  fe29 r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const uint32_t v = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a.n[i], 0x110 + N, 0xF, 0xF, true);   // row_shr:N
+    r.n[i] = keep ? v : (i == 0 ? 1u : 0u);
+  }
+  return r;
+}
+// x and y of an entry (five quads); the beta*x column is left as it is
+S2K_DEV void ke_store_xy(uint4* __restrict__ e, const fe29& x, const fe29& y) {
+  e[0] = make_uint4(x.n[0], x.n[1], x.n[2], x.n[3]);
+  e[1] = make_uint4(x.n[4], x.n[5], x.n[6], x.n[7]);
+  e[2] = make_uint4(y.n[0], y.n[1], y.n[2], y.n[3]);
+  e[3] = make_uint4(y.n[4], y.n[5], y.n[6], y.n[7]);
+  e[6] = make_uint4(x.n[8], y.n[8], 0u, 0u);
+}
+struct ke_xy_raw {
+  uint4 a, b, c, d, t;
+};
+S2K_DEV ke_xy_raw ke_fetch_xy(const uint4* e) {                // the 80 bytes asked for; the limbs cut when they are wanted
+  ke_xy_raw r;
+  r.a = e[0]; r.b = e[1]; r.c = e[2]; r.d = e[3]; r.t = e[6];
+  return r;
+}
+S2K_DEV void ke_xy_point(const ke_xy_raw& r, fe29& x, fe29& y) {
+  x.n[0] = r.a.x; x.n[1] = r.a.y; x.n[2] = r.a.z; x.n[3] = r.a.w; x.n[4] = r.b.x; x.n[5] = r.b.y; x.n[6] = r.b.z; x.n[7] = r.b.w;
+  y.n[0] = r.c.x; y.n[1] = r.c.y; y.n[2] = r.c.z; y.n[3] = r.c.w; y.n[4] = r.d.x; y.n[5] = r.d.y; y.n[6] = r.d.z; y.n[7] = r.d.w;
+  x.n[8] = r.t.x;
+  y.n[8] = r.t.y;
+}
+// Where the intermediate form waits for the cofactor.  The seven H_j of a lane stay on chip: 63 words per lane in LDS,
+// [word][lane], which no two lanes of a wave share a bank in - 63 KiB per block, two blocks per CU, two waves per SIMD.
+// The eight (x, y) do not fit beside them (16 elements per lane: 144 KiB per block, or 144 registers), so a lane writes them
+// to its own entries - where the final values go - and reads them back itself: in program order, no other lane touches them,
+// and with all addresses known the entries j - 1 and j - 2 are in flight while entry j is scaled.
+template <int CHUNKS>
+__global__ void __launch_bounds__(256, 2)
+k_key_finish(const uint32_t* __restrict__ counters, uint32_t max_tables, uint32_t part, uint32_t nparts, uint4* ktab) {
+  static_assert(CHUNKS == 8, "the cofactors come from the eight lanes of a key");
+  using G = kt_geom<CHUNKS>;
+  __shared__ uint32_t hpark[7 * 9][256];
+  uint32_t id = blockIdx.x * 256 + threadIdx.x, lo, hi;
+  table_range(counters, max_tables, part, nparts, lo, hi);
+  const uint32_t t = lo + id / CHUNKS, c = id % CHUNKS;
+  if (t >= hi) return;                                    // (the eight lanes of a key leave together)
+  uint4* kt = ktab + (size_t)t * (G::SLOTS * 8);
+  uint4* e0 = kt + (size_t)(c * 8) * 8;
+  uint4* el = kt + (size_t)G::LEAD * 8;
+  // the chunk's base point (k_key_chain) and the lead pair's Z
+  const fe29 zl = ke_load(el, TB_BX);                     // (the two lead points share their Z)
+  fe29 zt;
+  coz29 s;
+  {
+    jpt29 a0;
+    fe29 zb;
+    ke_load3(e0, a0.x, a0.y, zb);
+    a0.z = fe29_one();
+    const jpt29 d = jpt29_double(a0);
+    const fe29 c2 = fe29_sqr(d.z);
+    const fe29 c3 = fe29_mul(c2, d.z);
+    s.px = d.x;
+    s.py = d.y;                                           // 2p - a product, limb by limb
+    s.qx = fe29_mul(a0.x, c2);
+    s.qy = fe29_mul(a0.y, c3);
+    zt = fe29_mul(d.z, zb);                               // the running Z_j * D.z * Z_base
+  }
+  ke_store_xy(e0, s.qx, s.qy);
+#pragma unroll 1
+  for (int j = 1; j < 8; ++j) {
+    const fe29 h = coz29_add_update(s);
+    ke_store_xy(e0 + (size_t)j * 8, s.qx, s.qy);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) hpark[(j - 1) * 9 + i][threadIdx.x] = h.n[i];
+    zt = fe29_mul(zt, h);
+  }
+  // the entries come back from an offset the compiler knows nothing about (it is 0: no forwarding of 16 stored elements)
+  uint32_t back = 0;
+  asm volatile("" : "+s"(back));
+  const uint4* er = e0 + back;
+  ke_xy_raw r1 = ke_fetch_xy(er + (size_t)7 * 8), r2 = ke_fetch_xy(er + (size_t)6 * 8);
+  // W / Z_total of this lane's chunk: the product of the other seven chunks' Z_total and the lead pair's Z, from an
+  // exclusive prefix product (lane 0 starts it with the lead pair's Z) and an exclusive suffix product over the key's lanes
+  fe29 pre = fe29_select(c == 0, fe29_group_shr<1>(zt, c > 0), zl);
+  pre = fe29_mul(pre, fe29_group_shr<1>(pre, c > 0));
+  pre = fe29_mul(pre, fe29_group_shr<2>(pre, c > 1));
+  pre = fe29_mul(pre, fe29_group_shr<4>(pre, c > 3));     // Z_lead z_0 ... z_(c-1)
+  fe29 suf = fe29_group_shl<1>(zt, c < 7);
+  suf = fe29_mul(suf, fe29_group_shl<1>(suf, c < 7));
+  suf = fe29_mul(suf, fe29_group_shl<2>(suf, c < 6));
+  suf = fe29_mul(suf, fe29_group_shl<4>(suf, c < 4));     // z_(c+1) ... z_7
+  fe29 rr = fe29_mul(pre, suf);
+  const fe29 co = fe29_mul(suf, zt);                      // lane 0: z_0 ... z_7, the lead pair's cofactor
+  // lane 0 asks for the lead pair now and finishes it after the walk
+  ke_xy_raw l1 = {}, l2 = {};
+  if (c == 0) {
+    l1 = ke_fetch_xy(el);
+    l2 = ke_fetch_xy(el + 8);
+  }
+  // the scaling walk of k_key_scale, from the top entry down: entry j - 1 sits one addition lower (H_j)
+  const fe29 beta = fe29_from_words(FE_BETA);
+  auto walk = [&](int j, ke_xy_raw& r) {                 // entry j from r, which then asks for entry j - 2
+    fe29 cx, cy;
+    ke_xy_point(r, cx, cy);
+    if (j > 1) r = ke_fetch_xy(er + (size_t)(j - 2) * 8);
+    const fe29 q2 = fe29_sqr(rr);
+    const fe29 q3 = fe29_mul(q2, rr);
+    const fe29 x = fe29_mul(cx, q2);
+    const fe29 y = fe29_mul(cy, q3);
+    ke_store3(e0 + (size_t)j * 8, x, y, fe29_mul(x, beta));
+    if (j > 0) {
+      fe29 h;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) h.n[i] = hpark[(j - 1) * 9 + i][threadIdx.x];
+      rr = fe29_mul(rr, h);
+    }
+  };
+#pragma unroll 1
+  for (int j = 7; j > 0; j -= 2) {                        // (two entries per trip: no copy waits for a load)
+    walk(j, r1);
+    walk(j - 1, r2);
+  }
+  if (c == 0) {   // W, and the two lead points
+    scr_store<CHUNKS>(kt, G::W_SLOT, fe29_mul(co, zl));
+    fe29 lx, ly, dx, dy;
+    ke_xy_point(l1, lx, ly);
+    ke_xy_point(l2, dx, dy);
+    const fe29 s2 = fe29_sqr(co), s3 = fe29_mul(s2, co);
+    ke_store3(el, fe29_mul(lx, s2), fe29_mul(ly, s3), fe29_zero());
+    ke_store3(el + 8, fe29_mul(dx, s2), fe29_mul(dy, s3), fe29_zero());
+  }
+}
+
 // Grouping for the BIP-340 whole-batch check: EVERY key forms a group; groups of more than
 // KG_VGROUP signatures are cut into virtual groups of that size (each gets its own term: the lane that
 // sums a group's coefficients walks its members one by one).  vslot[t]: slot of virtual group t,
@@ -814,7 +985,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_chains(s2k_ctx* ctx, 
 
 // odd multiples, inversion, scaling for the tables of part `part` of `nparts`
 __attribute__((visibility("hidden"))) int s2k_internal_key_tables(s2k_ctx* ctx, hipStream_t st, const key_groups* g, uint32_t part,
-                                                                  uint32_t nparts, hipEvent_t ev_after_odd) {
+                                                                  uint32_t nparts, hipEvent_t ev_mid) {
   uint4* ktab = const_cast<uint4*>(g->ktab);
   const size_t max_tables = g->max_tables;
   // The scaling pass: lane per chunk (k_key_scale) unless S2K_KEY_SCALE_WIDE is set.  The lane-per-entry form through LDS
@@ -827,7 +998,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_tables(s2k_ctx* ctx, 
   if (g->chunks == KS_CHUNKS) {
     k_key_odd<KS_CHUNKS><<<blocks_for(max_tables * KS_CHUNKS), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
     HIP_TRY(ctx, hipGetLastError());
-    if (ev_after_odd) HIP_TRY(ctx, hipEventRecord(ev_after_odd, st));
+    if (ev_mid) HIP_TRY(ctx, hipEventRecord(ev_mid, st));
     k_key_cofactors<KS_CHUNKS><<<(unsigned)((max_tables + 63) / 64), 64, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
     HIP_TRY(ctx, hipGetLastError());
     if (scale_old) k_key_scale<KS_CHUNKS><<<blocks_for(max_tables * KS_CHUNKS), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
@@ -835,9 +1006,19 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_tables(s2k_ctx* ctx, 
     HIP_TRY(ctx, hipGetLastError());
     return S2K_OK;
   }
+  // The per-call tables: one kernel (k_key_finish) unless S2K_KEY_TABLES_SPLIT is set, which brings back the three kernels
+  // above exactly as they were launched, for A/B runs and for the tests that compare the two (read at every call, so that a
+  // process can switch).  profiles/r07_key_finish_ab.txt.
+  const char* split = getenv("S2K_KEY_TABLES_SPLIT");
+  if (!(split && *split && *split != '0')) {
+    if (ev_mid) HIP_TRY(ctx, hipEventRecord(ev_mid, st));
+    k_key_finish<KT_CHUNKS><<<blocks_for(max_tables * KT_CHUNKS), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
+    HIP_TRY(ctx, hipGetLastError());
+    return S2K_OK;
+  }
   k_key_odd<KT_CHUNKS><<<blocks_for(max_tables * KT_CHUNKS), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
   HIP_TRY(ctx, hipGetLastError());
-  if (ev_after_odd) HIP_TRY(ctx, hipEventRecord(ev_after_odd, st));
+  if (ev_mid) HIP_TRY(ctx, hipEventRecord(ev_mid, st));
   k_key_cofactors<KT_CHUNKS><<<(unsigned)((max_tables + 63) / 64), 64, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
   HIP_TRY(ctx, hipGetLastError());
   if (scale_old) k_key_scale<KT_CHUNKS><<<blocks_for(max_tables * KT_CHUNKS), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);

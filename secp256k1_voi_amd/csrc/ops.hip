@@ -314,6 +314,18 @@ k_fp29_op(int op, uint32_t lazy, uint32_t n, hp_args args, uint8_t* __restrict__
       }
       break;
     }
+    case S2K_HP_XYZZ_ADD_FIRST: {
+      // P = (a, b) and Q = (d, e), both affine and taken as they are (x [1], y [<= 2]): the first addition of k_generator_part
+      const pt29 q = xyzz29_to_pt29(xyzz29_add_affine_first(a, b, d, e));
+      if (fe29_is_zero(q.z)) {
+        f = 0;
+      } else {
+        fe29 zi = fe29_inv(q.z);
+        r = fe29_mul(q.x, zi);
+        r2 = fe29_mul(q.y, zi);
+      }
+      break;
+    }
     case S2K_HP_XYZZ_ROUND: {
       xyzz29 xa;
       const fe29 c2 = fe29_sqr(c), c3 = fe29_mul(c2, c);
@@ -851,7 +863,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex serves S2K_IMPL_FAST only (8x32: s2k_fp_op_batch)");
   const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN, AFF_*: bits 20.. of `lazy` = how often the operation is chained (0: once)
   lazy &= 0xfffffu;
-  if (op < 0 || op > S2K_HP_AFF_ADD) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (op < 0 || op > S2K_HP_XYZZ_ADD_FIRST) return fail(ctx, S2K_ERR_ARG, "bad op");
   if (op == S2K_HP_FER_SWAPS && n < 8) return fail(ctx, S2K_ERR_ARG, "S2K_HP_FER_SWAPS writes 256 bytes: n >= 8");
   if (n == 0) return S2K_OK;
   if (!in || !in[0] || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
@@ -874,7 +886,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
     k_pt29r_op<<<blocks_for(64 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_AFF_DBL || op == S2K_HP_AFF_ADD)
     k_aff_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
-  else if (op >= S2K_HP_SC26_MUL)
+  else if (op >= S2K_HP_SC26_MUL && op <= S2K_HP_SC_GT_HALF_N)
     k_sc_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_PT29Q_DBL || op == S2K_HP_PT29Q_ADD)
     k_pt29q_op<<<blocks_for(4 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
