@@ -215,6 +215,43 @@ int s2k_ecdsa_recover_batch_device(s2k_ctx *ctx, size_t n, const void *d_digest3
                                    const void *d_recovery_id, uint32_t flags, void *d_pub65, void *d_ok,
                                    void *hip_stream);
 
+/* ---- recoverable ECDSA signatures: the whole batch as one multi-scalar multiplication ---------- */
+/* A recoverable signature (r, s, v) - ParseCompactRecoverableSignature's output (s11n.go:156-168) - names the
+ * point R exactly, so a batch can be checked the way BIP-340 batches are (below): with u1_i = e_i / s_i,
+ * u2_i = r_i / s_i (mod n) and R_i = RecoverPoint(r_i, v_i) (point_s11n.go:245-282),
+ *   sum a_i R_i  -  (sum a_i u1_i) G  -  sum over the K distinct keys Q of (sum of a_i u2_i over Q's items) Q  ==  infinity,
+ * ONE multi-scalar multiplication of n + 2K + 2 terms (a_0 = 1, a_i = 128 bits of SHA-256(key || i), key =
+ * SHA-256(seed32 || 32 bytes of getrandom(2)); the items are grouped by the 64 bytes of their key on the device).
+ * Item i is GOOD iff r_i, s_i in [1, n), (flags & S2K_ECDSA_REJECT_MALLEABLE => s_i <= n/2), v_i <= 3,
+ * x = r_i + (v_i & 2 ? n : 0) < p and on the curve, (X_i, Y_i) canonical and on the curve (NewPublicKey,
+ * secec.go:188-216), and R_i = u1_i G + u2_i Q_i for R_i = the point (x, y) with the parity of y = v_i & 1,
+ * e_i = digest32 reduced mod n: secec.RecoverPublicKey(digest, r, s, v) (ecdsa.go:244-282) succeeds and returns
+ * exactly the supplied key.  A good item is one VerifyRaw accepts; a plain-valid signature with the wrong v is
+ * not good.  Like s2k_ecdsa_recover_batch, s > n/2 is accepted unless the flag is set.
+ *   *all_valid = 1 iff every item is good (false accept probability 2^-128); n == 0: 1.
+ * It does not say which item fails - s2k_ecdsa_verify_recoverable_batch_bisect does.  The reference verifies one
+ * signature at a time (ecdsa.go:234).  flags: S2K_ECDSA_REJECT_MALLEABLE only; n at most 0x0fffffff.  The host-pointer
+ * forms are synchronous and take turns per device like the BIP-340 ones (below). */
+int s2k_ecdsa_batch_verify_rlc(s2k_ctx *ctx, size_t n, const uint8_t *pub_xy /* n*64 */, const uint8_t *digest32 /* n*32 */,
+                               const uint8_t *r /* n*32 */, const uint8_t *s /* n*32 */, const uint8_t *recovery_id /* n */,
+                               uint32_t flags, const uint8_t *seed32, int *all_valid);
+int s2k_ecdsa_batch_verify_rlc_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, const void *d_digest32, const void *d_r,
+                                      const void *d_s, const void *d_recovery_id, uint32_t flags,
+                                      const uint8_t *seed32 /* host */, int *all_valid /* host */, void *hip_stream);
+/* Per-item verdicts at the price of the whole-batch check when everything is good: valid[i] = 1 iff item i is good
+ * (above).  One combination over the batch; when it is rejected the failing items are located by bisection on the kept
+ * terms exactly as s2k_schnorr_verify_batch_bisect does (same driver), and ranges of <= 2^17 items (or everything left,
+ * once more than 8 ranges fail on one level) go through s2k_ecdsa_recover_batch_device and a comparison of the
+ * recovered key with the supplied one.  stats (host, may be NULL): [0] sub-range combinations, [1] items verified
+ * one by one, [2] levels descended, [3] 1 = bisection abandoned. */
+int s2k_ecdsa_verify_recoverable_batch_bisect(s2k_ctx *ctx, size_t n, const uint8_t *pub_xy, const uint8_t *digest32,
+                                              const uint8_t *r, const uint8_t *s, const uint8_t *recovery_id, uint32_t flags,
+                                              const uint8_t *seed32, uint8_t *valid /* n */, uint32_t stats[4]);
+int s2k_ecdsa_verify_recoverable_batch_bisect_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, const void *d_digest32,
+                                                     const void *d_r, const void *d_s, const void *d_recovery_id,
+                                                     uint32_t flags, const uint8_t *seed32 /* host */, void *d_valid,
+                                                     uint32_t stats[4] /* host */, void *hip_stream);
+
 /* ---- key sets: per-key precomputation kept across calls ------------------------------- */
 /* The reference caches per-key state in secec.PublicKey (secec/secec.go:80-85: the decoded point and its encodings,
  * built once by NewPublicKey, :188-216) and every Verify starts from it.  The device analogue: a KEY SET holds, for a

@@ -229,6 +229,10 @@ def load_library() -> C.CDLL:
     lib.s2k_ecdsa_verify_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, vp]
     lib.s2k_ecdsa_recover_batch.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, vp]
     lib.s2k_ecdsa_recover_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, vp, vp]
+    lib.s2k_ecdsa_batch_verify_rlc.argtypes = [vp, sz, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ci)]
+    lib.s2k_ecdsa_batch_verify_rlc_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ci), vp]
+    lib.s2k_ecdsa_verify_recoverable_batch_bisect.argtypes = [vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    lib.s2k_ecdsa_verify_recoverable_batch_bisect_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     lib.s2k_pack_valid_device.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.s2k_keyset_create.argtypes = [vp, sz, vp, C.POINTER(vp)]
     lib.s2k_keyset_create_ex.argtypes = [vp, sz, vp, ci, C.POINTER(vp)]
@@ -388,6 +392,8 @@ EXPORTED_SYMBOLS = [
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_pack_valid_device", "s2k_host_alloc", "s2k_host_free", "s2k_host_register", "s2k_host_unregister", "s2k_ecdsa_recover_batch", "s2k_ecdsa_recover_batch_device",
+    "s2k_ecdsa_batch_verify_rlc", "s2k_ecdsa_batch_verify_rlc_device",
+    "s2k_ecdsa_verify_recoverable_batch_bisect", "s2k_ecdsa_verify_recoverable_batch_bisect_device",
     "s2k_parse_asn1_signature", "s2k_parse_compact_signature", "s2k_is_valid_signature_encoding_bip0066",
     "s2k_ecdsa_verify_encoded_batch",
     "s2k_ecdsa_verify_batch_submit", "s2k_ecdsa_verify_encoded_batch_submit", "s2k_wait", "s2k_poll", "s2k_wait_all",
@@ -998,6 +1004,75 @@ class Engine(_TicketOwner):
             return out, {"sub_combinations": int(stats[0]), "verified_one_by_one": int(stats[1]), "levels": int(stats[2]),
                          "abandoned": bool(stats[3])}
         return out
+
+    # ---- recoverable ECDSA signatures: the whole batch as one multi-scalar multiplication ----
+    @staticmethod
+    def _recoverable_args(pub_xy, digest32, r, s, recovery_id, seed32):
+        """The five input arrays as (n, 64 / 32 / 32 / 32) and (n,) uint8 and the 32 seed bytes; ValueError on a row
+        width other than 64/32/32/32/1, on lengths that disagree and on a seed that is not 32 bytes."""
+        for a, w in ((pub_xy, 64), (digest32, 32), (r, 32), (s, 32)):
+            if isinstance(a, np.ndarray) and a.ndim == 2 and a.shape[1] != w:
+                raise ValueError(f"row width {a.shape[1]}, expected {w}")
+        r = _arr(r, 32)
+        n = r.shape[0]
+        pub_xy, digest32, s = _arr(pub_xy, 64, n), _arr(digest32, 32, n), _arr(s, 32, n)
+        rid = _arr(recovery_id, 1, n).reshape(-1)
+        seed = np.frombuffer(bytes(seed32) if seed32 is not None else os.urandom(32), dtype=np.uint8)
+        if seed.size != 32:
+            raise ValueError("seed32 must be 32 bytes")
+        return n, pub_xy, digest32, r, s, rid, seed
+
+    def ecdsa_batch_verify_rlc(self, pub_xy, digest32, r, s, recovery_id, seed32: bytes | None = None,
+                               reject_malleable: bool = False) -> bool:
+        """True iff for every item RecoverPublicKey(digest, r, s, recovery_id) is exactly the supplied key - one MSM of
+        n + 2K + 2 terms for K distinct keys (s2k_ecdsa_batch_verify_rlc)."""
+        n, pub_xy, digest32, r, s, rid, seed = self._recoverable_args(pub_xy, digest32, r, s, recovery_id, seed32)
+        res = C.c_int(0)
+        self._check(self._lib.s2k_ecdsa_batch_verify_rlc(self._h, n, pub_xy.ctypes.data, digest32.ctypes.data, r.ctypes.data,
+                                                         s.ctypes.data, rid.ctypes.data, REJECT_MALLEABLE if reject_malleable else 0,
+                                                         seed.ctypes.data, C.byref(res)))
+        return bool(res.value)
+
+    def ecdsa_verify_recoverable_batch(self, pub_xy, digest32, r, s, recovery_id, seed32: bytes | None = None,
+                                       reject_malleable: bool = False, return_stats: bool = False):
+        """Per-item verdicts (uint8 0/1) of the same contract at the price of the whole-batch check when everything is
+        good; a rejected batch is bisected (s2k_ecdsa_verify_recoverable_batch_bisect)."""
+        n, pub_xy, digest32, r, s, rid, seed = self._recoverable_args(pub_xy, digest32, r, s, recovery_id, seed32)
+        out = np.zeros(n, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint32)
+        self._check(self._lib.s2k_ecdsa_verify_recoverable_batch_bisect(self._h, n, pub_xy.ctypes.data, digest32.ctypes.data,
+                                                                        r.ctypes.data, s.ctypes.data, rid.ctypes.data,
+                                                                        REJECT_MALLEABLE if reject_malleable else 0,
+                                                                        seed.ctypes.data, out.ctypes.data, stats.ctypes.data))
+        if return_stats:
+            return out, {"sub_combinations": int(stats[0]), "verified_one_by_one": int(stats[1]), "levels": int(stats[2]),
+                         "abandoned": bool(stats[3])}
+        return out
+
+    def ecdsa_batch_verify_rlc_device(self, n, d_pub_xy, d_digest32, d_r, d_s, d_recovery_id, seed32: bytes | None = None,
+                                      flags=0, stream=0) -> bool:
+        """Device-pointer form (integer device addresses; synchronises `stream` for the verdict)."""
+        seed = np.frombuffer(bytes(seed32) if seed32 is not None else os.urandom(32), dtype=np.uint8)
+        if seed.size != 32:
+            raise ValueError("seed32 must be 32 bytes")
+        res = C.c_int(0)
+        self._check(self._lib.s2k_ecdsa_batch_verify_rlc_device(self._h, int(n), d_pub_xy, d_digest32, d_r, d_s, d_recovery_id,
+                                                                int(flags), seed.ctypes.data, C.byref(res), stream))
+        return bool(res.value)
+
+    def ecdsa_verify_recoverable_batch_device(self, n, d_pub_xy, d_digest32, d_r, d_s, d_recovery_id, d_valid,
+                                              seed32: bytes | None = None, flags=0, stream=0, return_stats: bool = False):
+        """Device-pointer form of ecdsa_verify_recoverable_batch: the verdicts go to d_valid (n bytes), enqueued on `stream`."""
+        seed = np.frombuffer(bytes(seed32) if seed32 is not None else os.urandom(32), dtype=np.uint8)
+        if seed.size != 32:
+            raise ValueError("seed32 must be 32 bytes")
+        stats = np.zeros(4, dtype=np.uint32)
+        self._check(self._lib.s2k_ecdsa_verify_recoverable_batch_bisect_device(self._h, int(n), d_pub_xy, d_digest32, d_r, d_s,
+                                                                               d_recovery_id, int(flags), seed.ctypes.data, d_valid,
+                                                                               stats.ctypes.data, stream))
+        if return_stats:
+            return {"sub_combinations": int(stats[0]), "verified_one_by_one": int(stats[1]), "levels": int(stats[2]),
+                    "abandoned": bool(stats[3])}
 
     def ecdsa_recover_batch(self, digest32, r, s, recovery_id, force_complete: bool = False):
         """RecoverPublicKey over a batch: returns (pub65 (n,65) uint8, ok (n,) uint8)."""

@@ -116,7 +116,8 @@ struct s2k_ctx {
   size_t seg_host_bytes = 0;
   void* h2c_dev = nullptr;      // hashing to the curve (h2c.hip): status word and DST_prime on the device, allocated on its first call
   void* h2c_host = nullptr;     // ... and the pinned host block both travel through
-  void* rlc_save = nullptr;     // kept terms of a rejected BIP-340 batch while its failing signatures are located
+  void* rlc_save = nullptr;     // kept terms of a rejected whole-batch check (BIP-340, recoverable ECDSA) while its failing
+                                // signatures are located; the ECDSA leaf verifier's recovered keys
   size_t rlc_save_bytes = 0;
   // host-buffer entry point: device staging for inputs / verdicts, a copy stream and a compute
   // stream, events that chain them (created on first use)
@@ -507,6 +508,9 @@ struct key_groups32 {
   uint32_t ngroups, nleft;                  // (host values)
 };
 int s2k_internal_key_group32(s2k_ctx* ctx, size_t n, const uint8_t* d_pk32, hipStream_t st, key_groups32* out);
+// the same grouping for keys of key_bytes = 32 (x-only) or 64 (X || Y, the recoverable-ECDSA whole-batch check): every one
+// of the key's bytes is compared
+int s2k_internal_key_group_all(s2k_ctx* ctx, size_t n, const uint8_t* d_keys, int key_bytes, hipStream_t st, key_groups32* out);
 int s2k_internal_key_reserve32(s2k_ctx* ctx, size_t n);
 // key sets (s2k_keyset_*): buffer layout, table build, scratch reservation, sort of a batch by key index
 size_t s2k_internal_keyset_bytes(size_t n, size_t off[5]);

@@ -1348,10 +1348,16 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_reserve32(s2k_ctx* ct
   return ctx_reserve(ctx, &ctx->kg, &ctx->kg_bytes, words * sizeof(uint32_t));
 }
 
-// BIP-340 whole-batch check (msm.hip): all n x-only keys grouped, every group gets (virtual) group indices.
+// Whole-batch checks (msm.hip): all n keys grouped - x-only keys of 32 bytes (BIP-340) or X || Y of 64 (recoverable ECDSA) -,
+// every group gets (virtual) group indices.
 // Synchronises the stream to hand the counts to the host (they size the multiscalar multiplication).
 __attribute__((visibility("hidden"))) int s2k_internal_key_group32(s2k_ctx* ctx, size_t n, const uint8_t* d_pk32,
                                                                    hipStream_t st, key_groups32* out) {
+  return s2k_internal_key_group_all(ctx, n, d_pk32, 32, st, out);
+}
+__attribute__((visibility("hidden"))) int s2k_internal_key_group_all(s2k_ctx* ctx, size_t n, const uint8_t* d_keys, int key_bytes,
+                                                                     hipStream_t st, key_groups32* out) {
+  if (key_bytes != 32 && key_bytes != 64) return fail(ctx, S2K_ERR_ARG, "internal: keys of %d bytes", key_bytes);
   uint32_t bits = ctx->kg_hash_bits ? ctx->kg_hash_bits : pow2_at_least(2 * n);
   if (bits < 4) bits = 4;
   if (bits > 30) bits = 30;
@@ -1375,7 +1381,10 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_group32(s2k_ctx* ctx,
   uint32_t* vslot = left + np;
   HIP_TRY(ctx, hipMemsetAsync(counters, 0, (KG_COUNTERS + slots) * sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(rep, 0xff, slots * sizeof(uint32_t), st));
-  k_key_insert<32><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_pk32, (uint32_t)(slots - 1), ctx->kg_seed, rep, cnt, slot_of, pos_of);
+  if (key_bytes == 64)
+    k_key_insert<64><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_keys, (uint32_t)(slots - 1), ctx->kg_seed, rep, cnt, slot_of, pos_of);
+  else
+    k_key_insert<32><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_keys, (uint32_t)(slots - 1), ctx->kg_seed, rep, cnt, slot_of, pos_of);
   HIP_TRY(ctx, hipGetLastError());
   k_key_alloc_all<<<(unsigned)((slots + 256 * ALLOC_ITEMS - 1) / (256 * ALLOC_ITEMS)), 256, 0, st>>>((uint32_t)slots, cnt, base, tix, vslot, counters);
   HIP_TRY(ctx, hipGetLastError());

@@ -169,6 +169,16 @@ S2K_DEV void msm_store_split(uint32_t* __restrict__ scw, uint32_t* __restrict__ 
   msm_store_term(scw, ptw, N, t2, k2, bx, y, neg2);
 }
 
+// (x, y) canonical and y^2 == x^3 + 7 on the 9x29 field (a third of the instructions of the 8x32 form): the point check of
+// a record (xyOnCurve, point_s11n.go:298-307) and NewPublicKey's validation of an X || Y key (secec.go:188-216)
+S2K_DEV bool xy_on_curve_words(const uint32_t xw[8], const uint32_t yw[8]) {
+  if (!fe_is_canonical_raw(xw) || !fe_is_canonical_raw(yw)) return false;
+  const fe29 x = fe29_from_words(xw), y = fe29_from_words(yw);
+  fe29 rhs = fe29_mul(fe29_sqr(x), x);
+  rhs.n[0] += 7;
+  return fe29_eq(fe29_sqr(y), rhs);
+}
+
 // bytes -> terms: scalar reduced mod n and split, affine point words; flag per term
 // (0 identity, 1 finite, 2 malformed).  Input i becomes terms i and n + i.
 __global__ void __launch_bounds__(256)
@@ -188,14 +198,7 @@ k_msm_parse(uint32_t n, const uint8_t* __restrict__ scalars, const uint8_t* __re
   if (rec[0] == 0x04) {
     load_be32_unaligned(a.x.v, rec + 1);
     load_be32_unaligned(a.y.v, rec + 33);
-    bool on = fe_is_canonical_raw(a.x.v) && fe_is_canonical_raw(a.y.v);
-    if (on) {   // y^2 == x^3 + 7 on the 9x29 field (a third of the instructions of the 8x32 form; xyOnCurve, point_s11n.go:298-307)
-      const fe29 x = fe29_from_words(a.x.v), y = fe29_from_words(a.y.v);
-      fe29 rhs = fe29_mul(fe29_sqr(x), x);
-      rhs.n[0] += 7;
-      on = fe29_eq(fe29_sqr(y), rhs);
-    }
-    f = on ? 1 : 2;
+    f = xy_on_curve_words(a.x.v, a.y.v) ? 1 : 2;
   } else if (rec[0] != 0x00) {
     f = 2;
   }
@@ -1312,6 +1315,37 @@ S2K_DEV bool lift_x_words(uint32_t yw[8], const uint32_t xw[8]) {
   fe29_to_words(yw, y);
   return true;
 }
+// the root whose parity is `odd` (0 / 1): the even root, or p minus it (p is odd and y != 0 on this curve)
+S2K_DEV bool lift_x_parity_words(uint32_t yw[8], const uint32_t xw[8], uint32_t odd) {
+  uint32_t even[8], other[8];
+  if (!lift_x_words(even, xw)) return false;
+  u256_sub(other, FE_P, even);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) yw[w] = odd ? other[w] : even[w];
+  return true;
+}
+// a_i = low 128 bits of SHA-256(key || i), a_0 = 1: the coefficients of the whole-batch checks
+S2K_DEV sc rlc_coefficient(const uint32_t key_be[8], size_t i) {
+  sc a = sc_zero();
+  if (i == 0) {
+    a.v[0] = 1;
+    return a;
+  }
+  uint32_t st[8], w[16];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    st[j] = SHA256_IV[j];
+    w[j] = key_be[j];
+  }
+  w[8] = (uint32_t)(i >> 32);
+  w[9] = (uint32_t)i;
+  w[10] = 0x80000000u;
+  w[11] = w[12] = w[13] = w[14] = 0;
+  w[15] = 40 * 8;
+  sha256_compress(st, w);
+  a.v[0] = st[7]; a.v[1] = st[6]; a.v[2] = st[5]; a.v[3] = st[4];
+  return a;
+}
 
 struct rlc_key {   // PRF key of the coefficients, passed by value as a kernel argument
   uint32_t w[8];
@@ -1352,25 +1386,7 @@ k_schnorr_rlc_prep(uint32_t n, size_t N, const uint8_t* __restrict__ pk, const u
 #pragma unroll
   for (int w = 0; w < 8; ++w) e_raw[w] = dg[7 - w];
   sc e = sc_reduce_once(e_raw);
-  // a_i = low 128 bits of SHA-256(seed || i), a_0 = 1
-  sc a = sc_zero();
-  if (i == 0) {
-    a.v[0] = 1;
-  } else {
-    uint32_t st[8], w[16];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      st[j] = SHA256_IV[j];
-      w[j] = seed_be.w[j];
-    }
-    w[8] = (uint32_t)(i >> 32);
-    w[9] = (uint32_t)i;
-    w[10] = 0x80000000u;
-    w[11] = w[12] = w[13] = w[14] = 0;
-    w[15] = 40 * 8;
-    sha256_compress(st, w);
-    a.v[0] = st[7]; a.v[1] = st[6]; a.v[2] = st[5]; a.v[3] = st[4];
-  }
+  const sc a = rlc_coefficient(seed_be.w, i);
   sc a_m = sc_to_mont(a);
   sc ae = sc_montmul(e, a_m), as = sc_montmul(s, a_m);
   // -a_i * R_i and -(a_i e_i) * P_i are entered as a_i * (-R_i) and (a_i e_i) * (-P_i): negating the
@@ -1396,6 +1412,114 @@ k_schnorr_rlc_prep(uint32_t n, size_t N, const uint8_t* __restrict__ pk, const u
   flag[i] = ok ? 1 : 0;
 }
 
+// Recoverable ECDSA signatures as the same kind of sum (header: s2k_ecdsa_batch_verify_rlc):
+//   sum a_i * R_i  -  (sum a_i u1_i) * G  -  sum (a_i u2_i) * Q_i  ==  infinity,   u1 = e / s, u2 = r / s, R_i = RecoverPoint(r_i, v_i),
+// in the layouts of the BIP-340 forms above.  Terms [0, n) = a_i * R_i (a 128-bit coefficient, never negated); the key terms
+// are (a_i u2_i) * (-Q_i), negated on the point as there - per signature at [n, 2n) and [2n, 3n) in the plain form, per
+// distinct key behind n in the aggregated one (ae_out gets a_i u2_i; k_ecdsa_key_check judges the keys, k_rlc_key_terms sums);
+// as_out gets a_i u1_i, whose sum k_schnorr_rlc_sum enters negated with G.  An item that fails one of its own checks
+// (ranges of r and s, low s under the flag, v, x = r + n below p, x on the curve; plain form: its key) leaves the combination.
+// One lane per signature with an inversion of its own (sc_modinv: safegcd): no lane shares a product with another, so an s
+// that has no inverse cannot spoil a neighbour's (the simpler of the two ways; k_scalar_prep's shared inversion would save most of it).
+template <bool AGG>
+__global__ void __launch_bounds__(256)
+k_ecdsa_rlc_prep(uint32_t n, size_t N, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig,
+                 const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, const uint8_t* __restrict__ recid,
+                 uint32_t flags, rlc_key seed_be, uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw,
+                 uint8_t* __restrict__ flag, uint32_t* __restrict__ as_out, uint32_t* __restrict__ ae_out,
+                 uint32_t* __restrict__ status) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  sc r, s;
+  uint32_t e_raw[8];
+  load_be32(r.v, rsig + i * 32);
+  load_be32(s.v, ssig + i * 32);
+  load_be32(e_raw, dig + i * 32);
+  const uint32_t v = recid[i];
+  const bool s_ok = sc_is_canonical_raw(s.v) && !sc_is_zero(s);
+  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && s_ok && v <= 3u;
+  if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);
+  // RecoverPoint (point_s11n.go:245-282): bit 1 of v means x = r + n, which must stay below p; bit 0 is the parity of y
+  uint32_t xw[8], ry[8];
+  {
+    uint32_t rn[8];
+    const uint32_t carry = u256_add(rn, r.v, SC_N);
+    const bool high = (v & 2u) != 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) xw[w] = high ? rn[w] : r.v[w];
+    ok = ok && !(high && carry != 0);
+  }
+  ok = lift_x_parity_words(ry, xw, v & 1u) && ok;          // (refuses x >= p)
+  uint32_t qx[8], qy[8];
+  if constexpr (!AGG) {
+    load_be32(qx, pub + i * 64);
+    load_be32(qy, pub + i * 64 + 32);
+    ok = xy_on_curve_words(qx, qy) && ok;
+  }
+  if (!ok) atomicOr(status, 2u);
+  sc s_inv = s;
+  if (!s_ok) {            // (rejected above; the inversion wants a canonical value)
+    s_inv = sc_zero();
+    s_inv.v[0] = 1;
+  }
+  const sc s_inv_m = sc_to_mont(sc_modinv(s_inv));
+  const sc e = sc_reduce_once(e_raw);
+  const sc a = rlc_coefficient(seed_be.w, i);
+  const sc a_m = sc_to_mont(a);
+  const sc au1 = sc_montmul(sc_montmul(e, s_inv_m), a_m), au2 = sc_montmul(sc_montmul(r, s_inv_m), a_m);
+  if (ok) msm_store_term(scw, ptw, N, i, a, xw, ry, false);                           // a_i < 2^128 already
+  if constexpr (AGG) {
+    uint4* rec = reinterpret_cast<uint4*>(ae_out + (size_t)i * 8);
+    rec[0] = make_uint4(au2.v[0], au2.v[1], au2.v[2], au2.v[3]);
+    rec[1] = make_uint4(au2.v[4], au2.v[5], au2.v[6], au2.v[7]);
+  } else {
+    uint32_t nqy[8];
+    u256_sub(nqy, FE_P, qy);
+    if (ok) msm_store_split(scw, ptw, N, (size_t)n + i, 2 * (size_t)n + i, au2, qx, nqy);
+    flag[(size_t)n + i] = ok ? 1 : 0;
+    flag[2 * (size_t)n + i] = ok ? 1 : 0;
+  }
+#pragma unroll
+  for (int w = 0; w < 8; ++w) as_out[(size_t)w * n + i] = ok ? au1.v[w] : 0u;
+  flag[i] = ok ? 1 : 0;
+}
+// The aggregated form's keys are X || Y: no square root per key, only NewPublicKey's validation, once per group
+// (ky[w][t] = Y, kok[t] = 1 if the key is a point of the curve: what k_rlc_key_lift leaves for x-only keys).
+__global__ void __launch_bounds__(64)
+k_ecdsa_key_check(uint32_t ngroups, uint32_t nleft, size_t kstride, const uint32_t* __restrict__ vslot, const uint32_t* __restrict__ rep,
+                  const uint32_t* __restrict__ left, const uint8_t* __restrict__ pub, uint32_t* __restrict__ ky, uint8_t* __restrict__ kok) {
+  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= ngroups + nleft) return;
+  const uint32_t key_sig = t < ngroups ? rep[vslot[t]] : left[t - ngroups];
+  uint32_t qx[8], qy[8];
+  load_be32(qx, pub + (size_t)key_sig * 64);
+  load_be32(qy, pub + (size_t)key_sig * 64 + 32);
+  const bool key_ok = xy_on_curve_words(qx, qy);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) ky[(size_t)w * kstride + t] = key_ok ? qy[w] : 0u;
+  kok[t] = key_ok ? 1 : 0;
+}
+// The leaf of the ECDSA bisection, behind s2k_ecdsa_recover_batch_device: valid[i] = RecoverPublicKey succeeded and returned
+// exactly the supplied key (k.Equal(q) compares the serialised points, secec.go:121-129; a recovered key is a canonical point
+// of the curve, so a supplied key that NewPublicKey refuses equals none), and s <= n/2 under the flag.
+__global__ void __launch_bounds__(256)
+k_ecdsa_rlc_leaf(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ ssig, uint32_t flags,
+                 const uint8_t* __restrict__ rec65, const uint8_t* __restrict__ ok, uint8_t* __restrict__ valid) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* a = pub + i * 64;
+  const uint8_t* b = rec65 + i * 65;
+  uint32_t diff = b[0] ^ 0x04u;
+  for (int j = 0; j < 64; ++j) diff |= (uint32_t)(a[j] ^ b[1 + j]);
+  bool good = ok[i] == 1 && diff == 0;
+  if (flags & S2K_ECDSA_REJECT_MALLEABLE) {
+    sc s;
+    load_be32(s.v, ssig + i * 32);
+    good = good && !sc_is_gt_half_n(s);
+  }
+  valid[i] = good ? 1 : 0;
+}
+
 // Aggregated key terms, in two kernels.  Lane t < ngroups: virtual group t (the signatures perm[first .. first + count)
 // of one key); lane ngroups + q: the signature left[q] on its own.
 // k_rlc_key_lift lifts the group's key ONCE (a square root: the expensive part; it needs the grouping only, so it runs on
@@ -1415,7 +1539,9 @@ k_rlc_key_lift(uint32_t ngroups, uint32_t nleft, size_t kstride, const uint32_t*
 }
 // k_rlc_key_terms: the group's coefficient is the sum of a_i e_i over its members that are still in the combination
 // (flag).  A key that does not lift takes its signatures out of the combination (flag, a_i s_i) and fails the batch
-// (status).  Terms n + 2t, n + 2t + 1 (N: plane stride of the term arrays).
+// (status).  Terms n + 2t, n + 2t + 1 (N: plane stride of the term arrays).  KEYBYTES: 32 (x-only, BIP-340) or 64 (X || Y, ECDSA);
+// either way the term's point is the key's (x, -y), y from ky.
+template <int KEYBYTES>
 __global__ void __launch_bounds__(64)
 k_rlc_key_terms(uint32_t n, size_t N, uint32_t ngroups, uint32_t nleft, const uint32_t* __restrict__ vslot,
                 const uint32_t* __restrict__ rep, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
@@ -1465,7 +1591,7 @@ k_rlc_key_terms(uint32_t n, size_t N, uint32_t ngroups, uint32_t nleft, const ui
   const size_t t1 = (size_t)n + 2 * (size_t)t, t2 = t1 + 1;
   if (key_ok && any) {
     uint32_t pk_le[8], py[8], npy[8];
-    load_be32(pk_le, pk + (size_t)key_sig * 32);
+    load_be32(pk_le, pk + (size_t)key_sig * KEYBYTES);
 #pragma unroll
     for (int w = 0; w < 8; ++w) py[w] = ky[(size_t)w * kstride + t];
     u256_sub(npy, FE_P, py);
@@ -1477,12 +1603,14 @@ k_rlc_key_terms(uint32_t n, size_t N, uint32_t ngroups, uint32_t nleft, const ui
 
 // sum of n scalars mod n in two launches: RLC_SUM_BLOCKS workgroups leave one partial sum each in
 // `part` (8 words each), then one workgroup folds those and writes the result as terms 3n, 3n + 1
-// with the point G (as == nullptr selects the second stage); N terms in arrays of plane stride tstride
+// with the point G (as == nullptr selects the second stage) - with -G when `negate` (the ECDSA form subtracts the generator's
+// term; the full-width coefficient is negated, it is split anyway); N terms in arrays of plane stride tstride
 constexpr uint32_t RLC_SUM_BLOCKS = 256;
 // (`as` has plane stride `stride`; a sub-range of a saved batch passes as + lo with the batch's stride)
 __global__ void __launch_bounds__(256)
 k_schnorr_rlc_sum(uint32_t n, size_t stride, const uint32_t* __restrict__ as, uint32_t* __restrict__ part,
-                  uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag, size_t N, size_t tstride) {
+                  uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag, size_t N, size_t tstride,
+                  uint32_t negate) {
   __shared__ uint32_t sh[256][8];
   sc acc = sc_zero();
   if (as) {
@@ -1521,6 +1649,7 @@ k_schnorr_rlc_sum(uint32_t n, size_t stride, const uint32_t* __restrict__ as, ui
     sc tot;                                   // the generator's terms are the last two of the N
 #pragma unroll
     for (int w = 0; w < 8; ++w) tot.v[w] = sh[0][w];
+    if (negate) tot = sc_neg(tot);
     msm_store_split(scw, ptw, tstride, N - 2, N - 1, tot, FE_GX, FE_GY);
     flag[N - 2] = 1;
     flag[N - 1] = 1;
@@ -1746,11 +1875,47 @@ enum rlc_mode {
   RLC_AGGREGATED,        // one term pair per distinct key; combination evaluated
   RLC_PLAIN_TERMS_ONLY   // one term pair per signature (the layout the bisection gathers from); terms only
 };
+// The two signature schemes that are checked this way share everything behind their front end: the term arrays and
+// their two layouts, the grouping of the keys, the key terms, the generator's term, the multiscalar core, the bisection.
+enum rlc_scheme { RLC_BIP340, RLC_ECDSA };
+struct rlc_batch {        // the device pointers of one batch
+  rlc_scheme scheme;
+  const uint8_t* key;     // BIP-340: x-only keys, 32 bytes each; ECDSA: X || Y, 64 bytes each
+  // BIP-340
+  const uint8_t* msgs;
+  const uint64_t* msg_offsets;
+  size_t msg_len;
+  const uint8_t* sig;
+  // ECDSA, recoverable signatures
+  const uint8_t *dig, *r, *s, *recid;
+  uint32_t flags;         // S2K_ECDSA_REJECT_MALLEABLE
+};
+static rlc_batch rlc_batch_bip340(const void* d_pk, const void* d_msgs, const void* d_msg_offsets, size_t msg_len, const void* d_sig) {
+  rlc_batch b{};
+  b.scheme = RLC_BIP340;
+  b.key = (const uint8_t*)d_pk;
+  b.msgs = (const uint8_t*)d_msgs;
+  b.msg_offsets = (const uint64_t*)d_msg_offsets;
+  b.msg_len = msg_len;
+  b.sig = (const uint8_t*)d_sig;
+  return b;
+}
+static rlc_batch rlc_batch_ecdsa(const void* d_pub, const void* d_dig, const void* d_r, const void* d_s, const void* d_recid, uint32_t flags) {
+  rlc_batch b{};
+  b.scheme = RLC_ECDSA;
+  b.key = (const uint8_t*)d_pub;
+  b.dig = (const uint8_t*)d_dig;
+  b.r = (const uint8_t*)d_r;
+  b.s = (const uint8_t*)d_s;
+  b.recid = (const uint8_t*)d_recid;
+  b.flags = flags;
+  return b;
+}
 // `seed_be`: the coefficient key; derived here from seed32 and OS randomness when `fresh`, otherwise taken
 // as it is (a second pass over the same batch must use the coefficients of the first).
-static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_pk, const void* d_msgs,
-                        const void* d_msg_offsets, size_t msg_len, const void* d_sig, const uint8_t* seed32, msm_ws& m,
+static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, msm_ws& m,
                         uint32_t** as_out, uint8_t h[192], rlc_mode mode, rlc_key& seed_be, bool fresh) {
+  const bool ecdsa = in.scheme == RLC_ECDSA;
   if (fresh) {
     uint8_t mix[64], key[32];
     memcpy(mix, seed32, 32);
@@ -1764,6 +1929,7 @@ static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_pk
   const size_t cap = 3 * n + 2;
   size_t N = cap;
   // aux: 256 bytes | partial sums of the generator's coefficient | a_i s_i planes | a_i e_i records, lifted keys (aggregated)
+  // (ECDSA: a_i u1_i planes, a_i u2_i records, the keys' Y)
   const size_t as_bytes = n * 8 * 4, kstride = (n + 63) & ~(size_t)63;
   int rc = msm_setup(ctx, cap, 256 + RLC_SUM_BLOCKS * 32 + as_bytes + (mode == RLC_AGGREGATED ? as_bytes + kstride * 36 : 0), m);
   if (rc) return rc;
@@ -1785,37 +1951,50 @@ static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_pk
     HIP_TRY(ctx, hipMemsetAsync(m.flag, 0, cap, st));     // the key terms set their own flags
     HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
-    k_schnorr_rlc_prep<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, (const uint8_t*)d_pk, (const uint8_t*)d_sig,
-                                                            (const uint8_t*)d_msgs, (const uint64_t*)d_msg_offsets,
-                                                            (uint32_t)msg_len, seed_be, m.scw, m.ptw, m.flag, as, ae, m.status);
+    if (ecdsa)
+      k_ecdsa_rlc_prep<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.dig, in.r, in.s, in.recid, in.flags, seed_be,
+                                                            m.scw, m.ptw, m.flag, as, ae, m.status);
+    else
+      k_schnorr_rlc_prep<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.sig, in.msgs, in.msg_offsets,
+                                                              (uint32_t)in.msg_len, seed_be, m.scw, m.ptw, m.flag, as, ae, m.status);
     key_groups32 kg;
-    rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "k_schnorr_rlc_prep launch failed");
-    if (rc == S2K_OK) rc = s2k_internal_key_group32(ctx, n, (const uint8_t*)d_pk, ctx->s_aux, &kg);   // (synchronises the second stream)
+    rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "whole-batch preparation: launch failed");
+    if (rc == S2K_OK) rc = s2k_internal_key_group_all(ctx, n, in.key, ecdsa ? 64 : 32, ctx->s_aux, &kg);   // (synchronises the second stream)
     uint32_t lanes = 0;
     if (rc == S2K_OK) {
       lanes = kg.ngroups + kg.nleft;
       N = n + 2 * (size_t)lanes + 2;
-      k_rlc_key_lift<<<(lanes + 63) / 64, 64, 0, ctx->s_aux>>>(kg.ngroups, kg.nleft, kstride, kg.vslot, kg.rep, kg.left, (const uint8_t*)d_pk, ky, kok);
-      if (hipGetLastError() != hipSuccess) rc = fail(ctx, S2K_ERR_HIP, "k_rlc_key_lift launch failed");
+      if (ecdsa)
+        k_ecdsa_key_check<<<(lanes + 63) / 64, 64, 0, ctx->s_aux>>>(kg.ngroups, kg.nleft, kstride, kg.vslot, kg.rep, kg.left, in.key, ky, kok);
+      else
+        k_rlc_key_lift<<<(lanes + 63) / 64, 64, 0, ctx->s_aux>>>(kg.ngroups, kg.nleft, kstride, kg.vslot, kg.rep, kg.left, in.key, ky, kok);
+      if (hipGetLastError() != hipSuccess) rc = fail(ctx, S2K_ERR_HIP, "whole-batch key check: launch failed");
     }
     ctx_aux_join(ctx, st);            // error or not: nothing stays in flight on the second stream alone
     if (rc) {
       (void)ctx_leave(ctx, st);
       return rc;
     }
-    k_rlc_key_terms<<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)n, cap, kg.ngroups, kg.nleft, kg.vslot, kg.rep, kg.cnt, kg.base, kg.tix,
-                                                      kg.perm, kg.left, (const uint8_t*)d_pk, kstride, ky, kok, ae, as, m.scw, m.ptw, m.flag, m.status);
+    if (ecdsa)
+      k_rlc_key_terms<64><<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)n, cap, kg.ngroups, kg.nleft, kg.vslot, kg.rep, kg.cnt, kg.base, kg.tix,
+                                                            kg.perm, kg.left, in.key, kstride, ky, kok, ae, as, m.scw, m.ptw, m.flag, m.status);
+    else
+      k_rlc_key_terms<32><<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)n, cap, kg.ngroups, kg.nleft, kg.vslot, kg.rep, kg.cnt, kg.base, kg.tix,
+                                                            kg.perm, kg.left, in.key, kstride, ky, kok, ae, as, m.scw, m.ptw, m.flag, m.status);
     HIP_TRY(ctx, hipGetLastError());
   } else {
-    k_schnorr_rlc_prep<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, (const uint8_t*)d_pk, (const uint8_t*)d_sig,
-                                                             (const uint8_t*)d_msgs, (const uint64_t*)d_msg_offsets,
-                                                             (uint32_t)msg_len, seed_be, m.scw, m.ptw, m.flag, as, nullptr, m.status);
+    if (ecdsa)
+      k_ecdsa_rlc_prep<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.dig, in.r, in.s, in.recid, in.flags, seed_be,
+                                                             m.scw, m.ptw, m.flag, as, nullptr, m.status);
+    else
+      k_schnorr_rlc_prep<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.sig, in.msgs, in.msg_offsets,
+                                                               (uint32_t)in.msg_len, seed_be, m.scw, m.ptw, m.flag, as, nullptr, m.status);
     HIP_TRY(ctx, hipGetLastError());
   }
   if (as_out) *as_out = as;
   if (mode == RLC_PLAIN_TERMS_ONLY) return S2K_OK;
-  k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>((uint32_t)n, n, as, sum_part, m.scw, m.ptw, m.flag, N, cap);
-  k_schnorr_rlc_sum<<<1, 256, 0, st>>>((uint32_t)n, n, nullptr, sum_part, m.scw, m.ptw, m.flag, N, cap);
+  k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>((uint32_t)n, n, as, sum_part, m.scw, m.ptw, m.flag, N, cap, 0u);
+  k_schnorr_rlc_sum<<<1, 256, 0, st>>>((uint32_t)n, n, nullptr, sum_part, m.scw, m.ptw, m.flag, N, cap, ecdsa ? 1u : 0u);
   HIP_TRY(ctx, hipGetLastError());
   uint8_t* d_out = (uint8_t*)m.status + 64;   // 65-byte record inside the 256-byte status slot
   rc = msm_core(ctx, st, N, m, d_out, /*affine=*/as_out != nullptr);   // the verdict alone needs no coordinates; the bisection does
@@ -1823,6 +2002,19 @@ static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_pk
   HIP_TRY(ctx, hipMemcpyAsync(h, m.status, 64 + 65, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   ctx->have_last = false;
+  return S2K_OK;
+}
+
+// the whole-batch verdict of a checked, non-empty batch (the context entered)
+static int rlc_verdict(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, int* all_valid) {
+  msm_ws m;
+  uint8_t h[192];
+  rlc_key coeff;
+  int rc = rlc_run_full(ctx, st, n, in, seed32, m, nullptr, h, RLC_AGGREGATED, coeff, true);
+  if (rc) return rc;
+  uint32_t h_status;
+  memcpy(&h_status, h, 4);
+  *all_valid = (h_status == 0 && h[64] == 0x00) ? 1 : 0;
   return S2K_OK;
 }
 
@@ -1842,15 +2034,7 @@ int s2k_schnorr_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pk
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
-  msm_ws m;
-  uint8_t h[192];
-  rlc_key coeff;
-  rc = rlc_run_full(ctx, st, n, d_pk, d_msgs, d_msg_offsets, msg_len, d_sig, seed32, m, nullptr, h, RLC_AGGREGATED, coeff, true);
-  if (rc) return rc;
-  uint32_t h_status;
-  memcpy(&h_status, h, 4);
-  *all_valid = (h_status == 0 && h[64] == 0x00) ? 1 : 0;
-  return S2K_OK;
+  return rlc_verdict(ctx, st, n, rlc_batch_bip340(d_pk, d_msgs, d_msg_offsets, msg_len, d_sig), seed32, all_valid);
 }
 
 // Per-signature verdicts at the price of the whole-batch check when (as usual) everything verifies:
@@ -1858,38 +2042,48 @@ int s2k_schnorr_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pk
 // bisection on the kept terms (header).  stats (host, optional): [0] sub-range multiscalar
 // multiplications, [1] signatures verified one by one, [2] levels descended, [3] 1 = gave up
 // bisecting (many failing ranges) and verified the rest one by one.
-int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d_pk, const void* d_msgs,
-                                           const void* d_msg_offsets, size_t msg_len, const void* d_sig,
-                                           const uint8_t* seed32, void* d_valid, uint32_t* stats, void* hip_stream) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (n == 0) return S2K_OK;
-  if (!d_pk || !d_sig || !d_valid || (!d_msgs && (d_msg_offsets || msg_len))) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  int rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  const uint8_t *pk = (const uint8_t*)d_pk, *sig = (const uint8_t*)d_sig, *msgs = (const uint8_t*)d_msgs;
-  const uint64_t* offs = (const uint64_t*)d_msg_offsets;
-  uint8_t* valid = (uint8_t*)d_valid;
+// The driver behind both schemes' bisect calls (a checked, non-empty batch; the context entered).
+static int rlc_bisect(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, uint8_t* valid, uint32_t* stats) {
+  const bool ecdsa = in.scheme == RLC_ECDSA;
+  int rc;
   // Below LEAF signatures a range is verified signature by signature: a combination costs at least the
   // multiscalar floor (0.75 ms + preparation), per-signature verification 0.56 ms per 2^16 signatures.
   constexpr uint32_t LEAF = 1u << 17;
   constexpr size_t MAX_FAILING = 8;        // more failing ranges than this on one level: stop bisecting
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // The leaf verifier is the ground truth the combination is allowed to skip.  BIP-340: s2k_schnorr_verify_batch.  ECDSA: the
+  // keys recovered by s2k_ecdsa_recover_batch_device into `leaf` (65-byte records, then the ok bytes; it lies behind the kept
+  // terms in rlc_save, sized for the whole batch: once bisecting is abandoned a range can be any size) and k_ecdsa_rlc_leaf.
+  const size_t leaf_bytes = ecdsa ? pad(n * 65) + pad(n) : 0;
+  uint8_t* leaf = nullptr;
   auto verify_each = [&](uint32_t lo, uint32_t cnt) -> int {
     if (stats) stats[1] += cnt;
-    return s2k_schnorr_verify_batch_device(ctx, cnt, pk + (size_t)lo * 32, offs ? msgs : (msgs ? msgs + (size_t)lo * msg_len : nullptr),
-                                           offs ? offs + lo : nullptr, msg_len, sig + (size_t)lo * 64, 0, valid + lo, st);
+    if (!ecdsa)
+      return s2k_schnorr_verify_batch_device(ctx, cnt, in.key + (size_t)lo * 32,
+                                             in.msg_offsets ? in.msgs : (in.msgs ? in.msgs + (size_t)lo * in.msg_len : nullptr),
+                                             in.msg_offsets ? in.msg_offsets + lo : nullptr, in.msg_len, in.sig + (size_t)lo * 64, 0, valid + lo, st);
+    uint8_t *rec = leaf, *okb = leaf + pad(n * 65);
+    int r = s2k_ecdsa_recover_batch_device(ctx, cnt, in.dig + (size_t)lo * 32, in.r + (size_t)lo * 32, in.s + (size_t)lo * 32, in.recid + lo,
+                                           0u, rec, okb, st);
+    if (r) return r;
+    k_ecdsa_rlc_leaf<<<blocks_for(cnt), 256, 0, st>>>(cnt, in.key + (size_t)lo * 64, in.s + (size_t)lo * 32, in.flags, rec, okb, valid + lo);
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx_leave(ctx, st);
   };
-  if (n <= LEAF) return verify_each(0, (uint32_t)n);
+  if (n <= LEAF) {
+    if (ecdsa) {
+      rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, leaf_bytes);
+      if (rc) return rc;
+      leaf = (uint8_t*)ctx->rlc_save;
+    }
+    return verify_each(0, (uint32_t)n);
+  }
 
   msm_ws m;
   uint32_t* as = nullptr;
   uint8_t h[192];
   rlc_key coeff;
-  rc = rlc_run_full(ctx, st, n, d_pk, d_msgs, d_msg_offsets, msg_len, d_sig, seed32, m, &as, h, RLC_AGGREGATED, coeff, true);
+  rc = rlc_run_full(ctx, st, n, in, seed32, m, &as, h, RLC_AGGREGATED, coeff, true);
   if (rc) return rc;
   if (h[64] == 0x00) {   // the combination of every liftable signature vanishes: those are all valid
     k_rlc_mark_valid<<<blocks_for(n), 256, 0, st>>>(0u, (uint32_t)n, m.flag, valid);
@@ -1900,17 +2094,17 @@ int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d
   // coefficients of the pass that has just failed: its error point h + 64 is the plain form's as well.
   {
     uint8_t h2[192];
-    rc = rlc_run_full(ctx, st, n, d_pk, d_msgs, d_msg_offsets, msg_len, d_sig, seed32, m, &as, h2, RLC_PLAIN_TERMS_ONLY, coeff, false);
+    rc = rlc_run_full(ctx, st, n, in, seed32, m, &as, h2, RLC_PLAIN_TERMS_ONLY, coeff, false);
     if (rc) return rc;
   }
   // keep the terms: the sub-range runs re-carve the multiscalar workspace
   const size_t NS = 3 * n;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t o_scw = 0, o_ptw = pad(NS * 4 * 4), o_flag = o_ptw + pad(NS * 16 * 4), o_as = o_flag + pad(n),
-               total = o_as + pad(n * 8 * 4);
+               o_leaf = o_as + pad(n * 8 * 4), total = o_leaf + leaf_bytes;
   rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, total);
   if (rc) return rc;
   uint8_t* sv = (uint8_t*)ctx->rlc_save;
+  leaf = sv + o_leaf;
   uint32_t *s_scw = (uint32_t*)(sv + o_scw), *s_ptw = (uint32_t*)(sv + o_ptw), *s_as = (uint32_t*)(sv + o_as);
   uint8_t* s_flag = sv + o_flag;
   k_rlc_save<<<blocks_for(NS), 256, 0, st>>>((uint32_t)n, m.scw, m.ptw, m.flag, s_scw, s_ptw, s_flag);
@@ -1926,8 +2120,8 @@ int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d
     uint32_t* sum_part = (uint32_t*)w.aux;
     HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, w.zero_bytes, st));
     k_rlc_gather<<<blocks_for(3 * (size_t)cnt), 256, 0, st>>>(lo, cnt, (uint32_t)n, s_scw, s_ptw, s_flag, w.scw, w.ptw, w.flag);
-    k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>(cnt, n, s_as + lo, sum_part, w.scw, w.ptw, w.flag, N, N);
-    k_schnorr_rlc_sum<<<1, 256, 0, st>>>(cnt, n, nullptr, sum_part, w.scw, w.ptw, w.flag, N, N);
+    k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>(cnt, n, s_as + lo, sum_part, w.scw, w.ptw, w.flag, N, N, 0u);
+    k_schnorr_rlc_sum<<<1, 256, 0, st>>>(cnt, n, nullptr, sum_part, w.scw, w.ptw, w.flag, N, N, ecdsa ? 1u : 0u);
     HIP_TRY(ctx, hipGetLastError());
     uint8_t* d_out = (uint8_t*)w.status + 64;
     r = msm_core(ctx, st, N, w, d_out);
@@ -1982,6 +2176,22 @@ int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d
     cur.swap(next);
   }
   return ctx_leave(ctx, st);
+}
+
+int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d_pk, const void* d_msgs,
+                                           const void* d_msg_offsets, size_t msg_len, const void* d_sig,
+                                           const uint8_t* seed32, void* d_valid, uint32_t* stats, void* hip_stream) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n == 0) return S2K_OK;
+  if (!d_pk || !d_sig || !d_valid || (!d_msgs && (d_msg_offsets || msg_len))) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  int rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  return rlc_bisect(ctx, st, n, rlc_batch_bip340(d_pk, d_msgs, d_msg_offsets, msg_len, d_sig), seed32, (uint8_t*)d_valid, stats);
 }
 
 int s2k_schnorr_verify_batch_bisect(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets,
@@ -2040,6 +2250,109 @@ int s2k_schnorr_batch_verify_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pk, cons
   if (rc) return rc;
   HIP_TRY(ctx, phase.landed(st));
   return s2k_schnorr_batch_verify_rlc_device(ctx, n, d[0], d[1], msg_offsets ? d[2] : nullptr, msg_len, d[3], seed32, all_valid, st);
+}
+
+// ---- recoverable ECDSA signatures (header: the contract; above: k_ecdsa_rlc_prep) ----
+// refusals shared by the four entry points: S2K_ERR_ARG before any launch
+static int ecdsa_rlc_check_args(s2k_ctx* ctx, size_t n, const void* pub, const void* dig, const void* r, const void* s, const void* recid,
+                                uint32_t flags) {
+  if (!pub || !dig || !r || !s || !recid) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n > 0x0fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
+  if (flags & ~S2K_ECDSA_REJECT_MALLEABLE) return fail(ctx, S2K_ERR_ARG, "unknown flag bits (S2K_ECDSA_REJECT_MALLEABLE only)");
+  return S2K_OK;
+}
+
+int s2k_ecdsa_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pub, const void* d_dig, const void* d_r, const void* d_s,
+                                      const void* d_recid, uint32_t flags, const uint8_t* seed32, int* all_valid, void* hip_stream) {
+  if (all_valid) *all_valid = 0;
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
+  int rc = ecdsa_rlc_check_args(ctx, n, d_pub, d_dig, d_r, d_s, d_recid, flags);
+  if (rc) return rc;
+  if (n == 0) {
+    *all_valid = 1;   // an empty batch has no failing item
+    return S2K_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  return rlc_verdict(ctx, st, n, rlc_batch_ecdsa(d_pub, d_dig, d_r, d_s, d_recid, flags), seed32, all_valid);
+}
+
+int s2k_ecdsa_verify_recoverable_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d_pub, const void* d_dig, const void* d_r,
+                                                     const void* d_s, const void* d_recid, uint32_t flags, const uint8_t* seed32,
+                                                     void* d_valid, uint32_t* stats, void* hip_stream) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!seed32 || !d_valid) return fail(ctx, S2K_ERR_ARG, "null argument");
+  int rc = ecdsa_rlc_check_args(ctx, n, d_pub, d_dig, d_r, d_s, d_recid, flags);
+  if (rc) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n == 0) return S2K_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  return rlc_bisect(ctx, st, n, rlc_batch_ecdsa(d_pub, d_dig, d_r, d_s, d_recid, flags), seed32, (uint8_t*)d_valid, stats);
+}
+
+// stage (pub, digest, r, s, recovery id [, valid]) of a batch in the context's buffers on its compute stream
+static int stage_ecdsa_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                           const uint8_t* recid, uint8_t* d[6], hipStream_t* st_out) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ctx_streams(ctx);
+  if (rc) return rc;
+  const size_t sizes[6] = {n * 64, n * 32, n * 32, n * 32, n, n};
+  rc = ctx_stage(ctx, sizes, 6, d);
+  if (rc) return rc;
+  hipStream_t st = ctx->s_comp;
+  const uint8_t* src[5] = {pub, dig, r, s, recid};
+  for (int k = 0; k < 5; ++k) HIP_TRY(ctx, hipMemcpyAsync(d[k], src[k], sizes[k], hipMemcpyHostToDevice, st));
+  *st_out = st;
+  return S2K_OK;
+}
+
+int s2k_ecdsa_batch_verify_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                               const uint8_t* recid, uint32_t flags, const uint8_t* seed32, int* all_valid) {
+  if (all_valid) *all_valid = 0;
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
+  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
+  if (rc) return rc;
+  if (n == 0) {
+    *all_valid = 1;
+    return S2K_OK;
+  }
+  uint8_t* d[6];
+  hipStream_t st;
+  s2k_phase_guard phase(ctx->device, n * 161);           // (two verifiers on two threads: engine_internal.h)
+  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
+  if (rc) return rc;
+  HIP_TRY(ctx, phase.landed(st));
+  return s2k_ecdsa_batch_verify_rlc_device(ctx, n, d[0], d[1], d[2], d[3], d[4], flags, seed32, all_valid, st);
+}
+
+int s2k_ecdsa_verify_recoverable_batch_bisect(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
+                                              const uint8_t* s, const uint8_t* recid, uint32_t flags, const uint8_t* seed32,
+                                              uint8_t* valid, uint32_t* stats) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!seed32 || !valid) return fail(ctx, S2K_ERR_ARG, "null argument");
+  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
+  if (rc) return rc;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (n == 0) return S2K_OK;
+  uint8_t* d[6];
+  hipStream_t st;
+  s2k_phase_guard phase(ctx->device, n * 161);           // (two verifiers on two threads: engine_internal.h)
+  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
+  if (rc) return rc;
+  HIP_TRY(ctx, phase.landed(st));
+  rc = s2k_ecdsa_verify_recoverable_batch_bisect_device(ctx, n, d[0], d[1], d[2], d[3], d[4], flags, seed32, d[5], stats, st);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(valid, d[5], n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->have_last = false;
+  return S2K_OK;
 }
 
 }  // extern "C"
