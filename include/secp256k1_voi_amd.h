@@ -656,6 +656,59 @@ int s2k_multi_scalar_mult_segments_device(s2k_ctx *ctx, size_t n, const void *d_
 int s2k_debug_msm_segments_plan(size_t n, size_t n_seg, const uint64_t *seg_offsets, uint32_t piece_terms, uint64_t crossover,
                                 uint64_t summary[8], size_t piece_cap, uint32_t *piece_first, uint32_t *piece_len,
                                 uint32_t *piece_dest, uint32_t *seg_desc);
+
+/* ---- point sets: fixed-base segmented sums from tables kept across calls -------------------
+ * A caller that holds one []*Point across many MultiScalarMultVartime calls (vector commitments under one generator list,
+ * coefficient sums over a fixed key list) pays the per-term table and all the doublings of s2k_multi_scalar_mult_segments
+ * again in every call.  A POINT SET (the sibling of s2k_keyset; the reference's analogue is its precomputed generator table,
+ * point_mul_table.go) holds, for a fixed list of m points, the true-affine multiples mag * 2^(c pos) * P_i for every digit
+ * position pos of a c-bit signed recoding of a 128-bit half scalar and 1 <= mag <= 2^(c-1): a term of a sum is then
+ * 2 * positions table additions and no doubling.  The set is an explicit object, not a cache: built once by the caller,
+ * destroyed by the caller BEFORE its context, owned by the context that made it (it remembers the context's generation and
+ * device; a set used with another context is S2K_ERR_ARG) and, like every object of a context, not locked.
+ *   window_bits  4 or 8; 0 = automatic: 8 when m tables of that width take at most half of the device memory free at the
+ *                time (capped by keyset_free_bytes of s2k_set_table_memory_budgets when that is set), else 4, and
+ *                S2K_ERR_NOMEM when neither fits (an explicit width that does not fit: S2K_ERR_NOMEM as well).  The build
+ *                needs half as much again as scratch, freed before the call returns.  Anything else, m == 0 or a null
+ *                pointer: S2K_ERR_ARG before any launch.
+ *   geometry     (s2k_pointset_geometry, a pure host function) out = {positions, entries per position, table bytes per point}:
+ *                {33, 8, 16896} at 4 bits, {17, 128, 139264} at 8.  The layout is uniform: the last position, which only ever
+ *                holds the recoding's carry digit (0 or 1), has all its entries too.
+ *   records      0x04 || X || Y, canonical and on the curve, or the 65-byte identity record, exactly what the multiscalar
+ *                calls accept.  A malformed record is S2K_ERR_ARG and no set is made.  An identity record is allowed, has no
+ *                table and contributes nothing to any sum.
+ * s2k_debug_pointset_entry copies entry (pos, mag) of point i to the host as X || Y (32 big-endian bytes each); for an
+ * identity record it gives 64 zero bytes. */
+typedef struct s2k_pointset s2k_pointset;
+int s2k_pointset_create(s2k_ctx *ctx, size_t m, const uint8_t *points65 /* m*65, host */, int window_bits, s2k_pointset **out);
+void s2k_pointset_destroy(s2k_pointset *ps);
+size_t s2k_pointset_size(const s2k_pointset *ps);
+int s2k_pointset_window_bits(const s2k_pointset *ps);
+size_t s2k_pointset_device_bytes(const s2k_pointset *ps);
+int s2k_pointset_geometry(int window_bits, uint64_t out[3]);
+int s2k_debug_pointset_entry(const s2k_pointset *ps, size_t i, unsigned pos, unsigned mag, uint8_t out64[64]);
+/* out[j] = sum of k[i] * P[point_index[i]] over i in [seg_offsets[j], seg_offsets[j+1]), P the points of the set: byte for
+ * byte the record s2k_multi_scalar_mult_segments gives on the expanded point array, hence Point.MultiScalarMultVartime on
+ * that slice (point_mul_multi.go:73-117).  ONLY the Vartime form: variable time (data-dependent table addresses and digit
+ * additions), public scalars only; the constant-time Point.MultiScalarMult binds to s2k_ct_multi_scalar_mult, never to
+ * this.  point_index == NULL is the dense shape: the term at position t of its segment uses point t (a segment longer
+ * than the set is S2K_ERR_ARG before any launch).  An index >= m anywhere is S2K_ERR_ARG for the call.  Offsets, empty
+ * segments, n_seg == 0, the term limit and the single synchronisation at the end are those of
+ * s2k_multi_scalar_mult_segments.  Segments of at most S2K_POINTSET_CROSSOVER (16384) terms run in pieces of S2K_POINTSET_T
+ * (8) terms, one lane per piece, complete additions only; longer ones are expanded from the set's records and take the
+ * bucket method of s2k_multi_scalar_mult.  Both environment variables are read at every call: do not change them while
+ * another thread is inside the library.  Workspace: the segmented call's block of the context (72 or 136 bytes per term
+ * at 8- or 4-bit digits, 128 per piece). */
+int s2k_pointset_multi_scalar_mult_segments(s2k_ctx *ctx, const s2k_pointset *ps, size_t n, const uint8_t *k /* n*32 */,
+                                            const uint32_t *point_index /* n, or NULL */, size_t n_seg,
+                                            const uint64_t *seg_offsets /* n_seg+1 */, uint8_t *out /* n_seg*65 */);
+int s2k_pointset_multi_scalar_mult_segments_device(s2k_ctx *ctx, const s2k_pointset *ps, size_t n, const void *d_k,
+                                                   const void *d_point_index /* n uint32, or NULL */, size_t n_seg,
+                                                   const uint64_t *seg_offsets /* host */, void *d_out /* n_seg*65 */,
+                                                   void *hip_stream);
+/* The argument check of the two calls above as a pure function (no device, no context): m the size of the set, `indexed`
+ * non-zero when a point_index array is given.  S2K_OK, or S2K_ERR_ARG as the call would answer before any launch. */
+int s2k_debug_pointset_check_args(size_t m, size_t n, int indexed, size_t n_seg, const uint64_t *seg_offsets);
 /* SEC1 decode of n fixed-size encodings (enc_len = 33: SetCompressedBytes point_s11n.go:140;
  * enc_len = 65: SetUncompressedBytes :178).  ok[i] = 1 and out[i] = point on success,
  * ok[i] = 0 and out[i] = zeros otherwise. */

@@ -321,6 +321,19 @@ def load_library() -> C.CDLL:
     lib.s2k_multi_scalar_mult_segments.argtypes = [vp, sz, vp, vp, sz, vp, vp]
     lib.s2k_multi_scalar_mult_segments_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
     lib.s2k_debug_msm_segments_plan.argtypes = [sz, sz, vp, u32, C.c_uint64, vp, sz, vp, vp, vp, vp]
+    lib.s2k_pointset_create.argtypes = [vp, sz, vp, ci, C.POINTER(vp)]
+    lib.s2k_pointset_destroy.argtypes = [vp]
+    lib.s2k_pointset_destroy.restype = None
+    lib.s2k_pointset_size.argtypes = [vp]
+    lib.s2k_pointset_size.restype = sz
+    lib.s2k_pointset_window_bits.argtypes = [vp]
+    lib.s2k_pointset_device_bytes.argtypes = [vp]
+    lib.s2k_pointset_device_bytes.restype = sz
+    lib.s2k_pointset_geometry.argtypes = [ci, vp]
+    lib.s2k_debug_pointset_entry.argtypes = [vp, sz, C.c_uint, C.c_uint, vp]
+    lib.s2k_debug_pointset_check_args.argtypes = [sz, sz, ci, sz, vp]
+    lib.s2k_pointset_multi_scalar_mult_segments.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
+    lib.s2k_pointset_multi_scalar_mult_segments_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, vp]
     lib.s2k_h2c_dst_prime.argtypes = [C.c_char_p, sz, C.c_char_p, C.POINTER(sz)]
     lib.s2k_expand_message_xmd_batch.argtypes = [vp, sz, C.c_char_p, sz, vp, vp, sz, sz, vp]
     lib.s2k_map_to_curve_batch.argtypes = [vp, sz, sz, sz, vp, vp]
@@ -411,6 +424,9 @@ EXPORTED_SYMBOLS = [
     "s2k_point_add_batch", "s2k_point_double_batch", "s2k_point_decode_batch",
     "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device",
     "s2k_multi_scalar_mult_segments", "s2k_multi_scalar_mult_segments_device", "s2k_debug_msm_segments_plan",
+    "s2k_pointset_create", "s2k_pointset_destroy", "s2k_pointset_size", "s2k_pointset_window_bits", "s2k_pointset_device_bytes",
+    "s2k_pointset_geometry", "s2k_debug_pointset_entry", "s2k_debug_pointset_check_args",
+    "s2k_pointset_multi_scalar_mult_segments", "s2k_pointset_multi_scalar_mult_segments_device",
     "s2k_h2c_dst_prime", "s2k_expand_message_xmd_batch", "s2k_map_to_curve_batch", "s2k_hash_to_curve_batch", "s2k_hash_to_curve_batch_device",
     "s2k_fp_op_batch", "s2k_fn_op_batch", "s2k_fn_split_glv_batch", "s2k_debug_gtable_entry", "s2k_generator_window_bits",
     "s2k_double_scalar_mult_basepoint_batch_ex", "s2k_fp_op_batch_ex", "s2k_fn_split_glv_batch_ex",
@@ -527,6 +543,15 @@ def check_segment_offsets(offsets, n: int) -> np.ndarray:
     if int(off[-1]) != int(n):
         raise ValueError(f"offsets must end at the number of terms ({int(off[-1])} != {int(n)})")
     return off
+
+
+def pointset_geometry(window_bits: int) -> tuple:
+    """(digit positions, entries per position, table bytes per point) of a point set at 4- or 8-bit digits
+    (s2k_pointset_geometry; no device).  ValueError for any other width."""
+    out = np.zeros(3, dtype=np.uint64)
+    if load_library().s2k_pointset_geometry(int(window_bits), out.ctypes.data) != 0:
+        raise ValueError("secp256k1: point-set digit width is 4 or 8")
+    return tuple(int(x) for x in out)
 
 
 def msm_segments_plan(n: int, offsets, piece_terms: int = 0, crossover: int = 0, arrays: bool = True) -> dict:
@@ -1251,6 +1276,11 @@ class Engine(_TicketOwner):
     def multi_scalar_mult_device(self, n, d_scalars, d_points, d_out65, stream=0):
         self._check(self._lib.s2k_multi_scalar_mult_device(self._h, int(n), d_scalars, d_points, d_out65, stream))
 
+    def pointset_create(self, points, window_bits: int = 0) -> "PointSet":
+        """Tables of a fixed list of points (m x 65-byte records), built once (s2k_pointset_create): segmented sums then name
+        their points by index.  window_bits: 4, 8 or 0 (automatic).  Call .close() (or let it be collected) before the engine."""
+        return PointSet(self, points, window_bits)
+
     def multi_scalar_mult_segments(self, scalars, points, offsets) -> np.ndarray:
         """out[j] = sum of scalars[i] * points[i] over offsets[j] <= i < offsets[j + 1] (MultiScalarMultVartime per segment):
         (n_seg, 65) records, an empty segment gives the identity record.  Public scalars only."""
@@ -1588,6 +1618,71 @@ class GroupKeySet:
         if self._k and self._grp._h:
             self._grp._lib.s2k_group_keyset_destroy(self._k)
         self._k = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PointSet:
+    """Handle of s2k_pointset_*: the multiples mag * 2^(c pos) * P of a fixed list of points on the engine's device."""
+
+    def __init__(self, engine: "Engine", points, window_bits: int = 0):
+        points = _arr(points, 65)
+        self._eng = engine
+        k = C.c_void_p()
+        engine._check(engine._lib.s2k_pointset_create(engine._h, points.shape[0], points.ctypes.data, int(window_bits), C.byref(k)))
+        self._k = k
+
+    def __len__(self):
+        return int(self._eng._lib.s2k_pointset_size(self._k))
+
+    def window_bits(self) -> int:
+        return int(self._eng._lib.s2k_pointset_window_bits(self._k))
+
+    def device_bytes(self) -> int:
+        return int(self._eng._lib.s2k_pointset_device_bytes(self._k))
+
+    def entry(self, i: int, pos: int, mag: int) -> bytes:
+        """Table entry (pos, mag) of point i as X || Y (s2k_debug_pointset_entry); 64 zero bytes for an identity record."""
+        out = np.zeros(64, dtype=np.uint8)
+        self._eng._check(self._eng._lib.s2k_debug_pointset_entry(self._k, int(i), int(pos), int(mag), out.ctypes.data))
+        return out.tobytes()
+
+    def multi_scalar_mult_segments(self, scalars, offsets, point_index=None) -> np.ndarray:
+        """out[j] = sum of scalars[i] * P[point_index[i]] over offsets[j] <= i < offsets[j + 1], P the points of the set:
+        (n_seg, 65) records, those of Engine.multi_scalar_mult_segments on the expanded point array.  point_index None: the
+        term at position t of its segment uses point t.  Public scalars only."""
+        scalars = _arr(scalars, 32)
+        n = scalars.shape[0]
+        off = check_segment_offsets(offsets, n)
+        n_seg = off.shape[0] - 1
+        idx = None
+        if point_index is not None:
+            idx = np.ascontiguousarray(np.asarray(point_index, dtype=np.uint32).reshape(-1))
+            if idx.shape[0] != n:
+                raise ValueError("secp256k1: len(scalars) != len(point_index)")
+        out = np.zeros((n_seg, 65), dtype=np.uint8)
+        e = self._eng
+        e._check(e._lib.s2k_pointset_multi_scalar_mult_segments(e._h, self._k, n, scalars.ctypes.data if n else None,
+                                                                idx.ctypes.data if idx is not None else None, n_seg, off.ctypes.data,
+                                                                out.ctypes.data if n_seg else None))
+        return out
+
+    def multi_scalar_mult_segments_device(self, n, d_scalars, d_point_index, offsets, d_out, stream=0):
+        """The same on device buffers (d_point_index: n uint32 or None; d_out: n_seg * 65 bytes); `offsets` stays host memory.
+        Synchronises `stream` once."""
+        off = check_segment_offsets(offsets, int(n))
+        e = self._eng
+        e._check(e._lib.s2k_pointset_multi_scalar_mult_segments_device(e._h, self._k, int(n), d_scalars, d_point_index, off.shape[0] - 1,
+                                                                       off.ctypes.data, d_out, stream))
+
+    def close(self):
+        if self._k:
+            self._eng._lib.s2k_pointset_destroy(self._k)
+            self._k = None
 
     def __del__(self):
         try:

@@ -2591,6 +2591,9 @@ static hipError_t gtable_debug_publish(int device, int bits) {
   return hipSuccess;
 }
 
+// (pointset.hip: a point set's tables count against the same cap as a key set's joint tables)
+__attribute__((visibility("hidden"))) size_t s2k_internal_keyset_budget() { return g_keyset_budget.load(); }
+
 extern "C" {
 // Bytes per device the generator tables of this process may take (0 = no limit but the device's free memory).  Applies to
 // automatic contexts created after the call; the first table (0.8 GiB) is always built.

@@ -231,6 +231,7 @@ inline std::atomic<size_t>& s2k_internal_key_table_limit() {   // s2k_set_table_
   static std::atomic<size_t> v{0};
   return v;
 }
+extern "C" size_t s2k_internal_keyset_budget();     // engine.hip: the keyset_free_bytes of s2k_set_table_memory_budgets (0: none)
 gt_view s2k_internal_gt_load(const s2k_ctx* ctx);   // engine.hip: the generator table a call that starts now uses (one load per call)
 size_t s2k_internal_gt_pending_bytes(int device);   // engine.hip: device memory the background table build is about to allocate
 
