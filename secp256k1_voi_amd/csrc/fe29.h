@@ -3,7 +3,9 @@
 //
 // Same construction as fe26.h (v_mad_u64_u32 column chains, no carry instructions, replacement
 // for the reference's fiat field, internal/fiat/secp256k1montgomery/secp256k1montgomery.go:87,418)
-// with one limb fewer: a product is 81 + 17 multiply-adds instead of 100 + 19 and every linear
+// with one limb fewer: a product is 81 + 17 + 7 multiply-adds (limb products, folds by R0 / R1,
+// carries of the upper columns: those are split on the register boundary, their low register
+// being the digit, see tools/gen_fe29_mul.py) instead of 100 + 19 and every linear
 // operation touches 9 words instead of 10 (about 15 % fewer VALU cycles per multiplication,
 // measured in profiles/).  2^261 = 2^5 (2^32 + 977) = R1 * 2^29 + R0, R0 = 0x7A20, R1 = 0x100.
 //
@@ -160,26 +162,27 @@ S2K_DEV bool fe29_is_zero(const fe29& a) {
 S2K_DEV bool fe29_eq(const fe29& a, const fe29& b) { return fe29_is_zero(fe29_add(a, fe29_negate(b, 1))); }
 
 // Common tail of the products.  On entry t[0..7] are 29-bit digits, t[8] the digit of column 8,
-// c the carry into column 8, d the carry out of column 16 (weight 2^(29*17) = 2^232 * 2^261).
+// c the carry into column 8, h the carry out of column 16 as the generated code leaves it: the
+// high register of that column's sum, weight 2^(29*16+32) = 8 * 2^232 * 2^261.
 // Everything at or above bit 256 goes back in with 2^256 = 0x3D1 + 8 * 2^29, using 32x32
-// products only (the fold count is c_lo + d * R1 * 2^5 = c_lo + d * 2^13).
-S2K_DEV fe29 fe29_mul_tail(uint32_t t[9], uint64_t c, uint64_t d) {
-  const uint32_t d32 = (uint32_t)d;
+// products only (the fold count is c_lo + 8 h * R1 * 2^5 = c_lo + h * 2^16; the factor 8 is in
+// the constants, so h needs no instruction of its own).
+S2K_DEV fe29 fe29_mul_tail(uint32_t t[9], uint64_t c, uint32_t h) {
   c += t[8];
-  mad64s(c, d32, F29_R0);
+  mad64s(c, h, F29_R0 << 3);
   fe29 r;
   r.n[8] = (uint32_t)c & F29_M8;
   c >>= 24;
   const uint32_t clo = (uint32_t)c;
-  const uint32_t k0 = F29_R0 >> 5, k0s = (F29_R0 >> 5) << 13, k1 = F29_R1 >> 5, k1s = (F29_R1 >> 5) << 13;
+  const uint32_t k0 = F29_R0 >> 5, k0s = (F29_R0 >> 5) << 16, k1 = F29_R1 >> 5, k1s = (F29_R1 >> 5) << 16;
   uint64_t e = t[0];
   asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0"
-      : "+&v"(e) : "v"(clo), "s"(k0), "v"(d32), "s"(k0s) : "vcc");
+      : "+&v"(e) : "v"(clo), "s"(k0), "v"(h), "s"(k0s) : "vcc");
   r.n[0] = (uint32_t)e & F29_M;
   e >>= 29;
   e += t[1];
   asm("v_mad_u64_u32 %0, vcc, %1, %2, %0\n\tv_mad_u64_u32 %0, vcc, %3, %4, %0"
-      : "+&v"(e) : "v"(clo), "s"(k1), "v"(d32), "s"(k1s) : "vcc");
+      : "+&v"(e) : "v"(clo), "s"(k1), "v"(h), "s"(k1s) : "vcc");
   r.n[1] = (uint32_t)e & F29_M;
   e >>= 29;
   r.n[2] = t[2] + (uint32_t)e;

@@ -715,7 +715,8 @@ k_msm_stitch(msm_parts P, uint32_t nkeys, size_t stride, const uint32_t* __restr
   pt_store(sums, stride, key, r);
 }
 // one workgroup per queued bucket: the threads take the pieces round robin, then a tree in LDS
-__global__ void __launch_bounds__(256)
+// (3 waves per SIMD asked for: the allocator ends at 167 - 172 registers by itself, on either side of the 168 that three waves leave)
+__global__ void __launch_bounds__(256, 3)
 k_msm_stitch_big(msm_parts P, uint32_t nkeys, size_t stride, const uint32_t* __restrict__ offset,
                  const uint32_t* __restrict__ xsum, const uint32_t* __restrict__ list, const uint32_t* __restrict__ ptw,
                  uint32_t* __restrict__ sums, const uint32_t* __restrict__ big) {

@@ -9,6 +9,14 @@ k = 0..L-2 the high column L+k is reduced into the low column k with
 100, 8 reduction steps instead of 9; the price is headroom: a column holds at most 8 products
 of full-size limbs, so (limb bound of a) * (limb bound of b) must stay below 2^61 (fe29.h).
 
+The upper columns 9..16 are split on the register boundary, not at bit 29: their digits are never
+output limbs, only multiplied by R0 and R1 into lower columns, so a 64-bit column sum d of weight
+2^(29k) is taken as lo32(d) * 2^(29k) + (hi32(d) * 8) * 2^(29(k+1)).  The digit costs no
+instruction and the carry is one multiply-add by 8 that starts the next column's chain, in place
+of a mask and a 64-bit shift.  u * R0 < 2^47 and u * R1 < 2^40 leave the lower columns' headroom
+as it was.  Columns 0..8 keep their 29-bit masks: they are the result's limbs.  The carry out of
+column 16 goes to fe29_mul_tail as the high register (weight 2^(29*16+32)).
+
     python tools/gen_fe29_mul.py > secp256k1_voi_amd/csrc/fe29_mul_gen.h
 """
 from gen_chain import chain
@@ -50,6 +58,27 @@ def conversions():
         o.append(f"  w[{j}] = {' | '.join(parts)};\n")
     o.append("}\n")
     return "".join(o)
+
+
+def upper_chain(prods, maxn=12):
+    """One statement for an upper column after the first.  On entry d still holds the previous column's sum, whose low
+    register is the digit u and whose high register is the carry h.  The digit's R1 fold goes into the lower
+    accumulator c (by now at the next lower column), then d starts anew IN PLACE as h * 8 (an inline constant) and takes
+    the column's products.  d is a plain in/out operand, not an early-clobber one: u and h are parts of its incoming
+    value, so they may stay in its registers - u is read by the first instruction, h by the one that first writes d -
+    and no other input can share them, d being live into the statement.  The column needs no register beyond d's.
+    Products beyond `maxn` (30 operands per statement) follow in an ordinary chain."""
+    first, rest = prods[:maxn], prods[maxn:]
+    lines = ['"v_mad_u64_u32 %1, vcc, %2, %3, %1', '"v_mad_u64_u32 %0, vcc, %4, 8, 0']
+    ops = ['"v"(u)', '"s"(R1)', '"v"(h)']
+    n = 5
+    for x, y, kind in first:
+        lines.append(f'"v_mad_u64_u32 %0, vcc, %{n}, %{n + 1}, %0')
+        ops += [f'"v"({x})', f'"{kind}"({y})']
+        n += 2
+    body = "\\n\\t\"\n      ".join(lines) + '"'
+    out = f'  asm({body}\n      : "+v"(d), "+&v"(c)\n      : {", ".join(ops)}\n      : "vcc");\n'
+    return out + chain("d", rest)
 
 
 def gen(name, kind, addend=False):
@@ -110,25 +139,28 @@ def gen(name, kind, addend=False):
     o.append("  uint64_t d, c;\n")
     o.append(chain("d", fix(col(L - 1)), init=True))
     o.append(f"  t[{L - 1}] = (uint32_t)d & F29_M;\n  d >>= {W};\n")
-    o.append("  uint32_t u, uprev = 0;\n")
+    o.append("  uint32_t u, h;\n")
     for k in range(L - 1):
-        o.append(chain("d", fix(col(L + k))))
-        o.append(f"  u = (uint32_t)d & F29_M;\n  d >>= {W};\n")
-        lo = []
-        if k > 0:
-            lo.append(("uprev", "R1", "s"))
-        lo += fix(col(k))
+        # upper column L+k: the digit is the accumulator's low register as it stands (32 bits, not W), and the
+        # next upper column starts from the high register times 2^(32-W) = 8
+        if k == 0:
+            o.append(chain("d", fix(col(L + k))))
+        else:
+            o.append(upper_chain(fix(col(L + k))))
+        o.append("  u = (uint32_t)d;\n  h = (uint32_t)(d >> 32);\n")
+        lo = fix(col(k))
         lo.append(("u", "R0", "s"))
         o.append(chain("c", lo, init=(k == 0)))
-        o.append(f"  t[{k}] = (uint32_t)c & F29_M;\n  c >>= {W};\n  uprev = u;\n")
-    o.append(chain("c", [("uprev", "R1", "s")]))
-    o.append("  return fe29_mul_tail(t, c, d);\n}\n")
+        o.append(f"  t[{k}] = (uint32_t)c & F29_M;\n  c >>= {W};\n")
+    o.append(chain("c", [("u", "R1", "s")]))
+    o.append("  return fe29_mul_tail(t, c, h);\n}\n")
     return "".join(o)
 
 
 def main():
     print("// fe29_mul_gen.h — GENERATED by tools/gen_fe29_mul.py; do not edit by hand.")
     print("// Included by fe29.h inside namespace s2k (needs fe29, F29_*, fe29_mul_tail).")
+    print("// Upper columns 9..16: 32-bit digits (the low register of the column sum), carry = high register * 8.")
     print("// clang-format off")
     print(conversions())
     print(gen("fe29_mul", "mul"))
