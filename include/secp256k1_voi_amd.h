@@ -182,7 +182,7 @@ int s2k_ecdsa_verify_batch_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, 
  *               the context and survives mode changes; verdicts do not depend on it (s2k_ctx_key_grouping_adaptive)
  *   min_group   0 = default (4): measured break-even between 3 and 4 signatures per key
  *   hash_bits   0 = default (slots >= 2n); smaller values force probe chains (tests)
- *   max_tables  0 = default (2^22 tables of 9 KiB; the buffer is sized by the batch: n / min_group tables).  The threshold is raised until n / threshold tables
+ *   max_tables  0 = default (2^22 tables of 10 KiB; the buffer is sized by the batch: n / min_group tables).  The threshold is raised until n / threshold tables
  *               fit: a batch of n signatures builds tables for keys with at least
  *               max(min_group, ceil(n / max_tables)) signatures.  A device that has no memory for the buffer does not
  *               fail the verification: the cap is halved until the buffer fits, and below 1024 tables the batch is
@@ -192,6 +192,18 @@ int s2k_ecdsa_verify_batch_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, 
 #define S2K_KEYS_ALWAYS 2
 #define S2K_KEYS_ADAPTIVE 3
 int s2k_ctx_set_key_grouping(s2k_ctx *ctx, int mode, uint32_t min_group, uint32_t hash_bits, uint32_t max_tables);
+/* The tables an ECDSA verification call builds for its repeated keys, and the ladder over them.  Same verdicts either way.
+ *   S2K_LADDER_COMB (default): a signed 7-tooth comb - 64 entries per key select 7 bits of a half scalar per addition:
+ *               38 table additions and 18 doublings per signature (10 KiB per key)
+ *   S2K_LADDER_WINDOW: odd multiples of eight 16-bit chunks, 4 bits per addition: 64 additions and 12 doublings - what
+ *               BIP-340 calls and key sets use.  Also chosen for a context created with S2K_KEYED_LADDER=window in the
+ *               environment, and for any call made while S2K_KEY_TABLES_SPLIT is set. */
+#define S2K_LADDER_COMB 0
+#define S2K_LADDER_WINDOW 1
+int s2k_ctx_set_keyed_ladder(s2k_ctx *ctx, int ladder);
+/* What the last s2k_ecdsa_verify_batch[_device] call of the context enqueued for its repeated keys: S2K_LADDER_COMB,
+ * S2K_LADDER_WINDOW, or -1 when it built no tables (grouping off, a small batch, no memory).  No synchronisation. */
+int s2k_ctx_last_keyed_ladder(s2k_ctx *ctx);
 /* After the last s2k_ecdsa_verify_batch_device call has finished (synchronises the device):
  * stats[0] signatures verified from per-key tables, [1] tables built, [2] signatures through the
  * general kernel, [3] signatures re-done by the complete-formula kernel.  All zero after a call that took the ladders of

@@ -47,6 +47,7 @@ OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_NEG, OP_INV, OP_SQRT = range(7)
 IMPL_COMPLETE, IMPL_FAST = 0, 1
 CTX_WAIT_TABLES = 1
 KEYS_OFF, KEYS_AUTO, KEYS_ALWAYS, KEYS_ADAPTIVE = 0, 1, 2, 3     # s2k_ctx_set_key_grouping (a new context: KEYS_ADAPTIVE)
+LADDER_COMB, LADDER_WINDOW = 0, 1                                # s2k_ctx_set_keyed_ladder (a new context: LADDER_COMB)
 KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 = 0, 1, 2, 3, 4   # s2k_keyset_create_ex
 (HP_MUL, HP_SQR, HP_MUL_PLUS, HP_SQR_PLUS, HP_MUL_ADD_MUL, HP_MUL_ADD_SQR, HP_ADD, HP_NEGATE, HP_HALF, HP_NORMALIZE,
  HP_COND_NEGATE1, HP_INV, HP_SQRT, HP_EQ, HP_MUL_SMALL21, HP_NORMALIZE_WEAK, HP_JDBL, HP_JADD, HP_PT29_DBL, HP_PT29_ADD,
@@ -223,6 +224,8 @@ def load_library() -> C.CDLL:
     lib.s2k_ctx_profile_msm.argtypes = [vp, ci]
     lib.s2k_ctx_profile_read_msm.argtypes = [vp, vp, vp]
     lib.s2k_ctx_set_key_grouping.argtypes = [vp, ci, u32, u32, u32]
+    lib.s2k_ctx_set_keyed_ladder.argtypes = [vp, ci]
+    lib.s2k_ctx_last_keyed_ladder.argtypes = [vp]
     lib.s2k_ctx_key_grouping_stats.argtypes = [vp, vp]
     lib.s2k_ctx_key_grouping_adaptive.argtypes = [vp, vp, ci]
     lib.s2k_ecdsa_verify_batch.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp]
@@ -400,7 +403,7 @@ def load_library() -> C.CDLL:
 EXPORTED_SYMBOLS = [
     "s2k_ctx_create", "s2k_ctx_destroy", "s2k_last_error", "s2k_version", "s2k_build_config",
     "s2k_ctx_profile", "s2k_ctx_profile_read", "s2k_ctx_profile_read_stages", "s2k_ctx_profile_msm", "s2k_ctx_profile_read_msm",
-    "s2k_ctx_set_key_grouping", "s2k_ctx_key_grouping_stats", "s2k_ctx_key_grouping_adaptive",
+    "s2k_ctx_set_key_grouping", "s2k_ctx_set_keyed_ladder", "s2k_ctx_last_keyed_ladder", "s2k_ctx_key_grouping_stats", "s2k_ctx_key_grouping_adaptive",
     "s2k_ecdsa_verify_batch", "s2k_ecdsa_verify_batch_device", "s2k_ecdsa_workspace_bytes", "s2k_ctx_device_bytes",
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
@@ -1168,6 +1171,15 @@ class Engine(_TicketOwner):
         new engine starts with) = KEYS_AUTO that stops looking for repeated keys after two large batches without any and looks
         again every sixteenth batch (key_grouping_adaptive)."""
         self._check(self._lib.s2k_ctx_set_key_grouping(self._h, int(mode), int(min_group), int(hash_bits), int(max_tables)))
+
+    def set_keyed_ladder(self, ladder: int = LADDER_COMB):
+        """Tables and ladder of the repeated keys of an ECDSA call (s2k_ctx_set_keyed_ladder): LADDER_COMB (what a new engine
+        starts with: 38 additions and 18 doublings per signature) or LADDER_WINDOW (16-bit chunks: 64 and 12)."""
+        self._check(self._lib.s2k_ctx_set_keyed_ladder(self._h, int(ladder)))
+
+    def last_keyed_ladder(self) -> int:
+        """LADDER_COMB / LADDER_WINDOW: the tables the last ECDSA verification call built; -1: it built none."""
+        return int(self._lib.s2k_ctx_last_keyed_ladder(self._h))
 
     def key_grouping_stats(self):
         """Of the last ecdsa_verify_batch_device call -> dict(keyed, tables, general, complete)."""

@@ -539,11 +539,17 @@ S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const ui
 #ifndef S2K_JOINT_WAVES
 #define S2K_JOINT_WAVES 3
 #endif
+#ifndef S2K_COMB_WAVES
+#define S2K_COMB_WAVES 3
+#endif
 enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_ECDSA_KEYED = 4, MODE_ECDSA_LEFT = 5,
        MODE_SCHNORR_KEYED = 6, MODE_SCHNORR_LEFT = 7, MODE_ECDSA_KEYSET = 8, MODE_ECDSA_KEYSET_JOINT = 9,
        MODE_ECDSA_KEYSET_JOINT5 = 10, MODE_ECDSA_KEYSET_JOINT6 = 11,
        // BIP-340 over a key set's tables, same four layouts: the ECDSA mode + 4
-       MODE_SCHNORR_KEYSET = 12, MODE_SCHNORR_KEYSET_JOINT = 13, MODE_SCHNORR_KEYSET_JOINT5 = 14, MODE_SCHNORR_KEYSET_JOINT6 = 15 };
+       MODE_SCHNORR_KEYSET = 12, MODE_SCHNORR_KEYSET_JOINT = 13, MODE_SCHNORR_KEYSET_JOINT5 = 14, MODE_SCHNORR_KEYSET_JOINT6 = 15,
+       // MODE_ECDSA_KEYED over the key's COMB table (kc_geom): 38 additions and 18 doublings.  New modes go at the end:
+       // tools/isa_count.py finds the kernels by this number
+       MODE_ECDSA_COMB = 16 };
 constexpr uint8_t VERDICT_PENDING = 2;   // k_verify_fast -> k_affine_finish
 constexpr uint32_t KVF_FORCE_WORKLIST = 0x80000000u;   // top bit of k_verify_fast's first argument (batches are below 2^31)
 
@@ -592,6 +598,8 @@ S2K_DEV uint32_t ds4_next(digit_stream4& d) {
 //               planes and the verdict are the signature's, workspace columns are the lane's.
 //               KEYED lanes take their points from the key's precomputed affine table (table ptab[idx],
 //               no per-lane table, 12 doublings); LEFT lanes are the general path for the rest.
+// MODE_ECDSA_COMB: MODE_ECDSA_KEYED over the comb tables an ECDSA call builds by default (keyed.hip: k_key_chain on the comb's
+//               geometry, k_key_finish_comb): the same 64 entries per key serve 7 bits of a half scalar per addition.
 // MODE_SCHNORR_KEYED / MODE_SCHNORR_LEFT: the same for BIP-340 (tables of the lifted x-only keys); results go
 //               to k_affine_finish in the SIGNATURE's fin column.
 // Waves per SIMD the register allocator must leave room for.  Measured (2^20 signatures):
@@ -650,7 +658,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S2K_FA
 // resource usage is printed by tools/kernel_regs.sh.)
 __global__ void __launch_bounds__(256, (MODE == MODE_ECDSA_KEYSET_JOINT || MODE == MODE_ECDSA_KEYSET_JOINT5 || MODE == MODE_ECDSA_KEYSET_JOINT6 ||
                                         MODE == MODE_SCHNORR_KEYSET_JOINT || MODE == MODE_SCHNORR_KEYSET_JOINT5 || MODE == MODE_SCHNORR_KEYSET_JOINT6)
-                                           ? S2K_JOINT_WAVES : S2K_FAST_WAVES)
+                                           ? S2K_JOINT_WAVES : MODE == MODE_ECDSA_COMB ? S2K_COMB_WAVES : S2K_FAST_WAVES)
 #endif
 k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig,
               const uint32_t* __restrict__ prep, uint32_t* __restrict__ qt, uint32_t* __restrict__ fin,
@@ -663,9 +671,10 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
   constexpr int JW = KM == MODE_ECDSA_KEYSET_JOINT5 ? 5 : KM == MODE_ECDSA_KEYSET_JOINT6 ? 6 : 4;
   constexpr bool JOINTW = JW > 4;                            // ... over joint tables of 5- or 6-bit digits (kjw_geom: 26 / 22 positions)
   constexpr bool KEYSET = KM == MODE_ECDSA_KEYSET || JOINT || JOINTW;   // KEYED over a key set's 32-chunk tables: no doublings at all
-  constexpr bool KEYED = MODE == MODE_ECDSA_KEYED || MODE == MODE_SCHNORR_KEYED || KEYSET;
+  constexpr bool COMB = MODE == MODE_ECDSA_COMB;             // KEYED over the comb table of the key
+  constexpr bool KEYED = MODE == MODE_ECDSA_KEYED || MODE == MODE_SCHNORR_KEYED || KEYSET || COMB;
   constexpr bool GROUPED = KEYED || MODE == MODE_ECDSA_LEFT || MODE == MODE_SCHNORR_LEFT;
-  constexpr bool ECDSA = MODE == MODE_ECDSA || MODE == MODE_ECDSA_KEYED || MODE == MODE_ECDSA_LEFT || (KEYSET && !SKS);
+  constexpr bool ECDSA = MODE == MODE_ECDSA || MODE == MODE_ECDSA_KEYED || MODE == MODE_ECDSA_LEFT || (KEYSET && !SKS) || COMB;
   const bool force_wl = (n_and_flags & KVF_FORCE_WORKLIST) != 0;
   const uint32_t n = n_and_flags & ~KVF_FORCE_WORKLIST;
   size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;         // lane: workspace column
@@ -822,7 +831,72 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
   k1.v[4] = (pf & PF_K1_B128) ? 1u : 0u;   // odd by construction (sc_split_glv_odd): the signed
   k2.v[4] = (pf & PF_K2_B128) ? 1u : 0u;   // odd-digit recoding is exact, no final correction
   jpt29 acc;
-  if constexpr (KEYED) {
+  if constexpr (COMB) {
+    // The comb ladder (kc_geom, engine_internal.h).  k = 2^133 + sum_{i<133} b_i 2^i, b_i = 2 a_i - 1, a = k >> 1 (k odd,
+    // < 2^129: a has 128 bits).  Column j (18 down to 0) of a half is the bits a_(19 t + j) of the seven teeth t: the top
+    // tooth gives the sign, the lower six (complemented under a negative top tooth) the entry
+    // E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t.  A round is one doubling (none in front of the first round) and the two
+    // halves' additions: 38 additions and 18 doublings.  The lead 2^133 Q = 2^18 * 2^115 Q goes in first, for both halves at
+    // once (L +- phi(L), as in the window ladder).
+    // All in Jacobian coordinates: 38 * 11 + 18 * 7 = 544 products.  XYZZ additions (10 in 9 reductions) would want an XYZZ
+    // doubling (6 M + 3 S = 9: 542 products) or the change of form around every single doubling (4 products a round: 578),
+    // and a fourth coordinate in registers; jacobian29.h's pair is the one the general ladder runs and the models bound.
+    // Z = 0 is sticky through both (Z3 = Z1 H, Z3 = Y Z) and ends on the worklist exactly as before.
+    using G = kc_geom;
+    const uint4* kt = kg.ktab + (size_t)kg.ptab[idx] * (G::SLOTS * 8);
+    {
+      fe29 lx, ly;
+      ke_load_xy(kt + (size_t)(neg1 == neg2 ? G::LEAD : G::LEAD + 1) * 8, false, lx, ly);
+      acc.x = lx;
+      acc.y = fe29_cond_negate1(ly, neg1);
+      acc.z = fe29_one();
+    }
+    // tooth t of a half: bits 19 t .. 19 t + 18 of a = k >> 1 (tooth 6: 14 bits and zeros); bit j of it is a shift and a mask.
+    // The 19 columns of both halves (7 + 7 bits) are cut once and wait in LDS, one word per round and lane ([round][lane]: no
+    // two lanes of a wave share a bank, no lane reads another's): 19 KiB per block, and no register held across the ladder.
+    __shared__ uint32_t cols[G::SPACING][256];
+    {
+      uint32_t t1[G::TEETH], t2[G::TEETH];
+#pragma unroll
+      for (int t = 0; t < G::TEETH; ++t) {
+        const int bit = G::SPACING * t + 1, limb = bit >> 5, sh = bit & 31;      // (+ 1: a = k >> 1)
+        uint32_t v1 = k1.v[limb] >> sh, v2 = k2.v[limb] >> sh;
+        if (sh > 32 - G::SPACING) {
+          v1 |= k1.v[limb + 1] << (32 - sh);
+          v2 |= k2.v[limb + 1] << (32 - sh);
+        }
+        t1[t] = v1 & ((1u << G::SPACING) - 1u);
+        t2[t] = v2 & ((1u << G::SPACING) - 1u);
+      }
+#pragma unroll
+      for (int j = 0; j < G::SPACING; ++j) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int t = 0; t < G::TEETH; ++t) w |= (((t1[t] >> j) & 1u) << t) | (((t2[t] >> j) & 1u) << (8 + t));
+        cols[j][threadIdx.x] = w;
+      }
+    }
+#pragma unroll 1
+    for (int j = G::SPACING - 1;; --j) {
+      const uint32_t w12 = cols[j][threadIdx.x], w1 = w12 & 127u, w2 = w12 >> 8;
+#pragma unroll 1
+      for (int t = 0; t < 2; ++t) {
+        const uint32_t w = t ? w2 : w1;
+        const bool top = (w & 64u) != 0;
+        const bool neg = (t ? neg2 : neg1) != !top;
+        const uint32_t entry = (top ? w : ~w) & 63u;
+        fe29 x, y;
+        ke_load_xy(kt + (size_t)entry * 8, t != 0, x, y);
+        acc = jpt29_add_affine(acc, x, fe29_cond_negate1(y, neg));
+      }
+      if (j == 0) break;
+      acc = jpt29_double(acc);
+    }
+    // the table's points are affine on the curve isomorphic by W (keyed.hip): back on secp256k1 itself
+    // (W is asked for here and not in front of the ladder: held across it, its nine registers - and the teeth, were they not
+    // in LDS - cost the kernel its fourth wave per SIMD: 156 VGPRs, 132 with W loaded late, under 128 with both)
+    acc.z = fe29_mul(acc.z, ke_load(kt + (size_t)G::WENT * 8, G::W));
+  } else if constexpr (KEYED) {
     // k = 16^32 + sum_i d_i 16^i with d_i = 2 nib_i - 15, i = 4c + j: round j (3 down to 0) adds
     // d_(4c+j) * 2^(16c) Q for the eight chunks c, with four doublings between rounds; the leading
     // 16^32 Q = 16^3 * 2^116 Q goes in first (for both halves at once: one table point, see below).
@@ -2676,6 +2750,9 @@ int s2k_ctx_create_ex(int device_index, int gt_bits, uint32_t flags, s2k_ctx** o
     int np = atoi(v);
     if (np == 1 || np == 2) ctx->kg_parts = (uint32_t)np;
   }
+  if (const char* v = getenv("S2K_KEYED_LADDER")) {       // "window": the ECDSA calls of this context build 16-bit chunk tables (s2k_ctx_set_keyed_ladder)
+    if (!strcmp(v, "window")) ctx->kt_comb = false;
+  }
   if (const char* v = getenv("S2K_GP_FIRST_PERCENT")) {   // measurement knob (tools/keyed_probe.py)
     int pc = atoi(v);
     if (pc >= 0 && pc <= 100) ctx->gp_first_percent = (uint32_t)pc;
@@ -2867,6 +2944,7 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
   uint32_t* qt = ws + WS_QT * stride;
   ctx->kg_counters = nullptr;
   ctx->last_wl_count = nullptr;
+  ctx->kt_last = -1;
   auto wait_all = [&](hipStream_t on) {
     if (arrivals)
       for (int c = 0; c < arrivals->count; ++c) (void)hipStreamWaitEvent(on, arrivals->ev[c], 0);
@@ -2913,6 +2991,7 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
     // Signatures of keys that occur often enough: per-key tables (keyed.hip) and the short ladder; the
     // rest: the general kernel over the list `left`.
     key_groups kg;
+    ctx->kt_comb_call = ctx->kt_comb;
     rc = grouped_front(ctx, st, n, (const uint8_t*)d_pub, 64, prep, gp, stride,
                        [&](hipStream_t aux) {
                          if (!arrivals) {
@@ -2933,18 +3012,27 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
                          }
                        },
                        &kg, /*gp_in_prep=*/arrivals != nullptr);
+    ctx->kt_comb_call = false;
     if (rc) return rc;
+    ctx->kt_last = kg.chunks == KC_TEETH ? S2K_LADDER_COMB : S2K_LADDER_WINDOW;
     prof_mark(ctx, st, 2);
-    k_verify_fast<MODE_ECDSA_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                                   qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
-                                                                   stride, nullptr, clk, kg);
+    // the ladder of the tables the grouping built: the comb's, or the window ladder over the 16-bit chunks
+    auto keyed_ladder = [&](uint64_t* stamps) {
+      if (kg.chunks == KC_TEETH)
+        k_verify_fast<MODE_ECDSA_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
+                                                                      qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
+                                                                      stride, nullptr, stamps, kg);
+      else
+        k_verify_fast<MODE_ECDSA_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
+                                                                       qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
+                                                                       stride, nullptr, stamps, kg);
+    };
+    keyed_ladder(clk);
     HIP_TRY(ctx, hipGetLastError());
     if (kg.nparts > 1) {   // the other side of the split, once its tables (third stream) are there
       HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_part1, 0));
       kg.part = 1;
-      k_verify_fast<MODE_ECDSA_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                                     qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
-                                                                     stride, nullptr, nullptr, kg);
+      keyed_ladder(nullptr);
       HIP_TRY(ctx, hipGetLastError());
     }
     prof_mark(ctx, st, 3);
@@ -3277,6 +3365,15 @@ int s2k_ctx_set_key_grouping(s2k_ctx* ctx, int mode, uint32_t min_group, uint32_
   ctx->kg_table_cap = 0;           // (a cap found by an earlier allocation failure is tried afresh)
   return S2K_OK;
 }
+
+int s2k_ctx_set_keyed_ladder(s2k_ctx* ctx, int ladder) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (ladder != S2K_LADDER_COMB && ladder != S2K_LADDER_WINDOW) return fail(ctx, S2K_ERR_ARG, "keyed ladder %d", ladder);
+  ctx->kt_comb = ladder == S2K_LADDER_COMB;
+  return S2K_OK;
+}
+
+int s2k_ctx_last_keyed_ladder(s2k_ctx* ctx) { return ctx ? ctx->kt_last : -1; }
 
 int s2k_ctx_key_grouping_stats(s2k_ctx* ctx, uint32_t* stats) {
   if (!ctx || !stats) return fail(ctx, S2K_ERR_ARG, "null argument");
@@ -4073,6 +4170,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_pipe_slot(s2k_ctx* ctx, s
   sl.ctx->kg_min_group = ctx->kg_min_group;
   sl.ctx->kg_hash_bits = ctx->kg_hash_bits;
   sl.ctx->kg_max_tables = ctx->kg_max_tables;
+  sl.ctx->kt_comb = ctx->kt_comb;
   sl.ctx->row_max = ctx->row_max;
   sl.ctx->quad_max = ctx->quad_max;
   sl.direct = host_pinned(valid, n);

@@ -14,7 +14,7 @@
 
 using namespace s2k;
 
-// Most per-key tables a verification call builds (9 KiB each: 36 GiB at the cap; the buffer is sized by the batch,
+// Most per-key tables a verification call builds (10 KiB each: 40 GiB at the cap; the buffer is sized by the batch,
 // n / min_group tables, so a 2^20 batch holds 2.4 GB whatever this says).  Was 2^18 until the end of round 3: a batch of
 // 2^24 signatures of 2^20 keys then built no tables at all (threshold raised to 64 per key) and took 129 ms instead of 80.
 constexpr uint32_t KG_MAX_TABLES_DEFAULT = 1u << 22;
@@ -167,6 +167,11 @@ struct s2k_ctx {
   hipStream_t s_msm_tail = nullptr;  // multi-scalar multiplication in two parts (msm.hip): the upper windows' tail, beside the lower windows' bucket pass
   uint32_t kg_parts = 1;             // 1: all tables, then all ladders; 2: the two-part flow (S2K_KEYED_PARTS; measured slower)
   uint32_t gp_first_percent = 60;    // share of k_generator_part launched beside k_key_chain (the rest: beside k_key_finish)
+  // ECDSA calls build their per-key tables as a comb (kc_geom below) unless the window path is asked for
+  // (s2k_ctx_set_keyed_ladder; S2K_KEYED_LADDER=window when the context is created); kt_comb_call: what the call being
+  // enqueued uses (verify_batch_device decides, s2k_internal_key_group reads it: BIP-340 calls stay on window tables)
+  bool kt_comb = true, kt_comb_call = false;
+  int kt_last = -1;                  // S2K_LADDER_* of the last ECDSA verification call's tables (-1: it built none)
   void* kg = nullptr;
   size_t kg_bytes = 0;
   void* ktab = nullptr;
@@ -418,6 +423,7 @@ inline int ctx_stage(s2k_ctx* ctx, const size_t* sizes, int count, uint8_t** ptr
 template <int CHUNKS>
 struct kt_geom {
   static constexpr int DBL = 128 / CHUNKS;          // doublings from one chunk's base to the next (then 4 more to the lead point)
+  static constexpr int LEAD_DBL = 4;
   static constexpr int LEAD = CHUNKS * 8;           // entries of L + phi(L) and (LEAD + 1) L - phi(L): the two starting points of a ladder
   static constexpr int ENTRIES = LEAD + 2;
   static constexpr int SCR = ENTRIES;               // first scratch entry; three field elements per entry (keyed.hip: kt_scratch)
@@ -460,6 +466,33 @@ struct kjw_geom {
   static constexpr int LEAD_SHIFT = W * POS - 128;               // doublings from the chunk table's L = 2^128 Q to 2^(W POS) Q
 };
 static_assert(KT_SLOTS == 72 && KT_W_SLOT == 9 && kt_geom<32>::SLOTS == 288, "table geometry");
+// The per-call tables of the ECDSA flow as a signed Lim-Lee COMB (keyed.hip: k_key_chain<false, 7> / k_key_finish_comb; the ladder
+// is k_verify_fast<MODE_ECDSA_COMB>, engine.hip).  An odd half scalar k < 2^129 is k = 2^L + sum_{i<L} b_i 2^i with
+// b_i = 2 a_i - 1, a = (k - 1) / 2, for any L >= 128.  With L = TEETH * SPACING = 133 and i = 19 t + j the bits of column j
+// select +-E[idx], E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t, B_t = 2^(19 t) Q (the sign is the top tooth's; a negative top
+// tooth complements idx): 19 additions and 18 doublings per half, the doublings shared by the two halves - 38 additions and
+// 18 doublings per signature from the same 64 entries + lead pair (L + phi(L), L - phi(L), L = 2^115 Q) the window tables hold.
+struct kc_geom {
+  static constexpr int TEETH = 7, SPACING = 19, LEN = TEETH * SPACING;
+  static constexpr int LEAD_LOG2 = LEN - SPACING + 1;   // 115: the ladder's 18 doublings make the lead 2^133 Q
+  static constexpr int LEAD = 64, ENTRIES = 66;
+  // what k_key_chain reads of a geometry: SPACING doublings from one base to the next, one more to the lead point; the
+  // Jacobian bases B_t parked in the entries BASE_STEP * t until kc_sets (keyed.hip) has read them all
+  static constexpr int DBL = SPACING, LEAD_DBL = 1, BASE_STEP = 8;
+  // build scratch behind the entries: what k_key_finish_comb reads of a key - A_i = B_6 +- B_5 +- B_4 in ASET + i,
+  // C_j = B_3 +- B_2 +- B_1 +- B_0 in CSET + j (x, y over one common Z) and that Z in element ZAC of entry WENT, whose
+  // element W stays part of the table (the Z all entries of the key share).  Its lanes overwrite the entries while others
+  // still read these twelve points, hence not inside the 64: 80 slots of 128 bytes per key against the window tables' 72
+  // (66 + 6 of scratch), 10 KiB instead of 9.
+  static constexpr int ASET = ENTRIES, CSET = ASET + 4, WENT = CSET + 8, W = 0, ZAC = 1;
+  static constexpr int SLOTS = 80;
+};
+template <>
+struct kt_geom<kc_geom::TEETH> : kc_geom {};
+constexpr int KC_TEETH = kc_geom::TEETH;        // key_groups::chunks of a call on comb tables
+constexpr int KC_SLOTS = kc_geom::SLOTS;
+static_assert(kc_geom::LEN == 133 && kc_geom::LEAD_LOG2 == 115 && (kc_geom::TEETH - 1) * kc_geom::SPACING + 1 == kc_geom::LEAD_LOG2 &&
+              kc_geom::WENT < kc_geom::SLOTS && kc_geom::BASE_STEP * (kc_geom::TEETH - 1) < kc_geom::LEAD && KC_SLOTS >= KT_SLOTS, "comb geometry");
 static_assert(kjw_geom<5>::POS == 26 && kjw_geom<5>::LEAD_SHIFT == 2 && kjw_geom<6>::POS == 22 && kjw_geom<6>::LEAD_SHIFT == 4, "joint geometry");
 enum { KG_NKEYED = 0, KG_NTAB = 1, KG_NLEFT = 2, KG_SPLIT_T = 3, KG_SPLIT_LANE = 4, KG_ALLOC64 = 6 /* and 7 */, KG_COUNTERS = 16 };
 constexpr uint32_t KG_NONE = 0xffffffffu;
@@ -482,13 +515,14 @@ struct key_groups {        // device pointers of one call
   const uint32_t* trep;    // per table: a signature that carries the key
   const uint32_t* gp;      // per signature: u1*G (Jacobian, three fin-format elements; k_generator_part)
   uint32_t max_tables;
-  int chunks;              // table geometry: 8 (built per call) or 32 (key sets); 0 means 8
+  int chunks;              // table geometry: 8 (built per call) or 32 (key sets); 0 means 8; KC_TEETH (7): the comb tables of a call
   int key_bytes;           // 64: X || Y (ECDSA), 32: x-only (BIP-340)
   // two-part flow: part 0 = tables [0, counters[KG_SPLIT_T]) and lanes [0, counters[KG_SPLIT_LANE]), part 1 the
   // rest; nparts == 1: everything (kernels take these from the copy of the struct they are launched with)
   uint32_t part, nparts;
 };
-// groups the batch's signatures by public key, then builds the tables (enqueue only, no host sync)
+// groups the batch's signatures by public key, then builds the tables (enqueue only, no host sync); the tables' geometry
+// (out->chunks) is the comb's when key_bytes == 64 and ctx->kt_comb_call, else the 16-bit chunks'
 int s2k_internal_key_group(s2k_ctx* ctx, size_t n, const uint8_t* d_pub, int key_bytes, hipStream_t st, key_groups* out);
 int s2k_internal_key_reserve(s2k_ctx* ctx, size_t n, int key_bytes);   // grow the grouping arrays / table buffer (before any fork)
 size_t s2k_internal_key_bytes(const s2k_ctx* ctx, size_t n);            // what those hold for a batch of n

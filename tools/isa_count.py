@@ -13,6 +13,8 @@ those of the source:
                               (the last generator addition stands outside the loop)
   k_verify_fast<ECDSA_KEYED>  main loop of 4 rounds, entered past its first blocks (the change of form and the doubling loop
                               run between rounds only: 3 times; doubling loop 4 per time), chunk loop 8, addition loop 2
+  k_verify_fast<ECDSA_COMB>   round loop 19 (its exit test stands between the additions and the doubling: 18 doublings),
+                              addition loop 2
 
 This is what ties the roofline's instruction counts (profiles/r04_valu_counts.json, PMC) to the binary that is measured:
 tests/test_counts_cpu.py recounts the built library and compares, bench.py recounts the library it loaded.
@@ -244,6 +246,40 @@ def keyed(lib):
             "instructions": len(g.ins)}
 
 
+def comb(lib):
+    """k_verify_fast<ECDSA_COMB>: the round loop (19) around the addition loop (2); the doubling stands behind the loop's exit
+    test, so it runs 18 times"""
+    g = Cfg(disassemble(lib, "_Z13k_verify_fastILi16EE"))
+    top = g.top_level()
+    assert len(top) == 1, ("unexpected loop structure of k_verify_fast<ECDSA_COMB>", [g.loops[k]["entries"] for k in top])
+    add = g.children(top[0])
+    assert len(add) == 1 and not g.children(add[0]), ("unexpected loops inside the round loop", add)
+    trips = {top[0]: 19, add[0]: 2}
+    assert len(trips) == len(g.loops), "loops without a trip count"
+    w = g.weights(trips)
+    rnd, addb, head = g.loops[top[0]]["blocks"], g.loops[add[0]]["blocks"], g.loops[top[0]]["entries"]
+    assert len(head) == 1, ("round loop with several entries", head)
+    # the round's exit test (j == 0) stands in the block behind the addition loop; what lies between it and the loop's header
+    # is the doubling, which runs between rounds only.  (The compiler also leaves the loop from the doubling's block by a
+    # guard that is never taken, so Cfg.weights does not see ONE exiting block and the late blocks are found here.)
+    test = {s_ for b in addb for s_ in g.succ[b] if s_ in rnd and s_ not in addb}
+    assert len(test) == 1 and any(s_ not in rnd for t in test for s_ in g.succ[t]), ("exit test behind the addition loop not found", test)
+    dbl, stack = set(), [s_ for t in test for s_ in g.succ[t] if s_ in rnd and s_ != head[0]]
+    while stack:
+        x = stack.pop()
+        if x in dbl or x == head[0] or x in addb:
+            continue
+        dbl.add(x)
+        stack.extend(y for y in g.succ[x] if y in rnd)
+    for b in dbl:
+        w[b] = 18
+    # 18 doublings and 38 additions; what else the round holds (digit extraction) is small
+    assert {w[b] for b in addb} == {38} and 800 < g.valu_in(dbl) < 1100 and g.valu_in(rnd - addb - dbl) < 200, "trip weights are not the source's"
+    valu, mad = g.count(w)
+    return {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad,
+            "valu_per_trip": {"doubling": g.valu_in(dbl), "addition": g.valu_in(addb)}, "instructions": len(g.ins)}
+
+
 def keyset(lib):
     """k_verify_fast<ECDSA_KEYSET>: the ladder over a key set's 32-chunk tables - one chunk loop (32) around the addition loop (2)"""
     g = Cfg(disassemble(lib, "_Z13k_verify_fastILi8EE"))
@@ -288,7 +324,8 @@ def generator_windows(lib):
 def static_counts(lib=DEFAULT_LIB, gt_windows=None):
     if gt_windows is None:
         gt_windows = generator_windows(lib)
-    return {"k_verify_fast": general(lib, gt_windows), "k_verify_fast_keyed": keyed(lib), "k_verify_fast_keyset": keyset(lib),
+    return {"k_verify_fast": general(lib, gt_windows), "k_verify_fast_keyed": keyed(lib), "k_verify_fast_comb": comb(lib),
+            "k_verify_fast_keyset": keyset(lib),
             "k_verify_fast_keyset_joint": keyset_joint(lib), "k_verify_fast_keyset_joint5": keyset_joint_wide(lib, 5),
             "k_verify_fast_keyset_joint6": keyset_joint_wide(lib, 6)}
 
