@@ -21,15 +21,18 @@
 //                  8-entry tables of odd multiples, NO inversion: the key's 65 points are brought to one common
 //                  Z (the product W of the nine Z the build produces) and stored as affine points of the curve
 //                  isomorphic by W; beta*x column
-//   k_key_chain<false, KC_TEETH> / k_key_finish_comb   what an ECDSA call builds instead by default: the same 64 entries per key
+//   k_key_chain<false, KC_TEETH> / k_key_finish_comb_once   what an ECDSA call builds instead by default: the same 64 entries per key
 //                  arranged as a signed 7-tooth comb (kc_geom), 7 bits of a half scalar per table addition - 38 additions and
-//                  18 doublings per signature (k_verify_fast<MODE_ECDSA_COMB>); further down, beside kc_sets
+//                  18 doublings per signature (k_verify_fast<MODE_ECDSA_COMB>); further down, beside kc_sets.  The finish kernel
+//                  forms every cofactor before the first addition and writes each entry once; k_key_finish_comb, which parks
+//                  the sums in memory and fetches them back, stays behind S2K_KEY_FINISH_COMB=park (the same bytes)
 //
 // Nothing here touches the host between the launches; the counts stay on the device and the
 // ladder kernels read them.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "engine_internal.h"
 #include "aff29.h"
@@ -826,9 +829,13 @@ k_key_finish(const uint32_t* __restrict__ counters, uint32_t max_tables, uint32_
 //                      wave step through two levels of additions and three alignments whether it holds an operand or
 //                      not: ~50 products deep in all eight lanes, 400 lane-products per key against 186 here, where
 //                      the chain's 816 products already run one lane per key.
-//   k_key_finish_comb  lane per (key, j): the four conjugate additions A_i +- C_j, the cofactors W / Z of its four pairs
-//                      from its own four h and the other lanes' products (prefix / suffix over the key's eight lanes, as
-//                      k_key_finish), the scaling walk with the beta*x column.  84 products per lane.
+//   k_key_finish_comb_once   lane per (key, j): its four h = X(C_j) - X(A_i) by subtraction, the cofactors W / Z of its four
+//                      pairs from them and the other lanes' products (prefix / suffix over the key's eight lanes, as
+//                      k_key_finish), then the four conjugate additions A_i +- C_j, each pair scaled and stored at once with
+//                      the beta*x column.  84 products per lane; 0.67 ms for 2^16 keys, 0.11 GB read, 0.56 GB written.
+//   k_key_finish_comb  (S2K_KEY_FINISH_COMB=park) the same with the additions first: the eight sums parked in their entries,
+//                      the cofactors, the sums fetched back and scaled - 0.80 ms, 0.34 GB read, 1.04 GB written for the same
+//                      instructions.  Kept as the A/B reference: profiles/r12_finish_once_ab.txt.
 // Per key 816 + 186 + 8 * 84 + 7 = ~1680 products (the chunk tables: ~1700); measured: profiles/r11_comb_ab.txt.
 // x2 = x1 in any of these additions would need a relation a Q = +-b Q with a != +-b far below the group order: never for
 // a point of the curve.
@@ -1031,6 +1038,86 @@ k_key_finish_comb(const uint32_t* __restrict__ counters, uint32_t max_tables, ui
     ke_store3(el + 8, fe29_mul(dx, s2), fe29_mul(dy, s3), fe29_zero());
   }
 }
+// The same table with the COFACTORS FIRST: every entry is written once, in its final form.  The order above - add, park the
+// eight (x, y), form the cofactors, fetch the points back, scale - is k_key_finish's, where each h needs the addition before
+// it.  Here it does not: the twelve operands share one Z, so h_i = X(C_j) - X(A_i) is a subtraction of two values that are in
+// memory when the kernel starts, and e_i, the lane's product, the prefix / suffix products over the key's lanes, rr and co
+// are all known before any addition.  Each pair is then added, scaled and stored in one go: 5 KiB of parked writes per key
+// and the dependent read of the same 5 KiB go; what comes in is four subtractions per lane and the re-read of the four A_i
+// (512 bytes per key, shared by its eight lanes).  Operation for operation and operand for operand the values are those of
+// k_key_finish_comb - the park held raw limbs - so the tables are the same bytes.
+__global__ void __launch_bounds__(256, 2)
+k_key_finish_comb_once(const uint32_t* __restrict__ counters, uint32_t max_tables, uint32_t part, uint32_t nparts, uint4* ktab) {
+  using G = kc_geom;
+  __shared__ uint32_t epark[4 * 9][256];                   // the lane's four in-lane cofactors: [word][lane]
+  uint32_t id = blockIdx.x * 256 + threadIdx.x, lo, hi;
+  table_range(counters, max_tables, part, nparts, lo, hi);
+  const uint32_t t = lo + id / 8, j = id % 8;
+  if (t >= hi) return;                                    // (the eight lanes of a key leave together)
+  uint4* kt = ktab + (size_t)t * (G::SLOTS * 8);
+  uint4* el = kt + (size_t)G::LEAD * 8;
+  const uint4* ka = kt + (size_t)G::ASET * 8;             // A_0 .. A_3: read by all eight lanes, written by none
+  const fe29 zl = ke_load(el, TB_BX);                     // (the two lead points share their Z)
+  const fe29 zac = ke_load(kt + (size_t)G::WENT * 8, G::ZAC);
+  apt29 c;
+  ke_load_xy(kt + (size_t)(G::CSET + j) * 8, false, c.x, c.y);
+  // in-lane cofactors e_i = the product of the other three h, and the lane's product; h_i as coz29_conj forms it
+  fe29 pj;
+  {
+    fe29 h[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h[i] = fe29_normalize_weak(fe29_add(c.x, fe29_negate(ke_load(ka + (size_t)i * 8, TB_X), 1)));   // [1] + [2] -> [1]   X_C - X_A
+    const fe29 h01 = fe29_mul(h[0], h[1]), h23 = fe29_mul(h[2], h[3]);
+    const fe29 e[4] = {fe29_mul(h[1], h23), fe29_mul(h[0], h23), fe29_mul(h01, h[3]), fe29_mul(h01, h[2])};
+    pj = fe29_mul(h01, h23);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int w = 0; w < 9; ++w) epark[i * 9 + w][threadIdx.x] = e[i].n[w];
+  }
+  apt29 an;                                               // the next A_i, asked for before the key's lanes meet
+  ke_load_xy(ka + (size_t)3 * 8, false, an.x, an.y);
+  // W / (Z_AC * this lane's product): the lead pair's Z and the other seven lanes' products, from an exclusive prefix product
+  // (lane 0 starts it with the lead pair's Z) and an exclusive suffix product over the key's lanes
+  fe29 pre = fe29_select(j == 0, fe29_group_shr<1>(pj, j > 0), zl);
+  pre = fe29_mul(pre, fe29_group_shr<1>(pre, j > 0));
+  pre = fe29_mul(pre, fe29_group_shr<2>(pre, j > 1));
+  pre = fe29_mul(pre, fe29_group_shr<4>(pre, j > 3));
+  fe29 suf = fe29_group_shl<1>(pj, j < 7);
+  suf = fe29_mul(suf, fe29_group_shl<1>(suf, j < 7));
+  suf = fe29_mul(suf, fe29_group_shl<2>(suf, j < 6));
+  suf = fe29_mul(suf, fe29_group_shl<4>(suf, j < 4));
+  const fe29 rr = fe29_mul(pre, suf);
+  const fe29 co = fe29_mul(fe29_mul(suf, pj), zac);       // lane 0: Z_AC times all 32 h, the lead pair's cofactor
+  apt29 l1 = {}, l2 = {};
+  if (j == 0) {
+    ke_load_xy(el, false, l1.x, l1.y);
+    ke_load_xy(el + 8, false, l2.x, l2.y);
+  }
+  const fe29 beta = fe29_from_words(FE_BETA);
+#pragma unroll 1
+  for (int i = 3; i >= 0; --i) {                          // (the next A is in flight while this pair is added and scaled)
+    const apt29 a = an;
+    if (i > 0) ke_load_xy(ka + (size_t)(i - 1) * 8, false, an.x, an.y);
+    apt29 s, d;
+    coz29_conj(a, c, s, d);                               // over Z_AC h_i
+    fe29 e;
+#pragma unroll
+    for (int w = 0; w < 9; ++w) e.n[w] = epark[i * 9 + w][threadIdx.x];
+    const fe29 q = fe29_mul(rr, e);
+    const fe29 q2 = fe29_sqr(q), q3 = fe29_mul(q2, q);
+    s = coz29_rescale(s, q2, q3);
+    d = coz29_rescale(d, q2, q3);
+    ke_store3(kt + (size_t)kc_entry((uint32_t)i, j, false) * 8, s.x, s.y, fe29_mul(s.x, beta));
+    ke_store3(kt + (size_t)kc_entry((uint32_t)i, j, true) * 8, d.x, d.y, fe29_mul(d.x, beta));
+  }
+  if (j == 0) {   // W, and the two lead points
+    ke_store(kt + (size_t)G::WENT * 8, G::W, fe29_mul(co, zl));
+    const fe29 s2 = fe29_sqr(co), s3 = fe29_mul(s2, co);
+    ke_store3(el, fe29_mul(l1.x, s2), fe29_mul(l1.y, s3), fe29_zero());
+    ke_store3(el + 8, fe29_mul(l2.x, s2), fe29_mul(l2.y, s3), fe29_zero());
+  }
+}
 
 // Grouping for the BIP-340 whole-batch check: EVERY key forms a group; groups of more than
 // KG_VGROUP signatures are cut into virtual groups of that size (each gets its own term: the lane that
@@ -1230,7 +1317,14 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_tables(s2k_ctx* ctx, 
   static const bool scale_old = getenv("S2K_KEY_SCALE_WIDE") == nullptr;
   if (g->chunks == KC_TEETH) {   // the comb tables of an ECDSA call: one kernel, eight lanes per key
     if (ev_mid) HIP_TRY(ctx, hipEventRecord(ev_mid, st));
-    k_key_finish_comb<<<blocks_for(max_tables * 8), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
+    // Cofactors first, every entry written once (k_key_finish_comb_once) unless S2K_KEY_FINISH_COMB=park brings back the
+    // kernel that parks the sums and fetches them back - the same bytes either way; read at every call, so that a process
+    // can switch for A/B runs and for the tests that compare the two.  profiles/r12_finish_once_ab.txt.
+    const char* fin = getenv("S2K_KEY_FINISH_COMB");
+    if (fin && strcmp(fin, "park") == 0)
+      k_key_finish_comb<<<blocks_for(max_tables * 8), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
+    else
+      k_key_finish_comb_once<<<blocks_for(max_tables * 8), 256, 0, st>>>(g->counters, g->max_tables, part, nparts, ktab);
     HIP_TRY(ctx, hipGetLastError());
     return S2K_OK;
   }
