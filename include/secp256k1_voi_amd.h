@@ -192,16 +192,20 @@ int s2k_ecdsa_verify_batch_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, 
 #define S2K_KEYS_ALWAYS 2
 #define S2K_KEYS_ADAPTIVE 3
 int s2k_ctx_set_key_grouping(s2k_ctx *ctx, int mode, uint32_t min_group, uint32_t hash_bits, uint32_t max_tables);
-/* The tables an ECDSA verification call builds for its repeated keys, and the ladder over them.  Same verdicts either way.
+/* The tables an ECDSA or BIP-340 verification call (s2k_ecdsa_verify_batch*, s2k_schnorr_verify_batch*) builds for its
+ * repeated keys, and the ladder over them.  Same verdicts either way.
  *   S2K_LADDER_COMB (default): a signed 7-tooth comb - 64 entries per key select 7 bits of a half scalar per addition:
  *               38 table additions and 18 doublings per signature (10 KiB per key)
- *   S2K_LADDER_WINDOW: odd multiples of eight 16-bit chunks, 4 bits per addition: 64 additions and 12 doublings - what
- *               BIP-340 calls and key sets use.  Also chosen for a context created with S2K_KEYED_LADDER=window in the
- *               environment, and for any call made while S2K_KEY_TABLES_SPLIT is set. */
+ *   S2K_LADDER_WINDOW: odd multiples of eight 16-bit chunks, 4 bits per addition: 64 additions and 12 doublings.  Also
+ *               chosen for a context created with S2K_KEYED_LADDER=window in the environment, and for any call made while
+ *               S2K_KEY_TABLES_SPLIT is set.
+ * Key sets have their own layouts (s2k_keyset_create_ex below; S2K_KEYSET_COMB is the comb's): this setting does not
+ * touch them. */
 #define S2K_LADDER_COMB 0
 #define S2K_LADDER_WINDOW 1
 int s2k_ctx_set_keyed_ladder(s2k_ctx *ctx, int ladder);
-/* What the last s2k_ecdsa_verify_batch[_device] call of the context enqueued for its repeated keys: S2K_LADDER_COMB,
+/* What the last s2k_ecdsa_verify_batch[_device] or s2k_schnorr_verify_batch[_device] call of the context enqueued for its
+ * repeated keys: S2K_LADDER_COMB,
  * S2K_LADDER_WINDOW, or -1 when it built no tables (grouping off, a small batch, no memory).  No synchronisation. */
 int s2k_ctx_last_keyed_ladder(s2k_ctx *ctx);
 /* After the last s2k_ecdsa_verify_batch_device call has finished (synchronises the device):
@@ -290,16 +294,23 @@ int s2k_keyset_create(s2k_ctx *ctx, size_t n_keys, const uint8_t *pub_xy /* n_ke
  *                      0.81 MiB per key on top of the chunk tables (56 GB for 2^16 keys);
  *   S2K_KEYSET_JOINT6  on 6-bit digits: 22 positions, 2048 sums each - 22 additions, 2.75 MiB per key (for sets of up to
  *                      2^15 keys or so on a 288 GB device);
+ *   S2K_KEYSET_COMB    the signed 7-tooth comb of S2K_LADDER_COMB kept per key: 10 KiB per key and nothing else - 38 table
+ *                      additions and 18 doublings per signature.  The layout for long key lists: 3.6 times smaller than
+ *                      S2K_KEYSET_CHUNKS (2^22 keys: 40 GiB instead of 144).  Never chosen by S2K_KEYSET_AUTO;
  *   S2K_KEYSET_AUTO    (s2k_keyset_create) the widest of JOINT5 and JOINT that takes no more than half of the device memory
  *                      free at the time, else chunks.
- * Verdicts are identical in every layout.  s2k_keyset_layout tells which one a set has. */
+ * Verdicts are identical in every layout.  s2k_keyset_layout tells which one a set has.
+ * s2k_keyset_geometry (a pure host function: no device, no context) gives a layout's cost: out = {table additions per
+ * signature, doublings per signature, table bytes per key}; S2K_ERR_ARG for S2K_KEYSET_AUTO and unknown layouts. */
 #define S2K_KEYSET_AUTO 0
 #define S2K_KEYSET_CHUNKS 1
 #define S2K_KEYSET_JOINT 2
 #define S2K_KEYSET_JOINT5 3
 #define S2K_KEYSET_JOINT6 4
+#define S2K_KEYSET_COMB 5
 int s2k_keyset_create_ex(s2k_ctx *ctx, size_t n_keys, const uint8_t *pub_xy, int layout, s2k_keyset **out);
 int s2k_keyset_layout(const s2k_keyset *ks);
+int s2k_keyset_geometry(int layout, uint64_t out[3]);
 void s2k_keyset_destroy(s2k_keyset *ks);
 size_t s2k_keyset_size(const s2k_keyset *ks);
 size_t s2k_keyset_device_bytes(const s2k_keyset *ks);

@@ -48,7 +48,7 @@ IMPL_COMPLETE, IMPL_FAST = 0, 1
 CTX_WAIT_TABLES = 1
 KEYS_OFF, KEYS_AUTO, KEYS_ALWAYS, KEYS_ADAPTIVE = 0, 1, 2, 3     # s2k_ctx_set_key_grouping (a new context: KEYS_ADAPTIVE)
 LADDER_COMB, LADDER_WINDOW = 0, 1                                # s2k_ctx_set_keyed_ladder (a new context: LADDER_COMB)
-KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 = 0, 1, 2, 3, 4   # s2k_keyset_create_ex
+KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6, KEYSET_COMB = 0, 1, 2, 3, 4, 5   # s2k_keyset_create_ex
 (HP_MUL, HP_SQR, HP_MUL_PLUS, HP_SQR_PLUS, HP_MUL_ADD_MUL, HP_MUL_ADD_SQR, HP_ADD, HP_NEGATE, HP_HALF, HP_NORMALIZE,
  HP_COND_NEGATE1, HP_INV, HP_SQRT, HP_EQ, HP_MUL_SMALL21, HP_NORMALIZE_WEAK, HP_JDBL, HP_JADD, HP_PT29_DBL, HP_PT29_ADD,
  HP_PT29_ADD_MIXED, HP_INV_GCD, HP_JADD_FULL, HP_PT29Q_DBL, HP_PT29Q_ADD, HP_XYZZ_ADD, HP_XYZZ_ROUND,
@@ -333,6 +333,7 @@ def load_library() -> C.CDLL:
     lib.s2k_pointset_device_bytes.argtypes = [vp]
     lib.s2k_pointset_device_bytes.restype = sz
     lib.s2k_pointset_geometry.argtypes = [ci, vp]
+    lib.s2k_keyset_geometry.argtypes = [ci, vp]
     lib.s2k_debug_pointset_entry.argtypes = [vp, sz, C.c_uint, C.c_uint, vp]
     lib.s2k_debug_pointset_check_args.argtypes = [sz, sz, ci, sz, vp]
     lib.s2k_pointset_multi_scalar_mult_segments.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
@@ -405,7 +406,7 @@ EXPORTED_SYMBOLS = [
     "s2k_ctx_profile", "s2k_ctx_profile_read", "s2k_ctx_profile_read_stages", "s2k_ctx_profile_msm", "s2k_ctx_profile_read_msm",
     "s2k_ctx_set_key_grouping", "s2k_ctx_set_keyed_ladder", "s2k_ctx_last_keyed_ladder", "s2k_ctx_key_grouping_stats", "s2k_ctx_key_grouping_adaptive",
     "s2k_ecdsa_verify_batch", "s2k_ecdsa_verify_batch_device", "s2k_ecdsa_workspace_bytes", "s2k_ctx_device_bytes",
-    "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
+    "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_pack_valid_device", "s2k_host_alloc", "s2k_host_free", "s2k_host_register", "s2k_host_unregister", "s2k_ecdsa_recover_batch", "s2k_ecdsa_recover_batch_device",
     "s2k_ecdsa_batch_verify_rlc", "s2k_ecdsa_batch_verify_rlc_device",
@@ -554,6 +555,15 @@ def pointset_geometry(window_bits: int) -> tuple:
     out = np.zeros(3, dtype=np.uint64)
     if load_library().s2k_pointset_geometry(int(window_bits), out.ctypes.data) != 0:
         raise ValueError("secp256k1: point-set digit width is 4 or 8")
+    return tuple(int(x) for x in out)
+
+
+def keyset_geometry(layout: int) -> tuple:
+    """(table additions per signature, doublings per signature, table bytes per key) of a key-set layout, KEYSET_CHUNKS ..
+    KEYSET_COMB (s2k_keyset_geometry; no device).  ValueError for KEYSET_AUTO and unknown layouts."""
+    out = np.zeros(3, dtype=np.uint64)
+    if load_library().s2k_keyset_geometry(int(layout), out.ctypes.data) != 0:
+        raise ValueError("secp256k1: key-set layout without a fixed geometry")
     return tuple(int(x) for x in out)
 
 
@@ -838,7 +848,8 @@ class Engine(_TicketOwner):
     # ---- key sets ----------------------------------------------------------------------
     def keyset_create(self, pub_xy, layout: int = 0) -> "KeySet":
         """Per-key tables of a fixed list of public keys (n_keys x 64 bytes), built once (s2k_keyset_create[_ex]);
-        layout: KEYSET_AUTO (0), KEYSET_CHUNKS (1), KEYSET_JOINT (2)."""
+        layout: KEYSET_AUTO (0: the widest of JOINT5 and JOINT that fits, else CHUNKS), KEYSET_CHUNKS (1), KEYSET_JOINT (2),
+        KEYSET_JOINT5 (3), KEYSET_JOINT6 (4) or KEYSET_COMB (5: 10 KiB per key, for long key lists); keyset_geometry()."""
         return KeySet(self, pub_xy, layout)
 
     def ecdsa_verify_batch_keyset(self, keyset, key_index, digest32, r, s, reject_malleable: bool = False,
@@ -1173,12 +1184,12 @@ class Engine(_TicketOwner):
         self._check(self._lib.s2k_ctx_set_key_grouping(self._h, int(mode), int(min_group), int(hash_bits), int(max_tables)))
 
     def set_keyed_ladder(self, ladder: int = LADDER_COMB):
-        """Tables and ladder of the repeated keys of an ECDSA call (s2k_ctx_set_keyed_ladder): LADDER_COMB (what a new engine
+        """Tables and ladder of the repeated keys of an ECDSA or BIP-340 call (s2k_ctx_set_keyed_ladder): LADDER_COMB (what a new engine
         starts with: 38 additions and 18 doublings per signature) or LADDER_WINDOW (16-bit chunks: 64 and 12)."""
         self._check(self._lib.s2k_ctx_set_keyed_ladder(self._h, int(ladder)))
 
     def last_keyed_ladder(self) -> int:
-        """LADDER_COMB / LADDER_WINDOW: the tables the last ECDSA verification call built; -1: it built none."""
+        """LADDER_COMB / LADDER_WINDOW: the tables the last ECDSA or BIP-340 verification call built; -1: it built none."""
         return int(self._lib.s2k_ctx_last_keyed_ladder(self._h))
 
     def key_grouping_stats(self):
@@ -1714,7 +1725,7 @@ class KeySet:
         self._k = k
 
     def layout(self) -> int:
-        """KEYSET_CHUNKS or KEYSET_JOINT (s2k_keyset_layout)."""
+        """The layout the set has: KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 or KEYSET_COMB (s2k_keyset_layout)."""
         return int(self._eng._lib.s2k_keyset_layout(self._k))
 
     def __len__(self):

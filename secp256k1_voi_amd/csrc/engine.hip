@@ -549,7 +549,9 @@ enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_
        MODE_SCHNORR_KEYSET = 12, MODE_SCHNORR_KEYSET_JOINT = 13, MODE_SCHNORR_KEYSET_JOINT5 = 14, MODE_SCHNORR_KEYSET_JOINT6 = 15,
        // MODE_ECDSA_KEYED over the key's COMB table (kc_geom): 38 additions and 18 doublings.  New modes go at the end:
        // tools/isa_count.py finds the kernels by this number
-       MODE_ECDSA_COMB = 16 };
+       MODE_ECDSA_COMB = 16,
+       // MODE_SCHNORR_KEYED over the comb table (the lifted x-only keys of a call, or the X || Y keys of a comb key set)
+       MODE_SCHNORR_COMB = 17 };
 constexpr uint8_t VERDICT_PENDING = 2;   // k_verify_fast -> k_affine_finish
 constexpr uint32_t KVF_FORCE_WORKLIST = 0x80000000u;   // top bit of k_verify_fast's first argument (batches are below 2^31)
 
@@ -602,6 +604,9 @@ S2K_DEV uint32_t ds4_next(digit_stream4& d) {
 //               geometry, k_key_finish_comb): the same 64 entries per key serve 7 bits of a half scalar per addition.
 // MODE_SCHNORR_KEYED / MODE_SCHNORR_LEFT: the same for BIP-340 (tables of the lifted x-only keys); results go
 //               to k_affine_finish in the SIGNATURE's fin column.
+// MODE_SCHNORR_COMB: MODE_SCHNORR_KEYED over comb tables.  kg.key_bytes == 32: the tables of a call's lifted x-only keys;
+//               kg.key_bytes == 64: a comb key set (S2K_KEYSET_COMB), pub = the set's X || Y keys - an odd Y flips both half
+//               scalars' signs, as in the MODE_SCHNORR_KEYSET modes.
 // Waves per SIMD the register allocator must leave room for.  Measured (2^20 signatures):
 // unbounded (240 VGPRs, 2 waves) 11.08 ms; 3 waves (168 VGPRs, no spills) 10.89 ms; 4 waves
 // (128 VGPRs, 96 spilled) 11.45 ms.
@@ -658,7 +663,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S2K_FA
 // resource usage is printed by tools/kernel_regs.sh.)
 __global__ void __launch_bounds__(256, (MODE == MODE_ECDSA_KEYSET_JOINT || MODE == MODE_ECDSA_KEYSET_JOINT5 || MODE == MODE_ECDSA_KEYSET_JOINT6 ||
                                         MODE == MODE_SCHNORR_KEYSET_JOINT || MODE == MODE_SCHNORR_KEYSET_JOINT5 || MODE == MODE_SCHNORR_KEYSET_JOINT6)
-                                           ? S2K_JOINT_WAVES : MODE == MODE_ECDSA_COMB ? S2K_COMB_WAVES : S2K_FAST_WAVES)
+                                           ? S2K_JOINT_WAVES : (MODE == MODE_ECDSA_COMB || MODE == MODE_SCHNORR_COMB) ? S2K_COMB_WAVES : S2K_FAST_WAVES)
 #endif
 k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig,
               const uint32_t* __restrict__ prep, uint32_t* __restrict__ qt, uint32_t* __restrict__ fin,
@@ -671,10 +676,10 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
   constexpr int JW = KM == MODE_ECDSA_KEYSET_JOINT5 ? 5 : KM == MODE_ECDSA_KEYSET_JOINT6 ? 6 : 4;
   constexpr bool JOINTW = JW > 4;                            // ... over joint tables of 5- or 6-bit digits (kjw_geom: 26 / 22 positions)
   constexpr bool KEYSET = KM == MODE_ECDSA_KEYSET || JOINT || JOINTW;   // KEYED over a key set's 32-chunk tables: no doublings at all
-  constexpr bool COMB = MODE == MODE_ECDSA_COMB;             // KEYED over the comb table of the key
+  constexpr bool COMB = MODE == MODE_ECDSA_COMB || MODE == MODE_SCHNORR_COMB;   // KEYED over the comb table of the key
   constexpr bool KEYED = MODE == MODE_ECDSA_KEYED || MODE == MODE_SCHNORR_KEYED || KEYSET || COMB;
   constexpr bool GROUPED = KEYED || MODE == MODE_ECDSA_LEFT || MODE == MODE_SCHNORR_LEFT;
-  constexpr bool ECDSA = MODE == MODE_ECDSA || MODE == MODE_ECDSA_KEYED || MODE == MODE_ECDSA_LEFT || (KEYSET && !SKS) || COMB;
+  constexpr bool ECDSA = MODE == MODE_ECDSA || MODE == MODE_ECDSA_KEYED || MODE == MODE_ECDSA_LEFT || (KEYSET && !SKS) || MODE == MODE_ECDSA_COMB;
   const bool force_wl = (n_and_flags & KVF_FORCE_WORKLIST) != 0;
   const uint32_t n = n_and_flags & ~KVF_FORCE_WORKLIST;
   size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;         // lane: workspace column
@@ -777,6 +782,15 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
     const bool y_odd = (pub[(size_t)kg.ptab[idx] * 64 + 63] & 1u) != 0;
     neg1 = neg1 != y_odd;
     neg2 = neg2 != y_odd;
+  }
+  if constexpr (MODE == MODE_SCHNORR_COMB) {
+    // a comb key set holds X || Y as well (the same flip); the tables of a call are those of the lifted keys: nothing to do.
+    // One mode for both: the test is uniform over the launch
+    if (kg.key_bytes == 64) {
+      const bool y_odd = (pub[(size_t)kg.ptab[idx] * 64 + 63] & 1u) != 0;
+      neg1 = neg1 != y_odd;
+      neg2 = neg2 != y_odd;
+    }
   }
 
   // ---- table ----
@@ -2750,7 +2764,7 @@ int s2k_ctx_create_ex(int device_index, int gt_bits, uint32_t flags, s2k_ctx** o
     int np = atoi(v);
     if (np == 1 || np == 2) ctx->kg_parts = (uint32_t)np;
   }
-  if (const char* v = getenv("S2K_KEYED_LADDER")) {       // "window": the ECDSA calls of this context build 16-bit chunk tables (s2k_ctx_set_keyed_ladder)
+  if (const char* v = getenv("S2K_KEYED_LADDER")) {       // "window": the ECDSA and BIP-340 calls of this context build 16-bit chunk tables (s2k_ctx_set_keyed_ladder)
     if (!strcmp(v, "window")) ctx->kt_comb = false;
   }
   if (const char* v = getenv("S2K_GP_FIRST_PERCENT")) {   // measurement knob (tools/keyed_probe.py)
@@ -3113,6 +3127,7 @@ struct s2k_keyset {
   uint4* joint;       // device: the joint tables (320 KiB per key; 0.81 / 2.75 MiB at 5- / 6-bit digits), or null: the ladder over the 32-chunk tables
   size_t joint_bytes;
   int jw;             // digit width of the joint tables: 4, 5 or 6 (0: none)
+  int chunks;         // geometry of the tables in `base`: KS_CHUNKS, or KC_TEETH - a comb set (S2K_KEYSET_COMB; never with joint tables)
 };
 
 int s2k_keyset_create(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, s2k_keyset** out) {
@@ -3121,7 +3136,7 @@ int s2k_keyset_create(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, s2k_ke
 int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int layout, s2k_keyset** out) {
   if (!ctx || !out) return fail(ctx, S2K_ERR_ARG, "null argument");
   if (layout != S2K_KEYSET_AUTO && layout != S2K_KEYSET_CHUNKS && layout != S2K_KEYSET_JOINT && layout != S2K_KEYSET_JOINT5 &&
-      layout != S2K_KEYSET_JOINT6)
+      layout != S2K_KEYSET_JOINT6 && layout != S2K_KEYSET_COMB)
     return fail(ctx, S2K_ERR_ARG, "unknown key-set layout");
   *out = nullptr;
   if (n_keys == 0 || !pub_xy) return fail(ctx, S2K_ERR_ARG, "empty key set");
@@ -3136,7 +3151,8 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
   ks->device = ctx->device;
   ks->n = n_keys;
   size_t off[5];
-  ks->bytes = s2k_internal_keyset_bytes(n_keys, off);
+  ks->chunks = layout == S2K_KEYSET_COMB ? KC_TEETH : KS_CHUNKS;
+  ks->bytes = s2k_internal_keyset_bytes(n_keys, off, ks->chunks);
   hipError_t e = hipMalloc((void**)&ks->base, ks->bytes);
   if (e != hipSuccess) {
     delete ks;
@@ -3146,7 +3162,7 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
   rc = ctx_enter(ctx, st);
   if (rc == S2K_OK && hipMemcpyAsync(ks->base + off[0], pub_xy, n_keys * 64, hipMemcpyHostToDevice, st) != hipSuccess)
     rc = fail(ctx, S2K_ERR_HIP, "copy of the keys failed");
-  if (rc == S2K_OK) rc = s2k_internal_keyset_build(ctx, ks->base, n_keys, st);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_build(ctx, ks->base, n_keys, st, ks->chunks);
   // joint tables (one table addition per digit position instead of two; 320 KiB per key on top, 0.81 MiB at 5-bit digits: 26
   // positions, 2.75 MiB at 6-bit digits: 22): the layout asked for, or - S2K_KEYSET_AUTO - the widest of 5 and 4 bits that takes no
   // more than half of the device memory that is free now (2^16 keys at 5 bits are 56 GB: a quarter would ask for a device with
@@ -3155,7 +3171,7 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
   ks->joint_bytes = 0;
   ks->jw = 0;
   uint4* scratch = nullptr;
-  if (rc == S2K_OK && layout != S2K_KEYSET_CHUNKS) {
+  if (rc == S2K_OK && layout != S2K_KEYSET_CHUNKS && layout != S2K_KEYSET_COMB) {
     int w = layout == S2K_KEYSET_JOINT6 ? 6 : layout == S2K_KEYSET_JOINT5 ? 5 : layout == S2K_KEYSET_JOINT ? 4 : 0;
     // s2k_set_table_memory_budgets: no more than this many bytes count as free for joint tables (an operator's cap - and how
     // the choice of S2K_KEYSET_AUTO and the failure of an explicit layout are exercised without filling a 288 GB device)
@@ -3213,12 +3229,46 @@ void s2k_keyset_destroy(s2k_keyset* ks) {
 size_t s2k_keyset_size(const s2k_keyset* ks) { return ks ? ks->n : 0; }
 size_t s2k_keyset_device_bytes(const s2k_keyset* ks) { return ks ? ks->bytes + ks->joint_bytes : 0; }
 int s2k_keyset_layout(const s2k_keyset* ks) {
-  return !ks ? 0 : !ks->joint ? S2K_KEYSET_CHUNKS : ks->jw == 6 ? S2K_KEYSET_JOINT6 : ks->jw == 5 ? S2K_KEYSET_JOINT5 : S2K_KEYSET_JOINT;
+  return !ks ? 0 : ks->chunks == KC_TEETH ? S2K_KEYSET_COMB : !ks->joint ? S2K_KEYSET_CHUNKS : ks->jw == 6 ? S2K_KEYSET_JOINT6 : ks->jw == 5 ? S2K_KEYSET_JOINT5 : S2K_KEYSET_JOINT;
+}
+// pure host function: what a layout costs per signature and per key, from the geometries the kernels are built on
+int s2k_keyset_geometry(int layout, uint64_t out[3]) {
+  if (!out) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  const uint64_t chunk_bytes = (uint64_t)KS_SLOTS * 128;
+  switch (layout) {
+    case S2K_KEYSET_CHUNKS:
+      out[0] = 2 * KS_CHUNKS;
+      out[1] = 0;
+      out[2] = chunk_bytes;
+      return S2K_OK;
+    case S2K_KEYSET_JOINT:
+      out[0] = KS_CHUNKS;
+      out[1] = 0;
+      out[2] = chunk_bytes + KJ_KEY_QUADS * sizeof(uint4);
+      return S2K_OK;
+    case S2K_KEYSET_JOINT5:
+      out[0] = kjw_geom<5>::POS;
+      out[1] = 0;
+      out[2] = chunk_bytes + kjw_geom<5>::KEY_QUADS * sizeof(uint4);
+      return S2K_OK;
+    case S2K_KEYSET_JOINT6:
+      out[0] = kjw_geom<6>::POS;
+      out[1] = 0;
+      out[2] = chunk_bytes + kjw_geom<6>::KEY_QUADS * sizeof(uint4);
+      return S2K_OK;
+    case S2K_KEYSET_COMB:
+      out[0] = 2 * kc_geom::SPACING;
+      out[1] = kc_geom::SPACING - 1;
+      out[2] = (uint64_t)KC_SLOTS * 128;
+      return S2K_OK;
+    default:
+      return fail(nullptr, S2K_ERR_ARG, "key-set layout %d has no fixed geometry", layout);
+  }
 }
 int s2k_keyset_valid_keys(s2k_keyset* ks, uint8_t* valid) {
   if (!ks || !valid) return fail(nullptr, S2K_ERR_ARG, "null argument");
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off);
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   HIP_TRY(nullptr, hipSetDevice(ks->device));
   HIP_TRY(nullptr, hipMemcpy(valid, ks->base + off[2], ks->n, hipMemcpyDeviceToHost));
   return S2K_OK;
@@ -3256,7 +3306,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
   uint32_t* wl = wl_count + 64;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off);
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   ctx->last_wl_count = wl_count;
   HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));       // signatures naming no key of the set stay invalid
@@ -3273,7 +3323,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   k_generator_part<<<blocks_for(n), 256, 0, ctx->s_aux>>>(0u, (uint32_t)n, prep, ctx->gt_call, gp, stride);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);
@@ -3283,7 +3333,10 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   uint64_t* clk = ctx->prof_on ? ctx->clk : nullptr;
   kg.jtab = ks->joint;
   prof_mark(ctx, st, 2);
-  if (ks->joint && ks->jw == 6)
+  if (ks->chunks == KC_TEETH)   // a comb set: the ladder of a call's comb tables over the set's (the keyed prologue reads no key)
+    k_verify_fast<MODE_ECDSA_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin, ctx->gt_call,
+                                                                  (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
+  else if (ks->joint && ks->jw == 6)
     k_verify_fast<MODE_ECDSA_KEYSET_JOINT6><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin,
                                                                            ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
   else if (ks->joint && ks->jw == 5)
@@ -3619,6 +3672,7 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
   // [4] the worklist)
   prof_mark(ctx, st, 0);
   ctx->kg_counters = nullptr;
+  ctx->kt_last = -1;
   bool grouped = ctx->kg_mode != S2K_KEYS_OFF && n >= KG_MIN_BATCH;
   const bool row = n <= ctx->row_max && (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF);
   const bool quad = !row && n <= ctx->quad_max && (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF);
@@ -3634,23 +3688,33 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
     // signatures that share an x-only key: the grouped flow of the ECDSA path (s2k_ctx_set_key_grouping)
     uint32_t* gp = ws + WS_GP * stride;
     key_groups kg;
+    ctx->kt_comb_call = ctx->kt_comb;
     rc = grouped_front(ctx, st, n, pk, 32, prep, gp, stride,
                        [&](hipStream_t aux) {
                          k_schnorr_prep<<<blocks_for(n), 256, 0, aux>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
                        },
                        &kg);
+    ctx->kt_comb_call = false;
     if (rc) return rc;
+    ctx->kt_last = kg.chunks == KC_TEETH ? S2K_LADDER_COMB : S2K_LADDER_WINDOW;
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_fast<MODE_SCHNORR_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                                     (uint8_t*)d_valid, wl_count, wl, stride, nullptr, ctx->prof_on ? ctx->clk : nullptr, kg);
+    // the ladder of the tables the grouping built: the comb's, or the window ladder over the 16-bit chunks
+    auto keyed_ladder = [&](uint64_t* stamps) {
+      if (kg.chunks == KC_TEETH)
+        k_verify_fast<MODE_SCHNORR_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
+                                                                        (uint8_t*)d_valid, wl_count, wl, stride, nullptr, stamps, kg);
+      else
+        k_verify_fast<MODE_SCHNORR_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
+                                                                         (uint8_t*)d_valid, wl_count, wl, stride, nullptr, stamps, kg);
+    };
+    keyed_ladder(ctx->prof_on ? ctx->clk : nullptr);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     if (kg.nparts > 1) {
       HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_part1, 0));
       kg.part = 1;
-      k_verify_fast<MODE_SCHNORR_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                                       (uint8_t*)d_valid, wl_count, wl, stride, nullptr, nullptr, kg);
+      keyed_ladder(nullptr);
       HIP_TRY(ctx, hipGetLastError());
     }
     k_verify_fast<MODE_SCHNORR_LEFT><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
@@ -3773,7 +3837,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   const uint8_t* msgs = (const uint8_t*)d_msgs;
   const uint64_t* offs = (const uint64_t*)d_msg_offsets;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off);
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   const uint8_t* set_keys = ks->base + off[0];
   ctx->kg_counters = nullptr;
   ctx->last_wl_count = wl_count;
@@ -3788,7 +3852,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   k_generator_part<<<blocks_for(n), 256, 0, ctx->s_aux>>>(0u, (uint32_t)n, prep, ctx->gt_call, gp, stride);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);
@@ -3799,7 +3863,8 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
 #define S2K_SKS_LAUNCH(M) \
   k_verify_fast<M><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, set_keys, sig, prep, qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, \
                                                   nullptr, nullptr, kg)
-  if (ks->joint && ks->jw == 6) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT6);
+  if (ks->chunks == KC_TEETH) S2K_SKS_LAUNCH(MODE_SCHNORR_COMB);   // (kg.key_bytes == 64: the sign flip under an odd Y)
+  else if (ks->joint && ks->jw == 6) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT6);
   else if (ks->joint && ks->jw == 5) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT5);
   else if (ks->joint) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT);
   else S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET);

@@ -167,11 +167,11 @@ struct s2k_ctx {
   hipStream_t s_msm_tail = nullptr;  // multi-scalar multiplication in two parts (msm.hip): the upper windows' tail, beside the lower windows' bucket pass
   uint32_t kg_parts = 1;             // 1: all tables, then all ladders; 2: the two-part flow (S2K_KEYED_PARTS; measured slower)
   uint32_t gp_first_percent = 60;    // share of k_generator_part launched beside k_key_chain (the rest: beside k_key_finish)
-  // ECDSA calls build their per-key tables as a comb (kc_geom below) unless the window path is asked for
-  // (s2k_ctx_set_keyed_ladder; S2K_KEYED_LADDER=window when the context is created); kt_comb_call: what the call being
-  // enqueued uses (verify_batch_device decides, s2k_internal_key_group reads it: BIP-340 calls stay on window tables)
+  // ECDSA and BIP-340 verification calls build their per-key tables as a comb (kc_geom below) unless the window path is asked
+  // for (s2k_ctx_set_keyed_ladder; S2K_KEYED_LADDER=window when the context is created); kt_comb_call: what the call being
+  // enqueued uses (the verification entry points set it around grouped_front, s2k_internal_key_group reads it)
   bool kt_comb = true, kt_comb_call = false;
-  int kt_last = -1;                  // S2K_LADDER_* of the last ECDSA verification call's tables (-1: it built none)
+  int kt_last = -1;                  // S2K_LADDER_* of the last ECDSA or BIP-340 verification call's tables (-1: it built none)
   void* kg = nullptr;
   size_t kg_bytes = 0;
   void* ktab = nullptr;
@@ -466,8 +466,8 @@ struct kjw_geom {
   static constexpr int LEAD_SHIFT = W * POS - 128;               // doublings from the chunk table's L = 2^128 Q to 2^(W POS) Q
 };
 static_assert(KT_SLOTS == 72 && KT_W_SLOT == 9 && kt_geom<32>::SLOTS == 288, "table geometry");
-// The per-call tables of the ECDSA flow as a signed Lim-Lee COMB (keyed.hip: k_key_chain<false, 7> / k_key_finish_comb; the ladder
-// is k_verify_fast<MODE_ECDSA_COMB>, engine.hip).  An odd half scalar k < 2^129 is k = 2^L + sum_{i<L} b_i 2^i with
+// The per-call tables of the ECDSA and BIP-340 flows, and the tables of a comb key set, as a signed Lim-Lee COMB (keyed.hip:
+// k_key_chain<XONLY, 7> / k_key_finish_comb; the ladder is k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>, engine.hip).  An odd half scalar k < 2^129 is k = 2^L + sum_{i<L} b_i 2^i with
 // b_i = 2 a_i - 1, a = (k - 1) / 2, for any L >= 128.  With L = TEETH * SPACING = 133 and i = 19 t + j the bits of column j
 // select +-E[idx], E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t, B_t = 2^(19 t) Q (the sign is the top tooth's; a negative top
 // tooth complements idx): 19 additions and 18 doublings per half, the doublings shared by the two halves - 38 additions and
@@ -515,14 +515,14 @@ struct key_groups {        // device pointers of one call
   const uint32_t* trep;    // per table: a signature that carries the key
   const uint32_t* gp;      // per signature: u1*G (Jacobian, three fin-format elements; k_generator_part)
   uint32_t max_tables;
-  int chunks;              // table geometry: 8 (built per call) or 32 (key sets); 0 means 8; KC_TEETH (7): the comb tables of a call
+  int chunks;              // table geometry: 8 (built per call) or 32 (key sets); 0 means 8; KC_TEETH (7): the comb tables of a call or of a comb key set
   int key_bytes;           // 64: X || Y (ECDSA), 32: x-only (BIP-340)
   // two-part flow: part 0 = tables [0, counters[KG_SPLIT_T]) and lanes [0, counters[KG_SPLIT_LANE]), part 1 the
   // rest; nparts == 1: everything (kernels take these from the copy of the struct they are launched with)
   uint32_t part, nparts;
 };
 // groups the batch's signatures by public key, then builds the tables (enqueue only, no host sync); the tables' geometry
-// (out->chunks) is the comb's when key_bytes == 64 and ctx->kt_comb_call, else the 16-bit chunks'
+// (out->chunks) is the comb's when ctx->kt_comb_call (and S2K_KEY_TABLES_SPLIT is not set), else the 16-bit chunks'
 int s2k_internal_key_group(s2k_ctx* ctx, size_t n, const uint8_t* d_pub, int key_bytes, hipStream_t st, key_groups* out);
 int s2k_internal_key_reserve(s2k_ctx* ctx, size_t n, int key_bytes);   // grow the grouping arrays / table buffer (before any fork)
 size_t s2k_internal_key_bytes(const s2k_ctx* ctx, size_t n);            // what those hold for a batch of n
@@ -548,15 +548,16 @@ int s2k_internal_key_group32(s2k_ctx* ctx, size_t n, const uint8_t* d_pk32, hipS
 int s2k_internal_key_group_all(s2k_ctx* ctx, size_t n, const uint8_t* d_keys, int key_bytes, hipStream_t st, key_groups32* out);
 int s2k_internal_key_reserve32(s2k_ctx* ctx, size_t n);
 // key sets (s2k_keyset_*): buffer layout, table build, scratch reservation, sort of a batch by key index
-size_t s2k_internal_keyset_bytes(size_t n, size_t off[5]);
-int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st);
+// (chunks: the geometry of the set's tables, KS_CHUNKS - also what the joint layouts are built from - or KC_TEETH, a comb set)
+size_t s2k_internal_keyset_bytes(size_t n, size_t off[5], int chunks = KS_CHUNKS);
+int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st, int chunks = KS_CHUNKS);
 int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t n, uint4* joint, hipStream_t st);   // from the 32-chunk tables
 size_t s2k_internal_keyset_joint_bytes(size_t n, int w);                  // joint tables of n keys at digit width w (4, 5, 6)
 size_t s2k_internal_keyset_joint_scratch_bytes(size_t n, int w);          // build scratch of the wide layouts (0 at w = 4)
 int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t n, int w, uint4* joint, uint4* scratch, hipStream_t st);
 int s2k_internal_keyset_reserve(s2k_ctx* ctx, size_t nkeys, size_t n);
 int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys, size_t n, const uint32_t* d_kidx, hipStream_t st,
-                             key_groups* out);
+                             key_groups* out, int chunks = KS_CHUNKS);
 
 struct dev_buf {
   void* p = nullptr;

@@ -21,9 +21,9 @@
 //                  8-entry tables of odd multiples, NO inversion: the key's 65 points are brought to one common
 //                  Z (the product W of the nine Z the build produces) and stored as affine points of the curve
 //                  isomorphic by W; beta*x column
-//   k_key_chain<false, KC_TEETH> / k_key_finish_comb_once   what an ECDSA call builds instead by default: the same 64 entries per key
+//   k_key_chain<XONLY, KC_TEETH> / k_key_finish_comb_once   what an ECDSA or BIP-340 call builds instead by default, and a comb key set once: the same 64 entries per key
 //                  arranged as a signed 7-tooth comb (kc_geom), 7 bits of a half scalar per table addition - 38 additions and
-//                  18 doublings per signature (k_verify_fast<MODE_ECDSA_COMB>); further down, beside kc_sets.  The finish kernel
+//                  18 doublings per signature (k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>); further down, beside kc_sets.  The finish kernel
 //                  forms every cofactor before the first addition and writes each entry once; k_key_finish_comb, which parks
 //                  the sums in memory and fetches them back, stays behind S2K_KEY_FINISH_COMB=park (the same bytes)
 //
@@ -1277,10 +1277,11 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_group(s2k_ctx* ctx, s
   out->tinfo = tinfo;
   out->trep = trep;
   out->max_tables = (uint32_t)max_tables;
-  // ECDSA calls: comb tables (k_verify_fast<MODE_ECDSA_COMB>) unless the context asks for the window path; S2K_KEY_TABLES_SPLIT
-  // (the three kernels of the chunk tables, read at every call) implies it
+  // ECDSA and BIP-340 verification calls: comb tables (k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>) unless the
+  // context asks for the window path; S2K_KEY_TABLES_SPLIT (the three kernels of the chunk tables, read at every call)
+  // implies it
   const char* split = getenv("S2K_KEY_TABLES_SPLIT");
-  const bool comb = key_bytes == 64 && ctx->kt_comb_call && !(split && *split && *split != '0');
+  const bool comb = ctx->kt_comb_call && !(split && *split && *split != '0');
   out->chunks = comb ? KC_TEETH : KT_CHUNKS;
   out->key_bytes = key_bytes;
   return S2K_OK;
@@ -1291,7 +1292,9 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_chains(s2k_ctx* ctx, 
                                                                   const key_groups* g) {
   uint4* ktab = const_cast<uint4*>(g->ktab);     // (the context's table buffer, or a key set's own)
   const size_t max_tables = g->max_tables;
-  if (g->chunks == KC_TEETH)
+  if (g->chunks == KC_TEETH && g->key_bytes == 32)   // x-only keys: validated and lifted as for the window tables
+    k_key_chain<true, KC_TEETH><<<(unsigned)((max_tables + 63) / 64), 64, 0, st>>>(g->counters, g->max_tables, g->trep, d_pub, ktab, (uint8_t*)g->tinfo);
+  else if (g->chunks == KC_TEETH)
     k_key_chain<false, KC_TEETH><<<(unsigned)((max_tables + 63) / 64), 64, 0, st>>>(g->counters, g->max_tables, g->trep, d_pub, ktab, (uint8_t*)g->tinfo);
   else if (g->chunks == KS_CHUNKS)
     k_key_chain<false, KS_CHUNKS><<<(unsigned)((max_tables + 63) / 64), 64, 0, st>>>(g->counters, g->max_tables, g->trep, d_pub, ktab, (uint8_t*)g->tinfo);
@@ -1315,7 +1318,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_tables(s2k_ctx* ctx, 
   // instead of six is energy the ladder then does not get.  Kept as a knob because it is the measured answer to "make the
   // scaling pass faster" (VERDICT r04 next #4a).
   static const bool scale_old = getenv("S2K_KEY_SCALE_WIDE") == nullptr;
-  if (g->chunks == KC_TEETH) {   // the comb tables of an ECDSA call: one kernel, eight lanes per key
+  if (g->chunks == KC_TEETH) {   // the comb tables of a call or of a comb key set: one kernel, eight lanes per key
     if (ev_mid) HIP_TRY(ctx, hipEventRecord(ev_mid, st));
     // Cofactors first, every entry written once (k_key_finish_comb_once) unless S2K_KEY_FINISH_COMB=park brings back the
     // kernel that parks the sums and fetches them back - the same bytes either way; read at every call, so that a process
@@ -1548,27 +1551,28 @@ k_ksw_lead(uint32_t nkeys, const uint4* __restrict__ ktab, uint4* __restrict__ j
 }
 }  // namespace
 
-// device memory of a key set of n keys: keys | tables | validity | identity | counters
-__attribute__((visibility("hidden"))) size_t s2k_internal_keyset_bytes(size_t n, size_t off[5]) {
+// device memory of a key set of n keys: keys | tables | validity | identity | counters.  chunks: the tables' geometry,
+// KS_CHUNKS (36 KiB per key) or KC_TEETH (a comb set, S2K_KEYSET_COMB: 10 KiB per key)
+__attribute__((visibility("hidden"))) size_t s2k_internal_keyset_bytes(size_t n, size_t off[5], int chunks) {
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   off[0] = 0;
   off[1] = off[0] + al(n * 64);
-  off[2] = off[1] + al(n * (size_t)KS_SLOTS * 128);           // 36 KiB per key: the 32-chunk geometry (engine_internal.h)
+  off[2] = off[1] + al(n * (size_t)(chunks == KC_TEETH ? KC_SLOTS : KS_SLOTS) * 128);
   off[3] = off[2] + al(n + 64);
   off[4] = off[3] + al(n * 4);
   return off[4] + al(KG_COUNTERS * 4);
 }
 // builds the tables of the n keys at base + off[0] (already on the device) into the set's buffers
-__attribute__((visibility("hidden"))) int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st) {
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st, int chunks) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(n, off);
+  (void)s2k_internal_keyset_bytes(n, off, chunks);
   key_groups g{};
   g.counters = (uint32_t*)(base + off[4]);
   g.ktab = (const uint4*)(base + off[1]);
   g.tinfo = base + off[2];
   g.trep = (const uint32_t*)(base + off[3]);          // table t is the key of "signature" t: the identity
   g.max_tables = (uint32_t)n;
-  g.chunks = KS_CHUNKS;
+  g.chunks = chunks;
   g.key_bytes = 64;
   g.part = 0;
   g.nparts = 1;
@@ -1628,9 +1632,9 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_reserve(s2k_ctx* c
 }
 // signatures sorted by key index -> the lane lists of the keyed ladder over the set's tables (enqueue only)
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys, size_t n,
-                                                                   const uint32_t* d_kidx, hipStream_t st, key_groups* out) {
+                                                                   const uint32_t* d_kidx, hipStream_t st, key_groups* out, int chunks) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(nkeys, off);
+  (void)s2k_internal_keyset_bytes(nkeys, off, chunks);
   int rc = s2k_internal_keyset_reserve(ctx, nkeys, n);   // (a no-op when the caller has reserved already)
   if (rc) return rc;
   const size_t np = (n + 63) & ~(size_t)63, kp = (nkeys + 63) & ~(size_t)63;
@@ -1663,7 +1667,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx,
   out->tinfo = set_base + off[2];
   out->trep = (const uint32_t*)(set_base + off[3]);
   out->max_tables = (uint32_t)nkeys;
-  out->chunks = KS_CHUNKS;
+  out->chunks = chunks;
   out->key_bytes = 64;
   out->part = 0;
   out->nparts = 1;

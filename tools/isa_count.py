@@ -15,6 +15,7 @@ those of the source:
                               run between rounds only: 3 times; doubling loop 4 per time), chunk loop 8, addition loop 2
   k_verify_fast<ECDSA_COMB>   round loop 19 (its exit test stands between the additions and the doubling: 18 doublings),
                               addition loop 2
+  k_verify_fast<SCHNORR_KEYED> / <SCHNORR_COMB>   the BIP-340 ladders over the same tables: the loops of ECDSA_KEYED / ECDSA_COMB
 
 This is what ties the roofline's instruction counts (profiles/r04_valu_counts.json, PMC) to the binary that is measured:
 tests/test_counts_cpu.py recounts the built library and compares, bench.py recounts the library it loaded.
@@ -220,10 +221,11 @@ def general(lib, gt_windows=None):
     return {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad, "valu_per_trip": regions, "instructions": len(g.ins)}
 
 
-def keyed(lib):
-    g = Cfg(disassemble(lib, "_Z13k_verify_fastILi4EE"))
+def keyed(lib, mode=4, name="ECDSA_KEYED"):
+    """k_verify_fast<ECDSA_KEYED> (mode 4) or <SCHNORR_KEYED> (mode 6): the window ladder over the per-call tables"""
+    g = Cfg(disassemble(lib, "_Z13k_verify_fastILi%dEE" % mode))
     top = g.top_level()
-    assert len(top) == 1, ("unexpected loop structure of k_verify_fast<ECDSA_KEYED>", [g.loops[k]["entries"] for k in top])
+    assert len(top) == 1, ("unexpected loop structure of k_verify_fast<%s>" % name, [g.loops[k]["entries"] for k in top])
     kids = g.children(top[0])
     assert len(kids) == 2, ("unexpected loops inside the round loop", kids)
     chunk = [k for k in kids if g.children(k)]
@@ -246,12 +248,12 @@ def keyed(lib):
             "instructions": len(g.ins)}
 
 
-def comb(lib):
-    """k_verify_fast<ECDSA_COMB>: the round loop (19) around the addition loop (2); the doubling stands behind the loop's exit
-    test, so it runs 18 times"""
-    g = Cfg(disassemble(lib, "_Z13k_verify_fastILi16EE"))
+def comb(lib, mode=16, name="ECDSA_COMB"):
+    """k_verify_fast<ECDSA_COMB> (mode 16) or <SCHNORR_COMB> (mode 17): the round loop (19) around the addition loop (2); the
+    doubling stands behind the loop's exit test, so it runs 18 times"""
+    g = Cfg(disassemble(lib, "_Z13k_verify_fastILi%dEE" % mode))
     top = g.top_level()
-    assert len(top) == 1, ("unexpected loop structure of k_verify_fast<ECDSA_COMB>", [g.loops[k]["entries"] for k in top])
+    assert len(top) == 1, ("unexpected loop structure of k_verify_fast<%s>" % name, [g.loops[k]["entries"] for k in top])
     add = g.children(top[0])
     assert len(add) == 1 and not g.children(add[0]), ("unexpected loops inside the round loop", add)
     trips = {top[0]: 19, add[0]: 2}
@@ -327,7 +329,8 @@ def static_counts(lib=DEFAULT_LIB, gt_windows=None):
     return {"k_verify_fast": general(lib, gt_windows), "k_verify_fast_keyed": keyed(lib), "k_verify_fast_comb": comb(lib),
             "k_verify_fast_keyset": keyset(lib),
             "k_verify_fast_keyset_joint": keyset_joint(lib), "k_verify_fast_keyset_joint5": keyset_joint_wide(lib, 5),
-            "k_verify_fast_keyset_joint6": keyset_joint_wide(lib, 6)}
+            "k_verify_fast_keyset_joint6": keyset_joint_wide(lib, 6),
+            "k_verify_fast_schnorr_keyed": keyed(lib, 6, "SCHNORR_KEYED"), "k_verify_fast_schnorr_comb": comb(lib, 17, "SCHNORR_COMB")}
 
 
 if __name__ == "__main__":
