@@ -211,7 +211,8 @@ int s2k_ctx_last_keyed_ladder(s2k_ctx *ctx);
 /* After the last s2k_ecdsa_verify_batch_device call has finished (synchronises the device):
  * stats[0] signatures verified from per-key tables, [1] tables built, [2] signatures through the
  * general kernel, [3] signatures re-done by the complete-formula kernel.  All zero after a call that took the ladders of
- * small or mid-size batches (s2k_ctx_set_small_batch_max / s2k_ctx_set_mid_batch_max): they neither group nor have a worklist. */
+ * small or mid-size batches (s2k_ctx_set_small_batch_max / s2k_ctx_set_mid_batch_max) and after a key-set call that took the
+ * row ladder (s2k_ctx_set_keyset_small_batch_max): they neither group nor have a worklist. */
 int s2k_ctx_key_grouping_stats(s2k_ctx *ctx, uint32_t stats[4]);
 /* State of S2K_KEYS_ADAPTIVE, without synchronising: out[0] consecutive observed calls that found no group, [1] calls
  * still to be verified without looking, [2] calls verified without looking so far, [3] calls that looked again after a
@@ -377,6 +378,19 @@ int s2k_ctx_set_small_batch_max(s2k_ctx *ctx, uint32_t max_n);
  * is the latency of one wave's ladder - half as long this way as with a lane per signature (0.35 instead of 0.6-0.7 ms for
  * 2^12 .. 2^14 ECDSA signatures).  Same results (tests/test_gpu_round5.py). */
 int s2k_ctx_set_mid_batch_max(s2k_ctx *ctx, uint32_t max_n);
+/* Small calls over a key set.  s2k_ecdsa_verify_batch_keyset and s2k_schnorr_verify_batch_keyset (and their _device / _submit
+ * forms) of up to max_n signatures (default 2048, the measured crossover; 0 = never) run ONE launch with a wavefront per signature over the 32-chunk
+ * table of the signature's key (k_verify_row_keyset / k_schnorr_row_keyset: 64 complete additions on the key's isomorphic
+ * curve - b3 = 21 W^6 is a per-key field element there, pt29r_add_b3 -, then the generator part), instead of the chain of
+ * launches and the lane-per-signature ladder of larger calls.  Sets of layout S2K_KEYSET_CHUNKS, JOINT, JOINT5 and JOINT6
+ * take it (all keep the chunk table); S2K_KEYSET_COMB sets keep the lane-per-signature path at every size, as do calls with
+ * S2K_ECDSA_FORCE_WORKLIST.  Same verdicts (tests/test_gpu_keyset_row.py). */
+int s2k_ctx_set_keyset_small_batch_max(s2k_ctx *ctx, uint32_t max_n);
+/* What the last key-set verification call of the context enqueued: S2K_KEYSET_LADDER_LANE (a lane per signature),
+ * S2K_KEYSET_LADDER_ROW (a wavefront per signature), -1 before any.  No synchronisation. */
+#define S2K_KEYSET_LADDER_LANE 0
+#define S2K_KEYSET_LADDER_ROW 1
+int s2k_ctx_last_keyset_ladder(s2k_ctx *ctx);
 /* Times of a ticket on the device's clock, for placement diagnostics (s2k_group_member_stats_ex): after
  * s2k_ctx_ticket_timing(ctx, 1) every submitted ticket records three moments on the device's clock: t0 = its first host-to-device
  * copy is about to start, t1 = its last copy has ended, t2 = its verdicts are in host memory.  t0 <= t1 <= t2 by construction
@@ -433,6 +447,7 @@ const char *s2k_group_last_error(const s2k_group *g);
 int s2k_group_set_key_grouping(s2k_group *g, int mode, uint32_t min_group, uint32_t hash_bits, uint32_t max_tables);
 int s2k_group_set_small_batch_max(s2k_group *g, uint32_t max_n);   /* s2k_ctx_set_small_batch_max on every member (a member's shard is what counts as the batch) */
 int s2k_group_set_mid_batch_max(s2k_group *g, uint32_t max_n);     /* s2k_ctx_set_mid_batch_max on every member */
+int s2k_group_set_keyset_small_batch_max(s2k_group *g, uint32_t max_n);   /* s2k_ctx_set_keyset_small_batch_max on every member */
 int s2k_group_ecdsa_verify_batch(s2k_group *g, size_t n, const uint8_t *pub_xy, const uint8_t *digest32, const uint8_t *r,
                                  const uint8_t *s, uint32_t flags, uint8_t *valid);
 int s2k_group_ecdsa_verify_batch_submit(s2k_group *g, size_t n, const uint8_t *pub_xy, const uint8_t *digest32,
@@ -912,7 +927,12 @@ enum {
   S2K_HP_AFF_DBL, S2K_HP_AFF_ADD,
   /* xyzz29_add_affine_first (xyzz29.h: the first addition of k_generator_part, both points affine): P = (a, b), Q = (d, e) in
    * their lazy forms; out, out2 as XYZZ_ADD; flag = 0 when P and Q share their x (ZZ3 = ZZZ3 = 0) */
-  S2K_HP_XYZZ_ADD_FIRST
+  S2K_HP_XYZZ_ADD_FIRST,
+  /* fe29r.h, pt29r_add_b3: the complete addition on y^2 = x^3 + 7 c^6, the curve a key set's table entries live on (operand
+   * c is W, non-zero; b3 = 21 c^6 is a field element there, not a small constant).  P = (a, b) and Q = (d, e) are points of
+   * secp256k1 given affine ((0, 0): the identity), moved to that curve by (x c^2, y c^3) on the device, added there and
+   * moved back: out, out2, flag, bit 0 of `lazy` and chaining (P + k Q) as PT29R_ADD. */
+  S2K_HP_PT29R_ADD_B3
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);

@@ -1382,6 +1382,158 @@ k_verify_row(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restr
   if (lane == 0) out[sig] = verdict;
 }
 
+// ---- small calls over a KEY SET: the wave-per-signature ladder on the set's 32-chunk tables ----
+// Every layout but the comb keeps {1,3,..,15} 16^c Q, c < 32, and the lead pair L +- phi(L), L = 16^32 Q, per key
+// (kt_geom<32>): the key part of a signature is 64 table additions, no doubling, no table build, no curve check.  The entries
+// are AFFINE points of the key's isomorphic curve y^2 = x^3 + 7 W^6 (one shared Z = W per key, keyed.hip), and the complete
+// addition contains the curve constant: pt29r_add_b3 with b3 = 21 W^6, formed once per signature.  The sum goes back to
+// secp256k1 by pt29r_from_iso and takes the generator part as row_ladder does.
+// limb j (lane j of every row) of element `which` (0: x, 1: y, 2: beta x) of the 128-byte entry at e (lane_tables.h: ke_store3)
+S2K_DEV fer ke_row_load(const uint4* __restrict__ e, uint32_t which, const fer_consts& k) {
+  const uint32_t v = reinterpret_cast<const uint32_t*>(e)[k.j < 8 ? which * 8u + k.j : 24u + which];   // (lanes 9..15: limb 8's word)
+  return k.j <= 8 ? v : 0u;
+}
+struct row_iso {       // of the signature's key: W, W^3, 21 W^6
+  fer w, w3, b3;
+};
+S2K_DEV row_iso row_iso_of(const uint4* __restrict__ kt, const fer_consts& k) {
+  using G = kt_geom<KS_CHUNKS>;
+  row_iso r;
+  r.w = ke_row_load(kt + (size_t)(G::SCR + G::W_SLOT / 3) * 8, G::W_SLOT % 3, k);
+  r.w3 = fer_mul(fer_mul(r.w, r.w, k), r.w, k);
+  r.b3 = fer_small_norm(fer_mul(r.w3, r.w3, k), 21u, k);
+  return r;
+}
+// u * G + (+-k1) * Q + (+-k2) * lambda(Q), Q the key of table kt: u | k1 | k2 | flags in the 17 words `p` (LDS), the digits those
+// of k_verify_fast<MODE_ECDSA_KEYSET> (nibble c of (k - 1) / 2 selects +-(2j + 1) 16^c Q, the lead pair first).  `flip`
+// changes both signs (BIP-340 over a key stored with odd Y).  Digits and addresses are wave-uniform; the result is projective.
+S2K_DEV pt29r row_ladder_keyset(const uint4* __restrict__ kt, const row_iso& iso, const uint32_t* p, bool flip, gt_view gt,
+                                const fer_consts& k) {
+  using G = kt_geom<KS_CHUNKS>;
+  const fer one = k.j == 0 ? 1u : 0u;
+  const uint32_t pf = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[16]);
+  const bool neg1 = ((pf & PF_NEG1) != 0) != flip, neg2 = ((pf & PF_NEG2) != 0) != flip;
+  uint32_t a[4], b[4];       // (k1 - 1) / 2, (k2 - 1) / 2: 128 bits each
+  {
+    uint32_t k1[5], k2[5];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      k1[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[8 + w]);
+      k2[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[12 + w]);
+    }
+    k1[4] = (pf & PF_K1_B128) ? 1u : 0u;
+    k2[4] = (pf & PF_K2_B128) ? 1u : 0u;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      a[w] = (k1[w] >> 1) | (k1[w + 1] << 31);
+      b[w] = (k2[w] >> 1) | (k2[w + 1] << 31);
+    }
+  }
+  auto entry_of = [&](uint32_t c, uint32_t w, bool lam, bool sneg) -> pt29r {   // digit w (signed odd: 2w - 15) of chunk c
+    const bool neg = sneg != (w < 8u);
+    const uint4* e = kt + (size_t)(c * 8u + ((w < 8u) ? (7u - w) : (w - 8u))) * 8;
+    pt29r r;
+    r.x = ke_row_load(e, lam ? 2u : 0u, k);
+    r.y = ke_row_load(e, 1u, k);
+    r.z = one;
+    if (neg) r.y = fer_negate(r.y, 1, k);                           // [2]: the addition normalises y
+    return r;
+  };
+  pt29r acc;
+  {
+    const uint4* e = kt + (size_t)(neg1 == neg2 ? G::LEAD : G::LEAD + 1) * 8;   // +-(L +- phi(L))
+    acc.x = ke_row_load(e, 0u, k);
+    acc.y = ke_row_load(e, 1u, k);
+    acc.z = one;
+    if (neg1) acc.y = fer_negate(acc.y, 1, k);
+  }
+  pt29r a1 = entry_of(0u, a[0] & 15u, false, neg1), a2 = entry_of(0u, b[0] & 15u, true, neg2);
+#pragma unroll 1
+  for (uint32_t c = 0; c < (uint32_t)KS_CHUNKS; ++c) {
+    const pt29r c1 = a1, c2 = a2;
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      a[w] = (a[w] >> 4) | (a[w + 1] << 28);
+      b[w] = (b[w] >> 4) | (b[w + 1] << 28);
+    }
+    a[3] >>= 4;
+    b[3] >>= 4;
+    if (c + 1 < (uint32_t)KS_CHUNKS) {                              // in flight during the additions
+      a1 = entry_of(c + 1, a[0] & 15u, false, neg1);
+      a2 = entry_of(c + 1, b[0] & 15u, true, neg2);
+    }
+    acc = pt29r_add_b3(acc, c1, iso.b3, k);
+    acc = pt29r_add_b3(acc, c2, iso.b3, k);
+  }
+  acc = pt29r_from_iso(acc, iso.w, iso.w3, k);
+  uint32_t u[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) u[w] = p[w];
+  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
+#pragma unroll 1
+  for (uint32_t w = 0; w < gt.windows; ++w) {
+    pt29r q;
+    q.x = fer_from_words(g.x.v, k);
+    q.y = fer_from_words(g.y.v, k);
+    q.z = one;
+    if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));   // in flight during the addition
+    acc = pt29r_add(acc, q, k);
+  }
+  return acc;
+}
+
+// k_verify_row over a key set: the signature names its key by index; an index outside the set or a key the set marks invalid
+// gives 0 without touching a table.  The block's preparation wave is the critical path in front of the ladder here (there is
+// no table build to hide it behind); the signature waves form W^3 and 21 W^6 meanwhile.
+__global__ void __launch_bounds__(320)
+k_verify_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint4* __restrict__ ktab,
+                    const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
+                    const uint8_t* __restrict__ ssig, uint32_t flags, gt_view gt, uint8_t* __restrict__ out) {
+  __shared__ uint32_t prep_s[4][20];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (wave == 4) {                                              // the preparation wave
+    const uint32_t i = blockIdx.x * 4 + lane;
+    if (lane < 4 && i < n) scalar_prep_one(i, dig, rsig, ssig, nullptr, flags, prep_s[lane]);
+    __syncthreads();
+    return;
+  }
+  const uint32_t sig = blockIdx.x * 4 + wave;
+  const fer_consts k = fer_setup(lane);
+  bool ok = false;
+  const uint4* kt = ktab;
+  row_iso iso = {0u, 0u, 0u};
+  if (sig < n) {
+    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
+    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
+    if (ok) {                                                   // (wave-uniform)
+      kt = ktab + (size_t)key * (KS_SLOTS * 8);
+      iso = row_iso_of(kt, k);
+    }
+  }
+  __syncthreads();
+  if (sig >= n) return;
+  const uint32_t* p = prep_s[wave];
+  if (!(ok && (p[16] & PF_OK))) {
+    if (lane == 0) out[sig] = 0;
+    return;
+  }
+  const pt29r acc = row_ladder_keyset(kt, iso, p, false, gt, k);
+  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
+  uint8_t verdict = 0;
+  if (!fer_is_zero(acc.z, k)) {
+    uint32_t rw[8];
+    load_be32(rw, rsig + (size_t)sig * 32);
+    bool match = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(rw, k), acc.z, k), 1, k)), k);
+    if (u256_lt(rw, FE_P_MINUS_N)) {
+      uint32_t r2[8];
+      u256_add(r2, rw, SC_N);
+      match = match || fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(r2, k), acc.z, k), 1, k)), k);
+    }
+    verdict = match ? 1 : 0;
+  }
+  if (lane == 0) out[sig] = verdict;
+}
+
 // FOUR LANES per signature (pt29q.h: a point is X | Y | Z | Z on the lanes of a quad, a layer of the complete formulas one lane
 // product): the ladders for calls between the wave-per-signature kernels and the lane-per-signature ones - a
 // doubling is 550 dependent instructions where a lane needs 1 070, so a lone wave is through its 16 signatures in half the
@@ -1645,13 +1797,14 @@ S2K_DEV void schnorr_msg(const uint8_t* __restrict__ msgs, const uint64_t* __res
 }
 // parseSchnorrSignature (schnorr.go:420-449): r < p, s < n, e = H(r || P || m) mod n.
 // Returns ok; s and e as plain scalars.
-S2K_DEV bool schnorr_parse(size_t i, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
-                           const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-                           sc& s_out, sc& e_out) {
+// (pk_i: the 32 bytes of item i's x-only key, wherever they live)
+S2K_DEV bool schnorr_parse_key(size_t i, const uint8_t* __restrict__ pk_i, const uint8_t* __restrict__ sig,
+                               const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
+                               sc& s_out, sc& e_out) {
   uint32_t r_le[8], pk_le[8];
   load_be32(r_le, sig + i * 64);
   load_be32(s_out.v, sig + i * 64 + 32);
-  load_be32(pk_le, pk + i * 32);
+  load_be32(pk_le, pk_i);
   bool ok = fe_is_canonical_raw(r_le) && sc_is_canonical_raw(s_out.v);
   uint32_t r_be[8], pk_be[8], dg[8];
 #pragma unroll
@@ -1669,6 +1822,11 @@ S2K_DEV bool schnorr_parse(size_t i, const uint8_t* __restrict__ pk, const uint8
   e_out = sc_reduce_once(e_raw);
   if (!ok) s_out = sc_zero();
   return ok;
+}
+S2K_DEV bool schnorr_parse(size_t i, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
+                           const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
+                           sc& s_out, sc& e_out) {
+  return schnorr_parse_key(i, pk + i * 32, sig, msgs, offs, msg_len, s_out, e_out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1767,6 +1925,88 @@ k_schnorr_row(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __restr
   // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
   uint8_t verdict = 0;
   if (!fer_is_zero(acc.z, k)) {
+    const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
+    const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
+    verdict = (mx && my) ? 1 : 0;
+  }
+  if (lane == 0) out[sig] = verdict;
+}
+
+// k_schnorr_row over a key set (row_ladder_keyset above).  The key needs no lift - the set holds X || Y, an odd stored Y flips
+// both half scalars' signs as in k_verify_fast's key-set modes - but r does: one square-root chain per signature, about as
+// long as the ladder itself.  It runs BESIDE the ladder: the block's sixth wave lifts the four r of the block in its four
+// rows while the signature waves run; they read y_r (even) from LDS for the verdict only, behind a second barrier.  The
+// fifth wave hashes the four challenges (over the set's X) and splits -e, as in k_schnorr_row<true>.
+__global__ void __launch_bounds__(384)
+k_schnorr_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint8_t* __restrict__ set_keys,
+                     const uint4* __restrict__ ktab, const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ sig64,
+                     const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len, gt_view gt,
+                     uint8_t* __restrict__ out) {
+  __shared__ uint32_t prep_s[4][20];
+  __shared__ uint32_t yr_s[4][16];          // y_r of the block's signatures, limb j at word j; word 15: r is an x of the curve
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (wave == 4) {                                              // the preparation wave
+    const uint32_t i = blockIdx.x * 4 + lane;
+    if (lane < 4 && i < n) {
+      const uint32_t key = kidx[i];
+      sc s, e;
+      const bool ok = schnorr_parse_key(i, set_keys + (size_t)(key < nkeys ? key : 0u) * 64, sig64, msgs, offs, msg_len, s, e);   // (r < p, s < n)
+      sc k1, k2;
+      bool neg1, neg2;
+      sc_split_glv_odd(sc_neg(e), k1, neg1, k2, neg2);          // schnorr.go:244
+      uint32_t* o = prep_s[lane];
+#pragma unroll
+      for (int w = 0; w < 8; ++w) o[w] = s.v[w];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) o[8 + w] = k1.v[w];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) o[12 + w] = k2.v[w];
+      o[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
+    }
+    __syncthreads();
+    __syncthreads();
+    return;
+  }
+  const fer_consts k = fer_setup(lane);
+  if (wave == 5) {                                              // the lifting wave: row i takes r of the block's signature i
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 4 + k.row;
+    uint32_t rw[8];
+    load_be32(rw, sig64 + (size_t)(i < n ? i : n - 1) * 64);
+    const fer c = fer_curve_rhs(fer_from_words(rw, k), k);
+    const fer y = fer_sqrt_chain(c, k);
+    const bool is_root = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);     // (row by row)
+    const fer y_even = fer_norm(fer_is_odd(y, k) ? fer_negate(y, 1, k) : y, k);
+    yr_s[k.row][k.j] = k.j == 15 ? (is_root ? 1u : 0u) : y_even;
+    __syncthreads();
+    return;
+  }
+  const uint32_t sig = blockIdx.x * 4 + wave;
+  bool ok = false, flip = false;
+  const uint4* kt = ktab;
+  row_iso iso = {0u, 0u, 0u};
+  if (sig < n) {
+    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
+    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
+    if (ok) {                                                   // (wave-uniform)
+      kt = ktab + (size_t)key * (KS_SLOTS * 8);
+      iso = row_iso_of(kt, k);
+      flip = (set_keys[(size_t)key * 64 + 63] & 1u) != 0;       // BIP-340 multiplies lift_x(X): the point with even Y
+    }
+  }
+  __syncthreads();
+  const uint32_t* p = prep_s[wave];
+  ok = ok && (p[16] & PF_OK);
+  pt29r acc = pt29r_identity(k);
+  if (ok) acc = row_ladder_keyset(kt, iso, p, flip, gt, k);     // (wave-uniform)
+  __syncthreads();
+  if (sig >= n) return;
+  // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
+  uint8_t verdict = 0;
+  if (ok && yr_s[wave][15] && !fer_is_zero(acc.z, k)) {
+    uint32_t rw[8];
+    load_be32(rw, sig64 + (size_t)sig * 64);
+    const fer xR = fer_from_words(rw, k), yR = k.j <= 8 ? yr_s[wave][k.j] : 0u;
     const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
     const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
     verdict = (mx && my) ? 1 : 0;
@@ -3289,6 +3529,26 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
+  if (n <= ctx->ks_row_max && ks->chunks != KC_TEETH && !(flags & (S2K_ECDSA_FORCE_WORKLIST | S2K_ECDSA_FORCE_COMPLETE))) {
+    // small calls: a wave per signature over the set's 32-chunk tables (k_verify_row_keyset), one launch; nothing is sorted
+    // and nothing is left for a worklist
+    size_t off[5];
+    (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+    ctx->ks_last = S2K_KEYSET_LADDER_ROW;
+    ctx->kg_counters = nullptr;
+    ctx->last_wl_count = nullptr;
+    prof_mark(ctx, st, 0);
+    prof_mark(ctx, st, 1);
+    prof_mark(ctx, st, 2);
+    k_verify_row_keyset<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)ks->n, (const uint32_t*)d_key_index,
+                                                                 (const uint4*)(ks->base + off[1]), ks->base + off[2], (const uint8_t*)d_dig,
+                                                                 (const uint8_t*)d_r, (const uint8_t*)d_s, flags, ctx->gt_call, (uint8_t*)d_valid);
+    HIP_TRY(ctx, hipGetLastError());
+    prof_mark(ctx, st, 3);
+    prof_mark(ctx, st, 4);
+    prof_mark(ctx, st, 5);
+    return ctx_leave(ctx, st);
+  }
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
   rc = ctx_aux_streams(ctx);
@@ -3307,6 +3567,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   uint32_t* wl = wl_count + 64;
   size_t off[5];
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  ctx->ks_last = S2K_KEYSET_LADDER_LANE;
   ctx->last_wl_count = wl_count;
   HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));       // signatures naming no key of the set stay invalid
@@ -3427,6 +3688,7 @@ int s2k_ctx_set_keyed_ladder(s2k_ctx* ctx, int ladder) {
 }
 
 int s2k_ctx_last_keyed_ladder(s2k_ctx* ctx) { return ctx ? ctx->kt_last : -1; }
+int s2k_ctx_last_keyset_ladder(s2k_ctx* ctx) { return ctx ? ctx->ks_last : -1; }
 
 int s2k_ctx_key_grouping_stats(s2k_ctx* ctx, uint32_t* stats) {
   if (!ctx || !stats) return fail(ctx, S2K_ERR_ARG, "null argument");
@@ -3815,6 +4077,20 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
+  if (n <= ctx->ks_row_max && ks->chunks != KC_TEETH) {
+    // small calls: a wave per signature over the set's 32-chunk tables (k_schnorr_row_keyset), one launch
+    size_t off[5];
+    (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+    ctx->ks_last = S2K_KEYSET_LADDER_ROW;
+    ctx->kg_counters = nullptr;
+    ctx->last_wl_count = nullptr;
+    k_schnorr_row_keyset<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)ks->n, (const uint32_t*)d_key_index, ks->base + off[0],
+                                                                  (const uint4*)(ks->base + off[1]), ks->base + off[2], (const uint8_t*)d_sig, (const uint8_t*)d_msgs,
+                                                                  (const uint64_t*)d_msg_offsets,
+                                                                  (uint32_t)msg_len, ctx->gt_call, (uint8_t*)d_valid);
+    HIP_TRY(ctx, hipGetLastError());
+    return ctx_leave(ctx, st);
+  }
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
   rc = ctx_aux_streams(ctx);
@@ -3840,6 +4116,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   const uint8_t* set_keys = ks->base + off[0];
   ctx->kg_counters = nullptr;
+  ctx->ks_last = S2K_KEYSET_LADDER_LANE;
   ctx->last_wl_count = wl_count;
   HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));       // signatures naming no key of the set stay invalid
@@ -4237,6 +4514,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_pipe_slot(s2k_ctx* ctx, s
   sl.ctx->kg_max_tables = ctx->kg_max_tables;
   sl.ctx->kt_comb = ctx->kt_comb;
   sl.ctx->row_max = ctx->row_max;
+  sl.ctx->ks_row_max = ctx->ks_row_max;
   sl.ctx->quad_max = ctx->quad_max;
   sl.direct = host_pinned(valid, n);
   if (!sl.direct && sl.h_valid_bytes < n) {
@@ -4426,6 +4704,13 @@ int s2k_ctx_set_small_batch_max(s2k_ctx* ctx, uint32_t max_n) {
   return S2K_OK;
 }
 // ECDSA batches above that and up to max_n take the four-lanes-per-signature ladder (k_verify_quad); 0 switches it off.
+// Key-set calls of up to max_n signatures take the wave-per-signature ladder over the set's tables (k_verify_row_keyset /
+// k_schnorr_row_keyset); 0 switches it off.  Comb sets never take it.
+int s2k_ctx_set_keyset_small_batch_max(s2k_ctx* ctx, uint32_t max_n) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  ctx->ks_row_max = max_n;
+  return S2K_OK;
+}
 int s2k_ctx_set_mid_batch_max(s2k_ctx* ctx, uint32_t max_n) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   ctx->quad_max = max_n;

@@ -97,6 +97,15 @@ S2K_DEV void store_be32_unaligned(uint8_t* p, const uint32_t in[8]) {
 #ifndef S2K_ROW_MAX_DEFAULT
 #define S2K_ROW_MAX_DEFAULT 3072
 #endif
+// Largest key-set call the wave-per-signature ladder over the set's tables takes (k_verify_row_keyset / k_schnorr_row_keyset;
+// s2k_ctx_set_keyset_small_batch_max): the largest measured size at which it beats the lane-per-signature key-set path by
+// more than that path's own spread in both algorithms (profiles/r14_keyset_row_time.jsonl, device-resident, a JOINT5 set of
+// 1024 keys: ECDSA 0.14 against 0.28 ms up to 1024 signatures, 0.19 against 0.29 at 2048, 0.24 against 0.28 at 3072, 0.32
+// against 0.29 at 4096; BIP-340 0.10 against 0.33-0.39 up to 1024, 0.20 against 0.39 at 2048, 0.29 against 0.33 at 3072 - inside
+// that path's spread of 0.06 -, 0.39 against 0.33 at 4096)
+#ifndef S2K_KS_ROW_MAX_DEFAULT
+#define S2K_KS_ROW_MAX_DEFAULT 2048
+#endif
 
 // ---- host side ----
 struct s2k_ctx {
@@ -157,6 +166,8 @@ struct s2k_ctx {
   // repeated-key path (keyed.hip): grouping arrays and per-key tables, grown on demand
   uint32_t quad_max = S2K_QUAD_MAX_DEFAULT;   // ... and up to this many the four-lanes-per-signature ladder (s2k_ctx_set_mid_batch_max)
   uint32_t row_max = S2K_ROW_MAX_DEFAULT;   // batches of up to this many signatures take the wave-per-signature ladder (s2k_ctx_set_small_batch_max)
+  uint32_t ks_row_max = S2K_KS_ROW_MAX_DEFAULT;   // key-set calls of up to this many signatures take the row ladder over the set's tables (s2k_ctx_set_keyset_small_batch_max)
+  int ks_last = -1;                  // S2K_KEYSET_LADDER_* of the last key-set verification call (-1: none yet)
   int kg_mode = S2K_KEYS_ADAPTIVE;
   uint32_t kg_min_group = 0, kg_hash_bits = 0, kg_max_tables = KG_MAX_TABLES_DEFAULT;
   uint32_t kg_table_cap = 0;         // 0: none; else the table count the device had memory for (s2k_internal_key_reserve)

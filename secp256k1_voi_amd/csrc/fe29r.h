@@ -277,4 +277,39 @@ S2K_DEV pt29r pt29r_add(const pt29r& p, const pt29r& q, const fer_consts& k) {
   return r;
 }
 
+// Algorithm 7 on y^2 = x^3 + b with b3 = 3 b a FIELD ELEMENT (one unit, in all rows): the curve a key set's table entries
+// live on, y^2 = x^3 + 7 W^6 with b3 = 21 W^6 per key (keyed.hip).  As pt29r_add, the two small multiplications by 21
+// replaced by row products: b3 t2 rides in row 3 of the second layer (idle in pt29r_add), b3 y3' is a layer of its own.
+S2K_DEV pt29r pt29r_add_b3(const pt29r& p, const pt29r& q, fer b3, const fer_consts& k) {
+  const fer Y1 = fer_norm(p.y, k), Y2 = fer_norm(q.y, k);
+  const fer T = fer_mul(fer_sel(k, p.x, Y1, p.z, p.z), fer_sel(k, q.x, Y2, q.z, q.z), k);        // t0 | t1 | t2 | t2
+  fer t0, t1, t2, tu;
+  fer_bcast_rows(T, t0, t1, t2, tu);
+  const fer e = fer_negate(fer_add(fer_sel(k, t0, t1, t0, t0), fer_sel(k, t1, t2, t2, t2)), 2, k);
+  const fer A = fer_add(fer_sel(k, p.x, Y1, p.x, p.x), fer_sel(k, Y1, p.z, p.z, p.z));
+  const fer B = fer_add(fer_sel(k, q.x, Y2, q.x, q.x), fer_sel(k, Y2, q.z, q.z, q.z));
+  const fer U = fer_mul_plus(k.row == 3 ? b3 : A, k.row == 3 ? t2 : B, k.row == 3 ? 0u : e, k);   // t3 | t4 | y3' | b3 t2
+  const fer Ts = fer_small_norm(T, k.row == 0 ? 3u : 1u, k);                                      // 3 t0 | t1 | - | -
+  const fer Y = fer_mul(U, b3, k);                                                                // - | - | b3 y3' | -
+  fer t0p, t1n, t3, t4, t2p, y3;
+  fer_bcast_rows(Ts, t0p, t1n, tu, tu);
+  fer_bcast_rows(k.row == 2 ? Y : U, t3, t4, y3, t2p);
+  const fer V = fer_add(t1n, fer_negate(t2p, 1, k));        // t1 - t2'   [3]
+  const fer W = fer_add(t1n, t2p);                          // t1 + t2'   [2]
+  // X3 = t3 V - t4 y3 | Z3 = t4 W + t3 t0' | Y3 = W V + y3 t0'
+  const fer R = fer_mul_add_mul(fer_sel(k, t3, t4, W, W), fer_sel(k, V, W, V, V), fer_sel(k, fer_negate(t4, 1, k), t3, y3, y3),
+                                fer_sel(k, y3, t0p, t0p, t0p), k);
+  pt29r r;
+  fer_bcast_rows(R, r.x, r.z, r.y, tu);
+  return r;
+}
+// (x, y) -> (x / W^2, y / W^3) takes that curve back to secp256k1: (X : Y : Z) -> (X W : Y : Z W^3), one layer
+S2K_DEV pt29r pt29r_from_iso(const pt29r& p, fer w, fer w3, const fer_consts& k) {
+  const fer M = fer_mul(fer_sel2(k, p.x, p.z), fer_sel2(k, w, w3), k);       // X W | X W | Z W^3 | Z W^3
+  pt29r r;
+  fer_halves(M, r.x, r.z);
+  r.y = p.y;
+  return r;
+}
+
 }  // namespace s2k

@@ -502,6 +502,7 @@ k_pt29q_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
 // the four rows multiply the operands in four different lazy forms and must agree).  Inputs as for k_pt29q_op.
 //   FER_MUL a*b | FER_MUL_PLUS a*b+c | FER_MUL_ADD_MUL a*b+c*d | FER_SMALL 21 a  (out = row 0's result, flag = the rows agree)
 //   PT29R_DBL / PT29R_ADD: chained `reps` times like the quad forms
+//   PT29R_ADD_B3: pt29r_add_b3 on y^2 = x^3 + 7 c^6 (c = W), P and Q moved there and the sum moved back
 //   FER_SWAPS: out[0..255] = what v_permlane16_swap / v_permlane32_swap make of the lane numbers (n >= 8)
 __global__ void __launch_bounds__(256)
 k_pt29r_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
@@ -580,11 +581,29 @@ k_pt29r_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
     s.y = fe29_normalize_weak(e);
     s.z = fe29_one();
   }
+  fer w1 = 0, w3 = 0, b3 = 0;
+  if (op == S2K_HP_PT29R_ADD_B3) {
+    // c is W: P and Q move to y^2 = x^3 + 7 W^6 by (x W^2, y W^3), affine there; (0, 0) stands for the identity
+    const fe29 cw2 = fe29_sqr(cn), cw3 = fe29_mul(cw2, cn);
+    p.x = fe29_mul(a, cw2);
+    p.y = fe29_mul(b, cw3);
+    p.z = fe29_one();
+    s.x = fe29_mul(d, cw2);
+    s.y = fe29_mul(e, cw3);
+    s.z = fe29_one();
+    if (fe29_is_zero(a) && fe29_is_zero(b)) p = pt29_identity();
+    if (fe29_is_zero(d) && fe29_is_zero(e)) s = pt29_identity();
+    w1 = fer_from_fe29(cn, k);
+    w3 = fer_from_fe29(cw3, k);
+    b3 = fer_small_norm(fer_mul(w3, w3, k), 21u, k);
+  }
   p.y = fe29_lazy_form(p.y, lazy & 1u);        // y may come with two units
   pt29r rc = pt29r_from(p, k);
   const pt29r sc_ = pt29r_from(s, k);
 #pragma unroll 1
-  for (uint32_t i = 0; i < reps; ++i) rc = op == S2K_HP_PT29R_DBL ? pt29r_double(rc, k) : pt29r_add(rc, sc_, k);
+  for (uint32_t i = 0; i < reps; ++i)
+    rc = op == S2K_HP_PT29R_DBL ? pt29r_double(rc, k) : op == S2K_HP_PT29R_ADD_B3 ? pt29r_add_b3(rc, sc_, b3, k) : pt29r_add(rc, sc_, k);
+  if (op == S2K_HP_PT29R_ADD_B3) rc = pt29r_from_iso(rc, w1, w3, k);
   const pt29 r = pt29r_gather(rc, k);
   // the four rows must hold the same point
   uint32_t agree = 1;
@@ -863,7 +882,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex serves S2K_IMPL_FAST only (8x32: s2k_fp_op_batch)");
   const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN, AFF_*: bits 20.. of `lazy` = how often the operation is chained (0: once)
   lazy &= 0xfffffu;
-  if (op < 0 || op > S2K_HP_XYZZ_ADD_FIRST) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (op < 0 || op > S2K_HP_PT29R_ADD_B3) return fail(ctx, S2K_ERR_ARG, "bad op");
   if (op == S2K_HP_FER_SWAPS && n < 8) return fail(ctx, S2K_ERR_ARG, "S2K_HP_FER_SWAPS writes 256 bytes: n >= 8");
   if (n == 0) return S2K_OK;
   if (!in || !in[0] || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
@@ -882,7 +901,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   HIP_TRY(ctx, dout.alloc(n * 32));
   if (out2) HIP_TRY(ctx, dout2.alloc(n * 32));
   if (flag) HIP_TRY(ctx, dflag.alloc(n));
-  if (op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS)
+  if ((op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS) || op == S2K_HP_PT29R_ADD_B3)
     k_pt29r_op<<<blocks_for(64 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_AFF_DBL || op == S2K_HP_AFF_ADD)
     k_aff_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);

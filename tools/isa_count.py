@@ -16,6 +16,8 @@ those of the source:
   k_verify_fast<ECDSA_COMB>   round loop 19 (its exit test stands between the additions and the doubling: 18 doublings),
                               addition loop 2
   k_verify_fast<SCHNORR_KEYED> / <SCHNORR_COMB>   the BIP-340 ladders over the same tables: the loops of ECDSA_KEYED / ECDSA_COMB
+  k_verify_row                table 7 | 32 windows x (doubling loop 4, two additions) | generator part GT_WINDOWS      (a wave per signature)
+  k_verify_row_keyset / k_schnorr_row_keyset   chunk loop 32 (two additions each) | generator part GT_WINDOWS      (the same over a key set)
 
 This is what ties the roofline's instruction counts (profiles/r04_valu_counts.json, PMC) to the binary that is measured:
 tests/test_counts_cpu.py recounts the built library and compares, bench.py recounts the library it loaded.
@@ -316,6 +318,69 @@ def keyset_joint_wide(lib, w):
             "instructions": len(g.ins)}
 
 
+def _flat_weights(g, trips):
+    """block -> product of the trip counts of the loops around it, every block of a loop alike (the wave-per-signature
+    kernels' loops are entered in the middle - a prefetch stands in front of them - and leave at their end)"""
+    assert len(trips) == len(g.loops), "loops without a trip count"
+    w = [1] * len(g.blocks)
+    for k, l in enumerate(g.loops):
+        for b in l["blocks"]:
+            w[b] *= trips[k]
+    return w
+
+
+def _mads_in(g, body):
+    return sum(1 for b in body for i in range(*g.blocks[b]) if g.ins[i][1].startswith("v_mad_u64_u32"))
+
+
+SQRT_CHAIN_TRIPS = [3, 3, 2, 11, 22, 44, 88, 44, 3, 23, 6, 2]      # fer_sqrt_chain's squaring runs (engine.hip), in order
+
+
+def row_general(lib, gt_windows=None):
+    """k_verify_row, a wave per signature: the key's table (the loop's addition runs 7 times), 32 windows of 4 doublings and two
+    additions, gt_windows generator additions.  The straight-line code of the block's preparation wave is in the sum (as it is
+    in row_keyset's: the same function)."""
+    if gt_windows is None:
+        gt_windows = generator_windows(lib)
+    g = Cfg(disassemble(lib, "_Z12k_verify_rowj"))
+    top = g.top_level()
+    assert len(top) == 3, ("unexpected loop structure of k_verify_row", [g.loops[k]["entries"] for k in top])
+    dbl = g.children(top[1])
+    assert not g.children(top[0]) and len(dbl) == 1 and not g.children(dbl[0]) and not g.children(top[2]), "unexpected inner loops"
+    trips = {top[0]: 7, top[1]: 32, dbl[0]: 4, top[2]: gt_windows}
+    valu, mad = g.count(_flat_weights(g, trips))
+    return {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad,
+            "valu_per_trip": {"table": g.valu_in(g.loops[top[0]]["blocks"]), "window": g.valu_in(g.loops[top[1]]["blocks"]),
+                              "doubling": g.valu_in(g.loops[dbl[0]]["blocks"]), "generator": g.valu_in(g.loops[top[2]]["blocks"])},
+            "instructions": len(g.ins)}
+
+
+def row_keyset(lib, schnorr=False, gt_windows=None):
+    """k_verify_row_keyset / k_schnorr_row_keyset, a wave per signature over a key set's 32-chunk table: one loop over the 32
+    chunks with two additions on the key's isomorphic curve each (64 key additions), then gt_windows generator additions.
+    BIP-340: the squaring runs of the square-root chain belong to the block's LIFTING wave, not to a signature wave; they
+    are counted apart (valu_lift_wave: that wave's chain, for the block's four signatures at once)."""
+    if gt_windows is None:
+        gt_windows = generator_windows(lib)
+    name = "k_schnorr_row_keyset" if schnorr else "k_verify_row_keyset"
+    g = Cfg(disassemble(lib, "_Z20k_schnorr_row_keyset" if schnorr else "_Z19k_verify_row_keyset"))
+    top = g.top_level()
+    assert len(top) == (14 if schnorr else 2) and not any(g.children(k) for k in top), ("unexpected loop structure of " + name, [g.loops[k]["entries"] for k in top])
+    chunk, gen, sq = top[0], top[1], top[2:]
+    cb, gb = g.loops[chunk]["blocks"], g.loops[gen]["blocks"]
+    # two additions with five products each per chunk (one of them a sum of two), one addition of four per window
+    assert _mads_in(g, cb) > 2 * _mads_in(g, gb) and all(len(g.loops[k]["blocks"]) == 1 and _mads_in(g, g.loops[k]["blocks"]) == 15 for k in sq), \
+        "cannot tell the loops of %s apart" % name
+    trips = {chunk: 32, gen: gt_windows}
+    trips.update({k: 0 for k in sq})
+    valu, mad = g.count(_flat_weights(g, trips))
+    out = {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad, "key_additions": 64, "generator_additions": gt_windows,
+           "valu_per_trip": {"chunk": g.valu_in(cb), "generator": g.valu_in(gb)}, "instructions": len(g.ins)}
+    if schnorr:
+        out["valu_lift_wave"] = sum(t * g.valu_in(g.loops[k]["blocks"]) for t, k in zip(SQRT_CHAIN_TRIPS, sq))
+    return out
+
+
 def generator_windows(lib):
     """ceil(256 / window bits) of THIS library (s2k_generator_window_bits: a host function, no GPU needed)"""
     import ctypes
@@ -330,7 +395,9 @@ def static_counts(lib=DEFAULT_LIB, gt_windows=None):
             "k_verify_fast_keyset": keyset(lib),
             "k_verify_fast_keyset_joint": keyset_joint(lib), "k_verify_fast_keyset_joint5": keyset_joint_wide(lib, 5),
             "k_verify_fast_keyset_joint6": keyset_joint_wide(lib, 6),
-            "k_verify_fast_schnorr_keyed": keyed(lib, 6, "SCHNORR_KEYED"), "k_verify_fast_schnorr_comb": comb(lib, 17, "SCHNORR_COMB")}
+            "k_verify_fast_schnorr_keyed": keyed(lib, 6, "SCHNORR_KEYED"), "k_verify_fast_schnorr_comb": comb(lib, 17, "SCHNORR_COMB"),
+            "k_verify_row": row_general(lib, gt_windows), "k_verify_row_keyset": row_keyset(lib, False, gt_windows),
+            "k_schnorr_row_keyset": row_keyset(lib, True, gt_windows)}
 
 
 if __name__ == "__main__":
