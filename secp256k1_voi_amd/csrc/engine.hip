@@ -1,4 +1,4 @@
-// engine.hip — gfx950 kernels and the C-ABI of include/secp256k1_voi_amd.h.
+// engine.hip — gfx950 kernels and the C-ABI of include/secp256k1_voi_amd.h (the generator tables: gtable.hip).
 //
 // One lane per signature / per point; every lane of a wave runs the same instruction
 // stream (complete formulas, fixed windows), so there is no divergence on secret- or
@@ -36,80 +36,6 @@
 #include "sha256.h"
 
 using namespace s2k;
-
-// ---------------------------------------------------------------------------------------
-// Generator tables, resident in HBM:  GT_WINDOWS = ceil(256 / GT_BITS) tables of 2^GT_BITS affine
-// points (64 MiB at 16 bits, 3 GiB at 22, 11 GiB at 24, 40 GiB at 26: the default),
-//   T_0[d] = d * G - sum_{i>=1} B_i,   T_i[d] = (d + 1) * B_i,   B_i = 2^(GT_BITS i) * G,
-// so that  u*G = sum_i T_i[(u >> GT_BITS i) & mask]  with GT_WINDOWS mixed additions, no
-// doublings, no zero-digit special case (no entry is the identity) and no final correction.
-// The reference's scalarBaseMultVartime (point_mul_table.go:197-211) is the same idea with
-// 8-bit windows, sized for a CPU cache (510 KiB); HBM capacity buys wider windows here.  At 16
-// bits the even-numbered windows of the reference's table blob are entries of these tables
-// (tests/golden/gentable.json).
-// Entry layout: 16 x u32 = X limbs (little-endian words) then Y limbs, 64-byte aligned.
-// ---------------------------------------------------------------------------------------
-// bases[i] = B_i = 2^(bits i) G (affine, 16 words) for i < windows; bases[windows] = -sum_{i>=1} B_i
-__global__ void k_gen_gtable_bases(uint32_t* __restrict__ bases, uint32_t bits, uint32_t windows) {
-  apt g;
-  g.x = fe_from_limbs(FE_GX);
-  g.y = fe_from_limbs(FE_GY);
-  pt cur = pt_from_affine(g), sum = pt_identity();
-#pragma unroll 1
-  for (uint32_t i = 0; i <= windows; ++i) {
-    apt a;
-    if (i < windows) {
-      pt_to_affine(a, cur);
-      if (i >= 1) sum = pt_add_complete(sum, cur);
-#pragma unroll 1
-      for (uint32_t t = 0; t < bits; ++t) cur = pt_double_complete(cur);
-    } else {
-      pt_to_affine(a, pt_cond_neg(sum, true));
-    }
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      bases[i * 16 + w] = a.x.v[w];
-      bases[i * 16 + 8 + w] = a.y.v[w];
-    }
-  }
-}
-// one lane per entry: m * B_w by a double-and-add of bits + 1 steps (m = digit, or digit + 1 for w >= 1)
-// (block0: the first block of this launch - the background build launches a table window by window)
-__global__ void __launch_bounds__(256) k_gen_gtable(uint32_t* __restrict__ gt, const uint32_t* __restrict__ bases, uint32_t bits, uint32_t windows,
-                                                    uint32_t block0) {
-  size_t id = ((size_t)block0 + blockIdx.x) * 256 + threadIdx.x;
-  uint32_t window = (uint32_t)(id >> bits), digit = (uint32_t)id & ((1u << bits) - 1u);
-  apt b;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    b.x.v[w] = bases[window * 16 + w];
-    b.y.v[w] = bases[window * 16 + 8 + w];
-  }
-  uint32_t m = window ? digit + 1 : digit;      // <= 2^bits
-  pt acc = pt_identity();
-#pragma unroll 1
-  for (int bit = (int)bits; bit >= 0; --bit) {
-    acc = pt_double_complete(acc);
-    pt sum = pt_add_mixed(acc, b);
-    acc = pt_select((m >> bit) & 1u, acc, sum);
-  }
-  if (window == 0) {
-    apt c;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-      c.x.v[w] = bases[windows * 16 + w];
-      c.y.v[w] = bases[windows * 16 + 8 + w];
-    }
-    acc = pt_add_mixed(acc, c);
-  }
-  apt a;
-  pt_to_affine(a, acc);
-  uint4* o = reinterpret_cast<uint4*>(gt + (id << 4));
-  o[0] = make_uint4(a.x.v[0], a.x.v[1], a.x.v[2], a.x.v[3]);
-  o[1] = make_uint4(a.x.v[4], a.x.v[5], a.x.v[6], a.x.v[7]);
-  o[2] = make_uint4(a.y.v[0], a.y.v[1], a.y.v[2], a.y.v[3]);
-  o[3] = make_uint4(a.y.v[4], a.y.v[5], a.y.v[6], a.y.v[7]);
-}
 
 // one signature, complete formulas only (secec/ecdsa.go:392-470)
 S2K_DEV uint8_t verify_complete(size_t idx, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig,
@@ -2381,6 +2307,149 @@ static inline void prof_mark(s2k_ctx* ctx, hipStream_t st, int slot) {
   if (slot == PROF_EV - 1) ctx->prof_used += PROF_EV;
 }
 
+// The planes of ctx->ws for a batch of n (layout: WS_* below; lane_ws_of), after s2k_internal_ensure_ws(ctx, n).
+struct lane_ws {
+  uint32_t *qt, *fin, *prep, *gp, *pref, *smont, *wl_count, *wl;
+  size_t stride;
+};
+
+// One launcher per kernel: it enqueues on the stream it is given and does nothing else (error checks, events and profiling
+// marks stay with the flows).  `ctx` gives the call's generator table (gt_call) and the worklist kernels' grid.
+// launch_scalar_prep: signatures [first, first + count) on `lanes` lanes (the planes are linear in the signature index: a piece
+// is the same kernel on shifted pointers); launch_ladder: the only place that names an instantiation of k_verify_fast;
+// launch_schnorr_row: prep == nullptr is k_schnorr_row<true>, whose fifth wave prepares.
+static void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t count, uint32_t lanes, const uint8_t* dig, const uint8_t* r,
+                               const uint8_t* s, const uint8_t* recid, uint32_t flags) {
+  k_scalar_prep<<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)count, lanes, dig + first * 32, r + first * 32, s + first * 32,
+                                                  recid ? recid + first : nullptr, flags, w.prep + first, w.pref + first, w.smont + first,
+                                                  w.stride);
+}
+static void launch_generator_part(const s2k_ctx* ctx, hipStream_t st, const lane_ws& w, uint32_t first, uint32_t end) {
+  k_generator_part<<<blocks_for(end - first), 256, 0, st>>>(first, end, w.prep, ctx->gt_call, w.gp, w.stride);
+}
+static void launch_ladder(const s2k_ctx* ctx, hipStream_t st, int mode, size_t n, uint32_t kvf, const uint8_t* pub, const uint8_t* rsig,
+                          const lane_ws& w, uint8_t* out, uint8_t* out_pts, uint64_t* clk, const key_groups& kg) {
+#define S2K_LADDER(M)                                                                                                              \
+  case M:                                                                                                                          \
+    k_verify_fast<M><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count, \
+                                                    w.wl, w.stride, out_pts, clk, kg);                                             \
+    break;
+  switch (mode) {
+    S2K_LADDER(MODE_ECDSA)
+    S2K_LADDER(MODE_SCHNORR)
+    S2K_LADDER(MODE_RECOVER)
+    S2K_LADDER(MODE_POINT)
+    S2K_LADDER(MODE_ECDSA_KEYED)
+    S2K_LADDER(MODE_ECDSA_LEFT)
+    S2K_LADDER(MODE_SCHNORR_KEYED)
+    S2K_LADDER(MODE_SCHNORR_LEFT)
+    S2K_LADDER(MODE_ECDSA_KEYSET)
+    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT)
+    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT5)
+    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT6)
+    S2K_LADDER(MODE_SCHNORR_KEYSET)
+    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT)
+    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT5)
+    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT6)
+    S2K_LADDER(MODE_ECDSA_COMB)
+    S2K_LADDER(MODE_SCHNORR_COMB)
+    default:   // (a launch of nothing would leave the verdicts as they were and report success)
+      fprintf(stderr, "secp256k1_voi_amd: launch_ladder: no ladder of mode %d\n", mode);
+      abort();
+  }
+#undef S2K_LADDER
+}
+static void launch_affine_finish(hipStream_t st, int mode, size_t n, uint32_t T, const uint8_t* rsig, const lane_ws& w, uint8_t* out,
+                                 uint8_t* out_pts) {
+  if (mode == MODE_RECOVER)
+    k_affine_finish<MODE_RECOVER><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, rsig, w.fin, out, w.stride, out_pts);
+  else
+    k_affine_finish<MODE_SCHNORR><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, rsig, w.fin, out, w.stride, out_pts);
+}
+static void launch_ecdsa_verify(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig,
+                                const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
+  k_ecdsa_verify<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pub, dig, r, s, flags, out, ctx->gt_call, w.qt, w.stride);
+}
+static void launch_verify_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig,
+                                   const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
+  k_verify_fallback<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, pub, dig, r, s, flags, out, ctx->gt_call, w.qt, w.stride);
+}
+static void launch_verify_fallback_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* keys, const uint32_t* kidx,
+                                          const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
+  k_verify_fallback_keyset<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, keys, kidx, dig, r, s, flags, out, ctx->gt_call, w.qt,
+                                                                    w.stride);
+}
+static void launch_schnorr_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
+                                const uint64_t* offs, uint32_t msg_len) {
+  k_schnorr_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, w.prep, w.stride);
+}
+static void launch_schnorr_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
+                                    const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out) {
+  k_schnorr_fallback<<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, pk, sig, msgs, offs, msg_len, out, ctx->gt_call, w.qt,
+                                                    w.stride);
+}
+static void launch_schnorr_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
+                                    const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out) {
+  k_schnorr_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, pk, sig, msgs, offs, msg_len, out, ctx->gt_call, w.qt,
+                                                              w.stride);
+}
+static void launch_recover_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
+                                    const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
+  k_recover_fallback<<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, dig, r, s, recid, ok, pub65, ctx->gt_call, w.qt, w.stride);
+}
+static void launch_recover_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
+                                    const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
+  k_recover_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, dig, r, s, recid, ok, pub65, ctx->gt_call, w.qt, w.stride);
+}
+static void launch_hot_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2, const uint8_t* pts65, uint8_t* pub64,
+                            uint32_t* status) {
+  k_hot_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, u1, u2, pts65, pub64, w.prep, w.stride, w.wl_count, w.wl, status);
+}
+static void launch_point_fallback(const s2k_ctx* ctx, hipStream_t st, bool all, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2,
+                                  const uint8_t* pts65, uint8_t* out65, uint32_t* status) {
+  if (all)
+    k_point_fallback<true><<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, u1, u2, pts65, out65, ctx->gt_call, w.qt, w.stride,
+                                                          status);
+  else
+    k_point_fallback<false><<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, u1, u2, pts65, out65, ctx->gt_call, w.qt,
+                                                                     w.stride, status);
+}
+static void launch_verify_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                              uint32_t flags, uint8_t* out) {
+  k_verify_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, pub, dig, r, s, flags, ctx->gt_call, out);
+}
+static void launch_verify_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
+                                     const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
+  k_verify_row_keyset<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, ktab, tinfo, dig, r, s, flags, ctx->gt_call,
+                                                               out);
+}
+static void launch_schnorr_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
+                               const uint64_t* offs, uint32_t msg_len, const uint32_t* prep, size_t stride, uint8_t* out) {
+  if (!prep)
+    k_schnorr_row<true><<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, nullptr, 0, ctx->gt_call, out);
+  else
+    k_schnorr_row<false><<<(unsigned)((n + 3) / 4), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, prep, stride, ctx->gt_call, out);
+}
+static void launch_schnorr_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
+                                      const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
+                                      uint32_t msg_len, uint8_t* out) {
+  k_schnorr_row_keyset<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, set_keys, ktab, tinfo, sig, msgs, offs,
+                                                                msg_len, ctx->gt_call, out);
+}
+static void launch_recover_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                               const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
+  k_recover_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, dig, r, s, recid, ctx->gt_call, ok, pub65);
+}
+static void launch_verify_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* r, const lane_ws& w, uint8_t* out) {
+  k_verify_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, pub, r, w.prep, ctx->gt_call, out, w.stride);
+}
+static void launch_schnorr_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const lane_ws& w, uint8_t* out) {
+  k_schnorr_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, pk, sig, w.prep, ctx->gt_call, out, w.stride);
+}
+static void launch_recover_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* r, const lane_ws& w, uint8_t* out) {
+  k_recover_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, r, w.prep, ctx->gt_call, w.fin, out, w.stride);
+}
+
 // Front end of the grouped flows (ECDSA and BIP-340 verification): everything up to the ladders.
 // Caller's stream: grouping by key (k_key_insert / k_key_alloc / k_key_place), then the per-key tables.
 // Second stream: the scalar preparation (`launch_prep`), then the generator part u1*G in two pieces.  These
@@ -2445,8 +2514,8 @@ static bool kg_adaptive_decide(s2k_ctx* ctx) {
 }
 
 template <class PrepFn>
-static int grouped_front_forked(s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* d_keys, int key_bytes, uint32_t* prep,
-                                uint32_t* gp, size_t stride, PrepFn launch_prep, key_groups* kg, bool gp_in_prep) {
+static int grouped_front_forked(s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* d_keys, int key_bytes, const lane_ws& w,
+                                PrepFn launch_prep, key_groups* kg, bool gp_in_prep) {
   // One stream (a child context of submit / wait): the grouping and the tables first - they need the keys only, which
   // arrive first -, then the preparation and the generator part; other tickets' kernels fill the machine meanwhile.
   const bool one_stream = ctx->s_aux == st;
@@ -2457,13 +2526,13 @@ static int grouped_front_forked(s2k_ctx* ctx, hipStream_t st, size_t n, const ui
     launch_prep(ctx->s_aux);
     HIP_TRY(ctx, hipGetLastError());
     if (n_first && !gp_in_prep) {
-      k_generator_part<<<blocks_for(n_first), 256, 0, ctx->s_aux>>>(0u, n_first, prep, ctx->gt_call, gp, stride);
+      launch_generator_part(ctx, ctx->s_aux, w, 0u, n_first);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
   int rc = s2k_internal_key_group(ctx, n, d_keys, key_bytes, st, kg);
   if (rc) return rc;
-  kg->gp = gp;
+  kg->gp = w.gp;
   kg->part = 0;
   kg->nparts = ctx->kg_parts;
   prof_mark(ctx, st, 1);
@@ -2490,14 +2559,14 @@ static int grouped_front_forked(s2k_ctx* ctx, hipStream_t st, size_t n, const ui
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_mid, 0));
   }
   if (n_first < n) {
-    k_generator_part<<<blocks_for(n - n_first), 256, 0, ctx->s_aux>>>(n_first, (uint32_t)n, prep, ctx->gt_call, gp, stride);
+    launch_generator_part(ctx, ctx->s_aux, w, n_first, (uint32_t)n);
     HIP_TRY(ctx, hipGetLastError());
   }
   return S2K_OK;
 }
 template <class PrepFn>
-static int grouped_front(s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* d_keys, int key_bytes, uint32_t* prep,
-                         uint32_t* gp, size_t stride, PrepFn launch_prep, key_groups* kg, bool gp_in_prep = false) {
+static int grouped_front(s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* d_keys, int key_bytes, const lane_ws& w,
+                         PrepFn launch_prep, key_groups* kg, bool gp_in_prep = false) {
   int rc = ctx_aux_streams(ctx);
   if (rc) return rc;
   // the buffers the grouping needs are reserved BEFORE the fork: growing one is a device-wide synchronisation
@@ -2506,7 +2575,7 @@ static int grouped_front(s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* 
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
-  rc = grouped_front_forked(ctx, st, n, d_keys, key_bytes, prep, gp, stride, launch_prep, kg, gp_in_prep);
+  rc = grouped_front_forked(ctx, st, n, d_keys, key_bytes, w, launch_prep, kg, gp_in_prep);
   // error or not, the caller's stream waits for the second one again, and the context's next call for this one: an
   // error return leaves nothing of this call in flight behind the context's back
   ctx_aux_join(ctx, st);
@@ -2572,6 +2641,21 @@ int s2k_device_pci_bus_id(int device, char* out, size_t len) {
 constexpr size_t WS_QT = 0, WS_FIN = TBL_WORDS, WS_PREP = TBL_WORDS + FIN_WORDS, WS_PREF = WS_QT, WS_SMONT = WS_QT + 10,
                  WS_GP = WS_PREP + PREP_WORDS, WS_LANE_WORDS = WS_GP + 3 * FQT_FE_WORDS;
 static_assert(TBL_WORDS >= QT_WORDS, "the complete path's table must fit in the fast path's region");
+static lane_ws lane_ws_of(const s2k_ctx* ctx, size_t n) {
+  const size_t stride = lane_stride(n);
+  uint32_t* ws = (uint32_t*)ctx->ws;
+  lane_ws w;
+  w.qt = ws + WS_QT * stride;
+  w.fin = ws + WS_FIN * stride;
+  w.prep = ws + WS_PREP * stride;
+  w.gp = ws + WS_GP * stride;
+  w.pref = ws + WS_PREF * stride;
+  w.smont = ws + WS_SMONT * stride;
+  w.wl_count = ws + WS_LANE_WORDS * stride;
+  w.wl = w.wl_count + 64;
+  w.stride = stride;
+  return w;
+}
 
 size_t s2k_ecdsa_workspace_bytes(size_t n) {
   return (lane_stride(n) * WS_LANE_WORDS + 64 + lane_stride(n)) * sizeof(uint32_t);
@@ -2603,329 +2687,13 @@ __attribute__((visibility("hidden"))) int s2k_internal_ensure_ws(s2k_ctx* ctx, s
   return S2K_OK;
 }
 
-// The resident generator tables are shared by the contexts of a device (one context per goroutine / thread is the intended
-// use): per device one registry with its own lock, reference counted, the last context to go frees it.  A
-// registry holds tables of SEVERAL widths:
-//   * the first table (GT_BITS_FIRST = 20 bits, 0.8 GiB) is built inside the first s2k_ctx_create: < 0.1 s to a usable context;
-//   * an automatic context then starts ONE background thread per device that allocates and builds the wide table
-//     (GT_BITS_TARGET = 26 bits / 40 GiB when the device has twice that free and the budget allows, else 24 / 11 GiB, else 22 /
-//     3 GiB, else nothing) on a stream of its own, beside whatever the contexts are doing; when it is done, the next CALL of
-//     every automatic context uses it (ctx_enter loads the view once; a call never changes tables between its launches).  A
-//     failed allocation or build leaves the contexts on the table they have, and is not tried again while the registry lives;
-//   * s2k_ctx_create_ex with an explicit width uses exactly that table, built synchronously unless it exists or is being built.
-// The builder thread is never detached: the last context to go cancels it (it looks at the flag before it allocates, between
-// the windows of a table and before it publishes) and joins it; a process that exits with contexts alive does the same from an
-// atexit handler, so that no thread of this library is inside the HIP runtime while that is torn down.
-// The reference's analogue is a 510 KiB unpack at package init (point_mul_table.go:75-100).
 namespace {
-struct gtable_dev {
-  std::mutex m;
-  std::condition_variable cv;                     // a build has ended (either kind), the builder has been kicked or cancelled
-  std::atomic<uint32_t*> table[GT_BITS_MAX + 1];  // by width; non-null = built and readable
-  bool being_built[GT_BITS_MAX + 1] = {};         // a thread is building this width outside the lock (others wait for it)
-  std::atomic<int> auto_bits{0};                  // width the automatic contexts use now (0: registry empty)
-  int refs = 0;
-  std::atomic<bool> kicked{false};                // an entry point has enqueued its first call on the device (ctx_leave)
-  int target = 0;                                 // width the background build aims for (0: none wanted / none possible)
-  bool building = false;                          // the builder thread is running
-  bool gave_up = false;                           // a background build failed: not tried again by later contexts of this registry
-  bool closing = false;                           // the last context is waiting for the builder to end: nobody acquires meanwhile
-  std::atomic<bool> cancel{false};                // the builder is to stop at its next look
-  std::atomic<size_t> pending{0};                 // bytes the builder is about to take from the device (s2k_internal_gt_pending_bytes)
-  std::thread builder;
-  char note[200] = {0};                           // why the target is what it is (s2k_ctx_gt_note; read and written under m)
-  gtable_dev() {
-    for (auto& t : table) t.store(nullptr);
-  }
-};
-gtable_dev g_gtable[64];
-std::atomic<size_t> g_gt_budget{0};               // s2k_set_generator_table_budget: bytes per device the tables may take (0: by free memory)
 std::atomic<size_t> g_keyset_budget{0};           // s2k_set_table_memory_budgets: what counts as free for a key set's joint tables (0: what is free)
-
-// allocate and build the table of `bits` on `stream` (null: the default stream); synchronises that stream.  With `cancel` the
-// table is built window by window and the flag is looked at in between (hipErrorNotReady: cancelled, nothing is left allocated).
-hipError_t gtable_build(int bits, hipStream_t stream, uint32_t** out, const std::atomic<bool>* cancel = nullptr,
-                        std::atomic<size_t>* pending = nullptr) {
-  const uint32_t windows = gt_windows_of(bits);
-  uint32_t *table = nullptr, *bases = nullptr;
-  hipError_t e = hipMalloc((void**)&table, gt_bytes_of(bits));
-  if (pending) pending->store(0);                 // (taken, or not to be had)
-  if (e == hipSuccess) e = hipMalloc((void**)&bases, (windows + 1) * 64);
-  if (e == hipSuccess) {
-    k_gen_gtable_bases<<<1, 1, 0, stream>>>(bases, (uint32_t)bits, windows);
-    const unsigned per_window = (unsigned)(((size_t)1 << bits) / 256);
-    if (!cancel) {
-      k_gen_gtable<<<per_window * windows, 256, 0, stream>>>(table, bases, (uint32_t)bits, windows, 0u);
-      e = hipGetLastError();
-    } else {
-      for (uint32_t w = 0; w < windows && e == hipSuccess; ++w) {
-        if (cancel->load()) {
-          e = hipErrorNotReady;
-          break;
-        }
-        k_gen_gtable<<<per_window, 256, 0, stream>>>(table, bases, (uint32_t)bits, windows, w * per_window);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      }
-    }
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  else (void)hipStreamSynchronize(stream);
-  if (bases) (void)hipFree(bases);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (table) (void)hipFree(table);
-    return e;
-  }
-  *out = table;
-  return hipSuccess;
-}
-
-// does a wide table of `bits` fit NOW: twice its size free on the device, so that the tables never take more than half of
-// what is left for key sets, workspaces and other processes; and inside the budget.  Asked when the target is chosen and again
-// by the builder right before each allocation (half a second or more later).
-bool gtable_fits(int bits, size_t* free_out) {
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (free_out) *free_out = free_b;
-  const size_t need = gt_bytes_of(bits), budget = g_gt_budget.load();
-  if (budget && need + gt_bytes_of(GT_BITS_FIRST) > budget) return false;
-  return free_b >= 2 * need;
-}
-// the widest of 26 / 24 / 22 (not above `from`, above the first table) that fits; 0: none.  Caller holds g.m (the note).
-int gtable_pick_target(gtable_dev& g, int from) {
-  size_t free_b = 0;
-  const size_t budget = g_gt_budget.load();
-  for (int bits : {26, 24, 22}) {
-    if (bits > from || bits > GT_BITS_TARGET || bits <= GT_BITS_FIRST) continue;
-    if (!gtable_fits(bits, &free_b)) continue;
-    snprintf(g.note, sizeof g.note, "%d-bit windows: %.1f GiB of %.1f GiB free%s", bits, gt_bytes_of(bits) / 1073741824.0, free_b / 1073741824.0,
-             budget ? " (inside the budget)" : "");
-    return bits;
-  }
-  snprintf(g.note, sizeof g.note, "no wide table fits (%.1f GiB free, budget %.1f GiB): staying on %d bits", free_b / 1073741824.0,
-           budget / 1073741824.0, GT_BITS_FIRST);
-  return 0;
-}
-
-void gtable_builder_main(int device, int bits) {
-  gtable_dev& g = g_gtable[device];
-  // The allocation of tens of gigabytes holds the runtime's allocator for a second or two, and whatever another thread asks of
-  // the runtime meanwhile (its first call's workspace ...) waits behind it: 0.1-0.3 s from s2k_ctx_create to the first verdict
-  // became 2.3 s whenever the two collided.  So the build starts when the context's first call has been enqueued (ctx_leave),
-  // or after half a second without one.
-  {
-    std::unique_lock<std::mutex> lock(g.m);
-    g.cv.wait_for(lock, std::chrono::milliseconds(500), [&] { return g.kicked.load() || g.cancel.load(); });
-  }
-  hipError_t e = g.cancel.load() ? hipErrorNotReady : hipSetDevice(device);
-  hipStream_t st = nullptr;
-  if (e == hipSuccess) {
-    int lo = 0, hi = 0;                            // lowest priority: the build yields to verification kernels
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = 0;
-    e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, lo);
-  }
-  const int wanted = bits;
-  int built = 0;
-  uint32_t* table = nullptr;                       // ours to free unless it is published
-  std::unique_lock<std::mutex> lock(g.m);
-  while (e == hipSuccess && bits > GT_BITS_FIRST && !g.cancel.load()) {
-    if (g.table[bits].load()) {                    // a context with that explicit width built it meanwhile: use that one
-      built = bits;
-      break;
-    }
-    if (g.being_built[bits]) {                     // ... or is building it right now: wait for that to end, look again
-      g.cv.wait(lock, [&] { return !g.being_built[bits] || g.cancel.load(); });
-      continue;
-    }
-    bits = gtable_pick_target(g, bits);            // (the memory may have gone since the target was chosen)
-    if (!bits) break;
-    if (g.table[bits].load() || g.being_built[bits]) continue;
-    g.being_built[bits] = true;
-    g.pending.store(gt_bytes_of(bits));
-    lock.unlock();
-    const hipError_t be = gtable_build(bits, st, &table, &g.cancel, &g.pending);
-    lock.lock();
-    g.pending.store(0);
-    g.being_built[bits] = false;
-    g.cv.notify_all();
-    if (be == hipSuccess) {
-      built = bits;
-      break;
-    }
-    table = nullptr;
-    if (be == hipErrorNotReady) break;             // cancelled
-    bits -= 2;                                     // a failed allocation or build: the next width down that fits
-  }
-  if (g.cancel.load()) {                           // every context went away meanwhile: nobody wants the table
-    if (table) (void)hipFree(table);
-  } else if (built) {
-    if (table && g.table[built].load()) {          // (never two tables of one width: the one that is there stays)
-      (void)hipFree(table);
-    } else if (table) {
-      g.table[built].store(table, std::memory_order_release);
-    }
-    g.auto_bits.store(built, std::memory_order_release);
-    if (built != wanted) snprintf(g.note, sizeof g.note, "%d-bit windows (the table of %d bits could not be had)", built, wanted);
-    g.target = built;
-  } else {
-    if (e != hipSuccess || bits) snprintf(g.note, sizeof g.note, "the wide table could not be built: staying on %d bits", GT_BITS_FIRST);
-    g.target = 0;
-    g.gave_up = true;
-  }
-  g.building = false;
-  g.cv.notify_all();
-  lock.unlock();
-  if (st) (void)hipStreamDestroy(st);
-}
-
-// a process that exits with contexts alive: the builders are stopped and joined before static destruction and before the HIP
-// runtime's own exit handlers (registered earlier than this one, so run later)
-void gtable_at_exit() {
-  for (gtable_dev& g : g_gtable) {
-    std::thread t;
-    {
-      std::lock_guard<std::mutex> lock(g.m);
-      if (!g.builder.joinable()) continue;
-      g.cancel.store(true);
-      g.cv.notify_all();
-      t = std::move(g.builder);
-    }
-    t.join();
-  }
-}
 }  // namespace
-
-// fixed_bits == 0: the shared automatic tables (first table now, wide table in the background); else exactly that width
-static hipError_t gtable_acquire(int device, int fixed_bits) {
-  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
-  static std::once_flag at_exit_once;
-  std::call_once(at_exit_once, [] { (void)atexit(gtable_at_exit); });
-  gtable_dev& g = g_gtable[device];
-  std::unique_lock<std::mutex> lock(g.m);
-  g.cv.wait(lock, [&] { return !g.closing; });    // (the last context of an earlier generation is still joining its builder)
-  const int bits = fixed_bits ? fixed_bits : GT_BITS_FIRST;
-  while (!g.table[bits].load()) {
-    if (g.being_built[bits]) {                     // by the builder or by another context's creation: wait, do not build a second one
-      g.cv.wait(lock, [&] { return !g.being_built[bits]; });
-      continue;
-    }
-    g.being_built[bits] = true;
-    lock.unlock();                                 // (seconds for a wide table: the contexts of this device keep working)
-    uint32_t* t = nullptr;
-    const hipError_t e = gtable_build(bits, nullptr, &t);
-    lock.lock();
-    g.being_built[bits] = false;
-    g.cv.notify_all();
-    if (e != hipSuccess) return e;
-    g.table[bits].store(t, std::memory_order_release);
-  }
-  if (!fixed_bits) {
-    if (g.auto_bits.load() == 0) g.auto_bits.store(GT_BITS_FIRST, std::memory_order_release);
-    if (!g.building && !g.gave_up && g.target == 0 && g.auto_bits.load() == GT_BITS_FIRST && GT_BITS_TARGET > GT_BITS_FIRST) {
-      g.target = gtable_pick_target(g, GT_BITS_TARGET);
-      if (g.target) {
-        if (g.table[g.target].load()) {             // (built earlier for a context with that explicit width)
-          g.auto_bits.store(g.target, std::memory_order_release);
-        } else {
-          if (g.builder.joinable()) g.builder.join();   // (an earlier builder that has ended: building is false)
-          g.building = true;
-          g.cancel.store(false);
-          g.pending.store(gt_bytes_of(g.target));
-          g.builder = std::thread(gtable_builder_main, device, g.target);
-        }
-      }
-    }
-  }
-  ++g.refs;
-  return hipSuccess;
-}
-static void gtable_release(int device) {
-  gtable_dev& g = g_gtable[device];
-  std::unique_lock<std::mutex> lock(g.m);
-  if (g.refs <= 0 || --g.refs > 0) return;
-  // the last context: stop the builder (it frees what it has not published), wait for it, then free the tables
-  g.closing = true;
-  g.cancel.store(true);
-  g.cv.notify_all();
-  std::thread t = std::move(g.builder);
-  lock.unlock();
-  if (t.joinable()) t.join();
-  lock.lock();
-  (void)hipSetDevice(device);
-  for (auto& tb : g.table) {
-    uint32_t* p = tb.exchange(nullptr);
-    if (p) (void)hipFree(p);
-  }
-  g.auto_bits.store(0);
-  g.target = 0;
-  g.gave_up = false;
-  g.building = false;
-  g.pending.store(0);
-  g.kicked.store(false);
-  g.cancel.store(false);
-  g.closing = false;
-  g.cv.notify_all();
-}
-extern "C++" __attribute__((visibility("hidden"))) void s2k_internal_gt_kick(int device) {
-  gtable_dev& g = g_gtable[device];
-  if (g.kicked.load(std::memory_order_relaxed)) return;         // (every call after the first: one relaxed load)
-  g.kicked.store(true);
-  std::lock_guard<std::mutex> lock(g.m);                        // (so that the notification cannot fall between the builder's test and its wait)
-  g.cv.notify_all();
-}
-// the table a call that starts now uses (ctx_enter: once per call)
-extern "C++" __attribute__((visibility("hidden"))) gt_view s2k_internal_gt_load(const s2k_ctx* ctx) {
-  const gtable_dev& g = g_gtable[ctx->device];
-  const int bits = ctx->gt_fixed ? ctx->gt_fixed : g.auto_bits.load(std::memory_order_acquire);
-  gt_view v;
-  v.p = g.table[bits].load(std::memory_order_acquire);
-  v.bits = (uint32_t)bits;
-  v.windows = gt_windows_of(bits);
-  return v;
-}
-// bytes of device memory the background build of this device is about to allocate: whoever sizes something by what is free
-// (key-set layouts, the per-key table buffer) takes them off first
-extern "C++" __attribute__((visibility("hidden"))) size_t s2k_internal_gt_pending_bytes(int device) {
-  return device >= 0 && device < 64 ? g_gtable[device].pending.load() : 0;
-}
-// Test hook behind s2k_debug_gt_swap_in_call: make `bits` the width of the device's automatic contexts NOW (building the table
-// if the registry does not hold it) - what the background builder does at a moment nobody chooses.
-static hipError_t gtable_debug_publish(int device, int bits) {
-  gtable_dev& g = g_gtable[device];
-  std::unique_lock<std::mutex> lock(g.m);
-  while (!g.table[bits].load()) {
-    if (g.being_built[bits]) {
-      g.cv.wait(lock, [&] { return !g.being_built[bits]; });
-      continue;
-    }
-    g.being_built[bits] = true;
-    lock.unlock();
-    uint32_t* t = nullptr;
-    hipStream_t st = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = gtable_build(bits, st, &t);
-    if (st) (void)hipStreamDestroy(st);
-    lock.lock();
-    g.being_built[bits] = false;
-    g.cv.notify_all();
-    if (e != hipSuccess) return e;
-    g.table[bits].store(t, std::memory_order_release);
-  }
-  g.auto_bits.store(bits, std::memory_order_release);
-  return hipSuccess;
-}
-
 // (pointset.hip: a point set's tables count against the same cap as a key set's joint tables)
 __attribute__((visibility("hidden"))) size_t s2k_internal_keyset_budget() { return g_keyset_budget.load(); }
 
 extern "C" {
-// Bytes per device the generator tables of this process may take (0 = no limit but the device's free memory).  Applies to
-// automatic contexts created after the call; the first table (0.8 GiB) is always built.
-void s2k_set_generator_table_budget(size_t bytes) { g_gt_budget.store(bytes); }
 // Caps on the two other table kinds, per process (0 = none): what s2k_keyset_create_ex treats as free memory when it chooses or
 // checks a joint-table layout, and the largest per-key table buffer a verification call may allocate (larger requests are
 // treated as failed allocations: the table cap halves, below 1024 tables the batch is verified without tables).  These replace
@@ -2933,47 +2701,6 @@ void s2k_set_generator_table_budget(size_t bytes) { g_gt_budget.store(bytes); }
 void s2k_set_table_memory_budgets(size_t keyset_free_bytes, size_t key_table_bytes) {
   g_keyset_budget.store(keyset_free_bytes);
   s2k_internal_key_table_limit().store(key_table_bytes);
-}
-// info[0] = window bits the context's next call uses, [1] = bits the background build aims for (0: none), [2] = 1 while it
-// is running, [3] = bytes of generator tables the device holds for this process
-int s2k_ctx_gt_info(s2k_ctx* ctx, uint64_t info[4]) {
-  if (!ctx || !info) return fail(ctx, S2K_ERR_ARG, "null argument");
-  gtable_dev& g = g_gtable[ctx->device];
-  std::lock_guard<std::mutex> lock(g.m);
-  info[0] = (uint64_t)(ctx->gt_fixed ? ctx->gt_fixed : g.auto_bits.load());
-  info[1] = (uint64_t)(ctx->gt_fixed ? 0 : g.target);
-  info[2] = g.building && !ctx->gt_fixed ? 1 : 0;
-  uint64_t bytes = 0;
-  for (int b = GT_BITS_MIN; b <= GT_BITS_MAX; ++b)
-    if (g.table[b].load()) bytes += gt_bytes_of(b);
-  info[3] = bytes;
-  return S2K_OK;
-}
-// (a copy taken under the lock, owned by the context: the builder thread rewrites the registry's note)
-const char* s2k_ctx_gt_note(s2k_ctx* ctx) {
-  if (!ctx) return "";
-  gtable_dev& g = g_gtable[ctx->device];
-  std::lock_guard<std::mutex> lock(g.m);
-  snprintf(ctx->gt_note, sizeof ctx->gt_note, "%s", g.note);
-  return ctx->gt_note;
-}
-// blocks until the background build of the context's device has ended (either way); returns the window bits in use then
-int s2k_ctx_gt_wait(s2k_ctx* ctx) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  gtable_dev& g = g_gtable[ctx->device];
-  std::unique_lock<std::mutex> lock(g.m);
-  g.cv.wait(lock, [&] { return !g.building; });
-  return ctx->gt_fixed ? ctx->gt_fixed : g.auto_bits.load();
-}
-// Test hook (tests/test_gpu_round6.py): the next s2k_ecdsa_verify_batch_device call of this (automatic) context publishes the
-// table of `bits` for the device's automatic contexts BETWEEN its ladder launch and its worklist launch - the moment the
-// background build must not be visible inside a call.  One shot; 0 disarms.
-int s2k_debug_gt_swap_in_call(s2k_ctx* ctx, int bits) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (bits != 0 && (bits < 16 || bits > GT_BITS_MAX)) return fail(ctx, S2K_ERR_ARG, "generator window width %d: 0 or 16 .. %d", bits, GT_BITS_MAX);
-  if (ctx->gt_fixed && bits) return fail(ctx, S2K_ERR_ARG, "a context with an explicit table width never changes tables");
-  ctx->dbg_gt_swap = bits;
-  return S2K_OK;
 }
 }  // extern "C"
 
@@ -3019,7 +2746,7 @@ int s2k_ctx_create_ex(int device_index, int gt_bits, uint32_t flags, s2k_ctx** o
   if (e == hipSuccess) e = hipMalloc((void**)&ctx->clk, 64);
   if (e == hipSuccess) e = hipMemset(ctx->clk, 0, 64);
   if (e == hipSuccess) {
-    e = gtable_acquire(device_index, gt_bits);
+    e = s2k_internal_gt_acquire(device_index, gt_bits);
     if (e == hipSuccess) {
       ctx->gt_held = true;
       ctx->gt_fixed = gt_bits;
@@ -3062,7 +2789,7 @@ void s2k_ctx_destroy(s2k_ctx* ctx) {
     (void)hipDeviceSynchronize();
     (void)hipHostFree(ctx->kga_note);
   }
-  if (ctx->gt_held) gtable_release(ctx->device);
+  if (ctx->gt_held) s2k_internal_gt_release(ctx->device);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->msm_ws) (void)hipFree(ctx->msm_ws);
   if (ctx->seg_ws) (void)hipFree(ctx->seg_ws);
@@ -3193,9 +2920,9 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
   if (rc) return rc;
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
+  const lane_ws w = lane_ws_of(ctx, n);
+  const uint8_t *pub = (const uint8_t*)d_pub, *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s;
+  uint8_t* valid = (uint8_t*)d_valid;
   ctx->kg_counters = nullptr;
   ctx->last_wl_count = nullptr;
   ctx->kt_last = -1;
@@ -3205,19 +2932,10 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
   };
   if (flags & S2K_ECDSA_FORCE_COMPLETE) {
     wait_all(st);
-    k_ecdsa_verify<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, (const uint8_t*)d_pub, (const uint8_t*)d_dig,
-                                                  (const uint8_t*)d_r, (const uint8_t*)d_s, flags, (uint8_t*)d_valid,
-                                                  ctx->gt_call, qt, stride);
+    launch_ecdsa_verify(ctx, st, n, w, pub, dig, r, s, flags, valid);
     HIP_TRY(ctx, hipGetLastError());
     return ctx_leave(ctx, st);
   }
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* gp = ws + WS_GP * stride;
-  uint32_t* pref = ws + WS_PREF * stride;
-  uint32_t* smont = ws + WS_SMONT * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
   const uint32_t T = prep_lanes(n);
   const uint32_t kvf = (flags & S2K_ECDSA_FORCE_WORKLIST) ? KVF_FORCE_WORKLIST : 0u;
   uint64_t* clk = ctx->prof_on ? ctx->clk : nullptr;
@@ -3229,7 +2947,7 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
   // neither
   const bool quad = !row && n <= ctx->quad_max && !kvf && (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF);
   if (row || quad) grouped = false;
-  else HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));      // (these ladders have no worklist: one launch less)
+  else HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));      // (these ladders have no worklist: one launch less)
   ctx->kg_note_dst = nullptr;
   if (grouped && ctx->kg_mode == S2K_KEYS_ADAPTIVE && n >= KG_ADAPT_MIN_BATCH) grouped = kg_adaptive_decide(ctx);
   if (grouped) {
@@ -3239,30 +2957,26 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
     if (rc == S2K_ERR_NOMEM) grouped = false;
     else if (rc) return rc;
   }
-  ctx->last_wl_count = (row || quad) ? nullptr : wl_count;
+  ctx->last_wl_count = (row || quad) ? nullptr : w.wl_count;
   prof_mark(ctx, st, 0);
   if (grouped) {
     // Signatures of keys that occur often enough: per-key tables (keyed.hip) and the short ladder; the
     // rest: the general kernel over the list `left`.
     key_groups kg;
     ctx->kt_comb_call = ctx->kt_comb;
-    rc = grouped_front(ctx, st, n, (const uint8_t*)d_pub, 64, prep, gp, stride,
+    rc = grouped_front(ctx, st, n, pub, 64, w,
                        [&](hipStream_t aux) {
                          if (!arrivals) {
-                           k_scalar_prep<<<(T + 63) / 64, 64, 0, aux>>>((uint32_t)n, T, (const uint8_t*)d_dig, (const uint8_t*)d_r,
-                                                                        (const uint8_t*)d_s, nullptr, flags, prep, pref, smont, stride);
+                           launch_scalar_prep(aux, w, 0, n, T, dig, r, s, nullptr, flags);
                            return;
                          }
                          // piece by piece: the planes of the workspace are linear in the signature index, so a piece is
                          // the same kernels on shifted pointers
                          for (int c = 0; c < arrivals->count; ++c) {
                            const size_t lo = arrivals->lo[c], cnt = arrivals->cnt[c];
-                           const uint32_t Tc = prep_lanes(cnt);
                            (void)hipStreamWaitEvent(aux, arrivals->ev[c], 0);
-                           k_scalar_prep<<<(Tc + 63) / 64, 64, 0, aux>>>((uint32_t)cnt, Tc, (const uint8_t*)d_dig + lo * 32,
-                                                                         (const uint8_t*)d_r + lo * 32, (const uint8_t*)d_s + lo * 32,
-                                                                         nullptr, flags, prep + lo, pref + lo, smont + lo, stride);
-                           k_generator_part<<<blocks_for(cnt), 256, 0, aux>>>((uint32_t)lo, (uint32_t)(lo + cnt), prep, ctx->gt_call, gp, stride);
+                           launch_scalar_prep(aux, w, lo, cnt, prep_lanes(cnt), dig, r, s, nullptr, flags);
+                           launch_generator_part(ctx, aux, w, (uint32_t)lo, (uint32_t)(lo + cnt));
                          }
                        },
                        &kg, /*gp_in_prep=*/arrivals != nullptr);
@@ -3271,40 +2985,27 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
     ctx->kt_last = kg.chunks == KC_TEETH ? S2K_LADDER_COMB : S2K_LADDER_WINDOW;
     prof_mark(ctx, st, 2);
     // the ladder of the tables the grouping built: the comb's, or the window ladder over the 16-bit chunks
-    auto keyed_ladder = [&](uint64_t* stamps) {
-      if (kg.chunks == KC_TEETH)
-        k_verify_fast<MODE_ECDSA_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                                      qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
-                                                                      stride, nullptr, stamps, kg);
-      else
-        k_verify_fast<MODE_ECDSA_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                                       qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
-                                                                       stride, nullptr, stamps, kg);
-    };
-    keyed_ladder(clk);
+    const int keyed_mode = kg.chunks == KC_TEETH ? MODE_ECDSA_COMB : MODE_ECDSA_KEYED;
+    launch_ladder(ctx, st, keyed_mode, n, kvf, pub, r, w, valid, nullptr, clk, kg);
     HIP_TRY(ctx, hipGetLastError());
     if (kg.nparts > 1) {   // the other side of the split, once its tables (third stream) are there
       HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_part1, 0));
       kg.part = 1;
-      keyed_ladder(nullptr);
+      launch_ladder(ctx, st, keyed_mode, n, kvf, pub, r, w, valid, nullptr, nullptr, kg);
       HIP_TRY(ctx, hipGetLastError());
     }
     prof_mark(ctx, st, 3);
-    k_verify_fast<MODE_ECDSA_LEFT><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                                  qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl,
-                                                                  stride, nullptr, nullptr, kg);
+    launch_ladder(ctx, st, MODE_ECDSA_LEFT, n, kvf, pub, r, w, valid, nullptr, nullptr, kg);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 4);
   } else if (quad) {
     // four lanes per signature on the complete formulas (k_verify_quad), behind a preparation with one lane per signature
     wait_all(st);
-    k_scalar_prep<<<(unsigned)((n + 63) / 64), 64, 0, st>>>((uint32_t)n, (uint32_t)n, (const uint8_t*)d_dig, (const uint8_t*)d_r,
-                                                            (const uint8_t*)d_s, nullptr, flags, prep, pref, smont, stride);
+    launch_scalar_prep(st, w, 0, n, (uint32_t)n, dig, r, s, nullptr, flags);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep,
-                                                             ctx->gt_call, (uint8_t*)d_valid, stride);
+    launch_verify_quad(ctx, st, n, pub, r, w, valid);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -3315,8 +3016,7 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
     wait_all(st);
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (const uint8_t*)d_pub, (const uint8_t*)d_dig, (const uint8_t*)d_r,
-                                                          (const uint8_t*)d_s, flags, ctx->gt_call, (uint8_t*)d_valid);
+    launch_verify_row(ctx, st, n, pub, dig, r, s, flags, valid);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -3324,14 +3024,11 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
     return ctx_leave(ctx, st);
   } else {
     wait_all(st);
-    k_scalar_prep<<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, (const uint8_t*)d_dig, (const uint8_t*)d_r,
-                                                (const uint8_t*)d_s, nullptr, flags, prep, pref, smont, stride);
+    launch_scalar_prep(st, w, 0, n, T, dig, r, s, nullptr, flags);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_fast<MODE_ECDSA><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, (const uint8_t*)d_pub, (const uint8_t*)d_r, prep, qt, fin,
-                                                             ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk,
-                                                             key_groups{});
+    launch_ladder(ctx, st, MODE_ECDSA, n, kvf, pub, r, w, valid, nullptr, clk, key_groups{});
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -3339,14 +3036,12 @@ static int verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pub, const 
   if (ctx->dbg_gt_swap) {   // test hook: the wide table appears HERE, between the ladder and the kernel that finishes its tagged lanes
     const int bits = ctx->dbg_gt_swap;
     ctx->dbg_gt_swap = 0;
-    HIP_TRY(ctx, gtable_debug_publish(ctx->device, bits));
+    HIP_TRY(ctx, s2k_internal_gt_debug_publish(ctx->device, bits));
 #ifdef S2K_DEBUG_GT_PER_LAUNCH   // (variant build that restores the fault of round 5 - a view per launch - to show the test sees it)
     ctx->gt_call = s2k_internal_gt_load(ctx);
 #endif
   }
-  k_verify_fallback<<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, (const uint8_t*)d_pub, (const uint8_t*)d_dig,
-                                        (const uint8_t*)d_r, (const uint8_t*)d_s, flags, (uint8_t*)d_valid,
-                                        ctx->gt_call, qt, stride);
+  launch_verify_fallback(ctx, st, n, w, pub, dig, r, s, flags, valid);
   HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 5);
   return ctx_leave(ctx, st);
@@ -3369,6 +3064,17 @@ struct s2k_keyset {
   int jw;             // digit width of the joint tables: 4, 5 or 6 (0: none)
   int chunks;         // geometry of the tables in `base`: KS_CHUNKS, or KC_TEETH - a comb set (S2K_KEYSET_COMB; never with joint tables)
 };
+
+// The ladder of a key-set call, from the set's layout: the ECDSA mode, or its BIP-340 counterpart (the ECDSA mode + 4; a comb
+// set runs the ladder of a call's comb tables over the set's)
+static_assert(MODE_SCHNORR_KEYSET == MODE_ECDSA_KEYSET + 4 && MODE_SCHNORR_KEYSET_JOINT == MODE_ECDSA_KEYSET_JOINT + 4 &&
+                  MODE_SCHNORR_KEYSET_JOINT5 == MODE_ECDSA_KEYSET_JOINT5 + 4 && MODE_SCHNORR_KEYSET_JOINT6 == MODE_ECDSA_KEYSET_JOINT6 + 4,
+              "BIP-340 over a key set: the ECDSA mode + 4");
+static int keyset_ladder_mode(const s2k_keyset* ks, bool schnorr) {
+  if (ks->chunks == KC_TEETH) return schnorr ? MODE_SCHNORR_COMB : MODE_ECDSA_COMB;
+  const int m = !ks->joint ? MODE_ECDSA_KEYSET : ks->jw == 6 ? MODE_ECDSA_KEYSET_JOINT6 : ks->jw == 5 ? MODE_ECDSA_KEYSET_JOINT5 : MODE_ECDSA_KEYSET_JOINT;
+  return schnorr ? m + 4 : m;
+}
 
 int s2k_keyset_create(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, s2k_keyset** out) {
   return s2k_keyset_create_ex(ctx, n_keys, pub_xy, S2K_KEYSET_AUTO, out);
@@ -3540,9 +3246,8 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
     prof_mark(ctx, st, 0);
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_row_keyset<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)ks->n, (const uint32_t*)d_key_index,
-                                                                 (const uint4*)(ks->base + off[1]), ks->base + off[2], (const uint8_t*)d_dig,
-                                                                 (const uint8_t*)d_r, (const uint8_t*)d_s, flags, ctx->gt_call, (uint8_t*)d_valid);
+    launch_verify_row_keyset(ctx, st, n, ks->n, (const uint32_t*)d_key_index, (const uint4*)(ks->base + off[1]), ks->base + off[2],
+                             (const uint8_t*)d_dig, (const uint8_t*)d_r, (const uint8_t*)d_s, flags, (uint8_t*)d_valid);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -3555,23 +3260,15 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   if (rc) return rc;
   rc = s2k_internal_keyset_reserve(ctx, ks->n, n);      // before the fork: growing a buffer synchronises the device
   if (rc) return rc;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* gp = ws + WS_GP * stride;
-  uint32_t* pref = ws + WS_PREF * stride;
-  uint32_t* smont = ws + WS_SMONT * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
+  const lane_ws w = lane_ws_of(ctx, n);
+  const uint8_t *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s;
+  uint8_t* valid = (uint8_t*)d_valid;
   size_t off[5];
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
-  ctx->last_wl_count = wl_count;
-  HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
+  ctx->last_wl_count = w.wl_count;
+  HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));       // signatures naming no key of the set stay invalid
-  const uint32_t T = prep_lanes(n);
   const uint32_t kvf = (flags & S2K_ECDSA_FORCE_WORKLIST) ? KVF_FORCE_WORKLIST : 0u;
   // second stream: scalar preparation and generator part; caller's: the sort by key index
   // (stage times, s2k_ctx_profile_read_stages: [0] + [1] the sort with the second stream's work beside it, [2] the ladder)
@@ -3579,9 +3276,8 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   prof_mark(ctx, st, 1);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
-  k_scalar_prep<<<(T + 63) / 64, 64, 0, ctx->s_aux>>>((uint32_t)n, T, (const uint8_t*)d_dig, (const uint8_t*)d_r, (const uint8_t*)d_s,
-                                                      nullptr, flags, prep, pref, smont, stride);
-  k_generator_part<<<blocks_for(n), 256, 0, ctx->s_aux>>>(0u, (uint32_t)n, prep, ctx->gt_call, gp, stride);
+  launch_scalar_prep(ctx->s_aux, w, 0, n, prep_lanes(n), dig, r, s, nullptr, flags);
+  launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
   if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
@@ -3590,30 +3286,14 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
     (void)ctx_leave(ctx, st);
     return rc;
   }
-  kg.gp = gp;
-  uint64_t* clk = ctx->prof_on ? ctx->clk : nullptr;
+  kg.gp = w.gp;
   kg.jtab = ks->joint;
   prof_mark(ctx, st, 2);
-  if (ks->chunks == KC_TEETH)   // a comb set: the ladder of a call's comb tables over the set's (the keyed prologue reads no key)
-    k_verify_fast<MODE_ECDSA_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin, ctx->gt_call,
-                                                                  (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
-  else if (ks->joint && ks->jw == 6)
-    k_verify_fast<MODE_ECDSA_KEYSET_JOINT6><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin,
-                                                                           ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
-  else if (ks->joint && ks->jw == 5)
-    k_verify_fast<MODE_ECDSA_KEYSET_JOINT5><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin,
-                                                                           ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
-  else if (ks->joint)
-    k_verify_fast<MODE_ECDSA_KEYSET_JOINT><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin,
-                                                                          ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
-  else
-    k_verify_fast<MODE_ECDSA_KEYSET><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, nullptr, (const uint8_t*)d_r, prep, qt, fin, ctx->gt_call,
-                                                                    (uint8_t*)d_valid, wl_count, wl, stride, nullptr, clk, kg);
+  // (the keyed prologue reads no key: pub is null)
+  launch_ladder(ctx, st, keyset_ladder_mode(ks, /*schnorr=*/false), n, kvf, nullptr, r, w, valid, nullptr, ctx->prof_on ? ctx->clk : nullptr, kg);
   prof_mark(ctx, st, 3);
   HIP_TRY(ctx, hipGetLastError());
-  k_verify_fallback_keyset<<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, ks->base + off[0], (const uint32_t*)d_key_index,
-                                                                    (const uint8_t*)d_dig, (const uint8_t*)d_r, (const uint8_t*)d_s, flags,
-                                                                    (uint8_t*)d_valid, ctx->gt_call, qt, stride);
+  launch_verify_fallback_keyset(ctx, st, n, w, ks->base + off[0], (const uint32_t*)d_key_index, dig, r, s, flags, valid);
   HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 4);
   prof_mark(ctx, st, 5);
@@ -3735,20 +3415,12 @@ int s2k_ecdsa_recover_batch_device(s2k_ctx* ctx, size_t n, const void* d_dig, co
   if (rc) return rc;
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* pref = ws + WS_PREF * stride;
-  uint32_t* smont = ws + WS_SMONT * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
+  const lane_ws w = lane_ws_of(ctx, n);
   const uint8_t *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s,
                 *rid = (const uint8_t*)d_recid;
+  uint8_t *ok = (uint8_t*)d_ok, *pub65 = (uint8_t*)d_pub65;
   if (flags & S2K_ECDSA_FORCE_COMPLETE) {
-    k_recover_fallback<<<blocks_for(n), 256, 0, st>>>(wl_count, wl, (uint32_t)n, dig, r, s, rid, (uint8_t*)d_ok,
-                                                      (uint8_t*)d_pub65, ctx->gt_call, qt, stride);
+    launch_recover_fallback(ctx, st, n, w, dig, r, s, rid, ok, pub65);
     HIP_TRY(ctx, hipGetLastError());
     return ctx_leave(ctx, st);
   }
@@ -3759,7 +3431,7 @@ int s2k_ecdsa_recover_batch_device(s2k_ctx* ctx, size_t n, const void* d_dig, co
     // small batches: a wave per item, one launch (k_recover_row: preparation, ladder, inversion and record)
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_recover_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, dig, r, s, rid, ctx->gt_call, (uint8_t*)d_ok, (uint8_t*)d_pub65);
+    launch_recover_row(ctx, st, n, dig, r, s, rid, ok, pub65);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -3768,42 +3440,33 @@ int s2k_ecdsa_recover_batch_device(s2k_ctx* ctx, size_t n, const void* d_dig, co
   }
   if (n <= ctx->quad_max) {
     // four lanes per item (k_recover_quad) between a preparation and a finish with one lane per item
-    k_scalar_prep<<<(unsigned)((n + 63) / 64), 64, 0, st>>>((uint32_t)n, (uint32_t)n, dig, r, s, rid, 0u, prep, pref, smont, stride);
+    launch_scalar_prep(st, w, 0, n, (uint32_t)n, dig, r, s, rid, 0u);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemsetAsync(d_pub65, 0, n * 65, st));      // items without a key keep the zero record
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_recover_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, r, prep, ctx->gt_call, fin, (uint8_t*)d_ok, stride);
+    launch_recover_quad(ctx, st, n, r, w, ok);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
-    k_affine_finish<MODE_RECOVER><<<(unsigned)((n + 63) / 64), 64, 0, st>>>((uint32_t)n, (uint32_t)n, nullptr, fin, (uint8_t*)d_ok, stride,
-                                                                            (uint8_t*)d_pub65);
+    launch_affine_finish(st, MODE_RECOVER, n, (uint32_t)n, nullptr, w, ok, pub65);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 4);
     prof_mark(ctx, st, 5);
     return ctx_leave(ctx, st);
   }
-  HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
-  const uint32_t T = prep_lanes(n);
-  k_scalar_prep<<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, dig, r, s, rid, 0u, prep, pref, smont, stride);
+  HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
+  launch_scalar_prep(st, w, 0, n, prep_lanes(n), dig, r, s, rid, 0u);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemsetAsync(d_pub65, 0, n * 65, st));      // items without a key keep the zero record
   prof_mark(ctx, st, 1);
   prof_mark(ctx, st, 2);
-  k_verify_fast<MODE_RECOVER><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, nullptr, r, prep, qt, fin, ctx->gt_call,
-                                                             (uint8_t*)d_ok, wl_count, wl, stride, (uint8_t*)d_pub65, ctx->prof_on ? ctx->clk : nullptr,
-                                                             key_groups{});
+  launch_ladder(ctx, st, MODE_RECOVER, n, 0u, nullptr, r, w, ok, pub65, ctx->prof_on ? ctx->clk : nullptr, key_groups{});
   HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 3);
-  {
-    const uint32_t T = (uint32_t)((n + FIN_M - 1) / FIN_M);
-    k_affine_finish<MODE_RECOVER><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, nullptr, fin, (uint8_t*)d_ok, stride,
-                                                                 (uint8_t*)d_pub65);
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  launch_affine_finish(st, MODE_RECOVER, n, (uint32_t)((n + FIN_M - 1) / FIN_M), nullptr, w, ok, pub65);
+  HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 4);
-  k_recover_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, dig, r, s, rid, (uint8_t*)d_ok, (uint8_t*)d_pub65,
-                                                              ctx->gt_call, qt, stride);
+  launch_recover_worklist(ctx, st, n, w, dig, r, s, rid, ok, pub65);
   HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 5);
   return ctx_leave(ctx, st);
@@ -3912,20 +3575,15 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
   if (rc) return rc;
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
+  const lane_ws w = lane_ws_of(ctx, n);
   const uint8_t* pk = (const uint8_t*)d_pk;
   const uint8_t* sig = (const uint8_t*)d_sig;
   const uint8_t* msgs = (const uint8_t*)d_msgs;
   const uint64_t* offs = (const uint64_t*)d_msg_offsets;
+  const uint32_t mlen = (uint32_t)msg_len;
+  uint8_t* valid = (uint8_t*)d_valid;
   if (flags & S2K_ECDSA_FORCE_COMPLETE) {
-    k_schnorr_fallback<<<blocks_for(n), 256, 0, st>>>(wl_count, wl, (uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len,
-                                                      (uint8_t*)d_valid, ctx->gt_call, qt, stride);
+    launch_schnorr_fallback(ctx, st, n, w, pk, sig, msgs, offs, mlen, valid);
     HIP_TRY(ctx, hipGetLastError());
     return ctx_leave(ctx, st);
   }
@@ -3939,8 +3597,8 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
   const bool row = n <= ctx->row_max && (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF);
   const bool quad = !row && n <= ctx->quad_max && (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF);
   if (row || quad) grouped = false;
-  else HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
-  ctx->last_wl_count = (row || quad) ? nullptr : wl_count;
+  else HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
+  ctx->last_wl_count = (row || quad) ? nullptr : w.wl_count;
   if (grouped) {
     rc = s2k_internal_key_reserve(ctx, n, 32);
     if (rc == S2K_ERR_NOMEM) grouped = false;      // no room for per-key tables: the general ladder for everything
@@ -3948,47 +3606,34 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
   }
   if (grouped) {
     // signatures that share an x-only key: the grouped flow of the ECDSA path (s2k_ctx_set_key_grouping)
-    uint32_t* gp = ws + WS_GP * stride;
     key_groups kg;
     ctx->kt_comb_call = ctx->kt_comb;
-    rc = grouped_front(ctx, st, n, pk, 32, prep, gp, stride,
-                       [&](hipStream_t aux) {
-                         k_schnorr_prep<<<blocks_for(n), 256, 0, aux>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
-                       },
-                       &kg);
+    rc = grouped_front(ctx, st, n, pk, 32, w, [&](hipStream_t aux) { launch_schnorr_prep(aux, n, w, pk, sig, msgs, offs, mlen); }, &kg);
     ctx->kt_comb_call = false;
     if (rc) return rc;
     ctx->kt_last = kg.chunks == KC_TEETH ? S2K_LADDER_COMB : S2K_LADDER_WINDOW;
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
     // the ladder of the tables the grouping built: the comb's, or the window ladder over the 16-bit chunks
-    auto keyed_ladder = [&](uint64_t* stamps) {
-      if (kg.chunks == KC_TEETH)
-        k_verify_fast<MODE_SCHNORR_COMB><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                                        (uint8_t*)d_valid, wl_count, wl, stride, nullptr, stamps, kg);
-      else
-        k_verify_fast<MODE_SCHNORR_KEYED><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                                         (uint8_t*)d_valid, wl_count, wl, stride, nullptr, stamps, kg);
-    };
-    keyed_ladder(ctx->prof_on ? ctx->clk : nullptr);
+    const int keyed_mode = kg.chunks == KC_TEETH ? MODE_SCHNORR_COMB : MODE_SCHNORR_KEYED;
+    launch_ladder(ctx, st, keyed_mode, n, 0u, pk, sig, w, valid, nullptr, ctx->prof_on ? ctx->clk : nullptr, kg);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     if (kg.nparts > 1) {
       HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_part1, 0));
       kg.part = 1;
-      keyed_ladder(nullptr);
+      launch_ladder(ctx, st, keyed_mode, n, 0u, pk, sig, w, valid, nullptr, nullptr, kg);
       HIP_TRY(ctx, hipGetLastError());
     }
-    k_verify_fast<MODE_SCHNORR_LEFT><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                                    (uint8_t*)d_valid, wl_count, wl, stride, nullptr, nullptr, kg);
+    launch_ladder(ctx, st, MODE_SCHNORR_LEFT, n, 0u, pk, sig, w, valid, nullptr, nullptr, kg);
     HIP_TRY(ctx, hipGetLastError());
   } else if (quad) {
     // four lanes per signature (k_schnorr_quad) behind the preparation kernel; nothing left for the finish and worklist kernels
-    k_schnorr_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
+    launch_schnorr_prep(st, n, w, pk, sig, msgs, offs, mlen);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_schnorr_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, pk, sig, prep, ctx->gt_call, (uint8_t*)d_valid, stride);
+    launch_schnorr_quad(ctx, st, n, pk, sig, w, valid);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -4000,15 +3645,13 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
     if (n <= 1024) {
       prof_mark(ctx, st, 1);
       prof_mark(ctx, st, 2);
-      k_schnorr_row<true><<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, nullptr, 0,
-                                                                   ctx->gt_call, (uint8_t*)d_valid);
+      launch_schnorr_row(ctx, st, n, pk, sig, msgs, offs, mlen, nullptr, 0, valid);
     } else {
-      k_schnorr_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
+      launch_schnorr_prep(st, n, w, pk, sig, msgs, offs, mlen);
       HIP_TRY(ctx, hipGetLastError());
       prof_mark(ctx, st, 1);
       prof_mark(ctx, st, 2);
-      k_schnorr_row<false><<<(unsigned)((n + 3) / 4), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride,
-                                                                    ctx->gt_call, (uint8_t*)d_valid);
+      launch_schnorr_row(ctx, st, n, pk, sig, msgs, offs, mlen, w.prep, w.stride, valid);
     }
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
@@ -4016,24 +3659,18 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
     prof_mark(ctx, st, 5);
     return ctx_leave(ctx, st);
   } else {
-    k_schnorr_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
+    launch_schnorr_prep(st, n, w, pk, sig, msgs, offs, mlen);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    k_verify_fast<MODE_SCHNORR><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, prep, qt, fin, ctx->gt_call,
-                                                               (uint8_t*)d_valid, wl_count, wl, stride, nullptr, ctx->prof_on ? ctx->clk : nullptr,
-                                                               key_groups{});
+    launch_ladder(ctx, st, MODE_SCHNORR, n, 0u, pk, sig, w, valid, nullptr, ctx->prof_on ? ctx->clk : nullptr, key_groups{});
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
   }
-  {
-    const uint32_t T = (uint32_t)((n + FIN_M - 1) / FIN_M);
-    k_affine_finish<MODE_SCHNORR><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, sig, fin, (uint8_t*)d_valid, stride, nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  launch_affine_finish(st, MODE_SCHNORR, n, (uint32_t)((n + FIN_M - 1) / FIN_M), sig, w, valid, nullptr);
+  HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 4);
-  k_schnorr_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, pk, sig, msgs, offs, (uint32_t)msg_len,
-                                                              (uint8_t*)d_valid, ctx->gt_call, qt, stride);
+  launch_schnorr_worklist(ctx, st, n, w, pk, sig, msgs, offs, mlen, valid);
   HIP_TRY(ctx, hipGetLastError());
   prof_mark(ctx, st, 5);
   return ctx_leave(ctx, st);
@@ -4084,10 +3721,9 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
     ctx->ks_last = S2K_KEYSET_LADDER_ROW;
     ctx->kg_counters = nullptr;
     ctx->last_wl_count = nullptr;
-    k_schnorr_row_keyset<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)ks->n, (const uint32_t*)d_key_index, ks->base + off[0],
-                                                                  (const uint4*)(ks->base + off[1]), ks->base + off[2], (const uint8_t*)d_sig, (const uint8_t*)d_msgs,
-                                                                  (const uint64_t*)d_msg_offsets,
-                                                                  (uint32_t)msg_len, ctx->gt_call, (uint8_t*)d_valid);
+    launch_schnorr_row_keyset(ctx, st, n, ks->n, (const uint32_t*)d_key_index, ks->base + off[0], (const uint4*)(ks->base + off[1]),
+                              ks->base + off[2], (const uint8_t*)d_sig, (const uint8_t*)d_msgs, (const uint64_t*)d_msg_offsets,
+                              (uint32_t)msg_len, (uint8_t*)d_valid);
     HIP_TRY(ctx, hipGetLastError());
     return ctx_leave(ctx, st);
   }
@@ -4100,33 +3736,28 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   // the expanded x-only keys (what the preparation hashes and the worklist kernel lifts): the context's key-expansion buffer
   rc = ctx_reserve(ctx, &ctx->xkeys, &ctx->xkeys_bytes, n * 32 + 256);
   if (rc) return rc;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* gp = ws + WS_GP * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
+  const lane_ws w = lane_ws_of(ctx, n);
   uint8_t* pk = (uint8_t*)ctx->xkeys;
   const uint8_t* sig = (const uint8_t*)d_sig;
   const uint8_t* msgs = (const uint8_t*)d_msgs;
   const uint64_t* offs = (const uint64_t*)d_msg_offsets;
+  const uint32_t mlen = (uint32_t)msg_len;
+  uint8_t* valid = (uint8_t*)d_valid;
   size_t off[5];
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   const uint8_t* set_keys = ks->base + off[0];
   ctx->kg_counters = nullptr;
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
-  ctx->last_wl_count = wl_count;
-  HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
+  ctx->last_wl_count = w.wl_count;
+  HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
   HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));       // signatures naming no key of the set stay invalid
   k_ks_expand_x<<<blocks_for(2 * n), 256, 0, st>>>((uint32_t)n, (uint32_t)ks->n, (const uint32_t*)d_key_index, set_keys, pk);
   HIP_TRY(ctx, hipGetLastError());
   // second stream: challenge hashes, scalars and the generator part s*G; caller's: the sort by key index
   HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
-  k_schnorr_prep<<<blocks_for(n), 256, 0, ctx->s_aux>>>((uint32_t)n, pk, sig, msgs, offs, (uint32_t)msg_len, prep, stride);
-  k_generator_part<<<blocks_for(n), 256, 0, ctx->s_aux>>>(0u, (uint32_t)n, prep, ctx->gt_call, gp, stride);
+  launch_schnorr_prep(ctx->s_aux, n, w, pk, sig, msgs, offs, mlen);
+  launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
   if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
@@ -4135,26 +3766,15 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
     (void)ctx_leave(ctx, st);
     return rc;
   }
-  kg.gp = gp;
+  kg.gp = w.gp;
   kg.jtab = ks->joint;
-#define S2K_SKS_LAUNCH(M) \
-  k_verify_fast<M><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, set_keys, sig, prep, qt, fin, ctx->gt_call, (uint8_t*)d_valid, wl_count, wl, stride, \
-                                                  nullptr, nullptr, kg)
-  if (ks->chunks == KC_TEETH) S2K_SKS_LAUNCH(MODE_SCHNORR_COMB);   // (kg.key_bytes == 64: the sign flip under an odd Y)
-  else if (ks->joint && ks->jw == 6) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT6);
-  else if (ks->joint && ks->jw == 5) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT5);
-  else if (ks->joint) S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET_JOINT);
-  else S2K_SKS_LAUNCH(MODE_SCHNORR_KEYSET);
-#undef S2K_SKS_LAUNCH
+  // (a comb set: kg.key_bytes == 64 tells MODE_SCHNORR_COMB to flip the signs under an odd Y)
+  launch_ladder(ctx, st, keyset_ladder_mode(ks, /*schnorr=*/true), n, 0u, set_keys, sig, w, valid, nullptr, nullptr, kg);
   HIP_TRY(ctx, hipGetLastError());
-  {
-    const uint32_t T = (uint32_t)((n + FIN_M - 1) / FIN_M);
-    k_affine_finish<MODE_SCHNORR><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, sig, fin, (uint8_t*)d_valid, stride, nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  launch_affine_finish(st, MODE_SCHNORR, n, (uint32_t)((n + FIN_M - 1) / FIN_M), sig, w, valid, nullptr);
+  HIP_TRY(ctx, hipGetLastError());
   // (the worklist kernel re-does its lanes from the x-only key: lift_x gives the even-y point whatever the set's Y says)
-  k_schnorr_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, pk, sig, msgs, offs, (uint32_t)msg_len, (uint8_t*)d_valid,
-                                                              ctx->gt_call, qt, stride);
+  launch_schnorr_worklist(ctx, st, n, w, pk, sig, msgs, offs, mlen, valid);
   HIP_TRY(ctx, hipGetLastError());
   return ctx_leave(ctx, st);
 }
@@ -4815,32 +4435,21 @@ int s2k_double_scalar_mult_basepoint_batch_ex(s2k_ctx* ctx, uint32_t impl, size_
   HIP_TRY(ctx, hipMemcpyAsync(io + o_pts, points, n * 65, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(io + o_status, 0, 4, st));
   const uint8_t* d_u1 = io + o_u1;
-  const size_t stride = lane_stride(n);
-  uint32_t* ws = (uint32_t*)ctx->ws;
-  uint32_t* qt = ws + WS_QT * stride;
-  uint32_t* fin = ws + WS_FIN * stride;
-  uint32_t* prep = ws + WS_PREP * stride;
-  uint32_t* wl_count = ws + WS_LANE_WORDS * stride;
-  uint32_t* wl = wl_count + 64;
+  const lane_ws w = lane_ws_of(ctx, n);
   uint32_t* status = (uint32_t*)(io + o_status);
   if (impl == S2K_IMPL_COMPLETE) {
-    k_point_fallback<true><<<blocks_for(n), 256, 0, st>>>(wl_count, wl, (uint32_t)n, d_u1, io + o_u2, io + o_pts, io + o_out,
-                                                          ctx->gt_call, qt, stride, status);
+    launch_point_fallback(ctx, st, /*all=*/true, n, w, d_u1, io + o_u2, io + o_pts, io + o_out, status);
     HIP_TRY(ctx, hipGetLastError());
   } else {
-    HIP_TRY(ctx, hipMemsetAsync(wl_count, 0, sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
     HIP_TRY(ctx, hipMemsetAsync(io + o_out, 0, n * 65, st));   // (the ladder kernel leaves the records of undecided lanes alone)
-    k_hot_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_u1, io + o_u2, io + o_pts, io + o_pub, prep, stride, wl_count, wl,
-                                              status);
+    launch_hot_prep(st, n, w, d_u1, io + o_u2, io + o_pts, io + o_pub, status);
     HIP_TRY(ctx, hipGetLastError());
-    k_verify_fast<MODE_POINT><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, io + o_pub, nullptr, prep, qt, fin, ctx->gt_call,
-                                                             io + o_ok, wl_count, wl, stride, io + o_out, nullptr, key_groups{});
+    launch_ladder(ctx, st, MODE_POINT, n, 0u, io + o_pub, nullptr, w, io + o_ok, io + o_out, nullptr, key_groups{});
     HIP_TRY(ctx, hipGetLastError());
-    const uint32_t T = (uint32_t)((n + FIN_M - 1) / FIN_M);
-    k_affine_finish<MODE_RECOVER><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, nullptr, fin, io + o_ok, stride, io + o_out);
+    launch_affine_finish(st, MODE_RECOVER, n, (uint32_t)((n + FIN_M - 1) / FIN_M), nullptr, w, io + o_ok, io + o_out);
     HIP_TRY(ctx, hipGetLastError());
-    k_point_fallback<false><<<fallback_blocks(ctx, n), 256, 0, st>>>(wl_count, wl, (uint32_t)n, d_u1, io + o_u2, io + o_pts,
-                                                                     io + o_out, ctx->gt_call, qt, stride, status);
+    launch_point_fallback(ctx, st, /*all=*/false, n, w, d_u1, io + o_u2, io + o_pts, io + o_out, status);
     HIP_TRY(ctx, hipGetLastError());
   }
   uint32_t h_status = 0;

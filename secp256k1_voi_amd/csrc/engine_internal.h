@@ -1,4 +1,4 @@
-// engine_internal.h — pieces shared by the translation units of the engine (engine.hip, msm.hip).
+// engine_internal.h — pieces shared by the translation units of the engine (engine.hip, gtable.hip, keyed.hip, msm.hip ...).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +19,7 @@ using namespace s2k;
 // 2^24 signatures of 2^20 keys then built no tables at all (threshold raised to 64 per key) and took 129 ms instead of 80.
 constexpr uint32_t KG_MAX_TABLES_DEFAULT = 1u << 22;
 
-// ---- generator tables (layout: engine.hip) ----
+// ---- generator tables (layout, registry and background build: gtable.hip) ----
 // The window width is a RUNTIME property of a table since round 5: a context starts on a narrow table
 // that is built while it is created (S2K_GT_BITS_FIRST: 20 bits, 0.8 GiB, < 0.1 s) and moves to the wide one when a background
 // thread has built it (S2K_GT_BITS: the width an automatic context aims for when the device has the memory; else 24, else 22).
@@ -248,8 +248,14 @@ inline std::atomic<size_t>& s2k_internal_key_table_limit() {   // s2k_set_table_
   return v;
 }
 extern "C" size_t s2k_internal_keyset_budget();     // engine.hip: the keyset_free_bytes of s2k_set_table_memory_budgets (0: none)
-gt_view s2k_internal_gt_load(const s2k_ctx* ctx);   // engine.hip: the generator table a call that starts now uses (one load per call)
-size_t s2k_internal_gt_pending_bytes(int device);   // engine.hip: device memory the background table build is about to allocate
+gt_view s2k_internal_gt_load(const s2k_ctx* ctx);   // gtable.hip: the generator table a call that starts now uses (one load per call)
+size_t s2k_internal_gt_pending_bytes(int device);   // gtable.hip: device memory the background table build is about to allocate
+// a context's reference on its device's tables (fixed_bits == 0: the shared automatic tables - first table now, wide table in
+// the background; else exactly that width), and the test hook behind s2k_debug_gt_swap_in_call: `bits` becomes the width of
+// the device's automatic contexts now
+hipError_t s2k_internal_gt_acquire(int device, int fixed_bits);
+void s2k_internal_gt_release(int device);
+hipError_t s2k_internal_gt_debug_publish(int device, int bits);
 
 inline thread_local char g_err[512];
 
@@ -296,7 +302,7 @@ inline int ctx_enter(s2k_ctx* ctx, hipStream_t st) {
   if (ctx->have_last && ctx->last_stream != st) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_done, 0));
   return S2K_OK;
 }
-void s2k_internal_gt_kick(int device);      // engine.hip: a call has been enqueued on the device (the background table build may start)
+void s2k_internal_gt_kick(int device);      // gtable.hip: a call has been enqueued on the device (the background table build may start)
 inline int ctx_leave(s2k_ctx* ctx, hipStream_t st) {
   s2k_internal_gt_kick(ctx->device);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_done, st));

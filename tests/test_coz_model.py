@@ -375,7 +375,7 @@ def test_key_finish_values_are_the_table():
 
 # ==== k_generator_part: the first addition never meets equal x ============================================================
 def test_generator_windows_never_meet():
-    """T_0[d0] = (d0 - S) G with S = sum_{i>=1} 2^(b i), T_1[d1] = (d1 + 1) 2^b G (engine.hip).  For every window width the
+    """T_0[d0] = (d0 - S) G with S = sum_{i>=1} 2^(b i), T_1[d1] = (d1 + 1) 2^b G (gtable.hip).  For every window width the
     tables are built with, no pair of digits makes the two points equal or opposite: d0 - S = +-(d1 + 1) 2^b (mod n) has
     no solution with d0, d1 < 2^b, so the ZZ = 0 path of xyzz29_add_affine_first is reached by no u1 (its formula-level
     test runs it through s2k_fp_op_batch_ex instead)."""

@@ -645,7 +645,7 @@ def source(name):
 
 
 def test_call_site_table_is_complete():
-    for f in ("engine.hip", "keyed.hip", "msm.hip", "aff29.h"):
+    for f in ("engine.hip", "gtable.hip", "keyed.hip", "msm.hip", "aff29.h"):
         rows = [r for r in CALL_SITES if r[0] == f]
         s = source(f)
         assert len(ROOTS.findall(s)) == sum(r[2] for r in rows), f"{f}: a call of fe29_eq / is_zero / normalize / inv_gcd has no row"

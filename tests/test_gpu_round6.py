@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def last_addition_doubles(rnd, bits, count):
     """Signatures whose plain ladder over a `bits`-wide generator table meets P + P in its LAST addition:
-    u2 Q + u1 G - T_last = T_last, T_last = (top digit of u1 + 1) 2^(bits (W - 1)) G   (engine.hip: table layout)."""
+    u2 Q + u1 G - T_last = T_last, T_last = (top digit of u1 + 1) 2^(bits (W - 1)) G   (gtable.hip: table layout)."""
     W = (256 + bits - 1) // bits
     items = []
     for _ in range(count):

@@ -44,31 +44,35 @@ def code_objects(lib):
     return tmp, sorted(os.path.join(tmp, f) for f in os.listdir(tmp) if "gfx950" in f)
 
 
+def disassemble_symbol(obj, name):
+    """[(offset, opcode, branch_target_offset or None)] of the function `name` of the code object `obj`."""
+    out = subprocess.run([OBJDUMP, "-d", "--disassemble-symbols=" + name, obj], capture_output=True, text=True, check=True).stdout
+    ins, base = [], None
+    for l in out.splitlines():
+        m = re.match(r"^\s+(\S+)\s.*//\s*([0-9A-Fa-f]+):", l) or re.match(r"^\s+(\S+)\s*//\s*([0-9A-Fa-f]+):", l)
+        if not m:
+            continue
+        addr = int(m.group(2), 16)
+        if base is None:
+            base = addr
+        tgt = None
+        if m.group(1).startswith(("s_cbranch", "s_branch")):
+            t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>\s*$", l)
+            tgt = int(t.group(1), 16) if t else 0      # (no offset: the kernel's first instruction)
+        ins.append((addr - base, m.group(1), tgt))
+    return ins
+
+
 def disassemble(lib, mangled_prefix):
-    """[(offset, opcode, branch_target_offset or None)] of the kernel whose mangled name starts with `mangled_prefix`."""
+    """disassemble_symbol of the kernel whose mangled name starts with `mangled_prefix`."""
     tmp, objs = code_objects(lib)
     try:
         for obj in objs:
             syms = subprocess.run([OBJDUMP, "-t", obj], capture_output=True, text=True, check=True).stdout
             names = [l.split()[-1] for l in syms.splitlines() if l.split() and l.split()[-1].startswith(mangled_prefix) and " F " in l]
             names = [n for n in names if not n.endswith(".kd")]
-            if not names:
-                continue
-            out = subprocess.run([OBJDUMP, "-d", "--disassemble-symbols=" + names[0], obj], capture_output=True, text=True, check=True).stdout
-            ins, base = [], None
-            for l in out.splitlines():
-                m = re.match(r"^\s+(\S+)\s.*//\s*([0-9A-Fa-f]+):", l) or re.match(r"^\s+(\S+)\s*//\s*([0-9A-Fa-f]+):", l)
-                if not m:
-                    continue
-                addr = int(m.group(2), 16)
-                if base is None:
-                    base = addr
-                tgt = None
-                if m.group(1).startswith(("s_cbranch", "s_branch")):
-                    t = re.search(r"<[^>]*\+0x([0-9a-fA-F]+)>\s*$", l)
-                    tgt = int(t.group(1), 16) if t else 0      # (no offset: the kernel's first instruction)
-                ins.append((addr - base, m.group(1), tgt))
-            return ins
+            if names:
+                return disassemble_symbol(obj, names[0])
         raise RuntimeError("kernel %s* not found in %s" % (mangled_prefix, lib))
     finally:
         subprocess.run(["rm", "-rf", tmp])
