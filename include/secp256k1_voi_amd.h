@@ -323,6 +323,57 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, siz
                                          const void *d_digest32, const void *d_r, const void *d_s, uint32_t flags,
                                          void *d_valid, void *hip_stream);
 
+/* ---- key sets by key bytes: device index, lookup and a fused ECDSA call -------------------- */
+/* The calls above want every signature's key as an INDEX into the set; what a caller has is key bytes (the reference's shape
+ * is PublicKey.Verify(digest, sig), and every ingest path of this library produces key bytes).  The INDEX of a key set maps
+ * key bytes to key indices on the device: an open-addressing hash table over the set's keys (8 bytes per slot), hashed under
+ * a seed drawn per set from the operating system, every hit confirmed against all the bytes of the set's key.  The caller
+ * owns the set and decides that it has an index; nothing builds one implicitly, and a call by key bytes over a set without
+ * one is S2K_ERR_ARG.  Keys of the set that are no valid public keys are indexed like any other: a hit on one verifies false,
+ * which is what s2k_ecdsa_verify_batch answers under such a key.  A set that lists a key several times answers with the
+ * LOWEST of its indices.
+ *
+ * s2k_keyset_index_geometry (host only: no device, no context): out = {slots, bytes of the index}; log2_slots 0 = auto, the
+ *   power of two >= 2 * n_keys, at least 16.  S2K_ERR_ARG when 2^log2_slots <= n_keys, log2_slots > 31, or n_keys is 0 or
+ *   > 0x0fffffff.
+ * s2k_keyset_index_create builds the index of a set (an allocation of its own, NOT counted in s2k_keyset_device_bytes;
+ *   s2k_keyset_index_info tells its size).  Same threading rule as s2k_keyset_destroy.  A set has at most one index: a
+ *   second call is S2K_ERR_ARG.  Freed by s2k_keyset_destroy.
+ * s2k_keyset_index_info: out = {slots (0: the set has no index), bytes, occupied slots = distinct 64-byte keys of the set,
+ *   longest probe distance of a stored entry}.
+ * s2k_keyset_lookup[_device]: key_index[i] = the lowest index of a key of the set equal to the key_bytes bytes at
+ *   keys + i * stride (key_bytes 64: X || Y; 32: X alone - the x-only key of BIP-340, which stands for Q and -Q alike, as
+ *   s2k_schnorr_verify_batch_keyset defines it), else 0xFFFFFFFF.  stride >= key_bytes: 65-byte SEC1 records are looked
+ *   up from their second byte with stride 65 (no alignment is asked for).  Exact: never a false miss, never a false hit.
+ *   The device form only enqueues; its output feeds s2k_ecdsa_verify_batch_keyset_device /
+ *   s2k_schnorr_verify_batch_keyset_device on the same stream, which treat 0xFFFFFFFF as "no key": invalid.
+ * s2k_ecdsa_verify_batch_keyset_bykey[_device]: valid[i] = what s2k_ecdsa_verify_batch gives for the same arrays, bit for
+ *   bit.  Signatures whose key the set holds run on the set's tables (every layout), the others on the general ladder from
+ *   the key bytes supplied - NOT on tables built inside the call: a batch that mostly misses the set should use
+ *   s2k_ecdsa_verify_batch.  The device form is enqueued without a host synchronisation (lookup, sort, both ladders and the
+ *   complete-formula worklist in stream order); the host form stages 160 bytes per signature.
+ *   When s2k_ecdsa_verify_batch would take its wave-per-signature or four-lanes-per-signature ladder for this n (n at most
+ *   s2k_ctx_set_small_batch_max / s2k_ctx_set_mid_batch_max, grouping mode ADAPTIVE or OFF, no S2K_ECDSA_FORCE_WORKLIST), the
+ *   call IS s2k_ecdsa_verify_batch[_device] on the supplied arrays and the set is not used (s2k_ctx_key_grouping_stats reads
+ *   all zero afterwards).  Otherwise s2k_ctx_key_grouping_stats gives [0] signatures whose key the set holds, [1] 0,
+ *   [2] signatures on the general ladder, [3] the complete-formula worklist.
+ *   S2K_ERR_ARG: a set of another context or device, a set without an index, S2K_ECDSA_FORCE_COMPLETE.  n == 0: S2K_OK.
+ *   S2K_ECDSA_REJECT_MALLEABLE and S2K_ECDSA_FORCE_WORKLIST are honoured.
+ * Not provided: ticket (_submit) and group forms of the fused call, a fused BIP-340 call (s2k_keyset_lookup_device with
+ * key_bytes 32 in front of s2k_schnorr_verify_batch_keyset_device does it in two calls), adding or removing keys of a set. */
+int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2]);
+int s2k_keyset_index_create(s2k_keyset *ks, uint32_t log2_slots);
+int s2k_keyset_index_info(const s2k_keyset *ks, uint64_t out[4]);
+int s2k_keyset_lookup(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *keys, size_t key_bytes, size_t stride,
+                      uint32_t *key_index);
+int s2k_keyset_lookup_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_keys, size_t key_bytes, size_t stride,
+                             void *d_key_index, void *hip_stream);
+int s2k_ecdsa_verify_batch_keyset_bykey(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pub_xy, const uint8_t *digest32,
+                                        const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
+int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_pub_xy,
+                                               const void *d_digest32, const void *d_r, const void *d_s, uint32_t flags,
+                                               void *d_valid, void *hip_stream);
+
 /* Page-locked host buffers for the host-pointer entry points (no reference counterpart: the reference never leaves the
  * host; this is the price of the boundary, cf. secec.PublicKey.Verify, ecdsa.go:171-228, which a cgo shim batches into
  * s2k_ecdsa_verify_batch).  From pageable memory every copy is staged by the runtime and 2^20 verifications cost

@@ -251,6 +251,13 @@ def load_library() -> C.CDLL:
     lib.s2k_ecdsa_verify_batch_keyset.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp]
     lib.s2k_ecdsa_verify_batch_keyset_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp, vp]
     lib.s2k_ecdsa_verify_batch_keyset_submit.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp, vp]
+    lib.s2k_keyset_index_geometry.argtypes = [sz, u32, vp]
+    lib.s2k_keyset_index_create.argtypes = [vp, u32]
+    lib.s2k_keyset_index_info.argtypes = [vp, vp]
+    lib.s2k_keyset_lookup.argtypes = [vp, vp, sz, vp, sz, sz, vp]
+    lib.s2k_keyset_lookup_device.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp]
+    lib.s2k_ecdsa_verify_batch_keyset_bykey.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp]
+    lib.s2k_ecdsa_verify_batch_keyset_bykey_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp, vp]
     lib.s2k_host_alloc.argtypes = [sz]
     lib.s2k_host_alloc.restype = vp
     lib.s2k_host_free.argtypes = [vp]
@@ -412,6 +419,8 @@ EXPORTED_SYMBOLS = [
     "s2k_ecdsa_verify_batch", "s2k_ecdsa_verify_batch_device", "s2k_ecdsa_workspace_bytes", "s2k_ctx_device_bytes",
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
+    "s2k_keyset_index_geometry", "s2k_keyset_index_create", "s2k_keyset_index_info", "s2k_keyset_lookup", "s2k_keyset_lookup_device",
+    "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device",
     "s2k_pack_valid_device", "s2k_host_alloc", "s2k_host_free", "s2k_host_register", "s2k_host_unregister", "s2k_ecdsa_recover_batch", "s2k_ecdsa_recover_batch_device",
     "s2k_ecdsa_batch_verify_rlc", "s2k_ecdsa_batch_verify_rlc_device",
     "s2k_ecdsa_verify_recoverable_batch_bisect", "s2k_ecdsa_verify_recoverable_batch_bisect_device",
@@ -570,6 +579,16 @@ def keyset_geometry(layout: int) -> tuple:
     if load_library().s2k_keyset_geometry(int(layout), out.ctypes.data) != 0:
         raise ValueError("secp256k1: key-set layout without a fixed geometry")
     return tuple(int(x) for x in out)
+
+
+def keyset_index_geometry(n_keys: int, log2_slots: int = 0) -> tuple:
+    """(slots, bytes) of the index of a key set of n_keys keys (s2k_keyset_index_geometry; no device); log2_slots 0: the
+    power of two >= 2 * n_keys, at least 16.  ValueError when 2^log2_slots <= n_keys, log2_slots > 31 or n_keys is 0."""
+    out = np.zeros(2, dtype=np.uint64)
+    if int(n_keys) < 0 or not 0 <= int(log2_slots) < 1 << 32 or \
+            load_library().s2k_keyset_index_geometry(int(n_keys), int(log2_slots), out.ctypes.data) != 0:
+        raise ValueError(f"no key-set index of {n_keys} keys in 2^{log2_slots} slots")
+    return int(out[0]), int(out[1])
 
 
 def msm_segments_plan(n: int, offsets, piece_terms: int = 0, crossover: int = 0, arrays: bool = True) -> dict:
@@ -899,6 +918,52 @@ class Engine(_TicketOwner):
     def ecdsa_verify_batch_keyset_device(self, keyset, n, d_key_index, d_digest32, d_r, d_s, d_valid, flags=0, stream=0):
         self._check(self._lib.s2k_ecdsa_verify_batch_keyset_device(self._h, keyset._k, int(n), d_key_index, d_digest32, d_r, d_s,
                                                                    int(flags), d_valid, stream))
+
+    # ---- key sets by key bytes (the set needs an index: KeySet.index_create) ------------------
+    def keyset_lookup(self, keyset, keys, key_bytes: int = 64, stride: int = 0, offset: int = 0) -> np.ndarray:
+        """uint32 array: for every key the lowest index of a key of `keyset` with the same bytes (key_bytes 64: X || Y; 32:
+        X), else 0xFFFFFFFF (s2k_keyset_lookup).  `keys`: n rows of key_bytes bytes; or, with `stride`, a buffer of records
+        of `stride` bytes whose key begins `offset` bytes into each (65-byte SEC1 records: stride=65, offset=1)."""
+        key_bytes = int(key_bytes)
+        if key_bytes not in (32, 64):
+            raise ValueError("key_bytes is 64 or 32")
+        if stride:
+            stride, offset = int(stride), int(offset)
+            buf = _arr(keys, 1).reshape(-1)
+            if stride < key_bytes or offset < 0 or offset + key_bytes > stride or buf.size % stride:
+                raise ValueError(f"records of {stride} bytes with a {key_bytes}-byte key at offset {offset}: bad buffer of {buf.size} bytes")
+            n = buf.size // stride
+        else:
+            buf, stride, offset = _arr(keys, key_bytes), key_bytes, 0
+            n = buf.shape[0]
+        out = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.s2k_keyset_lookup(self._h, keyset._k, n, buf.ctypes.data + offset if n else None, key_bytes, stride,
+                                                out.ctypes.data))
+        return out
+
+    def keyset_lookup_device(self, keyset, n, d_keys, d_key_index, key_bytes: int = 64, stride: int = 0, stream=0):
+        """Device-pointer form (s2k_keyset_lookup_device): n keys of key_bytes bytes at d_keys + i * stride (0: key_bytes),
+        n uint32 indices to d_key_index; enqueued on `stream`."""
+        self._check(self._lib.s2k_keyset_lookup_device(self._h, keyset._k, int(n), d_keys, int(key_bytes), int(stride) or int(key_bytes),
+                                                       d_key_index, stream))
+
+    def ecdsa_verify_batch_bykey(self, keyset, pub_xy, digest32, r, s, reject_malleable: bool = False,
+                                 force_worklist: bool = False) -> np.ndarray:
+        """ecdsa_verify_batch's verdicts for the same arrays, with the signatures whose key `keyset` holds verified on its
+        tables and the others on the general ladder (s2k_ecdsa_verify_batch_keyset_bykey); host buffers."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        pub_xy, digest32, s = _arr(pub_xy, 64, n), _arr(digest32, 32, n), _arr(s, 32, n)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_verify_batch_keyset_bykey(self._h, keyset._k, n, pub_xy.ctypes.data, digest32.ctypes.data,
+                                                                  r.ctypes.data, s.ctypes.data,
+                                                                  (REJECT_MALLEABLE if reject_malleable else 0) |
+                                                                  (FORCE_WORKLIST if force_worklist else 0), out.ctypes.data))
+        return out
+
+    def ecdsa_verify_batch_bykey_device(self, keyset, n, d_pub_xy, d_digest32, d_r, d_s, d_valid, flags=0, stream=0):
+        self._check(self._lib.s2k_ecdsa_verify_batch_keyset_bykey_device(self._h, keyset._k, int(n), d_pub_xy, d_digest32, d_r, d_s,
+                                                                         int(flags), d_valid, stream))
 
     def ecdsa_verify_encoded_batch(self, pubs, digests, sigs, encoding=ENCODING_ASN1, digest_len=0,
                                    reject_malleable=False, bip0066=False, force_complete=False) -> np.ndarray:
@@ -1755,6 +1820,19 @@ class KeySet:
         out = np.zeros(len(self), dtype=np.uint8)
         self._eng._check(self._eng._lib.s2k_keyset_valid_keys(self._k, out.ctypes.data))
         return out
+
+    def index_create(self, log2_slots: int = 0):
+        """Build the set's index, key bytes -> key index, once (s2k_keyset_index_create): 2^log2_slots slots of 8 bytes, more
+        than the set has keys; 0: keyset_index_geometry's choice.  Engine.keyset_lookup and ecdsa_verify_batch_bykey need it."""
+        rc = self._eng._lib.s2k_keyset_index_create(self._k, int(log2_slots))
+        if rc != 0:
+            raise EngineError(f"s2k error {rc}: {self._eng._lib.s2k_last_error(None).decode()}")
+
+    def index_info(self) -> dict:
+        """slots (0: no index), bytes, occupied slots (= distinct 64-byte keys), longest probe distance (s2k_keyset_index_info)"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._eng._check(self._eng._lib.s2k_keyset_index_info(self._k, out.ctypes.data))
+        return dict(slots=int(out[0]), bytes=int(out[1]), occupied=int(out[2]), longest_probe=int(out[3]))
 
     def close(self):
         if self._k:

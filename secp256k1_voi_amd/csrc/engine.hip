@@ -21,6 +21,7 @@
 #include <thread>
 
 #include "engine_internal.h"
+#include "keyset_index.h"
 #include "fe.h"
 #include "fe29_inv.h"
 #include "jacobian29.h"
@@ -2814,6 +2815,7 @@ void s2k_ctx_destroy(s2k_ctx* ctx) {
   if (ctx->kg) (void)hipFree(ctx->kg);
   if (ctx->ktab) (void)hipFree(ctx->ktab);
   if (ctx->xkeys) (void)hipFree(ctx->xkeys);
+  if (ctx->ks_found) (void)hipFree(ctx->ks_found);
   for (size_t i = 0; i < ctx->prof_cap; ++i) (void)hipEventDestroy(ctx->prof_ev[i]);
   for (size_t i = 0; i < ctx->msm_prof_cap; ++i) (void)hipEventDestroy(ctx->msm_prof_ev[i]);
   delete[] ctx->msm_prof_ev;
@@ -3063,6 +3065,11 @@ struct s2k_keyset {
   size_t joint_bytes;
   int jw;             // digit width of the joint tables: 4, 5 or 6 (0: none)
   int chunks;         // geometry of the tables in `base`: KS_CHUNKS, or KC_TEETH - a comb set (S2K_KEYSET_COMB; never with joint tables)
+  // the index, key bytes -> key index (s2k_keyset_index_create; keyset_index.h): an allocation of its own, not counted in `bytes`
+  uint64_t* index;    // device: 2^index_log2 slots, then S2K_KSI_INFO_WORDS counters (null: the set has no index)
+  uint32_t index_log2;
+  uint64_t index_seed;          // hash seed (operating-system randomness, per set)
+  uint64_t index_occupied, index_longest;   // distinct 64-byte keys; longest probe distance of a stored entry
 };
 
 // The ladder of a key-set call, from the set's layout: the ECDSA mode, or its BIP-340 counterpart (the ECDSA mode + 4; a comb
@@ -3169,6 +3176,7 @@ void s2k_keyset_destroy(s2k_keyset* ks) {
   (void)hipSetDevice(ks->device);
   (void)hipDeviceSynchronize();
   if (ks->joint) (void)hipFree(ks->joint);
+  if (ks->index) (void)hipFree(ks->index);
   (void)hipFree(ks->base);
   delete ks;
 }
@@ -3340,6 +3348,242 @@ int s2k_ecdsa_verify_batch_keyset(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, 
   HIP_TRY(ctx, hipMemcpyAsync(d[3], s, n * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, phase.landed(st));
   rc = s2k_ecdsa_verify_batch_keyset_device(ctx, ks, n, d[0], d[1], d[2], d[3], flags, d[4], st);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(valid, d[4], n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->have_last = false;
+  return S2K_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Key sets by key bytes: the index of a set (keyset_index.h / keyset_index.hip) resolves the key bytes a caller has to the
+// key indices the set's tables are named by, on the device; s2k_ecdsa_verify_batch_keyset_bykey joins the lookup, the set's
+// ladder for the keys it knows and the general ladder for the rest, without a host round trip in between.
+// ---------------------------------------------------------------------------------------
+int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2]) {
+  if (!out) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (!ksi_geometry(n_keys, log2_slots, out))
+    return fail(nullptr, S2K_ERR_ARG, "key-set index: %zu keys in 2^%u slots (more slots than keys, at most 2^31; 1 .. 0x0fffffff keys)", n_keys, log2_slots);
+  return S2K_OK;
+}
+int s2k_keyset_index_create(s2k_keyset* ks, uint32_t log2_slots) {
+  if (!ks) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (ks->index) return fail(nullptr, S2K_ERR_ARG, "the key set has an index already");
+  uint64_t geo[2];
+  if (!ksi_geometry(ks->n, log2_slots, geo))
+    return fail(nullptr, S2K_ERR_ARG, "key-set index: %zu keys in 2^%u slots (more slots than keys, at most 2^31)", ks->n, log2_slots);
+  uint32_t lg = 0;
+  while (((uint64_t)1 << lg) < geo[0]) ++lg;
+  uint64_t seed = 0;
+  if (getrandom(&seed, sizeof seed, 0) != (ssize_t)sizeof seed) seed = 0x5ec9u;
+  HIP_TRY(nullptr, hipSetDevice(ks->device));
+  HIP_TRY(nullptr, hipDeviceSynchronize());            // (the rule of s2k_keyset_destroy: no call that uses the set is in progress)
+  uint64_t* slots = nullptr;
+  const size_t bytes = (size_t)geo[1];
+  hipError_t e = hipMalloc((void**)&slots, bytes + S2K_KSI_INFO_WORDS * sizeof(uint32_t));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(nullptr, S2K_ERR_NOMEM, "key-set index of %zu bytes: %s", bytes, hipGetErrorString(e));
+  }
+  uint32_t* info = reinterpret_cast<uint32_t*>(slots + geo[0]);
+  uint32_t h[S2K_KSI_INFO_WORDS] = {0, 0, 0, 0};
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  int rc = S2K_OK;
+  if (hipMemsetAsync(slots, 0xff, bytes, nullptr) != hipSuccess || hipMemsetAsync(info, 0, sizeof h, nullptr) != hipSuccess)
+    rc = fail(nullptr, S2K_ERR_HIP, "key-set index: memset failed");
+  if (rc == S2K_OK) rc = s2k_internal_ksi_build(nullptr, nullptr, ks->base + off[0], ks->n, slots, lg, seed, info);
+  if (rc == S2K_OK && hipMemcpy(h, info, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set index build failed");
+  // (cannot happen while there are more slots than keys: every probe loop is bounded all the same, and says so here)
+  if (rc == S2K_OK && h[S2K_KSI_FAILED]) rc = fail(nullptr, S2K_ERR_HIP, "key-set index: an insert found no slot");
+  if (rc) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(slots);
+    return rc;
+  }
+  ks->index = slots;
+  ks->index_log2 = lg;
+  ks->index_seed = seed;
+  ks->index_occupied = h[S2K_KSI_OCCUPIED];
+  ks->index_longest = h[S2K_KSI_LONGEST];
+  return S2K_OK;
+}
+int s2k_keyset_index_info(const s2k_keyset* ks, uint64_t out[4]) {
+  if (!ks || !out) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  out[0] = ks->index ? (uint64_t)1 << ks->index_log2 : 0;
+  out[1] = out[0] * sizeof(uint64_t);
+  out[2] = ks->index ? ks->index_occupied : 0;
+  out[3] = ks->index ? ks->index_longest : 0;
+  return S2K_OK;
+}
+
+// what every call by key bytes asks of its set (as the key-set calls do; a child context of submit / wait uses its parent's sets)
+static int keyset_index_check(s2k_ctx* ctx, const s2k_keyset* ks) {
+  const s2k_ctx* owner = ctx->parent ? ctx->parent : ctx;
+  if (!ks || ks->ctx != owner || ks->generation != owner->generation || ks->device != ctx->device)
+    return fail(ctx, S2K_ERR_ARG, "key set of another context");
+  if (!ks->index) return fail(ctx, S2K_ERR_ARG, "the key set has no index (s2k_keyset_index_create)");
+  return S2K_OK;
+}
+
+int s2k_keyset_lookup_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_keys, size_t key_bytes, size_t stride,
+                             void* d_key_index, void* hip_stream) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = keyset_index_check(ctx, ks);
+  if (rc) return rc;
+  if ((key_bytes != 64 && key_bytes != 32) || stride < key_bytes) return fail(ctx, S2K_ERR_ARG, "keys of 64 or 32 bytes, stride >= key_bytes");
+  if (n == 0) return S2K_OK;
+  if (!d_keys || !d_key_index) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, n, (const uint8_t*)d_keys, (int)key_bytes,
+                               stride, (uint32_t*)d_key_index);
+  if (rc) return rc;
+  return ctx_leave(ctx, st);
+}
+int s2k_keyset_lookup(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* keys, size_t key_bytes, size_t stride,
+                      uint32_t* key_index) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = keyset_index_check(ctx, ks);
+  if (rc) return rc;
+  if ((key_bytes != 64 && key_bytes != 32) || stride < key_bytes) return fail(ctx, S2K_ERR_ARG, "keys of 64 or 32 bytes, stride >= key_bytes");
+  if (n == 0) return S2K_OK;
+  if (!keys || !key_index) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ctx_streams(ctx);
+  if (rc) return rc;
+  const size_t in_bytes = (n - 1) * stride + key_bytes;       // (the last record may end with its key)
+  const size_t sizes[2] = {in_bytes, n * 4};
+  uint8_t* d[2];
+  rc = ctx_stage(ctx, sizes, 2, d);
+  if (rc) return rc;
+  hipStream_t st = ctx->s_comp;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(d[0], keys, in_bytes, hipMemcpyHostToDevice, st));
+  rc = s2k_keyset_lookup_device(ctx, ks, n, d[0], key_bytes, stride, d[1], st);
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(key_index, d[1], n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->have_last = false;
+  return S2K_OK;
+}
+
+// the plain call would take its wave-per-signature or four-lanes-per-signature ladder for this n (verify_batch_device): the
+// call by key bytes IS the plain call then, and the set is not used
+static bool bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags) {
+  const bool ladders = ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF;
+  return ladders && !(flags & S2K_ECDSA_FORCE_WORKLIST) && (n <= ctx->row_max || n <= ctx->quad_max);
+}
+static int bykey_check(s2k_ctx* ctx, const s2k_keyset* ks, uint32_t flags) {
+  int rc = keyset_index_check(ctx, ks);
+  if (rc) return rc;
+  if (flags & S2K_ECDSA_FORCE_COMPLETE) return fail(ctx, S2K_ERR_ARG, "S2K_ECDSA_FORCE_COMPLETE does not apply to key sets");
+  return S2K_OK;
+}
+
+int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig,
+                                               const void* d_r, const void* d_s, uint32_t flags, void* d_valid, void* hip_stream) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = bykey_check(ctx, ks, flags);
+  if (rc) return rc;
+  if (n == 0) return S2K_OK;
+  if (!d_pub_xy || !d_dig || !d_r || !d_s || !d_valid) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
+  if (bykey_delegates(ctx, n, flags)) return s2k_ecdsa_verify_batch_device(ctx, n, d_pub_xy, d_dig, d_r, d_s, flags, d_valid, hip_stream);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  rc = s2k_internal_ensure_ws(ctx, n);
+  if (rc) return rc;
+  rc = ctx_aux_streams(ctx);
+  if (rc) return rc;
+  // before the fork: growing a buffer synchronises the device
+  rc = s2k_internal_keyset_reserve(ctx, ks->n, n);
+  if (rc) return rc;
+  rc = ctx_reserve(ctx, &ctx->ks_found, &ctx->ks_found_bytes, ((n + 63) & ~(size_t)63) * sizeof(uint32_t));
+  if (rc) return rc;
+  const lane_ws w = lane_ws_of(ctx, n);
+  const uint8_t *pub = (const uint8_t*)d_pub_xy, *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s;
+  uint8_t* valid = (uint8_t*)d_valid;
+  uint32_t* found = (uint32_t*)ctx->ks_found;
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  ctx->ks_last = S2K_KEYSET_LADDER_LANE;
+  ctx->kt_last = -1;
+  ctx->last_wl_count = w.wl_count;
+  HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
+  HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));
+  const uint32_t kvf = (flags & S2K_ECDSA_FORCE_WORKLIST) ? KVF_FORCE_WORKLIST : 0u;
+  // second stream: scalar preparation and generator part of every signature; caller's: the lookup of the keys, then the sort
+  // by the indices it found - a key the set does not hold (0xFFFFFFFF) lands in the list `left`, as an index outside the set does
+  prof_mark(ctx, st, 0);
+  prof_mark(ctx, st, 1);
+  HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
+  launch_scalar_prep(ctx->s_aux, w, 0, n, prep_lanes(n), dig, r, s, nullptr, flags);
+  launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
+  rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
+  key_groups kg{};
+  if (rc == S2K_OK) rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, n, pub, 64, 64, found);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, found, st, &kg, ks->chunks);
+  ctx_aux_join(ctx, st);
+  if (rc) {
+    (void)ctx_leave(ctx, st);
+    return rc;
+  }
+  kg.gp = w.gp;
+  kg.jtab = ks->joint;
+  prof_mark(ctx, st, 2);
+  // the set's ladder over the keys it holds (its prologue reads no key), the general ladder over the rest with the caller's
+  // key bytes, and the complete formulas for the lanes either one tagged: hits and misses alike have their key in d_pub_xy
+  launch_ladder(ctx, st, keyset_ladder_mode(ks, /*schnorr=*/false), n, kvf, nullptr, r, w, valid, nullptr, ctx->prof_on ? ctx->clk : nullptr, kg);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 3);
+  launch_ladder(ctx, st, MODE_ECDSA_LEFT, n, kvf, pub, r, w, valid, nullptr, nullptr, kg);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 4);
+  launch_verify_fallback(ctx, st, n, w, pub, dig, r, s, flags, valid);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 5);
+  return ctx_leave(ctx, st);
+}
+
+int s2k_ecdsa_verify_batch_keyset_bykey(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pub, const uint8_t* dig,
+                                        const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* valid) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = bykey_check(ctx, ks, flags);
+  if (rc) return rc;
+  if (n == 0) return S2K_OK;
+  if (!pub || !dig || !r || !s || !valid) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (bykey_delegates(ctx, n, flags)) return s2k_ecdsa_verify_batch(ctx, n, pub, dig, r, s, flags, valid);   // (with its small-call route)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ctx_streams(ctx);
+  if (rc) return rc;
+  const size_t sizes[5] = {n * 64, n * 32, n * 32, n * 32, n};
+  uint8_t* d[5];
+  rc = ctx_stage(ctx, sizes, 5, d);
+  if (rc) return rc;
+  hipStream_t st = ctx->s_comp;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  s2k_phase_guard phase(ctx->device, n * 160);           // (two verifiers on two threads: engine_internal.h)
+  HIP_TRY(ctx, hipMemcpyAsync(d[0], pub, n * 64, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d[1], dig, n * 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d[2], r, n * 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d[3], s, n * 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, phase.landed(st));
+  rc = s2k_ecdsa_verify_batch_keyset_bykey_device(ctx, ks, n, d[0], d[1], d[2], d[3], flags, d[4], st);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(valid, d[4], n, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));

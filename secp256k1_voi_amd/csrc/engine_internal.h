@@ -189,6 +189,8 @@ struct s2k_ctx {
   size_t ktab_bytes = 0;
   void* xkeys = nullptr;             // BIP-340 over a key set: the x-only keys of a call's signatures, expanded from the set
   size_t xkeys_bytes = 0;
+  void* ks_found = nullptr;          // ECDSA over a key set by key bytes: the key indices the set's index found for a call's signatures
+  size_t ks_found_bytes = 0;
   uint32_t* kg_counters = nullptr;   // device, KG_COUNTERS words (of the last call; null: it did not group)
   uint32_t kg_last_max_tables = 0;   // table cap of that call (the device counter of tables is not clamped)
   uint32_t* last_wl_count = nullptr; // device: the last verification call's complete-formula worklist length
@@ -575,6 +577,16 @@ int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size
 int s2k_internal_keyset_reserve(s2k_ctx* ctx, size_t nkeys, size_t n);
 int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys, size_t n, const uint32_t* d_kidx, hipStream_t st,
                              key_groups* out, int chunks = KS_CHUNKS);
+
+// the index of a key set, key bytes -> key index (keyset_index.hip; the table and its probe loops: keyset_index.h).  Enqueue
+// only.  build: `slots` (2^log2_slots words of 64 bits) all ones and `info` (S2K_KSI_INFO_WORDS words) zero beforehand;
+// lookup: d_out[i] = the index of the set's key equal to the key_bytes (64: X || Y, 32: X) bytes at d_keys + i * stride, else
+// 0xFFFFFFFF
+enum { S2K_KSI_OCCUPIED = 0, S2K_KSI_LONGEST = 1, S2K_KSI_FAILED = 2, S2K_KSI_INFO_WORDS = 4 };
+int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys, uint64_t* slots, uint32_t log2_slots,
+                           uint64_t seed, uint32_t* info);
+int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, const uint64_t* slots, uint32_t log2_slots, uint64_t seed,
+                            size_t n, const uint8_t* d_keys, int key_bytes, size_t stride, uint32_t* d_out);
 
 struct dev_buf {
   void* p = nullptr;

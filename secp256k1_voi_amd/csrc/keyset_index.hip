@@ -1,0 +1,120 @@
+// keyset_index.hip — the index of a key set on the device: key bytes -> key index (keyset_index.h has the table and its
+// probe loops; engine.hip owns the set and the calls: s2k_keyset_index_create, s2k_keyset_lookup*,
+// s2k_ecdsa_verify_batch_keyset_bykey*).
+//   k_ksi_build    one lane per key of the set: ksi_insert with atomics; counts the occupied slots (= distinct 64-byte keys)
+//                  and keeps the longest probe distance of a stored entry
+//   k_ksi_lookup   one lane per looked-up key, read with the caller's stride: 64 bytes (X || Y) or 32 (X)
+#include "engine_internal.h"
+#include "keyset_index.h"
+
+namespace {
+struct ksi_dev_mem {
+  static __device__ __forceinline__ uint64_t load(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+  static __device__ __forceinline__ uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) {
+    return atomicCAS(reinterpret_cast<unsigned long long*>(p), (unsigned long long)expect, (unsigned long long)v);
+  }
+  static __device__ __forceinline__ void min_u64(uint64_t* p, uint64_t v) {
+    (void)atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+  }
+  // a key of the set: 64 bytes at a multiple of 64 from a 256-byte aligned base
+  static __device__ __forceinline__ void load_key(const uint8_t* p, uint32_t* out, int words) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (4 * i >= words) break;
+      const uint4 v = q[i];
+      out[4 * i] = v.x;
+      out[4 * i + 1] = v.y;
+      out[4 * i + 2] = v.z;
+      out[4 * i + 3] = v.w;
+    }
+  }
+};
+
+__global__ void __launch_bounds__(256)
+k_ksi_build(uint32_t nkeys, ksi_table t, uint32_t* __restrict__ info) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  bool fresh = false;
+  uint32_t d = 0;
+  if (i < nkeys) {
+    d = ksi_insert<ksi_dev_mem>(t, i, &fresh);
+    if (d == KSI_NONE) {
+      atomicOr(&info[S2K_KSI_FAILED], 1u);
+      d = 0;
+    }
+  }
+  // the two counters, once per wave (every lane of the wave is here: lanes past the last key count nothing)
+  const uint32_t nfresh = (uint32_t)__popcll(__ballot(fresh));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t v = __shfl_xor(d, o, 64);
+    d = v > d ? v : d;
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (nfresh) atomicAdd(&info[S2K_KSI_OCCUPIED], nfresh);
+    if (d) atomicMax(&info[S2K_KSI_LONGEST], d);
+  }
+}
+
+// WORDS little-endian words of a looked-up key at any address: quads when `wide` (base and stride multiples of 16), words
+// when `aligned4` (multiples of 4), else bytes (65-byte records read from their second byte)
+template <int WORDS>
+S2K_DEV void ksi_load_query(const uint8_t* p, bool wide, bool aligned4, uint32_t out[WORDS]) {
+  if (wide) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+    for (int i = 0; i < WORDS / 4; ++i) {
+      const uint4 v = q[i];
+      out[4 * i] = v.x;
+      out[4 * i + 1] = v.y;
+      out[4 * i + 2] = v.z;
+      out[4 * i + 3] = v.w;
+    }
+  } else if (aligned4) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i) out[i] = q[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i)
+      out[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
+  }
+}
+
+template <int KEYBYTES>
+__global__ void __launch_bounds__(256)
+k_ksi_lookup(uint32_t n, const uint8_t* __restrict__ q, size_t stride, bool wide, bool aligned4, ksi_table t, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[KEYBYTES / 4];
+  ksi_load_query<KEYBYTES / 4>(q + (size_t)i * stride, wide, aligned4, k);
+  out[i] = KEYBYTES == 64 ? ksi_lookup64<ksi_dev_mem>(t, k) : ksi_lookup32<ksi_dev_mem>(t, k);
+}
+}  // namespace
+
+// slots: 2^log2_slots entries, all KSI_EMPTY; info: S2K_KSI_INFO_WORDS words, all zero (both set by the caller on `st`)
+__attribute__((visibility("hidden"))) int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys,
+                                                                 uint64_t* slots, uint32_t log2_slots, uint64_t seed, uint32_t* info) {
+  if (nkeys == 0 || nkeys > KSI_MAX_KEYS || log2_slots > KSI_MAX_LOG2 || ((uint64_t)1 << log2_slots) <= nkeys)
+    return fail(ctx, S2K_ERR_ARG, "key-set index of %zu keys in 2^%u slots", nkeys, log2_slots);
+  const ksi_table t = {slots, (uint32_t)(((uint64_t)1 << log2_slots) - 1), seed, set_keys};
+  k_ksi_build<<<blocks_for(nkeys), 256, 0, st>>>((uint32_t)nkeys, t, info);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+
+// d_out[i] = index of the set's key equal to the key_bytes bytes at d_keys + i * stride, or KSI_NONE (enqueue only)
+__attribute__((visibility("hidden"))) int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, const uint64_t* slots,
+                                                                  uint32_t log2_slots, uint64_t seed, size_t n, const uint8_t* d_keys,
+                                                                  int key_bytes, size_t stride, uint32_t* d_out) {
+  if ((key_bytes != 64 && key_bytes != 32) || stride < (size_t)key_bytes || n >= S2K_MAX_BATCH || log2_slots > KSI_MAX_LOG2)
+    return fail(ctx, S2K_ERR_ARG, "key-set lookup: %zu keys of %d bytes at stride %zu", n, key_bytes, stride);
+  if (n == 0) return S2K_OK;
+  const ksi_table t = {const_cast<uint64_t*>(slots), (uint32_t)(((uint64_t)1 << log2_slots) - 1), seed, set_keys};
+  const uintptr_t both = (uintptr_t)d_keys | (uintptr_t)stride;
+  const bool wide = (both & 15u) == 0, aligned4 = (both & 3u) == 0;
+  if (key_bytes == 64) k_ksi_lookup<64><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_keys, stride, wide, aligned4, t, d_out);
+  else k_ksi_lookup<32><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d_keys, stride, wide, aligned4, t, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}

@@ -1,0 +1,23 @@
+"""Sanitizer run of the index of a key set (csrc/keyset_index.h: the open-addressing table, its insert and its two lookups,
+with the plain-memory policy): a stand-alone program, built for the host with AddressSanitizer + UndefinedBehaviorSanitizer
+and run on the CPU, that builds indexes sequentially and compares every lookup with a std::map - a nearly full table whose
+chains wrap past the last slot, one key in two slots, duplicates, pairs Q / -Q, one-bit neighbours; under a fixed hash seed and
+three others.  No device code is involved and nothing is loaded into Python."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+
+def test_keyset_index_under_sanitizers(tmp_path):
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "keyset_index_san")
+    subprocess.check_call([gxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(root, "secp256k1_voi_amd", "csrc"),
+                           os.path.join(root, "tests", "c", "keyset_index_main.cpp"), "-o", exe])
+    p = subprocess.run([exe, "0x5ec9", "1", "0xfeedfacecafebeef", "0x0123456789abcdef"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stdout.startswith("ok 4 seeds"), p.stdout + p.stderr[-2000:]
