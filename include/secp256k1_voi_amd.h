@@ -345,6 +345,12 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, siz
  *   keys + i * stride (key_bytes 64: X || Y; 32: X alone - the x-only key of BIP-340, which stands for Q and -Q alike, as
  *   s2k_schnorr_verify_batch_keyset defines it), else 0xFFFFFFFF.  stride >= key_bytes: 65-byte SEC1 records are looked
  *   up from their second byte with stride 65 (no alignment is asked for).  Exact: never a false miss, never a false hit.
+ *   key_bytes 33: SEC1 compressed keys, prefix || X (stride >= 33).  key_index[i] = what key_bytes 64 gives for the point
+ *   the 33 bytes decode to (SetCompressedBytes, point_s11n.go:140-176), and 0xFFFFFFFF when they decode to nothing (a prefix
+ *   other than 02 / 03, X >= p, X^3 + 7 not a square) or the set does not hold that point.  No square root is taken: the
+ *   answer is the set's VALID key (s2k_keyset_valid_keys) with this X and a Y of the asked parity - there is at most one
+ *   such point, so it is the decoded one; an off-curve (X, Y') of the same parity that the set lists too is never answered.
+ *   Every other key_bytes is S2K_ERR_ARG.
  *   The device form only enqueues; its output feeds s2k_ecdsa_verify_batch_keyset_device /
  *   s2k_schnorr_verify_batch_keyset_device on the same stream, which treat 0xFFFFFFFF as "no key": invalid.
  * s2k_ecdsa_verify_batch_keyset_bykey[_device]: valid[i] = what s2k_ecdsa_verify_batch gives for the same arrays, bit for
@@ -607,6 +613,35 @@ int s2k_ecdsa_verify_encoded_batch(s2k_ctx *ctx, size_t n, const uint8_t *pubs, 
                                    const uint8_t *digests, const uint64_t *dig_off, const uint8_t *sigs,
                                    const uint64_t *sig_off, int encoding, size_t digest_len, uint32_t flags,
                                    uint8_t *valid);
+/* s2k_ecdsa_verify_encoded_batch over a key set with an index (s2k_keyset_index_create): valid[i] = what
+ * s2k_ecdsa_verify_encoded_batch gives for the same arguments, bit for bit, in every layout of the set.  The parse step
+ * resolves each SEC1 key against the set's index: a 65-byte key as s2k_keyset_lookup with key_bytes 64 does, a 33-byte key
+ * as key_bytes 33 does - a compressed key the set holds is replaced by the set's own 64 bytes and costs NO square root.
+ * Compressed keys the set does not hold are collected in a list, and only that list is decompressed (densely: a batch with
+ * one such key per wave pays for list / 64 waves of roots, not for all of them).  Signatures whose key the set holds run on
+ * its tables, the others on the general ladder, as in s2k_ecdsa_verify_batch_keyset_bykey.
+ * encoding: S2K_ENCODING_ASN1 or S2K_ENCODING_COMPACT; flags: S2K_ECDSA_REJECT_MALLEABLE, S2K_ECDSA_BIP0066 and
+ * S2K_ECDSA_FORCE_WORKLIST are honoured.  S2K_ERR_ARG: S2K_ENCODING_COMPACT_RECOVERABLE (it recovers the key and has no use
+ * for a set), S2K_ECDSA_FORCE_COMPLETE, a set without an index, a set of another context or device.  n == 0: S2K_OK.
+ * The synchronous call works in pieces whose copies overlap the previous piece's kernels.  A piece the plain call would
+ * verify on its wave-per-signature or four-lanes-per-signature ladder (the rule of s2k_ecdsa_verify_batch_keyset_bykey) is
+ * parsed and verified exactly as s2k_ecdsa_verify_encoded_batch does, without the set; a call that is one such piece IS
+ * that call.  s2k_ctx_key_grouping_stats afterwards, of the LAST piece: [0] signatures that parsed and whose key the set
+ * holds, [1] 0, [2] signatures on the general ladder, [3] the complete-formula worklist.
+ * _submit: one ticket (s2k_wait), the whole batch in one piece, as s2k_ecdsa_verify_encoded_batch_submit; the set must stay
+ * alive until the ticket has been waited for.
+ * s2k_ctx_last_encoded_keyset_stats synchronises and gives, summed over the pieces of the context's last SYNCHRONOUS call:
+ * [0] signatures verified under a key of the set that came as 33 bytes, [1] as 65 bytes, [2] the length of the
+ * decompression list = square roots taken, [3] items of the pieces the set was not used for. */
+int s2k_ecdsa_verify_encoded_batch_keyset(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pubs, const uint64_t *pub_off,
+                                          const uint8_t *digests, const uint64_t *dig_off, const uint8_t *sigs,
+                                          const uint64_t *sig_off, int encoding, size_t digest_len, uint32_t flags,
+                                          uint8_t *valid);
+int s2k_ecdsa_verify_encoded_batch_keyset_submit(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pubs,
+                                                 const uint64_t *pub_off, const uint8_t *digests, const uint64_t *dig_off,
+                                                 const uint8_t *sigs, const uint64_t *sig_off, int encoding, size_t digest_len,
+                                                 uint32_t flags, uint8_t *valid, s2k_ticket *ticket);
+int s2k_ctx_last_encoded_keyset_stats(s2k_ctx *ctx, uint64_t out[4]);
 
 /* ---- BIP-340 Schnorr verification (batched) ---------------------------------------- */
 /* For each i < n: bitcoin.SchnorrPublicKey.Verify(msg_i, sig_i) for the x-only key pk_i

@@ -275,6 +275,9 @@ def load_library() -> C.CDLL:
     u64 = C.c_uint64
     lib.s2k_ecdsa_verify_batch_submit.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, C.POINTER(u64)]
     lib.s2k_ecdsa_verify_encoded_batch_submit.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, ci, sz, u32, vp, C.POINTER(u64)]
+    lib.s2k_ecdsa_verify_encoded_batch_keyset.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, sz, u32, vp]
+    lib.s2k_ecdsa_verify_encoded_batch_keyset_submit.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, sz, u32, vp, C.POINTER(u64)]
+    lib.s2k_ctx_last_encoded_keyset_stats.argtypes = [vp, C.POINTER(u64)]
     lib.s2k_wait.argtypes = [vp, u64]
     lib.s2k_poll.argtypes = [vp, u64]
     lib.s2k_wait_all.argtypes = [vp]
@@ -426,6 +429,7 @@ EXPORTED_SYMBOLS = [
     "s2k_ecdsa_verify_recoverable_batch_bisect", "s2k_ecdsa_verify_recoverable_batch_bisect_device",
     "s2k_parse_asn1_signature", "s2k_parse_compact_signature", "s2k_is_valid_signature_encoding_bip0066",
     "s2k_ecdsa_verify_encoded_batch",
+    "s2k_ecdsa_verify_encoded_batch_keyset", "s2k_ecdsa_verify_encoded_batch_keyset_submit", "s2k_ctx_last_encoded_keyset_stats",
     "s2k_ecdsa_verify_batch_submit", "s2k_ecdsa_verify_encoded_batch_submit", "s2k_wait", "s2k_poll", "s2k_wait_all",
     "s2k_device_count", "s2k_group_create", "s2k_group_destroy", "s2k_group_size", "s2k_group_last_error",
     "s2k_group_set_key_grouping", "s2k_group_set_small_batch_max", "s2k_group_set_mid_batch_max", "s2k_group_ecdsa_verify_batch", "s2k_group_ecdsa_verify_batch_submit", "s2k_group_wait",
@@ -922,11 +926,13 @@ class Engine(_TicketOwner):
     # ---- key sets by key bytes (the set needs an index: KeySet.index_create) ------------------
     def keyset_lookup(self, keyset, keys, key_bytes: int = 64, stride: int = 0, offset: int = 0) -> np.ndarray:
         """uint32 array: for every key the lowest index of a key of `keyset` with the same bytes (key_bytes 64: X || Y; 32:
-        X), else 0xFFFFFFFF (s2k_keyset_lookup).  `keys`: n rows of key_bytes bytes; or, with `stride`, a buffer of records
-        of `stride` bytes whose key begins `offset` bytes into each (65-byte SEC1 records: stride=65, offset=1)."""
+        X), else 0xFFFFFFFF (s2k_keyset_lookup).  key_bytes 33: SEC1 compressed keys, answered with the index of the point
+        they decode to (no square root is taken), 0xFFFFFFFF when they decode to nothing.  `keys`: n rows of key_bytes
+        bytes; or, with `stride`, a buffer of records of `stride` bytes whose key begins `offset` bytes into each (65-byte
+        SEC1 records: stride=65, offset=1)."""
         key_bytes = int(key_bytes)
-        if key_bytes not in (32, 64):
-            raise ValueError("key_bytes is 64 or 32")
+        if key_bytes not in (32, 33, 64):
+            raise ValueError("key_bytes is 64, 32 or 33")
         if stride:
             stride, offset = int(stride), int(offset)
             buf = _arr(keys, 1).reshape(-1)
@@ -967,13 +973,14 @@ class Engine(_TicketOwner):
 
     def ecdsa_verify_encoded_batch(self, pubs, digests, sigs, encoding=ENCODING_ASN1, digest_len=0,
                                    reject_malleable=False, bip0066=False, force_complete=False) -> np.ndarray:
-        """PublicKey.Verify(digest, sig, opts) for lists of SEC1 keys, digests and encoded signatures."""
-        n = len(pubs)
-        if len(digests) != n or len(sigs) != n:
+        """PublicKey.Verify(digest, sig, opts) for lists of SEC1 keys, digests and encoded signatures (or pre-built
+        (blob, offsets) pairs, as the submit form takes)."""
+        def cat(x):
+            return x if isinstance(x, tuple) else _concat(list(x))
+        (pb, po), (db, do), (sb, so) = cat(pubs), cat(digests), cat(sigs)
+        n = len(po) - 1
+        if len(do) - 1 != n or len(so) - 1 != n:
             raise ValueError("length mismatch")
-        pb, po = _concat(list(pubs))
-        db, do = _concat(list(digests))
-        sb, so = _concat(list(sigs))
         out = np.zeros(n, dtype=np.uint8)
         flags = (REJECT_MALLEABLE if reject_malleable else 0) | (BIP0066 if bip0066 else 0) | \
                 (FORCE_COMPLETE if force_complete else 0)
@@ -981,6 +988,47 @@ class Engine(_TicketOwner):
                                                              do.ctypes.data, sb.ctypes.data, so.ctypes.data, encoding,
                                                              digest_len, flags, out.ctypes.data))
         return out
+
+    def _encoded_keyset_args(self, pubs, digests, sigs, reject_malleable, bip0066, force_worklist):
+        def cat(x):
+            return x if isinstance(x, tuple) else _concat(list(x))
+        (pb, po), (db, do), (sb, so) = cat(pubs), cat(digests), cat(sigs)
+        n = len(po) - 1
+        if len(do) - 1 != n or len(so) - 1 != n:
+            raise ValueError("length mismatch")
+        flags = (REJECT_MALLEABLE if reject_malleable else 0) | (BIP0066 if bip0066 else 0) | (FORCE_WORKLIST if force_worklist else 0)
+        return n, [pb, po, db, do, sb, so], flags
+
+    def ecdsa_verify_encoded_batch_keyset(self, keyset, pubs, digests, sigs, encoding=ENCODING_ASN1, digest_len=0,
+                                          reject_malleable=False, bip0066=False, force_worklist=False) -> np.ndarray:
+        """ecdsa_verify_encoded_batch's verdicts for the same arguments, with the signatures whose key `keyset` holds verified
+        on its tables; a compressed key of the set costs no square root (s2k_ecdsa_verify_encoded_batch_keyset).  Lists of
+        byte strings, or pre-built (blob, offsets) pairs."""
+        n, a, flags = self._encoded_keyset_args(pubs, digests, sigs, reject_malleable, bip0066, force_worklist)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_verify_encoded_batch_keyset(self._h, keyset._k, n, *(x.ctypes.data for x in a), int(encoding),
+                                                                    int(digest_len), flags, out.ctypes.data))
+        return out
+
+    def ecdsa_verify_encoded_batch_keyset_submit(self, keyset, pubs, digests, sigs, encoding=ENCODING_ASN1, digest_len=0,
+                                                 reject_malleable=False, bip0066=False, force_worklist=False) -> "Ticket":
+        """s2k_ecdsa_verify_encoded_batch_keyset_submit: one ticket, the whole batch in one piece; the ticket keeps the
+        buffers and the set alive."""
+        n, a, flags = self._encoded_keyset_args(pubs, digests, sigs, reject_malleable, bip0066, force_worklist)
+        out = np.zeros(n, dtype=np.uint8)
+        t = C.c_uint64(0)
+        self._check(self._lib.s2k_ecdsa_verify_encoded_batch_keyset_submit(self._h, keyset._k, n, *(x.ctypes.data for x in a),
+                                                                           int(encoding), int(digest_len), flags, out.ctypes.data,
+                                                                           C.byref(t)))
+        return self._hold(int(t.value), out, a + [keyset])
+
+    def last_encoded_keyset_stats(self) -> dict:
+        """of the last synchronous ecdsa_verify_encoded_batch_keyset, summed over its pieces: signatures verified under a key
+        of the set that came as 33 / as 65 bytes, the length of the decompression list (= square roots taken), and the items
+        of the pieces the set was not used for (s2k_ctx_last_encoded_keyset_stats)"""
+        o = (C.c_uint64 * 4)()
+        self._check(self._lib.s2k_ctx_last_encoded_keyset_stats(self._h, o))
+        return {"hits33": int(o[0]), "hits65": int(o[1]), "roots": int(o[2]), "delegated": int(o[3])}
 
     def ecdsa_verify_batch_device(self, n, d_pub_xy, d_digest32, d_r, d_s, d_valid, flags=0, stream=0):
         """Device-pointer form: integer device addresses, enqueued on `stream` (a hipStream_t value)."""

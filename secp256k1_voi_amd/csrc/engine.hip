@@ -2816,6 +2816,7 @@ void s2k_ctx_destroy(s2k_ctx* ctx) {
   if (ctx->ktab) (void)hipFree(ctx->ktab);
   if (ctx->xkeys) (void)hipFree(ctx->xkeys);
   if (ctx->ks_found) (void)hipFree(ctx->ks_found);
+  if (ctx->ek_ctr) (void)hipFree(ctx->ek_ctr);
   for (size_t i = 0; i < ctx->prof_cap; ++i) (void)hipEventDestroy(ctx->prof_ev[i]);
   for (size_t i = 0; i < ctx->msm_prof_cap; ++i) (void)hipEventDestroy(ctx->msm_prof_ev[i]);
   delete[] ctx->msm_prof_ev;
@@ -3431,7 +3432,8 @@ int s2k_keyset_lookup_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   int rc = keyset_index_check(ctx, ks);
   if (rc) return rc;
-  if ((key_bytes != 64 && key_bytes != 32) || stride < key_bytes) return fail(ctx, S2K_ERR_ARG, "keys of 64 or 32 bytes, stride >= key_bytes");
+  if ((key_bytes != 64 && key_bytes != 32 && key_bytes != 33) || stride < key_bytes)
+    return fail(ctx, S2K_ERR_ARG, "keys of 64, 32 or 33 bytes, stride >= key_bytes");
   if (n == 0) return S2K_OK;
   if (!d_keys || !d_key_index) return fail(ctx, S2K_ERR_ARG, "null buffer");
   if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
@@ -3441,8 +3443,8 @@ int s2k_keyset_lookup_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const
   if (rc) return rc;
   size_t off[5];
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
-  rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, n, (const uint8_t*)d_keys, (int)key_bytes,
-                               stride, (uint32_t*)d_key_index);
+  rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n,
+                               (const uint8_t*)d_keys, (int)key_bytes, stride, (uint32_t*)d_key_index);
   if (rc) return rc;
   return ctx_leave(ctx, st);
 }
@@ -3451,7 +3453,8 @@ int s2k_keyset_lookup(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   int rc = keyset_index_check(ctx, ks);
   if (rc) return rc;
-  if ((key_bytes != 64 && key_bytes != 32) || stride < key_bytes) return fail(ctx, S2K_ERR_ARG, "keys of 64 or 32 bytes, stride >= key_bytes");
+  if ((key_bytes != 64 && key_bytes != 32 && key_bytes != 33) || stride < key_bytes)
+    return fail(ctx, S2K_ERR_ARG, "keys of 64, 32 or 33 bytes, stride >= key_bytes");
   if (n == 0) return S2K_OK;
   if (!keys || !key_index) return fail(ctx, S2K_ERR_ARG, "null buffer");
   if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
@@ -3490,6 +3493,20 @@ static int bykey_check(s2k_ctx* ctx, const s2k_keyset* ks, uint32_t flags) {
   if (flags & S2K_ECDSA_FORCE_COMPLETE) return fail(ctx, S2K_ERR_ARG, "S2K_ECDSA_FORCE_COMPLETE does not apply to key sets");
   return S2K_OK;
 }
+}  // extern "C"
+// (for the encoded entry points, ingest.hip: engine_internal.h)
+__attribute__((visibility("hidden"))) bool s2k_internal_bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags) {
+  return bykey_delegates(ctx, n, flags);
+}
+__attribute__((visibility("hidden"))) int s2k_internal_bykey_view(s2k_ctx* ctx, const s2k_keyset* ks, uint32_t flags, s2k_bykey_view* out) {
+  int rc = bykey_check(ctx, ks, flags);
+  if (rc) return rc;
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  *out = {ks->base + off[0], ks->base + off[2], ks->index, ks->index_log2, ks->index_seed};
+  return S2K_OK;
+}
+extern "C" {
 
 int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig,
                                                const void* d_r, const void* d_s, uint32_t flags, void* d_valid, void* hip_stream) {
@@ -3500,9 +3517,14 @@ int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* k
   if (!d_pub_xy || !d_dig || !d_r || !d_s || !d_valid) return fail(ctx, S2K_ERR_ARG, "null buffer");
   if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
   if (bykey_delegates(ctx, n, flags)) return s2k_ecdsa_verify_batch_device(ctx, n, d_pub_xy, d_dig, d_r, d_s, flags, d_valid, hip_stream);
+  return s2k_internal_bykey_device(ctx, ks, n, d_pub_xy, d_dig, d_r, d_s, flags, d_valid, (hipStream_t)hip_stream, nullptr);
+}
+}  // extern "C"
+__attribute__((visibility("hidden"))) int s2k_internal_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy,
+                                                                    const void* d_dig, const void* d_r, const void* d_s, uint32_t flags,
+                                                                    void* d_valid, hipStream_t st, const uint32_t* d_found) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  rc = ctx_enter(ctx, st);
+  int rc = ctx_enter(ctx, st);
   if (rc) return rc;
   rc = s2k_internal_ensure_ws(ctx, n);
   if (rc) return rc;
@@ -3516,7 +3538,9 @@ int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* k
   const lane_ws w = lane_ws_of(ctx, n);
   const uint8_t *pub = (const uint8_t*)d_pub_xy, *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s;
   uint8_t* valid = (uint8_t*)d_valid;
+  // (a caller that resolved the keys itself did so into this very buffer, reserved for at least n: it does not move here)
   uint32_t* found = (uint32_t*)ctx->ks_found;
+  if (d_found && d_found != found) return fail(ctx, S2K_ERR_ARG, "key indices outside the context's buffer");
   size_t off[5];
   (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
@@ -3535,7 +3559,8 @@ int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* k
   launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
-  if (rc == S2K_OK) rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, n, pub, 64, 64, found);
+  if (rc == S2K_OK && !d_found)
+    rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n, pub, 64, 64, found);
   if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, found, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
@@ -3558,6 +3583,7 @@ int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* k
   prof_mark(ctx, st, 5);
   return ctx_leave(ctx, st);
 }
+extern "C" {
 
 int s2k_ecdsa_verify_batch_keyset_bykey(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pub, const uint8_t* dig,
                                         const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* valid) {

@@ -191,6 +191,11 @@ struct s2k_ctx {
   size_t xkeys_bytes = 0;
   void* ks_found = nullptr;          // ECDSA over a key set by key bytes: the key indices the set's index found for a call's signatures
   size_t ks_found_bytes = 0;
+  // encoded ECDSA over a key set (ingest.hip): device counters of the last synchronous call (EK_* below; allocated on the
+  // first such call), the items of its pieces the set was not used for, and whether there was such a call at all
+  uint32_t* ek_ctr = nullptr;
+  uint64_t ek_delegated = 0;
+  bool ek_have = false;
   uint32_t* kg_counters = nullptr;   // device, KG_COUNTERS words (of the last call; null: it did not group)
   uint32_t kg_last_max_tables = 0;   // table cap of that call (the device counter of tables is not clamped)
   uint32_t* last_wl_count = nullptr; // device: the last verification call's complete-formula worklist length
@@ -586,7 +591,27 @@ enum { S2K_KSI_OCCUPIED = 0, S2K_KSI_LONGEST = 1, S2K_KSI_FAILED = 2, S2K_KSI_IN
 int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys, uint64_t* slots, uint32_t log2_slots,
                            uint64_t seed, uint32_t* info);
 int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, const uint64_t* slots, uint32_t log2_slots, uint64_t seed,
-                            size_t n, const uint8_t* d_keys, int key_bytes, size_t stride, uint32_t* d_out);
+                            const uint8_t* key_valid, size_t n, const uint8_t* d_keys, int key_bytes, size_t stride, uint32_t* d_out);
+
+// ECDSA by key bytes over a key set, for the encoded entry points (ingest.hip; engine.hip owns the set).
+//   s2k_internal_bykey_view      what s2k_ecdsa_verify_batch_keyset_bykey asks of its set and flags (own context, an index, no
+//                                S2K_ECDSA_FORCE_COMPLETE), then what a kernel needs to probe the set's index
+//   s2k_internal_bykey_delegates the plain call would take its wave-per-signature or four-lanes-per-signature ladder for this
+//                                n: the set is not used
+//   s2k_internal_bykey_device    s2k_ecdsa_verify_batch_keyset_bykey_device past its checks, never delegating.  d_found:
+//                                null, or the key indices of the n signatures already resolved (0xFFFFFFFF: not in the set;
+//                                the lookup launch is skipped) - ctx->ks_found, reserved and filled by the caller on `st`
+struct s2k_bykey_view {
+  const uint8_t* keys;        // the set's keys, 64 bytes each
+  const uint8_t* key_valid;   // one byte per key (s2k_keyset_valid_keys)
+  uint64_t* slots;            // the index
+  uint32_t log2_slots;
+  uint64_t seed;
+};
+int s2k_internal_bykey_view(s2k_ctx* ctx, const s2k_keyset* ks, uint32_t flags, s2k_bykey_view* out);
+bool s2k_internal_bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags);
+int s2k_internal_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig, const void* d_r,
+                              const void* d_s, uint32_t flags, void* d_valid, hipStream_t st, const uint32_t* d_found);
 
 struct dev_buf {
   void* p = nullptr;

@@ -6,7 +6,8 @@
 // The single-item parsers are host functions (no GPU needed).  The batch entry point uploads the
 // raw bytes and parses on the device, one lane per item (k_parse_encoded): at 10^8 verifications
 // per second a host loop over DER signatures (about 60 ns each) would be eight times slower than
-// the GPU.  Compressed keys are decompressed in the same kernel (one field square root).
+// the GPU.  Compressed keys are decompressed in the same kernel (one field square root).  Over a key set with an index
+// (s2k_ecdsa_verify_encoded_batch_keyset) the keys are resolved against the set instead: k_parse_encoded_keyset, k_decompress_list.
 #include <cstdint>
 #include <cstring>
 
@@ -14,6 +15,7 @@
 #include "der.h"
 #include "engine_internal.h"
 #include "fe29.h"
+#include "keyset_index.h"
 
 namespace {
 
@@ -70,30 +72,25 @@ S2K_DEV bool pe_stage(const uint8_t* __restrict__ blob, uint64_t lo, uint64_t hi
     *reinterpret_cast<uint4*>(lds + t) = *reinterpret_cast<const uint4*>(blob + a + t);
   return true;
 }
-__global__ void __launch_bounds__(256)
-k_parse_encoded(uint32_t first, uint32_t n, const uint8_t* __restrict__ pubs, const uint64_t* __restrict__ pub_off,
-                const uint8_t* __restrict__ digests, const uint64_t* __restrict__ dig_off, const uint8_t* __restrict__ sigs,
-                const uint64_t* __restrict__ sig_off, int encoding, uint32_t digest_len, int bip66, int low_s, uint8_t* __restrict__ xy,
-                uint8_t* __restrict__ dg, uint8_t* __restrict__ rr, uint8_t* __restrict__ ss, uint8_t* __restrict__ recid) {
-  __shared__ uint4 lds_pub[PE_PUB_CAP / 16], lds_dig[PE_DIG_CAP / 16], lds_sig[PE_SIG_CAP / 16];
-  const uint32_t b0 = blockIdx.x * 256;
-  if (b0 >= n) return;
-  const uint32_t cnt = n - b0 < 256u ? n - b0 : 256u;
-  const size_t i0 = (size_t)first + b0;                  // items [first, first + n) of the batch
-  uint64_t a_pub, a_dig, a_sig;
-  const bool st_pub = pe_stage(pubs, pub_off[i0], pub_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_pub), PE_PUB_CAP, a_pub);
-  const bool st_dig = pe_stage(digests, dig_off[i0], dig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_dig), PE_DIG_CAP, a_dig);
-  const bool st_sig = pe_stage(sigs, sig_off[i0], sig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_sig), PE_SIG_CAP, a_sig);
-  __syncthreads();
-  if (threadIdx.x >= cnt) return;
-  const size_t i = i0 + threadIdx.x;
-  const uint64_t po = pub_off[i], dof = dig_off[i], so = sig_off[i];
-  const uint8_t* pk = st_pub ? reinterpret_cast<const uint8_t*>(lds_pub) + (po - a_pub) : pubs + po;
-  const size_t pk_len = (size_t)(pub_off[i + 1] - po);
-  const uint8_t* d = st_dig ? reinterpret_cast<const uint8_t*>(lds_dig) + (dof - a_dig) : digests + dof;
-  const size_t d_len = (size_t)(dig_off[i + 1] - dof);
-  const uint8_t* sg = st_sig ? reinterpret_cast<const uint8_t*>(lds_sig) + (so - a_sig) : sigs + so;
-  size_t sg_len = (size_t)(sig_off[i + 1] - so);
+// What the key-set variant of the parse step gets on top (k_parse_encoded_keyset): the set's index and validity bytes, where the
+// key indices of the piece's items go, the decompression list and the counters of the call (s2k_ctx::ek_ctr).
+enum { EK_HIT33 = 0, EK_HIT65 = 1, EK_ROOTS = 2, EK_LIST = 3, EK_WORDS = 4 };   // [EK_LIST]: the list's length in the piece under way; [EK_ROOTS]: of the pieces before it
+enum { PE_KEY_NONE = 0, PE_KEY_HIT33 = 1, PE_KEY_HIT65 = 2, PE_KEY_ROOT = 3 };   // what became of an item's key
+struct pe_keyset {
+  ksi_table t;
+  const uint8_t* key_valid;
+  uint32_t* found;     // key index per item of the piece, or KSI_NONE
+  uint32_t* list;      // items (of the batch) whose compressed key the set does not hold: k_decompress_list takes their roots
+  uint32_t* ctr;
+};
+
+// One item of the parse step: item i of the batch, its three strings and their lengths.  KS = false is k_parse_encoded; KS = true
+// resolves the key against a set instead of decoding it (returns PE_KEY_*, *found the key's index in the set or KSI_NONE).
+template <bool KS>
+S2K_DEV int pe_item(size_t i, const uint8_t* pk, size_t pk_len, const uint8_t* d, size_t d_len, const uint8_t* sg, size_t sg_len, int encoding,
+                    uint32_t digest_len, int bip66, int low_s, uint8_t* __restrict__ xy, uint8_t* __restrict__ dg, uint8_t* __restrict__ rr,
+                    uint8_t* __restrict__ ss, uint8_t* __restrict__ recid, const pe_keyset* ks, uint32_t* found) {
+  int key = PE_KEY_NONE;
   uint32_t rw[8], sw[8], qw[16], dw[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) rw[j] = sw[j] = dw[j] = 0;
@@ -144,32 +141,56 @@ k_parse_encoded(uint32_t first, uint32_t n, const uint8_t* __restrict__ pubs, co
     }
     ok = rc == 0;
   }
+  if (KS) *found = KSI_NONE;
   if (ok) {
     if (pk_len == 65 && pk[0] == 0x04) {
       be_string_words(qw, pk + 1, 32);                   // canonical coordinates and the curve equation: k_verify_fast
       be_string_words(qw + 8, pk + 33, 32);
+      if constexpr (KS) {
+        // (the words as a 64-byte store puts them back are the key's bytes as little-endian words: what the index compares)
+        *found = ksi_lookup64<ksi_dev_mem>(ks->t, qw);
+        if (*found != KSI_NONE) key = PE_KEY_HIT65;
+      }
     } else if (pk_len == 33 && (pk[0] == 0x02 || pk[0] == 0x03)) {
       // SetCompressedBytes (point_s11n.go:140-176)
       uint32_t xb[8], xw[8];
       be_string_words(xb, pk + 1, 32);
 #pragma unroll
       for (int j = 0; j < 8; ++j) xw[j] = __builtin_bswap32(xb[7 - j]);   // little-endian words of the value
-      ok = fe_is_canonical_raw(xw);
-      if (ok) {
-        fe29 x = fe29_from_words(xw);
-        fe29 rhs = fe29_mul(fe29_sqr(x), x);
-        rhs.n[0] += 7;
-        fe29 y;
-        ok = fe29_sqrt(y, rhs);
-        y = fe29_normalize(y);
-        const bool want_odd = pk[0] == 0x03;
-        y = fe29_normalize(fe29_select(((y.n[0] & 1u) != 0) != want_odd, y, fe29_negate(y, 1)));
-        uint32_t yw[8];
-        fe29_to_words(yw, y);
+      if constexpr (KS) {
+        // a key the set holds decodes to the set's own 64 bytes: no root.  Any other canonical X goes on the list with the
+        // asked parity parked in the first word of Y (k_decompress_list: the root, or the item's failure)
+        *found = ksi_lookup33<ksi_dev_mem>(ks->t, ks->key_valid, pk[0], xb);
+        if (*found != KSI_NONE) {
+          ksi_dev_mem::load_key(ks->t.keys + (size_t)*found * 64, qw, 16);
+          key = PE_KEY_HIT33;
+        } else {
+          ok = fe_is_canonical_raw(xw);
+          if (ok) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          qw[j] = xb[j];
-          qw[8 + j] = __builtin_bswap32(yw[7 - j]);
+            for (int j = 0; j < 8; ++j) qw[j] = xb[j];
+            qw[8] = pk[0] & 1u;
+            key = PE_KEY_ROOT;
+          }
+        }
+      } else {
+        ok = fe_is_canonical_raw(xw);
+        if (ok) {
+          fe29 x = fe29_from_words(xw);
+          fe29 rhs = fe29_mul(fe29_sqr(x), x);
+          rhs.n[0] += 7;
+          fe29 y;
+          ok = fe29_sqrt(y, rhs);
+          y = fe29_normalize(y);
+          const bool want_odd = pk[0] == 0x03;
+          y = fe29_normalize(fe29_select(((y.n[0] & 1u) != 0) != want_odd, y, fe29_negate(y, 1)));
+          uint32_t yw[8];
+          fe29_to_words(yw, y);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            qw[j] = xb[j];
+            qw[8 + j] = __builtin_bswap32(yw[7 - j]);
+          }
         }
       }
     } else {
@@ -183,6 +204,126 @@ k_parse_encoded(uint32_t first, uint32_t n, const uint8_t* __restrict__ pubs, co
   store32(rr + i * 32, rw, ok);
   store32(ss + i * 32, sw, ok);
   if (recid) recid[i] = ok ? v : 0xff;                   // (0xff: no recovery id, RecoverPublicKey refuses it)
+  return key;
+}
+
+__global__ void __launch_bounds__(256)
+k_parse_encoded(uint32_t first, uint32_t n, const uint8_t* __restrict__ pubs, const uint64_t* __restrict__ pub_off,
+                const uint8_t* __restrict__ digests, const uint64_t* __restrict__ dig_off, const uint8_t* __restrict__ sigs,
+                const uint64_t* __restrict__ sig_off, int encoding, uint32_t digest_len, int bip66, int low_s, uint8_t* __restrict__ xy,
+                uint8_t* __restrict__ dg, uint8_t* __restrict__ rr, uint8_t* __restrict__ ss, uint8_t* __restrict__ recid) {
+  __shared__ uint4 lds_pub[PE_PUB_CAP / 16], lds_dig[PE_DIG_CAP / 16], lds_sig[PE_SIG_CAP / 16];
+  const uint32_t b0 = blockIdx.x * 256;
+  if (b0 >= n) return;
+  const uint32_t cnt = n - b0 < 256u ? n - b0 : 256u;
+  const size_t i0 = (size_t)first + b0;                  // items [first, first + n) of the batch
+  uint64_t a_pub, a_dig, a_sig;
+  const bool st_pub = pe_stage(pubs, pub_off[i0], pub_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_pub), PE_PUB_CAP, a_pub);
+  const bool st_dig = pe_stage(digests, dig_off[i0], dig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_dig), PE_DIG_CAP, a_dig);
+  const bool st_sig = pe_stage(sigs, sig_off[i0], sig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_sig), PE_SIG_CAP, a_sig);
+  __syncthreads();
+  if (threadIdx.x >= cnt) return;
+  const size_t i = i0 + threadIdx.x;
+  const uint64_t po = pub_off[i], dof = dig_off[i], so = sig_off[i];
+  const uint8_t* pk = st_pub ? reinterpret_cast<const uint8_t*>(lds_pub) + (po - a_pub) : pubs + po;
+  const size_t pk_len = (size_t)(pub_off[i + 1] - po);
+  const uint8_t* d = st_dig ? reinterpret_cast<const uint8_t*>(lds_dig) + (dof - a_dig) : digests + dof;
+  const size_t d_len = (size_t)(dig_off[i + 1] - dof);
+  const uint8_t* sg = st_sig ? reinterpret_cast<const uint8_t*>(lds_sig) + (so - a_sig) : sigs + so;
+  const size_t sg_len = (size_t)(sig_off[i + 1] - so);
+  (void)pe_item<false>(i, pk, pk_len, d, d_len, sg, sg_len, encoding, digest_len, bip66, low_s, xy, dg, rr, ss, recid, nullptr, nullptr);
+}
+
+// The parse step of the encoded calls over a key set: k_parse_encoded for digest and signature; the key of an item whose
+// digest and signature parsed is resolved against the set (pe_item<true>).  found[] is per item of the piece (the sort of
+// s2k_internal_bykey_device reads it); a compressed key the set does not hold is appended to the decompression list, one
+// atomic add per wave, and the three counters of the call likewise.
+__global__ void __launch_bounds__(256)
+k_parse_encoded_keyset(uint32_t first, uint32_t n, const uint8_t* __restrict__ pubs, const uint64_t* __restrict__ pub_off,
+                       const uint8_t* __restrict__ digests, const uint64_t* __restrict__ dig_off, const uint8_t* __restrict__ sigs,
+                       const uint64_t* __restrict__ sig_off, int encoding, uint32_t digest_len, int bip66, int low_s,
+                       uint8_t* __restrict__ xy, uint8_t* __restrict__ dg, uint8_t* __restrict__ rr, uint8_t* __restrict__ ss, pe_keyset ks) {
+  __shared__ uint4 lds_pub[PE_PUB_CAP / 16], lds_dig[PE_DIG_CAP / 16], lds_sig[PE_SIG_CAP / 16];
+  const uint32_t b0 = blockIdx.x * 256;
+  if (b0 >= n) return;
+  const uint32_t cnt = n - b0 < 256u ? n - b0 : 256u;
+  const size_t i0 = (size_t)first + b0;
+  uint64_t a_pub, a_dig, a_sig;
+  const bool st_pub = pe_stage(pubs, pub_off[i0], pub_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_pub), PE_PUB_CAP, a_pub);
+  const bool st_dig = pe_stage(digests, dig_off[i0], dig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_dig), PE_DIG_CAP, a_dig);
+  const bool st_sig = pe_stage(sigs, sig_off[i0], sig_off[i0 + cnt], reinterpret_cast<uint8_t*>(lds_sig), PE_SIG_CAP, a_sig);
+  __syncthreads();
+  // (no early exit: the lanes past the last item take part in the ballots below, and count nothing)
+  const bool live = threadIdx.x < cnt;
+  const size_t i = i0 + (live ? threadIdx.x : 0u);
+  int key = PE_KEY_NONE;
+  if (live) {
+    const uint64_t po = pub_off[i], dof = dig_off[i], so = sig_off[i];
+    const uint8_t* pk = st_pub ? reinterpret_cast<const uint8_t*>(lds_pub) + (po - a_pub) : pubs + po;
+    const size_t pk_len = (size_t)(pub_off[i + 1] - po);
+    const uint8_t* d = st_dig ? reinterpret_cast<const uint8_t*>(lds_dig) + (dof - a_dig) : digests + dof;
+    const size_t d_len = (size_t)(dig_off[i + 1] - dof);
+    const uint8_t* sg = st_sig ? reinterpret_cast<const uint8_t*>(lds_sig) + (so - a_sig) : sigs + so;
+    const size_t sg_len = (size_t)(sig_off[i + 1] - so);
+    uint32_t f;
+    key = pe_item<true>(i, pk, pk_len, d, d_len, sg, sg_len, encoding, digest_len, bip66, low_s, xy, dg, rr, ss, nullptr, &ks, &f);
+    ks.found[b0 + threadIdx.x] = f;
+  }
+  const unsigned long long m33 = __ballot(key == PE_KEY_HIT33), m65 = __ballot(key == PE_KEY_HIT65), mroot = __ballot(key == PE_KEY_ROOT);
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = 0;
+  if (lane == 0) {
+    if (m33) atomicAdd(&ks.ctr[EK_HIT33], (uint32_t)__popcll(m33));
+    if (m65) atomicAdd(&ks.ctr[EK_HIT65], (uint32_t)__popcll(m65));
+    if (mroot) base = atomicAdd(&ks.ctr[EK_LIST], (uint32_t)__popcll(mroot));
+  }
+  base = __shfl(base, 0, 64);
+  // (the list has room for every item of the piece, and each item is appended at most once)
+  if (key == PE_KEY_ROOT) ks.list[base + (uint32_t)__popcll(mroot & (((unsigned long long)1 << lane) - 1))] = (uint32_t)i;
+}
+
+// SetCompressedBytes for the items of the decompression list, densely: a lane per entry, so ceil(list / 64) waves pay for
+// square roots whatever share of the batch's waves held such an item.  The grid is fixed; the blocks read the list's length
+// (the worklist shape of k_verify_fallback).  An item's X is in xy already, the asked parity in the first word of its Y.  An
+// X with no root fails the item as k_parse_encoded does: r = s = digest = 0.
+__global__ void __launch_bounds__(256)
+k_decompress_list(const uint32_t* __restrict__ list, uint32_t* __restrict__ ctr, uint32_t cap, uint8_t* __restrict__ xy,
+                  uint8_t* __restrict__ dg, uint8_t* __restrict__ rr, uint8_t* __restrict__ ss) {
+  const uint32_t have = ctr[EK_LIST];
+  const uint32_t count = have < cap ? have : cap;
+  for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < count; e += gridDim.x * 256) {
+    const size_t i = list[e];
+    uint4* q = reinterpret_cast<uint4*>(xy + i * 64);
+    const uint4 a = q[0], b = q[1];
+    const uint32_t xb[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const bool want_odd = (q[2].x & 1u) != 0;
+    uint32_t xw[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xw[j] = __builtin_bswap32(xb[7 - j]);
+    fe29 x = fe29_from_words(xw);
+    fe29 rhs = fe29_mul(fe29_sqr(x), x);
+    rhs.n[0] += 7;
+    fe29 y;
+    const bool ok = fe29_sqrt(y, rhs);
+    y = fe29_normalize(y);
+    y = fe29_normalize(fe29_select(((y.n[0] & 1u) != 0) != want_odd, y, fe29_negate(y, 1)));
+    uint32_t yw[8], yb[8];
+    fe29_to_words(yw, y);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) yb[j] = __builtin_bswap32(yw[7 - j]);
+    store32(xy + i * 64 + 32, yb, true);
+    if (!ok) {
+      const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      store32(dg + i * 32, z, false);
+      store32(rr + i * 32, z, false);
+      store32(ss + i * 32, z, false);
+    }
+  }
+}
+// behind k_decompress_list, on the same stream: the piece's list joins the call's total and the next piece starts an empty one
+__global__ void k_decompress_list_close(uint32_t* __restrict__ ctr) {
+  ctr[EK_ROOTS] += ctr[EK_LIST];
+  ctr[EK_LIST] = 0;
 }
 
 // EncodingCompactRecoverable: valid iff the key recovered from (digest, r, s, v) is the key the caller holds
@@ -384,6 +525,177 @@ int s2k_ecdsa_verify_encoded_batch_submit(s2k_ctx* ctx, size_t n, const uint8_t*
     }
   }
   s2k_internal_pipe_issue(ctx, sl, ticket);
+  return S2K_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Encoded batches over a key set: s2k_ecdsa_verify_encoded_batch's verdicts, with the signatures whose key the set holds
+// verified on its tables.  The parse step resolves the SEC1 keys against the set's index (k_parse_encoded_keyset): a
+// compressed key the set holds costs no square root - the set has its Y -, the others go on a list whose roots are taken
+// densely (k_decompress_list); the key indices land where the sort of s2k_internal_bykey_device reads them.
+// A piece the plain call would verify on its wave-per-signature or four-lanes-per-signature ladder (s2k_internal_bykey_delegates)
+// is parsed and verified exactly as the plain call does: the set is not used for it.
+// Enqueue only; one_shot: the whole batch in one piece (submit / wait).  *delegated: the items of such pieces.
+// ---------------------------------------------------------------------------------------
+static int encoded_keyset_enqueue(s2k_ctx* ctx, const s2k_keyset* ks, const s2k_bykey_view& kv, size_t n, const uint8_t* pubs,
+                                  const uint64_t* pub_off, const uint8_t* digests, const uint64_t* dig_off, const uint8_t* sigs,
+                                  const uint64_t* sig_off, int encoding, size_t digest_len, uint32_t flags, uint8_t* h_out, bool one_shot,
+                                  uint64_t* delegated) {
+  const bool bip66 = (flags & S2K_ECDSA_BIP0066) != 0;
+  const uint32_t vflags = flags & (S2K_ECDSA_REJECT_MALLEABLE | S2K_ECDSA_FORCE_WORKLIST);
+  *delegated = 0;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ctx_streams(ctx);
+  if (rc) return rc;
+  // nothing is grouped here, so the pieces need not be the plain call's two halves: two full rounds of the ladder each
+  const size_t round = (size_t)3 * 4 * (size_t)ctx->cu_count * 64;
+  const size_t chunk = (one_shot || n <= 3 * round) ? n : 2 * round;
+  const size_t pub_bytes = pub_off[n], dig_bytes = dig_off[n], sig_bytes = sig_off[n];
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_pub = 0, o_dig = o_pub + al(pub_bytes), o_sig = o_dig + al(dig_bytes), o_po = o_sig + al(sig_bytes),
+               o_do = o_po + al((n + 1) * 8), o_so = o_do + al((n + 1) * 8), o_xy = o_so + al((n + 1) * 8), o_dg = o_xy + al(n * 64),
+               o_r = o_dg + al(n * 32), o_s = o_r + al(n * 32), o_v = o_s + al(n * 32), o_list = o_v + al(n),
+               total = o_list + al(chunk * sizeof(uint32_t));
+  // every buffer before the first launch: growing one synchronises the device
+  rc = ctx_reserve(ctx, &ctx->io, &ctx->io_bytes, total);
+  if (rc) return rc;
+  rc = ctx_reserve(ctx, &ctx->ks_found, &ctx->ks_found_bytes, ((chunk + 63) & ~(size_t)63) * sizeof(uint32_t));
+  if (rc) return rc;
+  if (!ctx->ek_ctr) HIP_TRY(ctx, hipMalloc((void**)&ctx->ek_ctr, 256));
+  uint8_t* io = (uint8_t*)ctx->io;
+  hipStream_t st = ctx->s_comp;
+  rc = ctx_enter(ctx, st);               // (the buffers above may be a call's on another stream)
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->ek_ctr, 0, EK_WORDS * sizeof(uint32_t), st));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_po, pub_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_do, dig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_so, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
+  const pe_keyset pk = {{kv.slots, (uint32_t)(((uint64_t)1 << kv.log2_slots) - 1), kv.seed, kv.keys}, kv.key_valid, (uint32_t*)ctx->ks_found,
+                        (uint32_t*)(io + o_list), ctx->ek_ctr};
+  int k = 0;
+  for (size_t lo = 0; lo < n; lo += chunk, ++k) {
+    const size_t cnt = n - lo < chunk ? n - lo : chunk, hi = lo + cnt;
+    HIP_TRY(ctx, hipMemcpyAsync(io + o_pub + pub_off[lo], pubs + pub_off[lo], pub_off[hi] - pub_off[lo], hipMemcpyHostToDevice, ctx->s_copy));
+    HIP_TRY(ctx, hipMemcpyAsync(io + o_dig + dig_off[lo], digests + dig_off[lo], dig_off[hi] - dig_off[lo], hipMemcpyHostToDevice, ctx->s_copy));
+    HIP_TRY(ctx, hipMemcpyAsync(io + o_sig + sig_off[lo], sigs + sig_off[lo], sig_off[hi] - sig_off[lo], hipMemcpyHostToDevice, ctx->s_copy));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_copied[k & 1], ctx->s_copy));
+    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_copied[k & 1], 0));
+    if (s2k_internal_bykey_delegates(ctx, cnt, flags)) {
+      k_parse_encoded<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)lo, (uint32_t)cnt, io + o_pub, (const uint64_t*)(io + o_po), io + o_dig,
+                                                      (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so), encoding,
+                                                      (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0,
+                                                      io + o_xy, io + o_dg, io + o_r, io + o_s, nullptr);
+      HIP_TRY(ctx, hipGetLastError());
+      rc = s2k_ecdsa_verify_batch_device(ctx, cnt, io + o_xy + lo * 64, io + o_dg + lo * 32, io + o_r + lo * 32, io + o_s + lo * 32, vflags,
+                                         io + o_v + lo, st);
+      if (rc) return rc;
+      *delegated += cnt;
+      continue;
+    }
+    k_parse_encoded_keyset<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)lo, (uint32_t)cnt, io + o_pub, (const uint64_t*)(io + o_po), io + o_dig,
+                                                           (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so), encoding,
+                                                           (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0,
+                                                           io + o_xy, io + o_dg, io + o_r, io + o_s, pk);
+    HIP_TRY(ctx, hipGetLastError());
+    k_decompress_list<<<fallback_blocks(ctx, cnt), 256, 0, st>>>(pk.list, pk.ctr, (uint32_t)cnt, io + o_xy, io + o_dg, io + o_r, io + o_s);
+    HIP_TRY(ctx, hipGetLastError());
+    k_decompress_list_close<<<1, 1, 0, st>>>(pk.ctr);
+    HIP_TRY(ctx, hipGetLastError());
+    rc = s2k_internal_bykey_device(ctx, ks, cnt, io + o_xy + lo * 64, io + o_dg + lo * 32, io + o_r + lo * 32, io + o_s + lo * 32, vflags,
+                                   io + o_v + lo, st, pk.found);
+    if (rc) return rc;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(h_out, io + o_v, n, hipMemcpyDeviceToHost, st));
+  return S2K_OK;
+}
+
+// what both entry points refuse before they look at the batch
+static int encoded_keyset_check(s2k_ctx* ctx, const s2k_keyset* ks, int encoding, uint32_t flags, s2k_bykey_view* kv) {
+  if (encoding == S2K_ENCODING_COMPACT_RECOVERABLE)
+    return fail(ctx, S2K_ERR_ARG, "S2K_ENCODING_COMPACT_RECOVERABLE recovers the key: it has no use for a key set");
+  return s2k_internal_bykey_view(ctx, ks, flags, kv);
+}
+
+int s2k_ecdsa_verify_encoded_batch_keyset(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pubs, const uint64_t* pub_off,
+                                          const uint8_t* digests, const uint64_t* dig_off, const uint8_t* sigs, const uint64_t* sig_off,
+                                          int encoding, size_t digest_len, uint32_t flags, uint8_t* valid) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  s2k_bykey_view kv;
+  int rc = encoded_keyset_check(ctx, ks, encoding, flags, &kv);
+  if (rc) return rc;
+  if (n == 0) return S2K_OK;
+  rc = encoded_check_args(ctx, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, &digest_len, &flags, valid);
+  if (rc) return rc;
+  const uint8_t* small_out = nullptr;
+  if (s2k_internal_bykey_delegates(ctx, n, flags)) {
+    // the whole call is one such piece: the plain call, with its route for small calls
+    ctx->ek_have = true;
+    ctx->ek_delegated = n;
+    if (ctx->ek_ctr) HIP_TRY(ctx, hipMemset(ctx->ek_ctr, 0, EK_WORDS * sizeof(uint32_t)));
+    rc = encoded_enqueue_inner(ctx, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, digest_len, flags, valid, /*one_shot=*/false,
+                               &small_out);
+  } else {
+    ctx->ek_have = true;
+    rc = encoded_keyset_enqueue(ctx, ks, kv, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, digest_len, flags, valid,
+                                /*one_shot=*/false, &ctx->ek_delegated);
+  }
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->s_comp));
+  if (small_out) memcpy(valid, small_out, n);
+  return S2K_OK;
+}
+
+// the same without the wait at the end: one ticket, the whole batch in one piece on the slot's child context (which verifies
+// over its parent's sets)
+int s2k_ecdsa_verify_encoded_batch_keyset_submit(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pubs, const uint64_t* pub_off,
+                                                 const uint8_t* digests, const uint64_t* dig_off, const uint8_t* sigs,
+                                                 const uint64_t* sig_off, int encoding, size_t digest_len, uint32_t flags, uint8_t* valid,
+                                                 s2k_ticket* ticket) {
+  if (!ctx || !ticket) return fail(ctx, S2K_ERR_ARG, "null argument");
+  *ticket = 0;
+  s2k_bykey_view kv;
+  int rc = encoded_keyset_check(ctx, ks, encoding, flags, &kv);
+  if (rc) return rc;
+  if (n) {
+    rc = encoded_check_args(ctx, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, &digest_len, &flags, valid);
+    if (rc) return rc;
+  }
+  s2k_ctx::pipe_slot* sl = nullptr;
+  rc = s2k_internal_pipe_slot(ctx, n, valid, &sl);
+  if (rc) return rc;
+  if (n) {
+    uint64_t delegated = 0;
+    rc = encoded_keyset_enqueue(sl->ctx, ks, kv, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, digest_len, flags,
+                                sl->direct ? valid : sl->h_valid, /*one_shot=*/true, &delegated);
+    if (rc) {
+      s2k_internal_drain(sl->ctx);
+      return fail(ctx, rc, "%s", sl->ctx->err);
+    }
+  }
+  s2k_internal_pipe_issue(ctx, sl, ticket);
+  return S2K_OK;
+}
+
+// of the context's last synchronous s2k_ecdsa_verify_encoded_batch_keyset, summed over its pieces: [0] items verified on the
+// set's tables that came with a 33-byte key, [1] with a 65-byte key, [2] the length of the decompression list (= square
+// roots taken), [3] items of the pieces the set was not used for.  Synchronises the device.
+int s2k_ctx_last_encoded_keyset_stats(s2k_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return fail(ctx, S2K_ERR_ARG, "null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!ctx->ek_have) return S2K_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (ctx->ek_ctr) {
+    uint32_t c[EK_WORDS];
+    HIP_TRY(ctx, hipMemcpy(c, ctx->ek_ctr, sizeof c, hipMemcpyDeviceToHost));
+    out[0] = c[EK_HIT33];
+    out[1] = c[EK_HIT65];
+    out[2] = (uint64_t)c[EK_ROOTS] + c[EK_LIST];
+  }
+  out[3] = ctx->ek_delegated;
   return S2K_OK;
 }
 

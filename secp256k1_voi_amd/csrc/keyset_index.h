@@ -1,5 +1,6 @@
 // keyset_index.h — the index of a key set: key bytes -> key index (s2k_keyset_index_create, s2k_keyset_lookup*).
-// Shared by the device (keyset_index.hip: k_ksi_build, k_ksi_lookup) and by host programs (tests/c/keyset_index_main.cpp):
+// Shared by the device (keyset_index.hip: k_ksi_build, k_ksi_lookup; ingest.hip: k_parse_encoded_keyset) and by host programs
+// (tests/c/keyset_index_main.cpp, tests/c/keyset_index33_main.cpp):
 // the probe and insert steps are written once over a small memory-access policy M, which on the device is atomics and
 // vector loads and on the host plain loads and stores.
 //
@@ -145,7 +146,33 @@ KSI_FN uint32_t ksi_lookup32(const ksi_table& t, const uint32_t x[8]) {
   return best;
 }
 
-// s2k_keyset_index_geometry: out = {slots, bytes}; log2_slots 0 = the power of two >= 2 n_keys, at least 16.  False: refused.
+// A 33-byte SEC1 compressed key `prefix || X` (x: the eight words of X): the index ksi_lookup64 would give for the point the
+// bytes decode to (SetCompressedBytes), or KSI_NONE - the bytes decode to nothing, or the set does not hold that point.  No
+// square root is taken: the walk over the chain of X keeps the LOWEST index of an entry with this X, a Y of the asked parity
+// (byte 63 of the key, bit 0) and a non-zero byte in `valid` (the set's validity array, one byte per key: canonical
+// coordinates on the curve).  A valid key with a given X and parity is unique, so such an entry IS the decoded point; a set
+// may also list (X, Y') off the curve with the same parity, which is not that point and is never answered.  A prefix other
+// than 02 / 03 matches nothing, and neither does an X >= p or an X with X^3 + 7 not a square: no valid key has such an X.
+template <class M>
+KSI_FN uint32_t ksi_lookup33(const ksi_table& t, const uint8_t* valid, uint32_t prefix, const uint32_t x[8]) {
+  if (prefix != 2u && prefix != 3u) return KSI_NONE;
+  uint32_t home, tag, best = KSI_NONE;
+  ksi_hash(x, t.seed, &home, &tag);
+  uint32_t s = home & t.mask;
+  for (uint32_t d = 0; d <= t.mask; ++d) {
+    const uint64_t e = M::load(&t.slots[s]);
+    if (e == KSI_EMPTY) break;
+    if ((uint32_t)(e >> 32) == tag && (uint32_t)e < best) {
+      uint32_t o[16];
+      M::load_key(t.keys + (size_t)(uint32_t)e * 64, o, 16);
+      if (ksi_same(x, o, 8) && ((o[15] >> 24) & 1u) == (prefix & 1u) && valid[(uint32_t)e] != 0) best = (uint32_t)e;
+    }
+    s = (s + 1) & t.mask;
+  }
+  return best;
+}
+
+// s2k_keyset_index_geometry: out ={slots, bytes}; log2_slots 0 = the power of two >= 2 n_keys, at least 16.  False: refused.
 inline bool ksi_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2]) {
   if (n_keys == 0 || n_keys > KSI_MAX_KEYS || log2_slots > KSI_MAX_LOG2) return false;
   if (log2_slots == 0) {
@@ -175,3 +202,29 @@ struct ksi_plain_mem {
       out[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
   }
 };
+
+#if defined(__HIPCC__)
+// device memory: many lanes at once (keyset_index.hip: build and lookup kernels; ingest.hip: the key-set parse kernel)
+struct ksi_dev_mem {
+  static __device__ __forceinline__ uint64_t load(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+  static __device__ __forceinline__ uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) {
+    return atomicCAS(reinterpret_cast<unsigned long long*>(p), (unsigned long long)expect, (unsigned long long)v);
+  }
+  static __device__ __forceinline__ void min_u64(uint64_t* p, uint64_t v) {
+    (void)atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+  }
+  // a key of the set: 64 bytes at a multiple of 64 from a 256-byte aligned base
+  static __device__ __forceinline__ void load_key(const uint8_t* p, uint32_t* out, int words) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (4 * i >= words) break;
+      const uint4 v = q[i];
+      out[4 * i] = v.x;
+      out[4 * i + 1] = v.y;
+      out[4 * i + 2] = v.z;
+      out[4 * i + 3] = v.w;
+    }
+  }
+};
+#endif
