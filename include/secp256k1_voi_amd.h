@@ -365,8 +365,32 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, siz
  *   [2] signatures on the general ladder, [3] the complete-formula worklist.
  *   S2K_ERR_ARG: a set of another context or device, a set without an index, S2K_ECDSA_FORCE_COMPLETE.  n == 0: S2K_OK.
  *   S2K_ECDSA_REJECT_MALLEABLE and S2K_ECDSA_FORCE_WORKLIST are honoured.
- * Not provided: ticket (_submit) and group forms of the fused call, a fused BIP-340 call (s2k_keyset_lookup_device with
- * key_bytes 32 in front of s2k_schnorr_verify_batch_keyset_device does it in two calls), adding or removing keys of a set. */
+ * s2k_schnorr_verify_batch_keyset_bykey[_device]: the BIP-340 counterpart.  pk: n x-only keys of 32 bytes; messages and
+ *   signatures as s2k_schnorr_verify_batch takes them (msgs NULL with msg_len 0 and no offsets: empty messages).  valid[i] =
+ *   what s2k_schnorr_verify_batch gives for the same arrays, bit for bit, in every layout of the set.  A signature runs on the
+ *   set's tables when the set holds a VALID key (s2k_keyset_valid_keys) with its X - of either parity of Y: the key stands
+ *   for lift_x(X) -, and otherwise on the general ladder, which lifts the key bytes supplied.
+ *   Invalid set entries: a key the set lists only as an entry that is no point (X, Y' off the curve; a coordinate >= p) counts
+ *   as a miss, wherever a real (X, Y) stands in the list; the key then goes through the general ladder and may verify.  This
+ *   is where the call differs from s2k_keyset_lookup_device with key_bytes 32 in front of
+ *   s2k_schnorr_verify_batch_keyset_device: that lookup answers the lowest index of ANY entry with this X, so the two-call
+ *   route rejects a signature under a key whose lowest entry is invalid, and rejects every key outside the set (0xFFFFFFFF is
+ *   "no key" there), where s2k_schnorr_verify_batch verifies them.  The fused call also reads the caller's key bytes in
+ *   place, where the by-index call first expands n * 32 bytes of keys from the set.
+ *   Delegation: the rule of the ECDSA call.  When s2k_schnorr_verify_batch_device would take its wave-per-signature or
+ *   four-lanes-per-signature ladder for this n (n at most s2k_ctx_set_small_batch_max / s2k_ctx_set_mid_batch_max, grouping
+ *   mode ADAPTIVE or OFF), the call IS s2k_schnorr_verify_batch[_device] on the supplied arrays, the set is not used and
+ *   s2k_ctx_key_grouping_stats reads all zero afterwards.  Otherwise s2k_ctx_key_grouping_stats gives [0] signatures on the
+ *   set's tables, [1] 0, [2] signatures on the general ladder, [3] the complete-formula worklist.
+ *   flags must be 0: S2K_ECDSA_FORCE_COMPLETE is S2K_ERR_ARG as for every key-set call, and so is every other flag.
+ *   S2K_ERR_ARG as well: a set of another context or device, a set without an index, n >= 2^30, msg_len > 0x7fffffff.
+ *   n == 0: S2K_OK, no buffer is touched.  The device form is enqueued without a host synchronisation; the host form stages
+ *   keys, messages, offsets and signatures on the context's compute stream.
+ * s2k_ecdsa_verify_batch_keyset_bykey_submit, s2k_schnorr_verify_batch_keyset_bykey_submit: the ticket forms (s2k_wait,
+ *   s2k_poll, s2k_wait_all; the rules of s2k_ecdsa_verify_batch_submit for the buffers).  The ticket runs the device form over
+ *   the context's set and index; a batch the rule above delegates runs the plain device call inside the ticket.
+ * Not provided: group forms of the fused calls, a BIP-340 form of the encoded call (s2k_ecdsa_verify_encoded_batch_keyset),
+ * adding or removing keys of a set. */
 int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2]);
 int s2k_keyset_index_create(s2k_keyset *ks, uint32_t log2_slots);
 int s2k_keyset_index_info(const s2k_keyset *ks, uint64_t out[4]);
@@ -379,6 +403,12 @@ int s2k_ecdsa_verify_batch_keyset_bykey(s2k_ctx *ctx, const s2k_keyset *ks, size
 int s2k_ecdsa_verify_batch_keyset_bykey_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_pub_xy,
                                                const void *d_digest32, const void *d_r, const void *d_s, uint32_t flags,
                                                void *d_valid, void *hip_stream);
+int s2k_schnorr_verify_batch_keyset_bykey(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pk /* n*32 */,
+                                          const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                                          const uint8_t *sig /* n*64 */, uint32_t flags, uint8_t *valid);
+int s2k_schnorr_verify_batch_keyset_bykey_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_pk, const void *d_msgs,
+                                                 const void *d_msg_offsets, size_t msg_len, const void *d_sig, uint32_t flags,
+                                                 void *d_valid, void *hip_stream);
 
 /* Page-locked host buffers for the host-pointer entry points (no reference counterpart: the reference never leaves the
  * host; this is the price of the boundary, cf. secec.PublicKey.Verify, ecdsa.go:171-228, which a cgo shim batches into
@@ -463,6 +493,15 @@ int s2k_ticket_times(s2k_ctx *ctx, s2k_ticket ticket, double ms[2]);
 int s2k_ecdsa_verify_batch_keyset_submit(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint32_t *key_index,
                                          const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags,
                                          uint8_t *valid, s2k_ticket *ticket);
+/* The fused calls by key bytes (s2k_ecdsa_verify_batch_keyset_bykey, s2k_schnorr_verify_batch_keyset_bykey: "key sets by key
+ * bytes" above) in the same form: the set needs its index, 160 bytes per ECDSA signature and 96 + the message per BIP-340
+ * signature cross PCIe, and a batch the fused call delegates runs the plain device call inside the ticket. */
+int s2k_ecdsa_verify_batch_keyset_bykey_submit(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pub_xy,
+                                               const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags,
+                                               uint8_t *valid, s2k_ticket *ticket);
+int s2k_schnorr_verify_batch_keyset_bykey_submit(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pk /* n*32 */,
+                                                 const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                                                 const uint8_t *sig /* n*64 */, uint32_t flags, uint8_t *valid, s2k_ticket *ticket);
 /* s2k_ecdsa_verify_encoded_batch (below) in the same form */
 int s2k_ecdsa_verify_encoded_batch_submit(s2k_ctx *ctx, size_t n, const uint8_t *pubs, const uint64_t *pub_off,
                                           const uint8_t *digests, const uint64_t *dig_off, const uint8_t *sigs,

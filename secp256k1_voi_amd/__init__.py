@@ -258,6 +258,7 @@ def load_library() -> C.CDLL:
     lib.s2k_keyset_lookup_device.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp]
     lib.s2k_ecdsa_verify_batch_keyset_bykey.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp]
     lib.s2k_ecdsa_verify_batch_keyset_bykey_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp, vp]
+    lib.s2k_ecdsa_verify_batch_keyset_bykey_submit.argtypes = [vp, vp, sz, vp, vp, vp, vp, u32, vp, vp]
     lib.s2k_host_alloc.argtypes = [sz]
     lib.s2k_host_alloc.restype = vp
     lib.s2k_host_free.argtypes = [vp]
@@ -318,6 +319,9 @@ def load_library() -> C.CDLL:
     lib.s2k_schnorr_verify_batch_keyset.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp]
     lib.s2k_schnorr_verify_batch_keyset_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp, vp]
     lib.s2k_schnorr_verify_batch_keyset_submit.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp, vp]
+    lib.s2k_schnorr_verify_batch_keyset_bykey.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp]
+    lib.s2k_schnorr_verify_batch_keyset_bykey_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp, vp]
+    lib.s2k_schnorr_verify_batch_keyset_bykey_submit.argtypes = [vp, vp, sz, vp, vp, vp, sz, vp, u32, vp, vp]
     lib.s2k_schnorr_batch_verify_rlc.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, C.POINTER(ci)]
     lib.s2k_schnorr_batch_verify_rlc_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, C.POINTER(ci), vp]
     lib.s2k_schnorr_verify_batch_bisect.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
@@ -423,7 +427,8 @@ EXPORTED_SYMBOLS = [
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_keyset_index_geometry", "s2k_keyset_index_create", "s2k_keyset_index_info", "s2k_keyset_lookup", "s2k_keyset_lookup_device",
-    "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device",
+    "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device", "s2k_ecdsa_verify_batch_keyset_bykey_submit",
+    "s2k_schnorr_verify_batch_keyset_bykey", "s2k_schnorr_verify_batch_keyset_bykey_device", "s2k_schnorr_verify_batch_keyset_bykey_submit",
     "s2k_pack_valid_device", "s2k_host_alloc", "s2k_host_free", "s2k_host_register", "s2k_host_unregister", "s2k_ecdsa_recover_batch", "s2k_ecdsa_recover_batch_device",
     "s2k_ecdsa_batch_verify_rlc", "s2k_ecdsa_batch_verify_rlc_device",
     "s2k_ecdsa_verify_recoverable_batch_bisect", "s2k_ecdsa_verify_recoverable_batch_bisect_device",
@@ -971,6 +976,26 @@ class Engine(_TicketOwner):
         self._check(self._lib.s2k_ecdsa_verify_batch_keyset_bykey_device(self._h, keyset._k, int(n), d_pub_xy, d_digest32, d_r, d_s,
                                                                          int(flags), d_valid, stream))
 
+    def ecdsa_verify_batch_bykey_submit(self, keyset, pub_xy, digest32, r, s, out=None, reject_malleable: bool = False) -> "Ticket":
+        """s2k_ecdsa_verify_batch_keyset_bykey_submit: ecdsa_verify_batch_bykey as a ticket (contiguous uint8 arrays are used as
+        they are and kept alive by the ticket, with the set)."""
+        arrs = []
+        for a, width in ((pub_xy, 64), (digest32, 32), (r, 32), (s, 32)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"]):
+                a = _arr(a, width)
+            arrs.append(a.reshape(-1, width))
+        n = arrs[2].shape[0]
+        for a in arrs:
+            if a.shape[0] != n:
+                raise ValueError(f"length mismatch: expected {n} items, got {a.shape[0]}")
+        out = _out_array(out, n)
+        t = C.c_uint64(0)
+        self._check(self._lib.s2k_ecdsa_verify_batch_keyset_bykey_submit(self._h, keyset._k, n, arrs[0].ctypes.data, arrs[1].ctypes.data,
+                                                                         arrs[2].ctypes.data, arrs[3].ctypes.data,
+                                                                         REJECT_MALLEABLE if reject_malleable else 0, out.ctypes.data,
+                                                                         C.byref(t)))
+        return self._hold(int(t.value), out, arrs + [keyset])
+
     def ecdsa_verify_encoded_batch(self, pubs, digests, sigs, encoding=ENCODING_ASN1, digest_len=0,
                                    reject_malleable=False, bip0066=False, force_complete=False) -> np.ndarray:
         """PublicKey.Verify(digest, sig, opts) for lists of SEC1 keys, digests and encoded signatures (or pre-built
@@ -1103,6 +1128,56 @@ class Engine(_TicketOwner):
     def schnorr_verify_batch_keyset_device(self, keyset, n, d_key_index, d_msgs, msg_len, d_sig, d_valid, stream=0):
         self._check(self._lib.s2k_schnorr_verify_batch_keyset_device(self._h, keyset._k, int(n), d_key_index, d_msgs, None, int(msg_len), d_sig, 0,
                                                                      d_valid, stream))
+
+    # ---- BIP-340 over a key set by x-only key bytes (the set needs an index: KeySet.index_create) ----
+    @staticmethod
+    def _schnorr_msgs(msgs, n):
+        """(message buffer or None, offsets or None, msg_len, arrays to keep alive) as the s2k_schnorr_* calls take them"""
+        if isinstance(msgs, (list, tuple)):
+            if len(msgs) != n:
+                raise ValueError(f"length mismatch: expected {n} messages, got {len(msgs)}")
+            offs = np.zeros(n + 1, dtype=np.uint64)
+            offs[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8)
+            return blob.ctypes.data, offs.ctypes.data, 0, [blob, offs]
+        m = msgs if (isinstance(msgs, np.ndarray) and msgs.dtype == np.uint8 and msgs.flags["C_CONTIGUOUS"]) else np.ascontiguousarray(msgs, dtype=np.uint8)
+        m = m.reshape(n, -1) if n else np.zeros((0, 0), np.uint8)
+        return (m.ctypes.data if m.size else None), None, m.shape[1], [m]
+
+    def schnorr_verify_batch_bykey(self, keyset, pk32, msgs, sig64) -> np.ndarray:
+        """schnorr_verify_batch's verdicts for the same arrays, with the signatures whose x-only key `keyset` holds as a valid
+        key (either parity of Y) verified on its tables and the others on the general ladder
+        (s2k_schnorr_verify_batch_keyset_bykey); host buffers.  `msgs`: a list of byte strings or an (n, L) uint8 array."""
+        pk32 = _arr(pk32, 32)
+        n = pk32.shape[0]
+        sig64 = _arr(sig64, 64, n)
+        m, offs, mlen, _keep = self._schnorr_msgs(msgs, n)       # (_keep: the message arrays live until the call returns)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_schnorr_verify_batch_keyset_bykey(self._h, keyset._k, n, pk32.ctypes.data, m, offs, mlen,
+                                                                    sig64.ctypes.data, 0, out.ctypes.data))
+        return out
+
+    def schnorr_verify_batch_bykey_device(self, keyset, n, d_pk, d_msgs, msg_len, d_sig, d_valid, d_msg_offsets=None, flags=0, stream=0):
+        """Device-pointer form (s2k_schnorr_verify_batch_keyset_bykey_device): integer device addresses, enqueued on `stream`;
+        messages of msg_len bytes each, or concatenated under d_msg_offsets (n + 1 uint64)."""
+        self._check(self._lib.s2k_schnorr_verify_batch_keyset_bykey_device(self._h, keyset._k, int(n), d_pk, d_msgs, d_msg_offsets, int(msg_len),
+                                                                           d_sig, int(flags), d_valid, stream))
+
+    def schnorr_verify_batch_bykey_submit(self, keyset, pk32, msgs, sig64, out=None) -> "Ticket":
+        """s2k_schnorr_verify_batch_keyset_bykey_submit: schnorr_verify_batch_bykey as a ticket (contiguous uint8 arrays are used
+        as they are and kept alive by the ticket, with the set)."""
+        pk32 = pk32 if (isinstance(pk32, np.ndarray) and pk32.dtype == np.uint8 and pk32.flags["C_CONTIGUOUS"]) else _arr(pk32, 32)
+        pk32 = pk32.reshape(-1, 32)
+        n = pk32.shape[0]
+        sig64 = sig64 if (isinstance(sig64, np.ndarray) and sig64.dtype == np.uint8 and sig64.flags["C_CONTIGUOUS"]) else _arr(sig64, 64, n)
+        if sig64.reshape(-1, 64).shape[0] != n:
+            raise ValueError(f"length mismatch: expected {n} signatures, got {sig64.reshape(-1, 64).shape[0]}")
+        m, offs, mlen, keep = self._schnorr_msgs(msgs, n)
+        out = _out_array(out, n)
+        t = C.c_uint64(0)
+        self._check(self._lib.s2k_schnorr_verify_batch_keyset_bykey_submit(self._h, keyset._k, n, pk32.ctypes.data, m, offs, mlen,
+                                                                           sig64.ctypes.data, 0, out.ctypes.data, C.byref(t)))
+        return self._hold(int(t.value), out, keep + [pk32, sig64, keyset])
 
     def schnorr_batch_verify_rlc(self, pk32, msgs, sig64, seed32: bytes | None = None) -> bool:
         """True iff every (key, message, signature) triple verifies — one MSM of n + 2K + 2 terms

@@ -4083,6 +4083,136 @@ int s2k_schnorr_verify_batch_keyset(s2k_ctx* ctx, const s2k_keyset* ks, size_t n
   return S2K_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// BIP-340 over a key set by x-only key bytes: the counterpart of s2k_ecdsa_verify_batch_keyset_bykey, with the verdicts of
+// s2k_schnorr_verify_batch for the same arrays.  The caller's d_pk already holds what k_ks_expand_x would write (the challenge
+// hashes, the general ladder and the worklist kernel read it in place), and the lookup is ksi_lookup32v: a key the set lists
+// only as an entry that is no point is a MISS and goes through the general ladder, which lifts it - s2k_keyset_lookup_device
+// with key_bytes 32 would answer that entry's index and the by-index call reject the signature.
+// ---------------------------------------------------------------------------------------
+static int schnorr_bykey_args(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* pk, const void* msgs, const void* msg_offsets,
+                              size_t msg_len, const void* sig, uint32_t flags, const void* valid) {
+  int rc = bykey_check(ctx, ks, flags);
+  if (rc) return rc;
+  if (flags) return fail(ctx, S2K_ERR_ARG, "s2k_schnorr_verify_batch_keyset_bykey takes no flags");
+  if (n == 0) return S2K_OK;
+  if (!pk || !sig || !valid || (!msgs && (msg_offsets || msg_len))) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n >= S2K_MAX_BATCH || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
+  return S2K_OK;
+}
+
+int s2k_schnorr_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pk, const void* d_msgs,
+                                                 const void* d_msg_offsets, size_t msg_len, const void* d_sig, uint32_t flags,
+                                                 void* d_valid, void* hip_stream) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = schnorr_bykey_args(ctx, ks, n, d_pk, d_msgs, d_msg_offsets, msg_len, d_sig, flags, d_valid);
+  if (rc || n == 0) return rc;
+  // the plain call would take k_schnorr_row or k_schnorr_quad for this n: the call IS the plain call, the set is not used
+  if (bykey_delegates(ctx, n, 0)) return s2k_schnorr_verify_batch_device(ctx, n, d_pk, d_msgs, d_msg_offsets, msg_len, d_sig, 0, d_valid, hip_stream);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  rc = s2k_internal_ensure_ws(ctx, n);
+  if (rc) return rc;
+  rc = ctx_aux_streams(ctx);
+  if (rc) return rc;
+  // before the fork: growing a buffer synchronises the device
+  rc = s2k_internal_keyset_reserve(ctx, ks->n, n);
+  if (rc) return rc;
+  rc = ctx_reserve(ctx, &ctx->ks_found, &ctx->ks_found_bytes, ((n + 63) & ~(size_t)63) * sizeof(uint32_t));
+  if (rc) return rc;
+  const lane_ws w = lane_ws_of(ctx, n);
+  const uint8_t* pk = (const uint8_t*)d_pk;
+  const uint8_t* sig = (const uint8_t*)d_sig;
+  const uint8_t* msgs = (const uint8_t*)d_msgs;
+  const uint64_t* offs = (const uint64_t*)d_msg_offsets;
+  const uint32_t mlen = (uint32_t)msg_len;
+  uint8_t* valid = (uint8_t*)d_valid;
+  uint32_t* found = (uint32_t*)ctx->ks_found;
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  const uint8_t* set_keys = ks->base + off[0];
+  ctx->ks_last = S2K_KEYSET_LADDER_LANE;
+  ctx->kt_last = -1;
+  ctx->last_wl_count = w.wl_count;
+  HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
+  HIP_TRY(ctx, hipMemsetAsync(d_valid, 0, n, st));
+  // second stream: challenge hashes (over the caller's key bytes), scalars and the generator part s*G of every signature;
+  // caller's: the lookup of the x-only keys among the set's valid keys, then the sort by the indices it found - a key the set
+  // does not hold as a point (0xFFFFFFFF) lands in the list `left`, in the form MODE_SCHNORR_LEFT reads behind grouped_front
+  // (signature indices, counted in KG_NLEFT; that ladder lifts the key itself and reads nothing else of the grouping)
+  prof_mark(ctx, st, 0);
+  prof_mark(ctx, st, 1);
+  HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
+  launch_schnorr_prep(ctx->s_aux, n, w, pk, sig, msgs, offs, mlen);
+  launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
+  rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
+  key_groups kg{};
+  if (rc == S2K_OK)
+    rc = s2k_internal_ksi_lookup(ctx, st, set_keys, ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n, pk, S2K_KSI_X_VALID, 32, found);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, found, st, &kg, ks->chunks);
+  ctx_aux_join(ctx, st);
+  if (rc) {
+    (void)ctx_leave(ctx, st);
+    return rc;
+  }
+  kg.gp = w.gp;
+  kg.jtab = ks->joint;
+  prof_mark(ctx, st, 2);
+  // the set's ladder over the hits (`pub`: the SET's keys - the sign flip under an odd Y; a comb set: kg.key_bytes == 64 says
+  // so to MODE_SCHNORR_COMB), the general ladder over the misses with the caller's x-only keys
+  launch_ladder(ctx, st, keyset_ladder_mode(ks, /*schnorr=*/true), n, 0u, set_keys, sig, w, valid, nullptr, ctx->prof_on ? ctx->clk : nullptr, kg);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 3);
+  launch_ladder(ctx, st, MODE_SCHNORR_LEFT, n, 0u, pk, sig, w, valid, nullptr, nullptr, kg);
+  HIP_TRY(ctx, hipGetLastError());
+  launch_affine_finish(st, MODE_SCHNORR, n, (uint32_t)((n + FIN_M - 1) / FIN_M), sig, w, valid, nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 4);
+  // (the worklist kernel re-does its lanes from the x-only key, hits and misses alike)
+  launch_schnorr_worklist(ctx, st, n, w, pk, sig, msgs, offs, mlen, valid);
+  HIP_TRY(ctx, hipGetLastError());
+  prof_mark(ctx, st, 5);
+  return ctx_leave(ctx, st);
+}
+
+// Host-buffer form: x-only keys, messages and signatures staged on the context's compute stream
+int s2k_schnorr_verify_batch_keyset_bykey(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pk, const uint8_t* msgs,
+                                          const uint64_t* msg_offsets, size_t msg_len, const uint8_t* sig, uint32_t flags, uint8_t* valid) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = schnorr_bykey_args(ctx, ks, n, pk, msgs, msg_offsets, msg_len, sig, flags, valid);
+  if (rc || n == 0) return rc;
+  if (bykey_delegates(ctx, n, 0)) return s2k_schnorr_verify_batch(ctx, n, pk, msgs, msg_offsets, msg_len, sig, 0, valid);   // (with its small-call route)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ctx_streams(ctx);
+  if (rc) return rc;
+  const size_t msg_bytes = msg_offsets ? (size_t)msg_offsets[n] : n * msg_len;
+  const size_t sizes[5] = {n * 32, msg_bytes + 16, msg_offsets ? (n + 1) * 8 : 8, n * 64, n};
+  uint8_t* d[5];
+  rc = ctx_stage(ctx, sizes, 5, d);
+  if (rc) return rc;
+  hipStream_t st = ctx->s_comp;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  s2k_phase_guard phase(ctx->device, n * 96 + msg_bytes);   // (two verifiers on two threads: engine_internal.h)
+  HIP_TRY(ctx, hipMemcpyAsync(d[0], pk, n * 32, hipMemcpyHostToDevice, st));
+  if (msg_bytes) HIP_TRY(ctx, hipMemcpyAsync(d[1], msgs, msg_bytes, hipMemcpyHostToDevice, st));
+  if (msg_offsets) HIP_TRY(ctx, hipMemcpyAsync(d[2], msg_offsets, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d[3], sig, n * 64, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, phase.landed(st));
+  rc = s2k_schnorr_verify_batch_keyset_bykey_device(ctx, ks, n, d[0], msgs ? d[1] : nullptr, msg_offsets ? d[2] : nullptr, msg_len, d[3], 0, d[4], st);
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(valid, d[4], n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->have_last = false;
+  return S2K_OK;
+}
+
 // Host-buffer entry point.  The batch is cut into chunks that are whole rounds of k_verify_fast
 // on this device (3 waves/SIMD x 4 SIMDs x CUs x 64 lanes; one round first, then two per chunk), and the
 // host-to-device copy of chunk j+1 runs on its own stream while chunk j is verified: for pageable
@@ -4532,6 +4662,90 @@ int s2k_schnorr_verify_batch_keyset_submit(s2k_ctx* ctx, const s2k_keyset* ks, s
       HIP_TRY(c, hipEventRecord(c->ev_copied[0], c->s_copy));
       HIP_TRY(c, hipStreamWaitEvent(c->s_comp, c->ev_copied[0], 0));
       rc2 = s2k_schnorr_verify_batch_keyset_device(c, ks, n, d[0], msgs ? d[1] : nullptr, msg_offsets ? d[2] : nullptr, msg_len, d[3], 0, d[4], c->s_comp);
+      if (rc2) return rc2;
+      HIP_TRY(c, hipMemcpyAsync(h_out, d[4], n, hipMemcpyDeviceToHost, c->s_comp));
+      return S2K_OK;
+    };
+    rc = enqueue();
+    if (rc) {
+      s2k_internal_drain(c);
+      return fail(ctx, rc, "%s", c->err);
+    }
+  }
+  s2k_internal_pipe_issue(ctx, sl, ticket);
+  return S2K_OK;
+}
+
+// The fused calls by key bytes in the ticket form: the copies on the copy stream in front of the device form, which runs on
+// the slot's child context over the parent's set and index (and, for a batch the plain call would verify on its
+// wave-per-signature or four-lanes-per-signature ladder, IS the plain device call inside the ticket).
+int s2k_ecdsa_verify_batch_keyset_bykey_submit(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pub, const uint8_t* dig,
+                                               const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* valid, s2k_ticket* ticket) {
+  if (!ctx || !ticket) return fail(ctx, S2K_ERR_ARG, "null argument");
+  *ticket = 0;
+  int rc = bykey_check(ctx, ks, flags);
+  if (rc) return rc;
+  if (n && (!pub || !dig || !r || !s || !valid)) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
+  s2k_ctx::pipe_slot* sl = nullptr;
+  rc = s2k_internal_pipe_slot(ctx, n, valid, &sl);
+  if (rc) return rc;
+  if (n) {
+    s2k_ctx* c = sl->ctx;
+    uint8_t* h_out = sl->direct ? valid : sl->h_valid;
+    auto enqueue = [&]() -> int {
+      const size_t sizes[5] = {n * 64, n * 32, n * 32, n * 32, n};
+      uint8_t* d[5];
+      int rc2 = ctx_stage(c, sizes, 5, d);
+      if (rc2) return rc2;
+      HIP_TRY(c, hipMemcpyAsync(d[0], pub, n * 64, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipMemcpyAsync(d[1], dig, n * 32, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipMemcpyAsync(d[2], r, n * 32, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipMemcpyAsync(d[3], s, n * 32, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipEventRecord(c->ev_copied[0], c->s_copy));
+      HIP_TRY(c, hipStreamWaitEvent(c->s_comp, c->ev_copied[0], 0));
+      rc2 = s2k_ecdsa_verify_batch_keyset_bykey_device(c, ks, n, d[0], d[1], d[2], d[3], flags, d[4], c->s_comp);
+      if (rc2) return rc2;
+      HIP_TRY(c, hipMemcpyAsync(h_out, d[4], n, hipMemcpyDeviceToHost, c->s_comp));
+      return S2K_OK;
+    };
+    rc = enqueue();
+    if (rc) {
+      s2k_internal_drain(c);
+      return fail(ctx, rc, "%s", c->err);
+    }
+  }
+  s2k_internal_pipe_issue(ctx, sl, ticket);
+  return S2K_OK;
+}
+
+int s2k_schnorr_verify_batch_keyset_bykey_submit(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const uint8_t* pk, const uint8_t* msgs,
+                                                 const uint64_t* msg_offsets, size_t msg_len, const uint8_t* sig, uint32_t flags,
+                                                 uint8_t* valid, s2k_ticket* ticket) {
+  if (!ctx || !ticket) return fail(ctx, S2K_ERR_ARG, "null argument");
+  *ticket = 0;
+  int rc = schnorr_bykey_args(ctx, ks, n, pk, msgs, msg_offsets, msg_len, sig, flags, valid);
+  if (rc) return rc;
+  s2k_ctx::pipe_slot* sl = nullptr;
+  rc = s2k_internal_pipe_slot(ctx, n, valid, &sl);
+  if (rc) return rc;
+  if (n) {
+    s2k_ctx* c = sl->ctx;
+    uint8_t* h_out = sl->direct ? valid : sl->h_valid;
+    auto enqueue = [&]() -> int {
+      const size_t msg_bytes = msg_offsets ? (size_t)msg_offsets[n] : n * msg_len;
+      const size_t sizes[5] = {n * 32, msg_bytes + 16, msg_offsets ? (n + 1) * 8 : 8, n * 64, n};
+      uint8_t* d[5];
+      int rc2 = ctx_stage(c, sizes, 5, d);
+      if (rc2) return rc2;
+      HIP_TRY(c, hipMemcpyAsync(d[0], pk, n * 32, hipMemcpyHostToDevice, c->s_copy));
+      if (msg_bytes) HIP_TRY(c, hipMemcpyAsync(d[1], msgs, msg_bytes, hipMemcpyHostToDevice, c->s_copy));
+      if (msg_offsets) HIP_TRY(c, hipMemcpyAsync(d[2], msg_offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipMemcpyAsync(d[3], sig, n * 64, hipMemcpyHostToDevice, c->s_copy));
+      HIP_TRY(c, hipEventRecord(c->ev_copied[0], c->s_copy));
+      HIP_TRY(c, hipStreamWaitEvent(c->s_comp, c->ev_copied[0], 0));
+      rc2 = s2k_schnorr_verify_batch_keyset_bykey_device(c, ks, n, d[0], msgs ? d[1] : nullptr, msg_offsets ? d[2] : nullptr, msg_len, d[3], 0,
+                                                         d[4], c->s_comp);
       if (rc2) return rc2;
       HIP_TRY(c, hipMemcpyAsync(h_out, d[4], n, hipMemcpyDeviceToHost, c->s_comp));
       return S2K_OK;

@@ -586,8 +586,10 @@ int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys
 // the index of a key set, key bytes -> key index (keyset_index.hip; the table and its probe loops: keyset_index.h).  Enqueue
 // only.  build: `slots` (2^log2_slots words of 64 bits) all ones and `info` (S2K_KSI_INFO_WORDS words) zero beforehand;
 // lookup: d_out[i] = the index of the set's key equal to the key_bytes (64: X || Y, 32: X) bytes at d_keys + i * stride, else
-// 0xFFFFFFFF
+// 0xFFFFFFFF.  key_bytes S2K_KSI_X_VALID: 32 bytes of X looked up among the set's VALID keys only (ksi_lookup32v: the fused
+// BIP-340 call's lookup; s2k_keyset_lookup* never passes it)
 enum { S2K_KSI_OCCUPIED = 0, S2K_KSI_LONGEST = 1, S2K_KSI_FAILED = 2, S2K_KSI_INFO_WORDS = 4 };
+constexpr int S2K_KSI_X_VALID = -32;
 int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys, uint64_t* slots, uint32_t log2_slots,
                            uint64_t seed, uint32_t* info);
 int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, const uint64_t* slots, uint32_t log2_slots, uint64_t seed,

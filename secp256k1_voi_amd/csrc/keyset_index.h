@@ -1,6 +1,6 @@
 // keyset_index.h — the index of a key set: key bytes -> key index (s2k_keyset_index_create, s2k_keyset_lookup*).
 // Shared by the device (keyset_index.hip: k_ksi_build, k_ksi_lookup; ingest.hip: k_parse_encoded_keyset) and by host programs
-// (tests/c/keyset_index_main.cpp, tests/c/keyset_index33_main.cpp):
+// (tests/c/keyset_index_main.cpp, tests/c/keyset_index33_main.cpp, tests/c/keyset_index32v_main.cpp):
 // the probe and insert steps are written once over a small memory-access policy M, which on the device is atomics and
 // vector loads and on the host plain loads and stores.
 //
@@ -166,6 +166,31 @@ KSI_FN uint32_t ksi_lookup33(const ksi_table& t, const uint8_t* valid, uint32_t 
       uint32_t o[16];
       M::load_key(t.keys + (size_t)(uint32_t)e * 64, o, 16);
       if (ksi_same(x, o, 8) && ((o[15] >> 24) & 1u) == (prefix & 1u) && valid[(uint32_t)e] != 0) best = (uint32_t)e;
+    }
+    s = (s + 1) & t.mask;
+  }
+  return best;
+}
+
+// An x-only key (BIP-340; x: the eight words of X) among the VALID keys of the set: the LOWEST index of an entry with this X and
+// a non-zero byte in `valid`, or KSI_NONE.  ksi_lookup32 answers an entry that is no point as readily as one that is; a
+// caller that goes on to verify under lift_x(X) on the set's tables (s2k_schnorr_verify_batch_keyset_bykey) must not be
+// handed (X, Y') off the curve where X itself lifts - that entry is skipped here, whether the real (X, Y) follows it, comes
+// before it or is missing.  Either parity of Y serves: X stands for Q and -Q alike and the set's ladders flip the half
+// scalars' signs under an odd Y.  An X >= p or an X with X^3 + 7 not a square matches nothing (no valid key has such an X);
+// no square root is taken.
+template <class M>
+KSI_FN uint32_t ksi_lookup32v(const ksi_table& t, const uint8_t* valid, const uint32_t x[8]) {
+  uint32_t home, tag, best = KSI_NONE;
+  ksi_hash(x, t.seed, &home, &tag);
+  uint32_t s = home & t.mask;
+  for (uint32_t d = 0; d <= t.mask; ++d) {
+    const uint64_t e = M::load(&t.slots[s]);
+    if (e == KSI_EMPTY) break;
+    if ((uint32_t)(e >> 32) == tag && (uint32_t)e < best) {
+      uint32_t o[8];
+      M::load_key(t.keys + (size_t)(uint32_t)e * 64, o, 8);
+      if (ksi_same(x, o, 8) && valid[(uint32_t)e] != 0) best = (uint32_t)e;
     }
     s = (s + 1) & t.mask;
   }
