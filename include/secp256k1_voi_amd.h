@@ -1057,10 +1057,21 @@ enum {
    * c is W, non-zero; b3 = 21 c^6 is a field element there, not a small constant).  P = (a, b) and Q = (d, e) are points of
    * secp256k1 given affine ((0, 0): the identity), moved to that curve by (x c^2, y c^3) on the device, added there and
    * moved back: out, out2, flag, bit 0 of `lazy` and chaining (P + k Q) as PT29R_ADD. */
-  S2K_HP_PT29R_ADD_B3
+  S2K_HP_PT29R_ADD_B3,
+  /* the comb ladder's column (jacobian29.h: coz29_pair_sum, jpt29_rescale, jpt29_add_affine), through s2k_fp_op_batch_ex8
+   * only - it takes more operands than s2k_fp_op_batch_ex has slots: acc + s1 E1 + s2 E2 for acc = (in[0], in[1]) lifted to
+   * Jacobian Z = in[2] as for JADD (bit 3 of in[2]'s lazy code: no lift; in[2] = 0: Z = 0), E1 = (in[3], in[4]) and E2 =
+   * (in[5], in[6]) affine with x1 != x2, in their lazy forms (one unit each), s1 = -1 when bit 0 of in[7] is set, s2 = -1 when
+   * its bit 1 is (in[7] NULL: both +1).  out, out2 = affine x, y; flag = 0 when Z3 = 0 (E1 = +-E2, acc = +-(s1 E1 + s2 E2),
+   * Z = 0).  reps == 0: once; reps >= 1: `reps` times the column with one jpt29_double behind it, as the ladder runs them. */
+  S2K_HP_JADD_PAIR
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);
+/* the same for operations of up to eight operands (S2K_HP_JADD_PAIR): `lazy` holds the 4-bit code of in[j] in bits
+ * 4j .. 4j + 3, so the chaining count has an argument of its own */
+int s2k_fp_op_batch_ex8(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, uint32_t reps, size_t n,
+                        const uint8_t *const in[8], uint8_t *out, uint8_t *out2, uint8_t *flag);
 /* The odd GLV split the verification ladder uses (sc_split_glv_odd): k == (-1)^s1 k1 + (-1)^s2 k2 lambda
  * (mod n) with k1, k2 ODD and below 2^129 (32-byte big-endian magnitudes), signs[i] = s1 | s2 << 1.
  * Serves splitGLV (point_mul_glv.go:59); impl must be S2K_IMPL_FAST. */

@@ -55,7 +55,7 @@ KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6, KEYSET_C
  HP_FER_MUL, HP_FER_MUL_PLUS, HP_FER_MUL_ADD_MUL, HP_FER_SMALL, HP_PT29R_DBL, HP_PT29R_ADD, HP_FER_SWAPS,
  HP_SC26_MUL, HP_SC26_SQR, HP_SC26_TO_MONT, HP_SC26_TO_SC, HP_SC26_INV, HP_SC26_CHAIN,
  HP_SC_MONTMUL, HP_SC_TO_MONT, HP_SC_MONT_INV, HP_SC_ADD, HP_SC_NEG, HP_SC_REDUCE_ONCE, HP_SC_GT_HALF_N,
- HP_AFF_DBL, HP_AFF_ADD, HP_XYZZ_ADD_FIRST, HP_PT29R_ADD_B3) = range(51)
+ HP_AFF_DBL, HP_AFF_ADD, HP_XYZZ_ADD_FIRST, HP_PT29R_ADD_B3, HP_JADD_PAIR) = range(52)
 KEYSET_LADDER_LANE, KEYSET_LADDER_ROW = 0, 1                     # s2k_ctx_last_keyset_ladder
 H2C_SSWU_RO, H2C_SSWU_NU = 0, 1        # s2k_hash_to_curve_batch: hash_to_curve (random oracle) / encode_to_curve (non-uniform)
 
@@ -331,6 +331,7 @@ def load_library() -> C.CDLL:
     lib.s2k_double_scalar_mult_basepoint_batch.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.s2k_double_scalar_mult_basepoint_batch_ex.argtypes = [vp, u32, sz, vp, vp, vp, vp]
     lib.s2k_fp_op_batch_ex.argtypes = [vp, u32, ci, u32, sz, vp, vp, vp, vp]
+    lib.s2k_fp_op_batch_ex8.argtypes = [vp, u32, ci, u32, u32, sz, vp, vp, vp, vp]
     lib.s2k_fn_split_glv_batch_ex.argtypes = [vp, u32, sz, vp, vp, vp, vp]
     lib.s2k_point_add_batch.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_point_double_batch.argtypes = [vp, sz, vp, vp]
@@ -455,7 +456,7 @@ EXPORTED_SYMBOLS = [
     "s2k_pointset_multi_scalar_mult_segments", "s2k_pointset_multi_scalar_mult_segments_device",
     "s2k_h2c_dst_prime", "s2k_expand_message_xmd_batch", "s2k_map_to_curve_batch", "s2k_hash_to_curve_batch", "s2k_hash_to_curve_batch_device",
     "s2k_fp_op_batch", "s2k_fn_op_batch", "s2k_fn_split_glv_batch", "s2k_debug_gtable_entry", "s2k_generator_window_bits",
-    "s2k_double_scalar_mult_basepoint_batch_ex", "s2k_fp_op_batch_ex", "s2k_fn_split_glv_batch_ex",
+    "s2k_double_scalar_mult_basepoint_batch_ex", "s2k_fp_op_batch_ex", "s2k_fp_op_batch_ex8", "s2k_fn_split_glv_batch_ex",
     "s2k_ct_scalar_mult", "s2k_ct_scalar_base_mult", "s2k_ct_ecdh", "s2k_ct_ecdsa_sign_raw", "s2k_ct_debug_fe_mul_count",
     "s2k_ct_multi_scalar_mult",
     "s2k_device_pci_bus_id", "s2k_device_numa_node", "s2k_bind_thread_to_node", "s2k_topology_prefer_node", "s2k_topology_node_count",
@@ -1463,6 +1464,17 @@ class Engine(_TicketOwner):
         out, out2, flag = (np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8))
         self._check(self._lib.s2k_fp_op_batch_ex(self._h, IMPL_FAST, op, lazy, n, ptrs, out.ctypes.data, out2.ctypes.data,
                                                  flag.ctypes.data))
+        return out, out2, flag
+
+    def fp_op_batch_ex8(self, op, operands, lazy=0, reps=0):
+        """The same for operations of up to eight operands (s2k_fp_op_batch_ex8: HP_JADD_PAIR, the comb ladder's column);
+        `lazy` holds operand j's code in bits 4j .. 4j + 3, `reps` chains the operation; returns (out, out2, flag)."""
+        ops = [(_arr(x, 32) if x is not None else None) for x in operands] + [None] * (8 - len(operands))
+        n = ops[0].shape[0]
+        ptrs = (C.c_void_p * 8)(*[(x.ctypes.data if x is not None else None) for x in ops])
+        out, out2, flag = (np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8))
+        self._check(self._lib.s2k_fp_op_batch_ex8(self._h, IMPL_FAST, op, lazy, reps, n, ptrs, out.ctypes.data, out2.ctypes.data,
+                                                  flag.ctypes.data))
         return out, out2, flag
 
     def fn_split_glv_odd_batch(self, k):

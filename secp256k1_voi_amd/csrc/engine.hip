@@ -466,6 +466,8 @@ S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const ui
 #ifndef S2K_JOINT_WAVES
 #define S2K_JOINT_WAVES 3
 #endif
+// The comb ladder: 145 VGPRs and three waves since a column adds its two entries to each other first; 4 here spills
+// (128 VGPRs, 23 spilled, 64 B scratch) and was timed no faster than the two-addition column it replaced.
 #ifndef S2K_COMB_WAVES
 #define S2K_COMB_WAVES 3
 #endif
@@ -779,10 +781,11 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
     // E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t.  A round is one doubling (none in front of the first round) and the two
     // halves' additions: 38 additions and 18 doublings.  The lead 2^133 Q = 2^18 * 2^115 Q goes in first, for both halves at
     // once (L +- phi(L), as in the window ladder).
-    // All in Jacobian coordinates: 38 * 11 + 18 * 7 = 544 products.  XYZZ additions (10 in 9 reductions) would want an XYZZ
+    // All in Jacobian coordinates, a round's two entries added to each other first: 19 * 20 + 18 * 7 = 506 products (two
+    // mixed additions a round: 19 * 22 + 18 * 7 = 544).  XYZZ additions (10 in 9 reductions) would want an XYZZ
     // doubling (6 M + 3 S = 9: 542 products) or the change of form around every single doubling (4 products a round: 578),
     // and a fourth coordinate in registers; jacobian29.h's pair is the one the general ladder runs and the models bound.
-    // Z = 0 is sticky through both (Z3 = Z1 H, Z3 = Y Z) and ends on the worklist exactly as before.
+    // Z = 0 is sticky through all of it (Z3 = Z1 H h, Z3 = Y Z) and ends on the worklist exactly as before.
     using G = kc_geom;
     const uint4* kt = kg.ktab + (size_t)kg.ptab[idx] * (G::SLOTS * 8);
     {
@@ -819,23 +822,27 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
     }
 #pragma unroll 1
     for (int j = G::SPACING - 1;; --j) {
+      // the column: E1 of the first half and phi(E2) of the second (the beta * x column) are affine over the same Z, so
+      // they are added to each other first (jacobian29.h: coz29_pair_sum, E2 with its sign relative to E1's) and their
+      // sum, over Z h, goes to the accumulator moved onto that curve: 15 M + 5 S against the 16 M + 6 S of two mixed
+      // additions, and both lookups of the column in flight together
       const uint32_t w12 = cols[j][threadIdx.x], w1 = w12 & 127u, w2 = w12 >> 8;
-#pragma unroll 1
-      for (int t = 0; t < 2; ++t) {
-        const uint32_t w = t ? w2 : w1;
-        const bool top = (w & 64u) != 0;
-        const bool neg = (t ? neg2 : neg1) != !top;
-        const uint32_t entry = (top ? w : ~w) & 63u;
-        fe29 x, y;
-        ke_load_xy(kt + (size_t)entry * 8, t != 0, x, y);
-        acc = jpt29_add_affine(acc, x, fe29_cond_negate1(y, neg));
-      }
+      const bool top1 = (w1 & 64u) != 0, top2 = (w2 & 64u) != 0;
+      const bool n1 = neg1 != !top1, n2 = neg2 != !top2;
+      fe29 x1, y1, x2, y2;
+      ke_load_xy(kt + (size_t)((top1 ? w1 : ~w1) & 63u) * 8, false, x1, y1);
+      ke_load_xy(kt + (size_t)((top2 ? w2 : ~w2) & 63u) * 8, true, x2, y2);
+      const coz29_sum t = coz29_pair_sum(x1, y1, x2, fe29_cond_negate1(y2, n1 != n2));
+      acc = jpt29_rescale(acc, t.hh, t.hhh);
+      acc = jpt29_add_affine(acc, t.x, fe29_cond_negate1(t.ny, !n1));   // (ny = -Y_T)
+      acc.z = fe29_mul(acc.z, t.h);
       if (j == 0) break;
       acc = jpt29_double(acc);
     }
     // the table's points are affine on the curve isomorphic by W (keyed.hip): back on secp256k1 itself
-    // (W is asked for here and not in front of the ladder: held across it, its nine registers - and the teeth, were they not
-    // in LDS - cost the kernel its fourth wave per SIMD: 156 VGPRs, 132 with W loaded late, under 128 with both)
+    // (W is asked for here and not in front of the ladder: nothing is held across it but the accumulator - neither W's nine
+    // registers nor the teeth, which wait in LDS.  The column's four coordinates and its pair sum are 145 VGPRs, three waves
+    // per SIMD; bounded to four, S2K_COMB_WAVES=4, the kernel spills 23 and loses what the column saves.)
     acc.z = fe29_mul(acc.z, ke_load(kt + (size_t)G::WENT * 8, G::W));
   } else if constexpr (KEYED) {
     // k = 16^32 + sum_i d_i 16^i with d_i = 2 nib_i - 15, i = 4c + j: round j (3 down to 0) adds

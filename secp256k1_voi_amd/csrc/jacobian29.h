@@ -75,4 +75,38 @@ S2K_DEV jpt29 jpt29_add(const jpt29& p, const jpt29& q) {
   return r;
 }
 
+// The comb ladder's column (engine.hip, k_verify_fast<.._COMB>): two table entries E1 = (x1, y1) and E2 = (x2, y2), affine
+// over one Z, are added to each other first and their sum T to the accumulator, 20 products in 18 reductions against
+// the 22 in 20 of two mixed additions.  T comes out over Z h, h = x2 - x1, and its h^2 and h^3 fall out of the co-Z
+// addition (keyed.hip: coz29_conj, the sum half), which a Jacobian + Jacobian addition spends 1 S + 1 M on.
+// x1 = x2 (E1 = +-E2) gives h = 0, and the accumulator's Z, which takes the factor h, is 0 from there on.
+struct coz29_sum {
+  fe29 x, ny;       // T = (x, -ny) over Z h: x [1], ny [1]
+  fe29 h, hh, hhh;  // h [1], h^2 [1], h^3 [3]
+};
+// E1 + E2: x1 [1], y1 [1], x2 [1], y2 [<= 2].  The caller gives E2 the sign it has RELATIVE to E1 and negates the sum
+// once: with y1 of one unit the two products of Y_T share a reduction (6 of the 7.8 units; 9 with y1 of two).  4 M + 2 S.
+S2K_DEV coz29_sum coz29_pair_sum(const fe29& x1, const fe29& y1, const fe29& x2, const fe29& y2) {
+  coz29_sum t;
+  t.h = fe29_normalize_weak(fe29_add(x2, fe29_negate(x1, 1)));   // [1] + [2] -> [1]   x2 - x1
+  t.hh = fe29_sqr(t.h);                                          // [1]   A
+  const fe29 b = fe29_mul(x1, t.hh);                             // [1]   B
+  const fe29 c = fe29_mul(x2, t.hh);                             // [1]   C
+  const fe29 nb = fe29_negate(b, 1);                             // [2]   -B
+  t.hhh = fe29_add(c, nb);                                       // [3]   C - B = h^3
+  const fe29 dy = fe29_normalize_weak(fe29_add(y2, fe29_negate(y1, 1)));   // [2] + [2] -> [1]   y2 - y1
+  t.x = fe29_sqr_plus(dy, fe29_negate(fe29_add(b, c), 2));       // [1]^2 + [3] -> [1]   dy^2 - B - C
+  t.ny = fe29_mul_add_mul(dy, fe29_add(t.x, nb), y1, t.hhh);     // [1]*[3] + [1]*[3], one reduction -> [1]   -Y_T
+  return t;
+}
+// P on the curve isomorphic by c, given zz = c^2 [1] and zzz = c^3 [<= 3]: (X c^2, Y c^3, Z), as jpt29_add moves its P.
+// The result of an addition there is back on P's own curve with its Z times c.  2 M.
+S2K_DEV jpt29 jpt29_rescale(const jpt29& p, const fe29& zz, const fe29& zzz) {
+  jpt29 r;
+  r.x = fe29_mul(p.x, zz);                                       // [1]
+  r.y = fe29_mul(p.y, zzz);                                      // [2]*[3] -> [1]
+  r.z = p.z;
+  return r;
+}
+
 }  // namespace s2k

@@ -437,6 +437,70 @@ k_aff_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8_t
   if (flag) flag[idx] = 1;
 }
 
+// S2K_HP_JADD_PAIR: the comb ladder's column (jacobian29.h: coz29_pair_sum, jpt29_rescale; the four lines are those of
+// k_verify_fast<.._COMB>).  in[0], in[1] = P affine, lifted to Jacobian with Z = in[2] as for S2K_HP_JADD (lazy code of in[2]
+// with bit 3: no lift, P = (in[0], in[1], 1) in their lazy forms; in[2] = 0: Z = 0); E1 = (in[3], in[4]) and E2 = (in[5],
+// in[6]) in their lazy forms (x [1], y [1]: E2's x is a free operand, the ladder passes beta * x); in[7]: bit 0 = E1 negative,
+// bit 1 = E2 negative.  reps == 0: the column once; reps >= 1: `reps` times the column and one jpt29_double behind it - the
+// ladder's own sequence.
+struct hp_args8 {
+  const uint8_t* in[8];
+};
+__global__ void __launch_bounds__(256)
+k_pair_op(uint32_t lazy, uint32_t n, uint32_t reps, hp_args8 args, uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
+          uint8_t* __restrict__ flag) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n) return;
+  fe29 v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = fe29_zero();
+    if (args.in[j]) {
+      uint32_t w[8];
+      load_be32(w, args.in[j] + idx * 32);
+      v[j] = fe29_lazy_form(fe29_from_words(w), (lazy >> (4 * j)) & 7u);
+    }
+  }
+  jpt29 acc;
+  if ((lazy >> 8) & 8u) {
+    acc.x = v[0];
+    acc.y = v[1];
+    acc.z = fe29_one();
+  } else {
+    const fe29 zz = fe29_sqr(v[2]);
+    acc.x = fe29_mul(v[0], zz);
+    acc.y = fe29_mul(v[1], fe29_mul(zz, v[2]));
+    acc.z = fe29_normalize_weak(v[2]);
+  }
+  const fe29 &x1 = v[3], &y1 = v[4], &x2 = v[5], &y2 = v[6];
+  const bool n1 = (v[7].n[0] & 1u) != 0, n2 = (v[7].n[0] & 2u) != 0;
+#pragma unroll 1
+  for (uint32_t i = 0; i < (reps ? reps : 1u); ++i) {
+    const coz29_sum t = coz29_pair_sum(x1, y1, x2, fe29_cond_negate1(y2, n1 != n2));
+    acc = jpt29_rescale(acc, t.hh, t.hhh);
+    acc = jpt29_add_affine(acc, t.x, fe29_cond_negate1(t.ny, !n1));
+    acc.z = fe29_mul(acc.z, t.h);
+    if (reps) acc = jpt29_double(acc);
+  }
+  fe29 r = fe29_zero(), r2 = fe29_zero();
+  uint8_t f = 1;
+  if (fe29_is_zero(acc.z)) {   // exceptional input of the incomplete formulas (or a true infinity)
+    f = 0;
+  } else {
+    const fe29 zi = fe29_inv(acc.z), zi2 = fe29_sqr(zi);
+    r = fe29_mul(acc.x, zi2);
+    r2 = fe29_mul(fe29_mul(acc.y, zi2), zi);
+  }
+  uint32_t w[8];
+  fe29_to_words(w, fe29_normalize(r));
+  store_be32(out + idx * 32, w);
+  if (out2) {
+    fe29_to_words(w, fe29_normalize(r2));
+    store_be32(out2 + idx * 32, w);
+  }
+  if (flag) flag[idx] = f;
+}
+
 // The quad-spread group law of pt29q.h, four lanes per item: inputs as for PT29_DBL / PT29_ADD above (P = (a : b : 1)
 // scaled by Z = c, c == 0: the identity; Q = (d, e) scaled by the same c, or affine when P is the identity); `reps`
 // > 1 chains the operation (r = r + Q / r = 2 r again and again) so that outputs are fed back as inputs.
@@ -911,6 +975,40 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
     k_pt29q_op<<<blocks_for(4 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else
     k_fp29_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  if (out2) HIP_TRY(ctx, hipMemcpy(out2, dout2.p, n * 32, hipMemcpyDeviceToHost));
+  if (flag) HIP_TRY(ctx, hipMemcpy(flag, dflag.p, n, hipMemcpyDeviceToHost));
+  return S2K_OK;
+}
+
+int s2k_fp_op_batch_ex8(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, uint32_t reps, size_t n, const uint8_t* const in[8],
+                        uint8_t* out, uint8_t* out2, uint8_t* flag) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex8 serves S2K_IMPL_FAST only");
+  if (op != S2K_HP_JADD_PAIR) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (n == 0) return S2K_OK;
+  if (!in || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  for (int j = 0; j < 8; ++j)
+    if (!in[j] && j != 2 && j != 7) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (!in[2] && !((lazy >> 8) & 8u)) return fail(ctx, S2K_ERR_ARG, "no Z to lift P to");
+  if (n > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  dev_buf din[8], dout, dout2, dflag;
+  hp_args8 args;
+  for (int j = 0; j < 8; ++j) {
+    args.in[j] = nullptr;
+    if (in[j]) {
+      HIP_TRY(ctx, din[j].upload(in[j], n * 32));
+      args.in[j] = (const uint8_t*)din[j].p;
+    }
+  }
+  HIP_TRY(ctx, dout.alloc(n * 32));
+  if (out2) HIP_TRY(ctx, dout2.alloc(n * 32));
+  if (flag) HIP_TRY(ctx, dflag.alloc(n));
+  k_pair_op<<<blocks_for(n), 256>>>(lazy, (uint32_t)n, reps, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipDeviceSynchronize());
   HIP_TRY(ctx, hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
