@@ -716,7 +716,8 @@ def test_encoded_batch_options(eng, oracle):
     # bitcoin.VerifyASN1: sighash byte appended, BIP-0066 shape, low-s
     with_hash = [s + b"\x01" for s in sigs_d]
     assert eng.ecdsa_verify_encoded_batch(pubs, digs, with_hash, bip0066=True).tolist() == exp_low
-    assert not eng.ecdsa_verify_encoded_batch(pubs, digs, sigs_d, bip0066=True).any() or True
+    # ... without the sighash byte the length rule d[1] == len - 3 of BIP-0066 fails for every one
+    assert exp_low.count(1) > 0 and not eng.ecdsa_verify_encoded_batch(pubs, digs, sigs_d, bip0066=True).any()
     # malformed keys: wrong prefix, wrong length, identity
     bad_pubs = [b"\x05" + pubs[1][1:], pubs[1][:64], b"\x00", b"\x02" + (2**256 - 1).to_bytes(32, "big")]
     got = eng.ecdsa_verify_encoded_batch(bad_pubs, digs[:4], sigs_d[:4])
