@@ -272,7 +272,7 @@ int s2k_ecdsa_verify_recoverable_batch_bisect_device(s2k_ctx *ctx, size_t n, con
 /* ---- key sets: per-key precomputation kept across calls ------------------------------- */
 /* The reference caches per-key state in secec.PublicKey (secec/secec.go:80-85: the decoded point and its encodings,
  * built once by NewPublicKey, :188-216) and every Verify starts from it.  The device analogue: a KEY SET holds, for a
- * fixed list of n_keys public keys (X || Y, 64 bytes each), the per-key tables the verification ladder otherwise
+ * list of n_keys public keys (X || Y, 64 bytes each; s2k_keyset_append adds to it), the per-key tables the verification ladder otherwise
  * builds inside every call for keys that repeat in the batch (9 KiB per key; a key that is not a valid public key gets
  * a table entry marked invalid: every signature under it verifies false, as NewPublicKey would have refused the key).
  * s2k_ecdsa_verify_batch_keyset[_device]: valid[i] = PublicKey(keys[key_index[i]]).VerifyRaw(digest_i, r_i, s_i)
@@ -316,7 +316,36 @@ void s2k_keyset_destroy(s2k_keyset *ks);
 size_t s2k_keyset_size(const s2k_keyset *ks);
 size_t s2k_keyset_device_bytes(const s2k_keyset *ks);
 /* valid[k] = 1 iff key k is a valid public key (canonical coordinates, on the curve): NewPublicKey's verdict per key. */
-int s2k_keyset_valid_keys(s2k_keyset *ks, uint8_t *valid /* n_keys, host */);
+int s2k_keyset_valid_keys(s2k_keyset *ks, uint8_t *valid /* s2k_keyset_size bytes, host */);
+/* Growing a set.  A set has a CAPACITY, the number of keys its device buffers have room for, and a live count
+ * (s2k_keyset_size) of keys that have tables; s2k_keyset_device_bytes is what is allocated, for the capacity.  A call's cost
+ * follows the live count alone: spare capacity is memory, not time.  A key index >= s2k_keyset_size names no key (valid[i] =
+ * 0), whether or not it is below the capacity.
+ * s2k_keyset_create_cap: s2k_keyset_create_ex with memory for `capacity` >= n_keys keys (0: n_keys, which is what
+ *   s2k_keyset_create[_ex] pass; at most 0x0fffffff).  S2K_KEYSET_AUTO chooses the layout by the bytes of the capacity.
+ *   n_keys == 0 stays S2K_ERR_ARG.
+ * s2k_keyset_append[_device]: n_new more keys (X || Y, 64 bytes each; host memory, or device memory of the set's device).
+ *   They get the indices size .. size + n_new - 1; *first_index (may be NULL) receives the old size.  Only the tables of the
+ *   new keys are built, by the kernels of the creation, in every layout; a key that is no valid public key gets a table marked
+ *   invalid, as at creation.  A set with an index has the new keys inserted into it (a duplicate of an older key keeps the
+ *   older index; -Q of a held Q is a second entry), so the calls by key bytes take the set's tables for them; an index that an
+ *   explicit log2_slots made too small for the new count is rebuilt at the automatic size of the capacity first.  The call is
+ *   synchronous and s2k_keyset_size moves only when tables and index are complete.  An append within the capacity moves no
+ *   device address.  S2K_ERR_ARG when size + n_new exceeds the capacity (s2k_keyset_reserve first): the set is untouched.  A
+ *   device failure leaves the size as it was, and the index without an entry for a row that did not become a key (or, when
+ *   that cannot be had either, the set without an index).  n_new == 0: S2K_OK.
+ * s2k_keyset_reserve: memory for `capacity` keys.  Synchronises the device, allocates, copies every section of the set and its
+ *   joint tables device to device and frees the old buffers after the copies.  Both copies exist for a moment: a set that
+ *   fills more than half of the free device memory (2^16 keys at S2K_KEYSET_JOINT5 are 56 GB) cannot grow this way -
+ *   S2K_ERR_NOMEM, the set intact - and should be given its capacity at creation.  capacity <= s2k_keyset_capacity: S2K_OK, nothing changes.  The
+ *   index is rebuilt when it has fewer than 2 * capacity slots.
+ * Threading: as s2k_keyset_destroy and s2k_keyset_index_create - no call or ticket that uses the set may be in progress.
+ * Not provided: removing keys. */
+int s2k_keyset_create_cap(s2k_ctx *ctx, size_t n_keys, const uint8_t *pub_xy, int layout, size_t capacity, s2k_keyset **out);
+size_t s2k_keyset_capacity(const s2k_keyset *ks);
+int s2k_keyset_reserve(s2k_keyset *ks, size_t capacity);
+int s2k_keyset_append(s2k_keyset *ks, size_t n_new, const uint8_t *pub_xy /* n_new*64, host */, uint32_t *first_index /* may be NULL */);
+int s2k_keyset_append_device(s2k_keyset *ks, size_t n_new, const void *d_pub_xy /* n_new*64 */, uint32_t *first_index);
 int s2k_ecdsa_verify_batch_keyset(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint32_t *key_index /* n */,
                                   const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
 int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_key_index /* n uint32 */,
@@ -334,7 +363,8 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, siz
  * LOWEST of its indices.
  *
  * s2k_keyset_index_geometry (host only: no device, no context): out = {slots, bytes of the index}; log2_slots 0 = auto, the
- *   power of two >= 2 * n_keys, at least 16.  S2K_ERR_ARG when 2^log2_slots <= n_keys, log2_slots > 31, or n_keys is 0 or
+ *   power of two >= 2 * n_keys, at least 16 (s2k_keyset_index_create with log2_slots 0 takes it for the set's CAPACITY; an
+ *   explicit log2_slots is checked against the keys there are).  S2K_ERR_ARG when 2^log2_slots <= n_keys, log2_slots > 31, or n_keys is 0 or
  *   > 0x0fffffff.
  * s2k_keyset_index_create builds the index of a set (an allocation of its own, NOT counted in s2k_keyset_device_bytes;
  *   s2k_keyset_index_info tells its size).  Same threading rule as s2k_keyset_destroy.  A set has at most one index: a
@@ -390,7 +420,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, siz
  *   s2k_poll, s2k_wait_all; the rules of s2k_ecdsa_verify_batch_submit for the buffers).  The ticket runs the device form over
  *   the context's set and index; a batch the rule above delegates runs the plain device call inside the ticket.
  * Not provided: group forms of the fused calls, a BIP-340 form of the encoded call (s2k_ecdsa_verify_encoded_batch_keyset),
- * adding or removing keys of a set. */
+ * removing keys of a set. */
 int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2]);
 int s2k_keyset_index_create(s2k_keyset *ks, uint32_t log2_slots);
 int s2k_keyset_index_info(const s2k_keyset *ks, uint64_t out[4]);
@@ -603,6 +633,15 @@ void s2k_group_keyset_destroy(s2k_group_keyset *gks);
 size_t s2k_group_keyset_size(const s2k_group_keyset *gks);
 int s2k_group_keyset_layout(const s2k_group_keyset *gks);
 size_t s2k_group_keyset_device_bytes(const s2k_group_keyset *gks);
+/* s2k_keyset_create_cap, s2k_keyset_reserve and s2k_keyset_append on every member's set, on the members' threads.  The first
+ * failing member's code is returned; members that had succeeded keep the keys appended (their sets are then longer than the
+ * group's), and s2k_group_keyset_size moves only when every member succeeded.  No group call that uses the set may be in
+ * progress. */
+int s2k_group_keyset_create_cap(s2k_group *g, size_t n_keys, const uint8_t *pub_xy, int layout, size_t capacity,
+                                s2k_group_keyset **out);
+size_t s2k_group_keyset_capacity(const s2k_group_keyset *gks);
+int s2k_group_keyset_reserve(s2k_group_keyset *gks, size_t capacity);
+int s2k_group_keyset_append(s2k_group_keyset *gks, size_t n_new, const uint8_t *pub_xy /* n_new*64, host */, uint32_t *first_index);
 int s2k_group_ecdsa_verify_batch_keyset(s2k_group *g, const s2k_group_keyset *gks, size_t n, const uint32_t *key_index,
                                         const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags,
                                         uint8_t *valid);

@@ -240,6 +240,12 @@ def load_library() -> C.CDLL:
     lib.s2k_pack_valid_device.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.s2k_keyset_create.argtypes = [vp, sz, vp, C.POINTER(vp)]
     lib.s2k_keyset_create_ex.argtypes = [vp, sz, vp, ci, C.POINTER(vp)]
+    lib.s2k_keyset_create_cap.argtypes = [vp, sz, vp, ci, sz, C.POINTER(vp)]
+    lib.s2k_keyset_capacity.argtypes = [vp]
+    lib.s2k_keyset_capacity.restype = sz
+    lib.s2k_keyset_reserve.argtypes = [vp, sz]
+    lib.s2k_keyset_append.argtypes = [vp, sz, vp, C.POINTER(u32)]
+    lib.s2k_keyset_append_device.argtypes = [vp, sz, vp, C.POINTER(u32)]
     lib.s2k_keyset_layout.argtypes = [vp]
     lib.s2k_keyset_destroy.argtypes = [vp]
     lib.s2k_keyset_destroy.restype = None
@@ -299,6 +305,11 @@ def load_library() -> C.CDLL:
     lib.s2k_group_schnorr_batch_verify_rlc.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
     lib.s2k_group_multi_scalar_mult.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_group_keyset_create.argtypes = [vp, sz, vp, ci, vp]
+    lib.s2k_group_keyset_create_cap.argtypes = [vp, sz, vp, ci, sz, vp]
+    lib.s2k_group_keyset_capacity.argtypes = [vp]
+    lib.s2k_group_keyset_capacity.restype = sz
+    lib.s2k_group_keyset_reserve.argtypes = [vp, sz]
+    lib.s2k_group_keyset_append.argtypes = [vp, sz, vp, C.POINTER(u32)]
     lib.s2k_group_keyset_destroy.argtypes = [vp]
     lib.s2k_group_keyset_destroy.restype = None
     lib.s2k_group_keyset_size.argtypes = [vp]
@@ -426,6 +437,7 @@ EXPORTED_SYMBOLS = [
     "s2k_ctx_set_key_grouping", "s2k_ctx_set_keyed_ladder", "s2k_ctx_last_keyed_ladder", "s2k_ctx_key_grouping_stats", "s2k_ctx_key_grouping_adaptive",
     "s2k_ecdsa_verify_batch", "s2k_ecdsa_verify_batch_device", "s2k_ecdsa_workspace_bytes", "s2k_ctx_device_bytes",
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
+    "s2k_keyset_create_cap", "s2k_keyset_capacity", "s2k_keyset_reserve", "s2k_keyset_append", "s2k_keyset_append_device",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_keyset_index_geometry", "s2k_keyset_index_create", "s2k_keyset_index_info", "s2k_keyset_lookup", "s2k_keyset_lookup_device",
     "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device", "s2k_ecdsa_verify_batch_keyset_bykey_submit",
@@ -442,6 +454,7 @@ EXPORTED_SYMBOLS = [
     "s2k_group_ecdsa_verify_encoded_batch", "s2k_group_ecdsa_verify_encoded_batch_submit",
     "s2k_group_member_stats", "s2k_group_schnorr_batch_verify_rlc", "s2k_group_multi_scalar_mult",
     "s2k_group_keyset_create", "s2k_group_keyset_destroy", "s2k_group_keyset_size", "s2k_group_keyset_layout", "s2k_group_keyset_device_bytes",
+    "s2k_group_keyset_create_cap", "s2k_group_keyset_capacity", "s2k_group_keyset_reserve", "s2k_group_keyset_append",
     "s2k_group_ecdsa_verify_batch_keyset", "s2k_group_ecdsa_verify_batch_keyset_submit",
     "s2k_schnorr_verify_batch", "s2k_schnorr_verify_batch_device",
     "s2k_schnorr_verify_batch_keyset", "s2k_schnorr_verify_batch_keyset_device", "s2k_schnorr_verify_batch_keyset_submit",
@@ -880,11 +893,12 @@ class Engine(_TicketOwner):
         self._inflight = {}
 
     # ---- key sets ----------------------------------------------------------------------
-    def keyset_create(self, pub_xy, layout: int = 0) -> "KeySet":
-        """Per-key tables of a fixed list of public keys (n_keys x 64 bytes), built once (s2k_keyset_create[_ex]);
+    def keyset_create(self, pub_xy, layout: int = 0, capacity: int = 0) -> "KeySet":
+        """Per-key tables of a list of public keys (n_keys x 64 bytes), built once (s2k_keyset_create_cap);
         layout: KEYSET_AUTO (0: the widest of JOINT5 and JOINT that fits, else CHUNKS), KEYSET_CHUNKS (1), KEYSET_JOINT (2),
-        KEYSET_JOINT5 (3), KEYSET_JOINT6 (4) or KEYSET_COMB (5: 10 KiB per key, for long key lists); keyset_geometry()."""
-        return KeySet(self, pub_xy, layout)
+        KEYSET_JOINT5 (3), KEYSET_JOINT6 (4) or KEYSET_COMB (5: 10 KiB per key, for long key lists); keyset_geometry().
+        capacity: keys the set has memory for (0: as many as pub_xy holds); KeySet.append adds keys up to it."""
+        return KeySet(self, pub_xy, layout, capacity)
 
     def ecdsa_verify_batch_keyset(self, keyset, key_index, digest32, r, s, reject_malleable: bool = False,
                                   force_worklist: bool = False) -> np.ndarray:
@@ -1803,9 +1817,10 @@ class Group(_TicketOwner):
         self._check(self._lib.s2k_group_multi_scalar_mult(self._h, n, k.ctypes.data, p.ctypes.data, out.ctypes.data))
         return out.tobytes()
 
-    def keyset_create(self, pub_xy, layout: int = 0) -> "GroupKeySet":
-        """The tables of a fixed list of public keys on every member's device (s2k_group_keyset_create)."""
-        return GroupKeySet(self, pub_xy, layout)
+    def keyset_create(self, pub_xy, layout: int = 0, capacity: int = 0) -> "GroupKeySet":
+        """The tables of a list of public keys on every member's device (s2k_group_keyset_create_cap); capacity: keys every
+        member's set has memory for (0: as many as pub_xy holds)."""
+        return GroupKeySet(self, pub_xy, layout, capacity)
 
     def ecdsa_verify_batch_keyset_submit(self, keyset, key_index, digest32, r, s, out=None, reject_malleable: bool = False) -> Ticket:
         ki = np.ascontiguousarray(key_index, dtype=np.uint32).reshape(-1)
@@ -1834,15 +1849,32 @@ class Group(_TicketOwner):
 
 
 class GroupKeySet:
-    """Handle of s2k_group_keyset_*: the per-key tables of a fixed key list on every device of a group."""
+    """Handle of s2k_group_keyset_*: the per-key tables of a key list on every device of a group."""
 
-    def __init__(self, group: "Group", pub_xy, layout: int = 0):
+    def __init__(self, group: "Group", pub_xy, layout: int = 0, capacity: int = 0):
         pub_xy = _arr(pub_xy, 64)
         self._grp = group
         k = C.c_void_p()
-        group._check(group._lib.s2k_group_keyset_create(group._h, pub_xy.shape[0], pub_xy.ctypes.data, int(layout), C.byref(k)))
+        group._check(group._lib.s2k_group_keyset_create_cap(group._h, pub_xy.shape[0], pub_xy.ctypes.data, int(layout), int(capacity),
+                                                            C.byref(k)))
         self._k = k
         group._keysets.add(self)
+
+    def capacity(self) -> int:
+        """keys every member's set has memory for (s2k_group_keyset_capacity)"""
+        return int(self._grp._lib.s2k_group_keyset_capacity(self._k))
+
+    def reserve(self, capacity: int):
+        """s2k_group_keyset_reserve: memory for `capacity` keys on every member"""
+        self._grp._check(self._grp._lib.s2k_group_keyset_reserve(self._k, int(capacity)))
+
+    def append(self, pub_xy) -> int:
+        """s2k_group_keyset_append: more keys (n x 64 bytes) on every member's set; the index of the first of them"""
+        pub_xy = _arr(pub_xy, 64)
+        first = C.c_uint32(0)
+        self._grp._check(self._grp._lib.s2k_group_keyset_append(self._k, pub_xy.shape[0], pub_xy.ctypes.data if pub_xy.shape[0] else None,
+                                                                C.byref(first)))
+        return int(first.value)
 
     def layout(self) -> int:
         return int(self._grp._lib.s2k_group_keyset_layout(self._k))
@@ -1932,14 +1964,47 @@ class PointSet:
 
 
 class KeySet:
-    """Handle of s2k_keyset_*: the per-key tables of a fixed key list on the engine's device."""
+    """Handle of s2k_keyset_*: the per-key tables of a key list on the engine's device.  len(): the keys it holds."""
 
-    def __init__(self, engine: "Engine", pub_xy, layout: int = 0):
+    def __init__(self, engine: "Engine", pub_xy, layout: int = 0, capacity: int = 0):
         pub_xy = _arr(pub_xy, 64)
         self._eng = engine
         k = C.c_void_p()
-        engine._check(engine._lib.s2k_keyset_create_ex(engine._h, pub_xy.shape[0], pub_xy.ctypes.data, int(layout), C.byref(k)))
+        engine._check(engine._lib.s2k_keyset_create_cap(engine._h, pub_xy.shape[0], pub_xy.ctypes.data, int(layout), int(capacity),
+                                                        C.byref(k)))
         self._k = k
+
+    def _check_own(self, rc):
+        # (these calls take no context: their message is the calling thread's)
+        if rc != 0:
+            raise EngineError(f"s2k error {rc}: {self._eng._lib.s2k_last_error(None).decode()}")
+
+    def capacity(self) -> int:
+        """keys the set has memory for (s2k_keyset_capacity); len() of them have tables"""
+        return int(self._eng._lib.s2k_keyset_capacity(self._k))
+
+    def reserve(self, capacity: int):
+        """Memory for `capacity` keys (s2k_keyset_reserve): new buffers, the set copied over on the device.  Needs room for
+        both copies for a moment: give a large set its capacity at creation.  A smaller capacity changes nothing."""
+        self._check_own(self._eng._lib.s2k_keyset_reserve(self._k, int(capacity)))
+
+    def append(self, pub_xy) -> int:
+        """More keys (n x 64 bytes: host bytes / arrays, or a torch uint8 tensor on the set's device), within the capacity
+        (s2k_keyset_append[_device]): only their tables are built, and the set's index follows.  Returns the index of the
+        first of them.  No call or ticket that uses the set may be in progress."""
+        first = C.c_uint32(0)
+        if hasattr(pub_xy, "data_ptr") and hasattr(pub_xy, "is_cuda"):
+            t = pub_xy
+            if not t.is_cuda or t.element_size() != 1 or t.numel() % 64:
+                raise ValueError("secp256k1: a device tensor of n x 64 bytes")
+            t = t.contiguous()
+            n = t.numel() // 64
+            self._check_own(self._eng._lib.s2k_keyset_append_device(self._k, n, t.data_ptr() if n else None, C.byref(first)))
+            return int(first.value)
+        pub_xy = _arr(pub_xy, 64)
+        n = pub_xy.shape[0]
+        self._check_own(self._eng._lib.s2k_keyset_append(self._k, n, pub_xy.ctypes.data if n else None, C.byref(first)))
+        return int(first.value)
 
     def layout(self) -> int:
         """The layout the set has: KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 or KEYSET_COMB (s2k_keyset_layout)."""

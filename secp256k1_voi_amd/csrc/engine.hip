@@ -3066,8 +3066,9 @@ struct s2k_keyset {
   s2k_ctx* ctx;       // the owner (compared, never followed after creation: the set may outlive it by accident)
   uint64_t generation;   // of the owner: a context destroyed and another created at the same address is not the owner
   int device;
-  size_t n;
-  uint8_t* base;      // device: keys | tables | validity | identity | counters (s2k_internal_keyset_bytes)
+  size_t n;           // live keys: what bounds a key index and sizes a call's scratch
+  size_t cap;         // keys the buffers have room for (>= n): every offset into `base` and `joint` comes from it
+  uint8_t* base;      // device: keys | tables | validity | identity | counters (s2k_internal_keyset_bytes of cap)
   size_t bytes;
   uint4* joint;       // device: the joint tables (320 KiB per key; 0.81 / 2.75 MiB at 5- / 6-bit digits), or null: the ladder over the 32-chunk tables
   size_t joint_bytes;
@@ -3092,9 +3093,13 @@ static int keyset_ladder_mode(const s2k_keyset* ks, bool schnorr) {
 }
 
 int s2k_keyset_create(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, s2k_keyset** out) {
-  return s2k_keyset_create_ex(ctx, n_keys, pub_xy, S2K_KEYSET_AUTO, out);
+  return s2k_keyset_create_cap(ctx, n_keys, pub_xy, S2K_KEYSET_AUTO, 0, out);
 }
 int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int layout, s2k_keyset** out) {
+  return s2k_keyset_create_cap(ctx, n_keys, pub_xy, layout, 0, out);
+}
+// capacity: keys the set has memory for (0: n_keys).  Every buffer is laid out for it; the tables of n_keys keys are built.
+int s2k_keyset_create_cap(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int layout, size_t capacity, s2k_keyset** out) {
   if (!ctx || !out) return fail(ctx, S2K_ERR_ARG, "null argument");
   if (layout != S2K_KEYSET_AUTO && layout != S2K_KEYSET_CHUNKS && layout != S2K_KEYSET_JOINT && layout != S2K_KEYSET_JOINT5 &&
       layout != S2K_KEYSET_JOINT6 && layout != S2K_KEYSET_COMB)
@@ -3102,6 +3107,8 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
   *out = nullptr;
   if (n_keys == 0 || !pub_xy) return fail(ctx, S2K_ERR_ARG, "empty key set");
   if (n_keys > 0x0fffffffu) return fail(ctx, S2K_ERR_ARG, "key set too large");
+  const size_t cap = capacity ? capacity : n_keys;
+  if (cap < n_keys || cap > 0x0fffffffu) return fail(ctx, S2K_ERR_ARG, "key set of %zu keys with a capacity of %zu (n_keys .. 0x0fffffff)", n_keys, cap);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc = ctx_streams(ctx);
   if (rc) return rc;
@@ -3111,23 +3118,25 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
   ks->generation = ctx->generation;
   ks->device = ctx->device;
   ks->n = n_keys;
+  ks->cap = cap;
   size_t off[5];
   ks->chunks = layout == S2K_KEYSET_COMB ? KC_TEETH : KS_CHUNKS;
-  ks->bytes = s2k_internal_keyset_bytes(n_keys, off, ks->chunks);
+  ks->bytes = s2k_internal_keyset_bytes(cap, off, ks->chunks);
   hipError_t e = hipMalloc((void**)&ks->base, ks->bytes);
   if (e != hipSuccess) {
     delete ks;
-    return fail(ctx, S2K_ERR_HIP, "key set of %zu keys (%zu bytes): %s", n_keys, ks->bytes, hipGetErrorString(e));
+    return fail(ctx, S2K_ERR_HIP, "key set of %zu keys (%zu bytes): %s", cap, ks->bytes, hipGetErrorString(e));
   }
   hipStream_t st = ctx->s_comp;
   rc = ctx_enter(ctx, st);
   if (rc == S2K_OK && hipMemcpyAsync(ks->base + off[0], pub_xy, n_keys * 64, hipMemcpyHostToDevice, st) != hipSuccess)
     rc = fail(ctx, S2K_ERR_HIP, "copy of the keys failed");
-  if (rc == S2K_OK) rc = s2k_internal_keyset_build(ctx, ks->base, n_keys, st, ks->chunks);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_build(ctx, ks->base, cap, 0, n_keys, st, ks->chunks);
   // joint tables (one table addition per digit position instead of two; 320 KiB per key on top, 0.81 MiB at 5-bit digits: 26
   // positions, 2.75 MiB at 6-bit digits: 22): the layout asked for, or - S2K_KEYSET_AUTO - the widest of 5 and 4 bits that takes no
   // more than half of the device memory that is free now (2^16 keys at 5 bits are 56 GB: a quarter would ask for a device with
-  // 224 GB free, which the 288 GB one never has once a context lives on it)
+  // 224 GB free, which the 288 GB one never has once a context lives on it).  The tables are sized, and the layout chosen, by
+  // the CAPACITY; the build's scratch by the keys there are
   ks->joint = nullptr;
   ks->joint_bytes = 0;
   ks->jw = 0;
@@ -3143,24 +3152,24 @@ int s2k_keyset_create_ex(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int
         const size_t promised = s2k_internal_gt_pending_bytes(ctx->device);   // what the background table build is about to take
         free_b -= promised < free_b ? promised : free_b;
         if (free_b > pretend_free) free_b = pretend_free;
-        if (s2k_internal_keyset_joint_bytes(n_keys, 5) + s2k_internal_keyset_joint_scratch_bytes(n_keys, 5) <= free_b / 2) w = 5;
-        else if (s2k_internal_keyset_joint_bytes(n_keys, 4) <= free_b / 2) w = 4;
+        if (s2k_internal_keyset_joint_bytes(cap, 5) + s2k_internal_keyset_joint_scratch_bytes(n_keys, 5) <= free_b / 2) w = 5;
+        else if (s2k_internal_keyset_joint_bytes(cap, 4) <= free_b / 2) w = 4;
       }
     }
     if (w) {
-      const size_t want = s2k_internal_keyset_joint_bytes(n_keys, w), want_scr = s2k_internal_keyset_joint_scratch_bytes(n_keys, w);
+      const size_t want = s2k_internal_keyset_joint_bytes(cap, w), want_scr = s2k_internal_keyset_joint_scratch_bytes(n_keys, w);
       hipError_t e2 = want + want_scr > pretend_free ? hipErrorOutOfMemory : hipMalloc((void**)&ks->joint, want);
       if (e2 == hipSuccess && want_scr) e2 = hipMalloc((void**)&scratch, want_scr);
       if (e2 == hipSuccess) {
         ks->joint_bytes = want;
         ks->jw = w;
-        rc = w == 4 ? s2k_internal_keyset_build_joint(ctx, ks->base, n_keys, ks->joint, st)
-                    : s2k_internal_keyset_build_joint_wide(ctx, ks->base, n_keys, w, ks->joint, scratch, st);
+        rc = w == 4 ? s2k_internal_keyset_build_joint(ctx, ks->base, cap, 0, n_keys, ks->joint, st)
+                    : s2k_internal_keyset_build_joint_wide(ctx, ks->base, cap, 0, n_keys, w, ks->joint, scratch, st);
       } else {
         (void)hipGetLastError();
         if (ks->joint) (void)hipFree(ks->joint);
         ks->joint = nullptr;
-        if (layout != S2K_KEYSET_AUTO) rc = fail(ctx, S2K_ERR_HIP, "joint tables of %zu keys (%zu bytes): %s", n_keys, want + want_scr, hipGetErrorString(e2));
+        if (layout != S2K_KEYSET_AUTO) rc = fail(ctx, S2K_ERR_HIP, "joint tables of %zu keys (%zu bytes): %s", cap, want + want_scr, hipGetErrorString(e2));
       }
     }
   }
@@ -3189,6 +3198,7 @@ void s2k_keyset_destroy(s2k_keyset* ks) {
   delete ks;
 }
 size_t s2k_keyset_size(const s2k_keyset* ks) { return ks ? ks->n : 0; }
+size_t s2k_keyset_capacity(const s2k_keyset* ks) { return ks ? ks->cap : 0; }
 size_t s2k_keyset_device_bytes(const s2k_keyset* ks) { return ks ? ks->bytes + ks->joint_bytes : 0; }
 int s2k_keyset_layout(const s2k_keyset* ks) {
   return !ks ? 0 : ks->chunks == KC_TEETH ? S2K_KEYSET_COMB : !ks->joint ? S2K_KEYSET_CHUNKS : ks->jw == 6 ? S2K_KEYSET_JOINT6 : ks->jw == 5 ? S2K_KEYSET_JOINT5 : S2K_KEYSET_JOINT;
@@ -3230,7 +3240,7 @@ int s2k_keyset_geometry(int layout, uint64_t out[3]) {
 int s2k_keyset_valid_keys(s2k_keyset* ks, uint8_t* valid) {
   if (!ks || !valid) return fail(nullptr, S2K_ERR_ARG, "null argument");
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   HIP_TRY(nullptr, hipSetDevice(ks->device));
   HIP_TRY(nullptr, hipMemcpy(valid, ks->base + off[2], ks->n, hipMemcpyDeviceToHost));
   return S2K_OK;
@@ -3255,7 +3265,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
     // small calls: a wave per signature over the set's 32-chunk tables (k_verify_row_keyset), one launch; nothing is sorted
     // and nothing is left for a worklist
     size_t off[5];
-    (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+    (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
     ctx->ks_last = S2K_KEYSET_LADDER_ROW;
     ctx->kg_counters = nullptr;
     ctx->last_wl_count = nullptr;
@@ -3280,7 +3290,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   const uint8_t *dig = (const uint8_t*)d_dig, *r = (const uint8_t*)d_r, *s = (const uint8_t*)d_s;
   uint8_t* valid = (uint8_t*)d_valid;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
   ctx->last_wl_count = w.wl_count;
   HIP_TRY(ctx, hipMemsetAsync(w.wl_count, 0, sizeof(uint32_t), st));
@@ -3296,7 +3306,7 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->cap, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);
@@ -3374,11 +3384,68 @@ int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2
     return fail(nullptr, S2K_ERR_ARG, "key-set index: %zu keys in 2^%u slots (more slots than keys, at most 2^31; 1 .. 0x0fffffff keys)", n_keys, log2_slots);
   return S2K_OK;
 }
+// A fresh index of the keys 0 .. nkeys - 1 of the set in 2^lg slots: allocated, filled and read back on the null stream
+// (synchronous).  The set is not touched: the caller puts the table in (keyset_index_adopt).
+static int keyset_index_make(const s2k_keyset* ks, size_t nkeys, uint32_t lg, uint64_t seed, uint64_t** out_slots, uint32_t h[S2K_KSI_INFO_WORDS]) {
+  const size_t nslots = (size_t)1 << lg, bytes = nslots * sizeof(uint64_t);
+  uint64_t* slots = nullptr;
+  hipError_t e = hipMalloc((void**)&slots, bytes + S2K_KSI_INFO_WORDS * sizeof(uint32_t));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(nullptr, S2K_ERR_NOMEM, "key-set index of %zu bytes: %s", bytes, hipGetErrorString(e));
+  }
+  uint32_t* info = reinterpret_cast<uint32_t*>(slots + nslots);
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
+  int rc = S2K_OK;
+  if (hipMemsetAsync(slots, 0xff, bytes, nullptr) != hipSuccess || hipMemsetAsync(info, 0, S2K_KSI_INFO_WORDS * sizeof(uint32_t), nullptr) != hipSuccess)
+    rc = fail(nullptr, S2K_ERR_HIP, "key-set index: memset failed");
+  if (rc == S2K_OK) rc = s2k_internal_ksi_build(nullptr, nullptr, ks->base + off[0], 0, nkeys, slots, lg, seed, info);
+  if (rc == S2K_OK && hipMemcpy(h, info, S2K_KSI_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(nullptr, S2K_ERR_HIP, "key-set index build failed");
+  // (cannot happen while there are more slots than keys: every probe loop is bounded all the same, and says so here)
+  if (rc == S2K_OK && h[S2K_KSI_FAILED]) rc = fail(nullptr, S2K_ERR_HIP, "key-set index: an insert found no slot");
+  if (rc) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(slots);
+    return rc;
+  }
+  *out_slots = slots;
+  return S2K_OK;
+}
+// (no call that uses the set is in progress and the device is idle: the table it had, if any, is freed)
+static void keyset_index_adopt(s2k_keyset* ks, uint64_t* slots, uint32_t lg, uint64_t seed, const uint32_t h[S2K_KSI_INFO_WORDS]) {
+  if (ks->index) (void)hipFree(ks->index);
+  ks->index = slots;
+  ks->index_log2 = lg;
+  ks->index_seed = seed;
+  ks->index_occupied = h[S2K_KSI_OCCUPIED];
+  ks->index_longest = h[S2K_KSI_LONGEST];
+}
+static uint32_t keyset_index_auto_log2(size_t n_keys) {
+  uint64_t geo[2] = {0, 0};
+  (void)ksi_geometry(n_keys, 0, geo);
+  uint32_t lg = 0;
+  while (((uint64_t)1 << lg) < geo[0]) ++lg;
+  return lg;
+}
+// The index of the keys 0 .. nkeys - 1 anew, at the automatic geometry of the set's capacity and with the seed it has
+static int keyset_index_rebuild(s2k_keyset* ks, size_t nkeys) {
+  const uint32_t lg = keyset_index_auto_log2(ks->cap);
+  uint64_t* slots = nullptr;
+  uint32_t h[S2K_KSI_INFO_WORDS] = {0, 0, 0, 0};
+  const int rc = keyset_index_make(ks, nkeys, lg, ks->index_seed, &slots, h);
+  if (rc) return rc;
+  keyset_index_adopt(ks, slots, lg, ks->index_seed, h);
+  return S2K_OK;
+}
 int s2k_keyset_index_create(s2k_keyset* ks, uint32_t log2_slots) {
   if (!ks) return fail(nullptr, S2K_ERR_ARG, "null argument");
   if (ks->index) return fail(nullptr, S2K_ERR_ARG, "the key set has an index already");
+  // 0: sized for the capacity, so that appends up to it never rebuild (cap == n: what it always was); an explicit size is
+  // the caller's, and only has to hold the keys there are
   uint64_t geo[2];
-  if (!ksi_geometry(ks->n, log2_slots, geo))
+  if (!ksi_geometry(log2_slots ? ks->n : ks->cap, log2_slots, geo))
     return fail(nullptr, S2K_ERR_ARG, "key-set index: %zu keys in 2^%u slots (more slots than keys, at most 2^31)", ks->n, log2_slots);
   uint32_t lg = 0;
   while (((uint64_t)1 << lg) < geo[0]) ++lg;
@@ -3387,33 +3454,141 @@ int s2k_keyset_index_create(s2k_keyset* ks, uint32_t log2_slots) {
   HIP_TRY(nullptr, hipSetDevice(ks->device));
   HIP_TRY(nullptr, hipDeviceSynchronize());            // (the rule of s2k_keyset_destroy: no call that uses the set is in progress)
   uint64_t* slots = nullptr;
-  const size_t bytes = (size_t)geo[1];
-  hipError_t e = hipMalloc((void**)&slots, bytes + S2K_KSI_INFO_WORDS * sizeof(uint32_t));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(nullptr, S2K_ERR_NOMEM, "key-set index of %zu bytes: %s", bytes, hipGetErrorString(e));
-  }
-  uint32_t* info = reinterpret_cast<uint32_t*>(slots + geo[0]);
   uint32_t h[S2K_KSI_INFO_WORDS] = {0, 0, 0, 0};
+  const int rc = keyset_index_make(ks, ks->n, lg, seed, &slots, h);
+  if (rc) return rc;
+  keyset_index_adopt(ks, slots, lg, seed, h);
+  return S2K_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Growing a set.  The buffers of a set are laid out for its capacity (s2k_keyset_create_cap, s2k_keyset_reserve); an append
+// copies the new keys behind the live ones and runs the SAME table kernels as the creation over the new rows only
+// (s2k_internal_keyset_build with first > 0), then inserts the new range into the index, and only then moves n: until that
+// moment every call sees the old set, and a failure leaves it.  Nothing here goes through a context - as
+// s2k_keyset_index_create, on the null stream with the device idle before and after.
+// ---------------------------------------------------------------------------------------
+// the index after keys first .. first + count - 1 have been written behind the `first` live ones
+static int keyset_index_grow(s2k_keyset* ks, size_t first, size_t count) {
+  if (first + count >= ((uint64_t)1 << ks->index_log2)) return keyset_index_rebuild(ks, first + count);   // (an explicit geometry, outgrown)
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
-  int rc = S2K_OK;
-  if (hipMemsetAsync(slots, 0xff, bytes, nullptr) != hipSuccess || hipMemsetAsync(info, 0, sizeof h, nullptr) != hipSuccess)
-    rc = fail(nullptr, S2K_ERR_HIP, "key-set index: memset failed");
-  if (rc == S2K_OK) rc = s2k_internal_ksi_build(nullptr, nullptr, ks->base + off[0], ks->n, slots, lg, seed, info);
-  if (rc == S2K_OK && hipMemcpy(h, info, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set index build failed");
-  // (cannot happen while there are more slots than keys: every probe loop is bounded all the same, and says so here)
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
+  uint32_t* info = reinterpret_cast<uint32_t*>(ks->index + ((size_t)1 << ks->index_log2));
+  uint32_t h[S2K_KSI_INFO_WORDS] = {0, 0, 0, 0};
+  int rc = s2k_internal_ksi_build(nullptr, nullptr, ks->base + off[0], first, count, ks->index, ks->index_log2, ks->index_seed, info);
+  if (rc) return rc;                // (refused before the launch: the table is as it was)
+  if (hipMemcpy(h, info, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set index: inserting the appended keys failed");
   if (rc == S2K_OK && h[S2K_KSI_FAILED]) rc = fail(nullptr, S2K_ERR_HIP, "key-set index: an insert found no slot");
-  if (rc) {
+  if (rc == S2K_OK) {
+    ks->index_occupied = h[S2K_KSI_OCCUPIED];
+    ks->index_longest = h[S2K_KSI_LONGEST];
+    return S2K_OK;
+  }
+  // some slots may name rows that are not going to be keys: the index of the live keys anew - or, failing that too, none
+  (void)hipGetLastError();
+  const uint32_t lg = ks->index_log2;
+  uint64_t* slots = nullptr;
+  if (keyset_index_make(ks, first, lg, ks->index_seed, &slots, h) == S2K_OK) keyset_index_adopt(ks, slots, lg, ks->index_seed, h);
+  else {
+    (void)hipFree(ks->index);
+    ks->index = nullptr;
+  }
+  return rc;
+}
+static int keyset_append(s2k_keyset* ks, size_t n_new, const void* src, bool on_device, uint32_t* first_index) {
+  if (!ks) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (n_new == 0) {
+    if (first_index) *first_index = (uint32_t)ks->n;
+    return S2K_OK;
+  }
+  if (!src) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (n_new > ks->cap - ks->n)
+    return fail(nullptr, S2K_ERR_ARG, "a key set of %zu keys with a capacity of %zu has no room for %zu more (s2k_keyset_reserve)", ks->n, ks->cap, n_new);
+  HIP_TRY(nullptr, hipSetDevice(ks->device));
+  HIP_TRY(nullptr, hipDeviceSynchronize());            // (the rule of s2k_keyset_destroy: no call that uses the set is in progress)
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
+  const size_t first = ks->n;
+  uint4* scratch = nullptr;
+  const size_t want_scr = ks->joint ? s2k_internal_keyset_joint_scratch_bytes(n_new, ks->jw) : 0;
+  if (want_scr && hipMalloc((void**)&scratch, want_scr) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(nullptr, S2K_ERR_NOMEM, "key-set append: %zu bytes of build scratch", want_scr);
+  }
+  int rc = S2K_OK;
+  if (hipMemcpy(ks->base + off[0] + first * 64, src, n_new * 64, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(nullptr, S2K_ERR_HIP, "copy of the keys failed");
+  if (rc == S2K_OK) rc = s2k_internal_keyset_build(nullptr, ks->base, ks->cap, first, n_new, nullptr, ks->chunks);
+  if (rc == S2K_OK && ks->joint)
+    rc = ks->jw == 4 ? s2k_internal_keyset_build_joint(nullptr, ks->base, ks->cap, first, n_new, ks->joint, nullptr)
+                     : s2k_internal_keyset_build_joint_wide(nullptr, ks->base, ks->cap, first, n_new, ks->jw, ks->joint, scratch, nullptr);
+  if (rc == S2K_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set append: the table build failed");
+  if (scratch) {
     (void)hipDeviceSynchronize();
-    (void)hipFree(slots);
+    (void)hipFree(scratch);
+  }
+  if (rc == S2K_OK && ks->index) rc = keyset_index_grow(ks, first, n_new);
+  if (rc) {
+    (void)hipGetLastError();
+    (void)hipMemset(ks->base + off[2] + first, 0, n_new);     // rows past n are "no key"
     return rc;
   }
-  ks->index = slots;
-  ks->index_log2 = lg;
-  ks->index_seed = seed;
-  ks->index_occupied = h[S2K_KSI_OCCUPIED];
-  ks->index_longest = h[S2K_KSI_LONGEST];
+  ks->n = first + n_new;
+  if (first_index) *first_index = (uint32_t)first;
+  return S2K_OK;
+}
+int s2k_keyset_append(s2k_keyset* ks, size_t n_new, const uint8_t* pub_xy, uint32_t* first_index) {
+  return keyset_append(ks, n_new, pub_xy, false, first_index);
+}
+int s2k_keyset_append_device(s2k_keyset* ks, size_t n_new, const void* d_pub_xy, uint32_t* first_index) {
+  return keyset_append(ks, n_new, d_pub_xy, true, first_index);
+}
+// Memory for `capacity` keys: new buffers, the live rows of every section copied to their new offsets, the old buffers freed
+// once the copies are done.  Both copies exist for a moment - a set that fills more than half of the device cannot grow this
+// way and has to be given its capacity at creation.
+int s2k_keyset_reserve(s2k_keyset* ks, size_t capacity) {
+  if (!ks) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (capacity <= ks->cap) return S2K_OK;
+  if (capacity > 0x0fffffffu) return fail(nullptr, S2K_ERR_ARG, "key set too large");
+  HIP_TRY(nullptr, hipSetDevice(ks->device));
+  HIP_TRY(nullptr, hipDeviceSynchronize());            // (the rule of s2k_keyset_destroy: no call that uses the set is in progress)
+  size_t off[5], noff[5];
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
+  const size_t nbytes = s2k_internal_keyset_bytes(capacity, noff, ks->chunks);
+  const size_t njoint = ks->joint ? s2k_internal_keyset_joint_bytes(capacity, ks->jw) : 0;
+  uint8_t* nbase = nullptr;
+  uint4* nj = nullptr;
+  hipError_t e = hipMalloc((void**)&nbase, nbytes);
+  if (e == hipSuccess && njoint) e = hipMalloc((void**)&nj, njoint);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (nbase) (void)hipFree(nbase);
+    return fail(nullptr, S2K_ERR_NOMEM, "key set of %zu keys (%zu bytes): %s", capacity, nbytes + njoint, hipGetErrorString(e));
+  }
+  const size_t n = ks->n, slot_bytes = (size_t)(ks->chunks == KC_TEETH ? KC_SLOTS : KS_SLOTS) * 128;
+  bool ok = hipMemsetAsync(nbase + noff[2], 0, noff[3] - noff[2], nullptr) == hipSuccess;     // validity: rows past n are "no key"
+  ok = ok && hipMemcpyAsync(nbase + noff[0], ks->base + off[0], n * 64, hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+  ok = ok && hipMemcpyAsync(nbase + noff[1], ks->base + off[1], n * slot_bytes, hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+  ok = ok && hipMemcpyAsync(nbase + noff[2], ks->base + off[2], n, hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+  ok = ok && s2k_internal_keyset_identity(nullptr, nbase, capacity, nullptr, ks->chunks) == S2K_OK;   // the identity of the whole capacity (the counters are the builds' scratch)
+  if (ok && nj) ok = hipMemcpyAsync(nj, ks->joint, s2k_internal_keyset_joint_bytes(n, ks->jw), hipMemcpyDeviceToDevice, nullptr) == hipSuccess;
+  ok = ok && hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipDeviceSynchronize();
+    if (nj) (void)hipFree(nj);
+    (void)hipFree(nbase);
+    return fail(nullptr, S2K_ERR_HIP, "key-set reserve: copying the set failed");
+  }
+  if (ks->joint) (void)hipFree(ks->joint);
+  (void)hipFree(ks->base);
+  ks->base = nbase;
+  ks->bytes = nbytes;
+  ks->joint = nj;
+  ks->joint_bytes = njoint;
+  ks->cap = capacity;
+  // the index holds key indices, not addresses: it stands - unless it is too small for what the set may now grow to
+  if (ks->index && ((uint64_t)1 << ks->index_log2) < 2 * (uint64_t)capacity) return keyset_index_rebuild(ks, ks->n);
   return S2K_OK;
 }
 int s2k_keyset_index_info(const s2k_keyset* ks, uint64_t out[4]) {
@@ -3449,7 +3624,7 @@ int s2k_keyset_lookup_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const
   rc = ctx_enter(ctx, st);
   if (rc) return rc;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n,
                                (const uint8_t*)d_keys, (int)key_bytes, stride, (uint32_t*)d_key_index);
   if (rc) return rc;
@@ -3509,7 +3684,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_bykey_view(s2k_ctx* ctx, 
   int rc = bykey_check(ctx, ks, flags);
   if (rc) return rc;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   *out = {ks->base + off[0], ks->base + off[2], ks->index, ks->index_log2, ks->index_seed};
   return S2K_OK;
 }
@@ -3549,7 +3724,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_bykey_device(s2k_ctx* ctx
   uint32_t* found = (uint32_t*)ctx->ks_found;
   if (d_found && d_found != found) return fail(ctx, S2K_ERR_ARG, "key indices outside the context's buffer");
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
   ctx->kt_last = -1;
   ctx->last_wl_count = w.wl_count;
@@ -3568,7 +3743,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_bykey_device(s2k_ctx* ctx
   key_groups kg{};
   if (rc == S2K_OK && !d_found)
     rc = s2k_internal_ksi_lookup(ctx, st, ks->base + off[0], ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n, pub, 64, 64, found);
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, found, st, &kg, ks->chunks);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->cap, ks->n, n, found, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);
@@ -3994,7 +4169,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   if (n <= ctx->ks_row_max && ks->chunks != KC_TEETH) {
     // small calls: a wave per signature over the set's 32-chunk tables (k_schnorr_row_keyset), one launch
     size_t off[5];
-    (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+    (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
     ctx->ks_last = S2K_KEYSET_LADDER_ROW;
     ctx->kg_counters = nullptr;
     ctx->last_wl_count = nullptr;
@@ -4021,7 +4196,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   const uint32_t mlen = (uint32_t)msg_len;
   uint8_t* valid = (uint8_t*)d_valid;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   const uint8_t* set_keys = ks->base + off[0];
   ctx->kg_counters = nullptr;
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
@@ -4037,7 +4212,7 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   launch_generator_part(ctx, ctx->s_aux, w, 0u, (uint32_t)n);
   rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "launch failed");
   key_groups kg{};
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->cap, ks->n, n, (const uint32_t*)d_key_index, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);
@@ -4138,7 +4313,7 @@ int s2k_schnorr_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset*
   uint8_t* valid = (uint8_t*)d_valid;
   uint32_t* found = (uint32_t*)ctx->ks_found;
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(ks->n, off, ks->chunks);
+  (void)s2k_internal_keyset_bytes(ks->cap, off, ks->chunks);
   const uint8_t* set_keys = ks->base + off[0];
   ctx->ks_last = S2K_KEYSET_LADDER_LANE;
   ctx->kt_last = -1;
@@ -4159,7 +4334,7 @@ int s2k_schnorr_verify_batch_keyset_bykey_device(s2k_ctx* ctx, const s2k_keyset*
   key_groups kg{};
   if (rc == S2K_OK)
     rc = s2k_internal_ksi_lookup(ctx, st, set_keys, ks->index, ks->index_log2, ks->index_seed, ks->base + off[2], n, pk, S2K_KSI_X_VALID, 32, found);
-  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->n, n, found, st, &kg, ks->chunks);
+  if (rc == S2K_OK) rc = s2k_internal_keyset_sort(ctx, ks->base, ks->cap, ks->n, n, found, st, &kg, ks->chunks);
   ctx_aux_join(ctx, st);
   if (rc) {
     (void)ctx_leave(ctx, st);

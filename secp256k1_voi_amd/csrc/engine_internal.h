@@ -573,24 +573,27 @@ int s2k_internal_key_group_all(s2k_ctx* ctx, size_t n, const uint8_t* d_keys, in
 int s2k_internal_key_reserve32(s2k_ctx* ctx, size_t n);
 // key sets (s2k_keyset_*): buffer layout, table build, scratch reservation, sort of a batch by key index
 // (chunks: the geometry of the set's tables, KS_CHUNKS - also what the joint layouts are built from - or KC_TEETH, a comb set)
-size_t s2k_internal_keyset_bytes(size_t n, size_t off[5], int chunks = KS_CHUNKS);
-int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st, int chunks = KS_CHUNKS);
-int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t n, uint4* joint, hipStream_t st);   // from the 32-chunk tables
+// (cap: the capacity the set's buffers are laid out for, s2k_keyset_capacity; first, count: a range of its keys; nkeys: its live keys)
+size_t s2k_internal_keyset_bytes(size_t cap, size_t off[5], int chunks = KS_CHUNKS);
+int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t cap, size_t first, size_t count, hipStream_t st, int chunks = KS_CHUNKS);
+int s2k_internal_keyset_identity(s2k_ctx* ctx, uint8_t* base, size_t cap, hipStream_t st, int chunks = KS_CHUNKS);
+int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first, size_t count, uint4* joint, hipStream_t st);   // from the 32-chunk tables
 size_t s2k_internal_keyset_joint_bytes(size_t n, int w);                  // joint tables of n keys at digit width w (4, 5, 6)
 size_t s2k_internal_keyset_joint_scratch_bytes(size_t n, int w);          // build scratch of the wide layouts (0 at w = 4)
-int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t n, int w, uint4* joint, uint4* scratch, hipStream_t st);
+int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first, size_t count, int w, uint4* joint, uint4* scratch, hipStream_t st);
 int s2k_internal_keyset_reserve(s2k_ctx* ctx, size_t nkeys, size_t n);
-int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys, size_t n, const uint32_t* d_kidx, hipStream_t st,
+int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t cap, size_t nkeys, size_t n, const uint32_t* d_kidx, hipStream_t st,
                              key_groups* out, int chunks = KS_CHUNKS);
 
 // the index of a key set, key bytes -> key index (keyset_index.hip; the table and its probe loops: keyset_index.h).  Enqueue
-// only.  build: `slots` (2^log2_slots words of 64 bits) all ones and `info` (S2K_KSI_INFO_WORDS words) zero beforehand;
+// only.  build: inserts the keys first .. first + count - 1; `slots` (2^log2_slots words of 64 bits) all ones and `info`
+// (S2K_KSI_INFO_WORDS words) zero before the first range, and left as the earlier ranges left them before a later one;
 // lookup: d_out[i] = the index of the set's key equal to the key_bytes (64: X || Y, 32: X) bytes at d_keys + i * stride, else
 // 0xFFFFFFFF.  key_bytes S2K_KSI_X_VALID: 32 bytes of X looked up among the set's VALID keys only (ksi_lookup32v: the fused
 // BIP-340 call's lookup; s2k_keyset_lookup* never passes it)
 enum { S2K_KSI_OCCUPIED = 0, S2K_KSI_LONGEST = 1, S2K_KSI_FAILED = 2, S2K_KSI_INFO_WORDS = 4 };
 constexpr int S2K_KSI_X_VALID = -32;
-int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys, uint64_t* slots, uint32_t log2_slots,
+int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t first, size_t count, uint64_t* slots, uint32_t log2_slots,
                            uint64_t seed, uint32_t* info);
 int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, const uint64_t* slots, uint32_t log2_slots, uint64_t seed,
                             const uint8_t* key_valid, size_t n, const uint8_t* d_keys, int key_bytes, size_t stride, uint32_t* d_out);

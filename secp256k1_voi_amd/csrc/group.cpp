@@ -18,9 +18,11 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -489,10 +491,20 @@ int s2k_group_ecdsa_verify_encoded_batch(s2k_group* g, size_t n, const uint8_t* 
 // Key sets across the group (s2k_keyset_*, engine.hip): every member builds the tables of ALL the keys on its own device -
 // a shard may name any key - side by side, one host thread each; a verification call is sharded like any other, the
 // members' shards go through s2k_ecdsa_verify_batch_keyset_submit over their own copy.
+// (weak: the contexts this file is linked against may be older than these calls, as for s2k_ctx_set_keyset_small_batch_max)
+extern "C" int s2k_keyset_create_cap(s2k_ctx* ctx, size_t n_keys, const uint8_t* pub_xy, int layout, size_t capacity, s2k_keyset** out)
+    __attribute__((weak));
+extern "C" size_t s2k_keyset_capacity(const s2k_keyset* ks) __attribute__((weak));
+extern "C" int s2k_keyset_reserve(s2k_keyset* ks, size_t capacity) __attribute__((weak));
+extern "C" int s2k_keyset_append(s2k_keyset* ks, size_t n_new, const uint8_t* pub_xy, uint32_t* first_index) __attribute__((weak));
 int s2k_group_keyset_create(s2k_group* g, size_t n_keys, const uint8_t* pub_xy, int layout, s2k_group_keyset** out) {
+  return s2k_group_keyset_create_cap(g, n_keys, pub_xy, layout, 0, out);
+}
+int s2k_group_keyset_create_cap(s2k_group* g, size_t n_keys, const uint8_t* pub_xy, int layout, size_t capacity, s2k_group_keyset** out) {
   if (!g || !out) return S2K_ERR_ARG;
   *out = nullptr;
   if (!pub_xy || n_keys == 0) return gfail(g, S2K_ERR_ARG, "empty key set");
+  if (capacity && !s2k_keyset_create_cap) return gfail(g, S2K_ERR_ARG, "contexts without s2k_keyset_create_cap");
   group_wait_idle(g);                              // the members' threads are parked: their contexts may be used from other threads
   s2k_group_keyset* gks = new (std::nothrow) s2k_group_keyset();
   if (!gks) return gfail(g, S2K_ERR_NOMEM, "out of host memory");
@@ -503,7 +515,10 @@ int s2k_group_keyset_create(s2k_group* g, size_t n_keys, const uint8_t* pub_xy, 
   std::vector<int> rcs(D, S2K_OK);
   std::vector<std::thread> th;
   for (size_t i = 0; i < D; ++i)
-    th.emplace_back([&, i] { rcs[i] = s2k_keyset_create_ex(g->members[i]->ctx, n_keys, pub_xy, layout, &gks->sets[i]); });
+    th.emplace_back([&, i] {
+      rcs[i] = capacity ? s2k_keyset_create_cap(g->members[i]->ctx, n_keys, pub_xy, layout, capacity, &gks->sets[i])
+                        : s2k_keyset_create_ex(g->members[i]->ctx, n_keys, pub_xy, layout, &gks->sets[i]);
+    });
   for (std::thread& t : th) t.join();
   for (size_t i = 0; i < D; ++i)
     if (rcs[i]) {
@@ -522,6 +537,43 @@ void s2k_group_keyset_destroy(s2k_group_keyset* gks) {
   delete gks;
 }
 size_t s2k_group_keyset_size(const s2k_group_keyset* gks) { return gks ? gks->n_keys : 0; }
+size_t s2k_group_keyset_capacity(const s2k_group_keyset* gks) {
+  return gks && !gks->sets.empty() && s2k_keyset_capacity ? s2k_keyset_capacity(gks->sets[0]) : s2k_group_keyset_size(gks);
+}
+// s2k_keyset_reserve / s2k_keyset_append on every member's set, side by side as the creation.  The first failing member's
+// code is returned; a member that succeeded keeps what it did, and the group's count moves only when all of them did.
+static int group_keyset_each(s2k_group_keyset* gks, const char* what, const std::function<int(s2k_keyset*)>& f) {
+  s2k_group* g = gks->group;
+  group_wait_idle(g);                              // no group call that uses the set is in progress
+  const size_t D = gks->sets.size();
+  std::vector<int> rcs(D, S2K_OK);
+  std::vector<std::string> errs(D);                // (these calls take no context: their message is the calling thread's)
+  std::vector<std::thread> th;
+  for (size_t i = 0; i < D; ++i)
+    th.emplace_back([&, i] {
+      rcs[i] = f(gks->sets[i]);
+      if (rcs[i]) errs[i] = s2k_last_error(nullptr);
+    });
+  for (std::thread& t : th) t.join();
+  for (size_t i = 0; i < D; ++i)
+    if (rcs[i]) return gfail(g, rcs[i], "key set %s on device %d: %s", what, g->members[i]->device, errs[i].c_str());
+  return S2K_OK;
+}
+int s2k_group_keyset_reserve(s2k_group_keyset* gks, size_t capacity) {
+  if (!gks) return S2K_ERR_ARG;
+  if (!s2k_keyset_reserve) return gfail(gks->group, S2K_ERR_ARG, "contexts without s2k_keyset_reserve");
+  return group_keyset_each(gks, "reserve", [=](s2k_keyset* ks) { return s2k_keyset_reserve(ks, capacity); });
+}
+int s2k_group_keyset_append(s2k_group_keyset* gks, size_t n_new, const uint8_t* pub_xy, uint32_t* first_index) {
+  if (!gks) return S2K_ERR_ARG;
+  if (!s2k_keyset_append) return gfail(gks->group, S2K_ERR_ARG, "contexts without s2k_keyset_append");
+  if (n_new && !pub_xy) return gfail(gks->group, S2K_ERR_ARG, "null argument");
+  const int rc = n_new ? group_keyset_each(gks, "append", [=](s2k_keyset* ks) { return s2k_keyset_append(ks, n_new, pub_xy, nullptr); }) : S2K_OK;
+  if (rc) return rc;
+  if (first_index) *first_index = (uint32_t)gks->n_keys;
+  gks->n_keys += n_new;
+  return S2K_OK;
+}
 // layout and device memory of the set on the group's first member (the members hold the same set; with S2K_KEYSET_AUTO a
 // member short of memory may have fallen back to chunk tables on its own)
 int s2k_group_keyset_layout(const s2k_group_keyset* gks) { return gks && !gks->sets.empty() ? s2k_keyset_layout(gks->sets[0]) : 0; }

@@ -1402,10 +1402,11 @@ k_ks_alloc(uint32_t nkeys, const uint32_t* __restrict__ cnt, uint32_t* __restric
     b += c[k];
   }
 }
-__global__ void __launch_bounds__(256) k_ks_iota(uint32_t n, uint32_t* __restrict__ a, uint32_t* __restrict__ counters) {
+// a[i] = i for i < n (the identity of a set's whole capacity; n = 0: it stands already), and the count of tables to build
+__global__ void __launch_bounds__(256) k_ks_iota(uint32_t n, uint32_t* __restrict__ a, uint32_t* __restrict__ counters, uint32_t ntab) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) a[i] = i;
-  if (i == 0) counters[KG_NTAB] = n;
+  if (i == 0) counters[KG_NTAB] = ntab;
 }
 
 // Joint tables of a key set (engine_internal.h: KJ_*), one lane per (key, digit position).  The position's eight odd
@@ -1551,8 +1552,9 @@ k_ksw_lead(uint32_t nkeys, const uint4* __restrict__ ktab, uint4* __restrict__ j
 }
 }  // namespace
 
-// device memory of a key set of n keys: keys | tables | validity | identity | counters.  chunks: the tables' geometry,
-// KS_CHUNKS (36 KiB per key) or KC_TEETH (a comb set, S2K_KEYSET_COMB: 10 KiB per key)
+// device memory of a key set with room for n keys (its CAPACITY, s2k_keyset_capacity - not the live count): keys | tables |
+// validity | identity | counters.  chunks: the tables' geometry, KS_CHUNKS (36 KiB per key) or KC_TEETH (a comb set,
+// S2K_KEYSET_COMB: 10 KiB per key)
 __attribute__((visibility("hidden"))) size_t s2k_internal_keyset_bytes(size_t n, size_t off[5], int chunks) {
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   off[0] = 0;
@@ -1562,33 +1564,52 @@ __attribute__((visibility("hidden"))) size_t s2k_internal_keyset_bytes(size_t n,
   off[4] = off[3] + al(n * 4);
   return off[4] + al(KG_COUNTERS * 4);
 }
-// builds the tables of the n keys at base + off[0] (already on the device) into the set's buffers
-__attribute__((visibility("hidden"))) int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t n, hipStream_t st, int chunks) {
+// builds the tables of the keys first .. first + count - 1 (already on the device, at base + off[0]) of a set laid out for cap
+// keys.  first = 0: the set's creation, which also fills the identity array for the whole capacity and clears the validity
+// bytes of the rows no key has yet; first > 0: an append (s2k_keyset_append) - the table kernels see a "set" of count keys
+// that starts at key `first`: keys, tables and validity moved there, the identity read from 0 (tinfo then starts at any byte
+// address: k_key_chain writes it, and everything else reads it, a byte at a time)
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t cap, size_t first, size_t count,
+                                                                   hipStream_t st, int chunks) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(n, off, chunks);
+  (void)s2k_internal_keyset_bytes(cap, off, chunks);
+  if (first + count > cap || count == 0) return fail(ctx, S2K_ERR_ARG, "internal: keys %zu + %zu of a set of %zu", first, count, cap);
+  const size_t slots = chunks == KC_TEETH ? KC_SLOTS : KS_SLOTS;
   key_groups g{};
   g.counters = (uint32_t*)(base + off[4]);
-  g.ktab = (const uint4*)(base + off[1]);
-  g.tinfo = base + off[2];
+  g.ktab = (const uint4*)(base + off[1]) + first * slots * 8;
+  g.tinfo = base + off[2] + first;
   g.trep = (const uint32_t*)(base + off[3]);          // table t is the key of "signature" t: the identity
-  g.max_tables = (uint32_t)n;
+  g.max_tables = (uint32_t)count;
   g.chunks = chunks;
   g.key_bytes = 64;
   g.part = 0;
   g.nparts = 1;
   HIP_TRY(ctx, hipMemsetAsync(g.counters, 0, KG_COUNTERS * sizeof(uint32_t), st));
-  k_ks_iota<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, (uint32_t*)(base + off[3]), g.counters);
+  if (first == 0 && cap > count) HIP_TRY(ctx, hipMemsetAsync(base + off[2] + count, 0, cap - count, st));   // "no key": valid = 0
+  if (first == 0) k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, (uint32_t*)(base + off[3]), g.counters, (uint32_t)count);
+  else k_ks_iota<<<1, 256, 0, st>>>(0u, (uint32_t*)(base + off[3]), g.counters, (uint32_t)count);
   HIP_TRY(ctx, hipGetLastError());
-  int rc = s2k_internal_key_chains(ctx, base + off[0], st, &g);
+  int rc = s2k_internal_key_chains(ctx, base + off[0] + first * 64, st, &g);
   if (rc) return rc;
   return s2k_internal_key_tables(ctx, st, &g, 0, 1, nullptr);
 }
-// the joint tables of a key set whose 32-chunk tables are built (same stream, behind them)
-__attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t n, uint4* joint,
-                                                                         hipStream_t st) {
+// the identity array of a set laid out for cap keys, alone: for buffers a set moves into (s2k_keyset_reserve)
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_identity(s2k_ctx* ctx, uint8_t* base, size_t cap, hipStream_t st, int chunks) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(n, off);
-  k_ks_joint<<<(unsigned)((n * KS_CHUNKS + 63) / 64), 64, 0, st>>>((uint32_t)n, (const uint4*)(base + off[1]), joint);
+  (void)s2k_internal_keyset_bytes(cap, off, chunks);
+  k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, (uint32_t*)(base + off[3]), (uint32_t*)(base + off[4]), 0u);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+// the joint tables of the keys first .. first + count - 1 of a key set (laid out for cap keys) whose 32-chunk tables are built
+// (same stream, behind them)
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first,
+                                                                         size_t count, uint4* joint, hipStream_t st) {
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(cap, off);
+  k_ks_joint<<<(unsigned)((count * KS_CHUNKS + 63) / 64), 64, 0, st>>>((uint32_t)count, (const uint4*)(base + off[1]) + first * (KS_SLOTS * 8),
+                                                                       joint + first * KJ_KEY_QUADS);
   HIP_TRY(ctx, hipGetLastError());
   return S2K_OK;
 }
@@ -1614,13 +1635,14 @@ static int keyset_build_joint_wide(s2k_ctx* ctx, const uint4* ktab, size_t n, ui
   HIP_TRY(ctx, hipGetLastError());
   return S2K_OK;
 }
-__attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t n, int w, uint4* joint,
-                                                                              uint4* scratch, hipStream_t st) {
+// (keys first .. first + count - 1 of a set laid out for cap keys; scratch: s2k_internal_keyset_joint_scratch_bytes(count, w))
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first,
+                                                                              size_t count, int w, uint4* joint, uint4* scratch, hipStream_t st) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(n, off);
-  const uint4* ktab = (const uint4*)(base + off[1]);
-  if (w == 5) return keyset_build_joint_wide<5>(ctx, ktab, n, joint, scratch, st);
-  if (w == 6) return keyset_build_joint_wide<6>(ctx, ktab, n, joint, scratch, st);
+  (void)s2k_internal_keyset_bytes(cap, off);
+  const uint4* ktab = (const uint4*)(base + off[1]) + first * (KS_SLOTS * 8);
+  if (w == 5) return keyset_build_joint_wide<5>(ctx, ktab, count, joint + first * kjw_geom<5>::KEY_QUADS, scratch, st);
+  if (w == 6) return keyset_build_joint_wide<6>(ctx, ktab, count, joint + first * kjw_geom<6>::KEY_QUADS, scratch, st);
   return fail(ctx, S2K_ERR_ARG, "joint tables of digit width %d", w);
 }
 // scratch of the sort below, in the context's grouping arrays: counters | cnt, base [nkeys] | slot_of, pos_of, perm, ptab, left [n]
@@ -1630,11 +1652,13 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_reserve(s2k_ctx* c
   if (words * sizeof(uint32_t) > ctx->kg_bytes) ctx->kg_counters = nullptr;
   return ctx_reserve(ctx, &ctx->kg, &ctx->kg_bytes, words * sizeof(uint32_t));
 }
-// signatures sorted by key index -> the lane lists of the keyed ladder over the set's tables (enqueue only)
-__attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t nkeys, size_t n,
+// signatures sorted by key index -> the lane lists of the keyed ladder over the set's tables (enqueue only).  cap: what the
+// set is laid out for; nkeys: its live keys - every launch and every scratch array here is sized by nkeys, so spare capacity
+// costs a call nothing
+__attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t cap, size_t nkeys, size_t n,
                                                                    const uint32_t* d_kidx, hipStream_t st, key_groups* out, int chunks) {
   size_t off[5];
-  (void)s2k_internal_keyset_bytes(nkeys, off, chunks);
+  (void)s2k_internal_keyset_bytes(cap, off, chunks);
   int rc = s2k_internal_keyset_reserve(ctx, nkeys, n);   // (a no-op when the caller has reserved already)
   if (rc) return rc;
   const size_t np = (n + 63) & ~(size_t)63, kp = (nkeys + 63) & ~(size_t)63;

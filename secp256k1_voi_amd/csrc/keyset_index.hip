@@ -1,8 +1,9 @@
 // keyset_index.hip — the index of a key set on the device: key bytes -> key index (keyset_index.h has the table and its
 // probe loops; engine.hip owns the set and the calls: s2k_keyset_index_create, s2k_keyset_lookup*,
 // s2k_ecdsa_verify_batch_keyset_bykey*).
-//   k_ksi_build    one lane per key of the set: ksi_insert with atomics; counts the occupied slots (= distinct 64-byte keys)
-//                  and keeps the longest probe distance of a stored entry
+//   k_ksi_build    one lane per key of a range of the set (all of it at creation, the new keys at s2k_keyset_append):
+//                  ksi_insert with atomics; counts the occupied slots (= distinct 64-byte keys) and keeps the longest probe
+//                  distance of a stored entry, both going on from what earlier ranges left in `info`
 //   k_ksi_lookup   one lane per looked-up key, read with the caller's stride: 64 bytes (X || Y), 32 (X) or 33 (SEC1
 //                  compressed: prefix || X, resolved without a square root - ksi_lookup33), or 32 bytes of X among the set's
 //                  valid keys only (S2K_KSI_X_VALID: ksi_lookup32v, the lookup of s2k_schnorr_verify_batch_keyset_bykey)
@@ -12,12 +13,12 @@
 namespace {
 
 __global__ void __launch_bounds__(256)
-k_ksi_build(uint32_t nkeys, ksi_table t, uint32_t* __restrict__ info) {
+k_ksi_build(uint32_t first, uint32_t count, ksi_table t, uint32_t* __restrict__ info) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   bool fresh = false;
   uint32_t d = 0;
-  if (i < nkeys) {
-    d = ksi_insert<ksi_dev_mem>(t, i, &fresh);
+  if (i < count) {
+    d = ksi_insert<ksi_dev_mem>(t, first + i, &fresh);
     if (d == KSI_NONE) {
       atomicOr(&info[S2K_KSI_FAILED], 1u);
       d = 0;
@@ -85,13 +86,15 @@ k_ksi_lookup(uint32_t n, const uint8_t* __restrict__ q, size_t stride, bool wide
 }
 }  // namespace
 
-// slots: 2^log2_slots entries, all KSI_EMPTY; info: S2K_KSI_INFO_WORDS words, all zero (both set by the caller on `st`)
-__attribute__((visibility("hidden"))) int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t nkeys,
+// inserts the keys first .. first + count - 1 of the set.  first = 0: slots (2^log2_slots entries) all KSI_EMPTY and info
+// (S2K_KSI_INFO_WORDS words) all zero, both set by the caller on `st`; first > 0: the table holds the keys below `first`
+__attribute__((visibility("hidden"))) int s2k_internal_ksi_build(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_keys, size_t first, size_t count,
                                                                  uint64_t* slots, uint32_t log2_slots, uint64_t seed, uint32_t* info) {
-  if (nkeys == 0 || nkeys > KSI_MAX_KEYS || log2_slots > KSI_MAX_LOG2 || ((uint64_t)1 << log2_slots) <= nkeys)
+  const size_t nkeys = first + count;
+  if (count == 0 || nkeys > KSI_MAX_KEYS || log2_slots > KSI_MAX_LOG2 || ((uint64_t)1 << log2_slots) <= nkeys)
     return fail(ctx, S2K_ERR_ARG, "key-set index of %zu keys in 2^%u slots", nkeys, log2_slots);
   const ksi_table t = {slots, (uint32_t)(((uint64_t)1 << log2_slots) - 1), seed, set_keys};
-  k_ksi_build<<<blocks_for(nkeys), 256, 0, st>>>((uint32_t)nkeys, t, info);
+  k_ksi_build<<<blocks_for(count), 256, 0, st>>>((uint32_t)first, (uint32_t)count, t, info);
   HIP_TRY(ctx, hipGetLastError());
   return S2K_OK;
 }
