@@ -376,6 +376,37 @@ bool s2k_internal_host_pinned(const void* p, size_t bytes);
 bool s2k_internal_small_call(const s2k_ctx* ctx, size_t n, uint32_t flags);
 int s2k_internal_small_block(s2k_ctx* ctx, const size_t* sizes, int count, uint8_t** host, uint8_t** dev);
 
+// Staging around a device form, for the host-pointer entry points that move their arrays whole (engine.hip).  A part is one
+// array: `reserve` bytes of the context's staging buffer, of which `bytes` come from `src` before the device form runs (an
+// input; nothing is copied for a null src or no bytes) or go to `dst` after it (a result).  `run` enqueues the device form on
+// the staged pointers d[0 .. count) and the stream it is given, for the context it is given.
+//   s2k_internal_staged_call    synchronous.  small: the page-locked block of s2k_internal_small_block, memcpy both ways, no
+//                               DMA; else copies, phase guard of `phase_bytes` and device form on s_comp, then the wait
+//   s2k_internal_staged_submit  the ticket form: a slot for n verdicts to `valid`, the copies in on the child's s_copy,
+//                               chained by ev_copied[0] into its s_comp; the result part lands in the slot's landing buffer
+// A device form that fails after copies were enqueued leaves the context drained (s2k_internal_drain) on every route.
+struct stage_part {
+  const void* src;
+  void* dst;
+  size_t bytes, reserve;
+};
+inline stage_part stage_in(const void* src, size_t bytes) { return {src, nullptr, bytes, bytes}; }
+inline stage_part stage_in(const void* src, size_t bytes, size_t reserve) { return {src, nullptr, bytes, reserve}; }
+inline stage_part stage_out(void* dst, size_t bytes) { return {nullptr, dst, bytes, bytes}; }
+constexpr int STAGE_MAX_PARTS = 6;
+class stage_run {      // a reference to the caller's lambda int(s2k_ctx* c, uint8_t* const* d, hipStream_t st), good for the call it is passed to
+  const void* f_;
+  int (*call_)(const void*, s2k_ctx*, uint8_t* const*, hipStream_t);
+
+ public:
+  template <class F>
+  stage_run(const F& f) : f_(&f), call_([](const void* p, s2k_ctx* c, uint8_t* const* d, hipStream_t st) { return (*static_cast<const F*>(p))(c, d, st); }) {}
+  int operator()(s2k_ctx* c, uint8_t* const* d, hipStream_t st) const { return call_(f_, c, d, st); }
+};
+int s2k_internal_staged_call(s2k_ctx* ctx, const stage_part* parts, int count, size_t phase_bytes, bool small, const stage_run& run);
+int s2k_internal_staged_submit(s2k_ctx* ctx, size_t n, uint8_t* valid, const stage_part* parts, int count, const stage_run& run,
+                               s2k_ticket* ticket);
+
 // Synchronous host-pointer entry points are transfer, kernels, answer in series.  Two verifiers (two contexts on two host
 // threads) that take whole batches alternately could hide one's transfer behind the other's kernels, but left alone they fall
 // into lock step - both copy, then both compute.  So the PHASES of such calls take turns per device: one call's transfer in,
@@ -575,6 +606,20 @@ int s2k_internal_key_reserve32(s2k_ctx* ctx, size_t n);
 // (chunks: the geometry of the set's tables, KS_CHUNKS - also what the joint layouts are built from - or KC_TEETH, a comb set)
 // (cap: the capacity the set's buffers are laid out for, s2k_keyset_capacity; first, count: a range of its keys; nkeys: its live keys)
 size_t s2k_internal_keyset_bytes(size_t cap, size_t off[5], int chunks = KS_CHUNKS);
+// the sections of a set's buffer, laid out for its capacity (the only reader of those five offsets besides the byte total)
+struct keyset_view {
+  uint8_t* keys;         // X || Y, 64 bytes per key
+  uint4* tables;         // the 32-chunk or comb tables: KS_SLOTS or KC_SLOTS entries of 128 bytes per key
+  uint8_t* valid;        // one byte per key: it is a public key (rows past the live keys: 0)
+  uint32_t* rep;         // the identity 0 .. cap - 1 (what key_groups::trep is for a set: table t is the key of "signature" t)
+  uint32_t* counters;    // KG_COUNTERS words: scratch of the table builds
+};
+inline keyset_view s2k_internal_keyset_view(const uint8_t* base, size_t cap, int chunks = KS_CHUNKS) {
+  size_t off[5];
+  (void)s2k_internal_keyset_bytes(cap, off, chunks);
+  uint8_t* b = const_cast<uint8_t*>(base);      // (a caller that holds the set const only reads through the view)
+  return {b + off[0], (uint4*)(b + off[1]), b + off[2], (uint32_t*)(b + off[3]), (uint32_t*)(b + off[4])};
+}
 int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t cap, size_t first, size_t count, hipStream_t st, int chunks = KS_CHUNKS);
 int s2k_internal_keyset_identity(s2k_ctx* ctx, uint8_t* base, size_t cap, hipStream_t st, int chunks = KS_CHUNKS);
 int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first, size_t count, uint4* joint, hipStream_t st);   // from the 32-chunk tables
@@ -607,8 +652,7 @@ int s2k_internal_ksi_lookup(s2k_ctx* ctx, hipStream_t st, const uint8_t* set_key
 //                                null, or the key indices of the n signatures already resolved (0xFFFFFFFF: not in the set;
 //                                the lookup launch is skipped) - ctx->ks_found, reserved and filled by the caller on `st`
 struct s2k_bykey_view {
-  const uint8_t* keys;        // the set's keys, 64 bytes each
-  const uint8_t* key_valid;   // one byte per key (s2k_keyset_valid_keys)
+  keyset_view set;            // the set's buffer: the probe reads `keys` and `valid`
   uint64_t* slots;            // the index
   uint32_t log2_slots;
   uint64_t seed;
@@ -617,6 +661,48 @@ int s2k_internal_bykey_view(s2k_ctx* ctx, const s2k_keyset* ks, uint32_t flags, 
 bool s2k_internal_bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags);
 int s2k_internal_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig, const void* d_r,
                               const void* d_s, uint32_t flags, void* d_valid, hipStream_t st, const uint32_t* d_found);
+
+// ---- engine.hip, for the key-set flows (keyset.hip): ladder modes, the lane workspace, stage-timing marks and launchers ----
+enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_ECDSA_KEYED = 4, MODE_ECDSA_LEFT = 5,
+       MODE_SCHNORR_KEYED = 6, MODE_SCHNORR_LEFT = 7, MODE_ECDSA_KEYSET = 8, MODE_ECDSA_KEYSET_JOINT = 9,
+       MODE_ECDSA_KEYSET_JOINT5 = 10, MODE_ECDSA_KEYSET_JOINT6 = 11,
+       // BIP-340 over a key set's tables, same four layouts: the ECDSA mode + 4
+       MODE_SCHNORR_KEYSET = 12, MODE_SCHNORR_KEYSET_JOINT = 13, MODE_SCHNORR_KEYSET_JOINT5 = 14, MODE_SCHNORR_KEYSET_JOINT6 = 15,
+       // MODE_ECDSA_KEYED over the key's COMB table (kc_geom): 38 additions and 18 doublings.  New modes go at the end:
+       // tools/isa_count.py finds the kernels by this number
+       MODE_ECDSA_COMB = 16,
+       // MODE_SCHNORR_KEYED over the comb table (the lifted x-only keys of a call, or the X || Y keys of a comb key set)
+       MODE_SCHNORR_COMB = 17 };
+constexpr uint32_t KVF_FORCE_WORKLIST = 0x80000000u;   // top bit of k_verify_fast's first argument (batches are below 2^31)
+constexpr int FIN_M = 16;                              // lanes per thread of k_affine_finish: its T argument is ceil(n / FIN_M)
+// The planes of ctx->ws for a batch of n (layout: WS_* in engine.hip; lane_ws_of), after s2k_internal_ensure_ws(ctx, n).
+struct lane_ws {
+  uint32_t *qt, *fin, *prep, *gp, *pref, *smont, *wl_count, *wl;
+  size_t stride;
+};
+extern "C" int s2k_internal_ensure_ws(s2k_ctx* ctx, size_t n);
+lane_ws lane_ws_of(const s2k_ctx* ctx, size_t n);
+void prof_mark(s2k_ctx* ctx, hipStream_t st, int slot);       // s2k_ctx_profile: event `slot` of the call's six, on st
+uint32_t prep_lanes(size_t n);                                // lanes of k_scalar_prep for n signatures
+void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t count, uint32_t lanes, const uint8_t* dig, const uint8_t* r,
+                        const uint8_t* s, const uint8_t* recid, uint32_t flags);
+void launch_generator_part(const s2k_ctx* ctx, hipStream_t st, const lane_ws& w, uint32_t first, uint32_t end);
+void launch_ladder(const s2k_ctx* ctx, hipStream_t st, int mode, size_t n, uint32_t kvf, const uint8_t* pub, const uint8_t* rsig, const lane_ws& w,
+                   uint8_t* out, uint8_t* out_pts, uint64_t* clk, const key_groups& kg);
+void launch_affine_finish(hipStream_t st, int mode, size_t n, uint32_t T, const uint8_t* rsig, const lane_ws& w, uint8_t* out, uint8_t* out_pts);
+void launch_verify_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
+                            const uint8_t* s, uint32_t flags, uint8_t* out);
+void launch_verify_fallback_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* keys, const uint32_t* kidx,
+                                   const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out);
+void launch_schnorr_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
+                         uint32_t msg_len);
+void launch_schnorr_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
+                             const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out);
+void launch_verify_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
+                              const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out);
+void launch_schnorr_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
+                               const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
+                               uint32_t msg_len, uint8_t* out);
 
 struct dev_buf {
   void* p = nullptr;

@@ -570,7 +570,7 @@ static int encoded_keyset_enqueue(s2k_ctx* ctx, const s2k_keyset* ks, const s2k_
   HIP_TRY(ctx, hipMemcpyAsync(io + o_po, pub_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_do, dig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_so, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
-  const pe_keyset pk = {{kv.slots, (uint32_t)(((uint64_t)1 << kv.log2_slots) - 1), kv.seed, kv.keys}, kv.key_valid, (uint32_t*)ctx->ks_found,
+  const pe_keyset pk = {{kv.slots, (uint32_t)(((uint64_t)1 << kv.log2_slots) - 1), kv.seed, kv.set.keys}, kv.set.valid, (uint32_t*)ctx->ks_found,
                         (uint32_t*)(io + o_list), ctx->ek_ctr};
   int k = 0;
   for (size_t lo = 0; lo < n; lo += chunk, ++k) {

@@ -1564,41 +1564,39 @@ __attribute__((visibility("hidden"))) size_t s2k_internal_keyset_bytes(size_t n,
   off[4] = off[3] + al(n * 4);
   return off[4] + al(KG_COUNTERS * 4);
 }
-// builds the tables of the keys first .. first + count - 1 (already on the device, at base + off[0]) of a set laid out for cap
+// builds the tables of the keys first .. first + count - 1 (already on the device, in the view's `keys`) of a set laid out for cap
 // keys.  first = 0: the set's creation, which also fills the identity array for the whole capacity and clears the validity
 // bytes of the rows no key has yet; first > 0: an append (s2k_keyset_append) - the table kernels see a "set" of count keys
 // that starts at key `first`: keys, tables and validity moved there, the identity read from 0 (tinfo then starts at any byte
 // address: k_key_chain writes it, and everything else reads it, a byte at a time)
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_build(s2k_ctx* ctx, uint8_t* base, size_t cap, size_t first, size_t count,
                                                                    hipStream_t st, int chunks) {
-  size_t off[5];
-  (void)s2k_internal_keyset_bytes(cap, off, chunks);
+  const keyset_view v = s2k_internal_keyset_view(base, cap, chunks);
   if (first + count > cap || count == 0) return fail(ctx, S2K_ERR_ARG, "internal: keys %zu + %zu of a set of %zu", first, count, cap);
   const size_t slots = chunks == KC_TEETH ? KC_SLOTS : KS_SLOTS;
   key_groups g{};
-  g.counters = (uint32_t*)(base + off[4]);
-  g.ktab = (const uint4*)(base + off[1]) + first * slots * 8;
-  g.tinfo = base + off[2] + first;
-  g.trep = (const uint32_t*)(base + off[3]);          // table t is the key of "signature" t: the identity
+  g.counters = v.counters;
+  g.ktab = v.tables + first * slots * 8;
+  g.tinfo = v.valid + first;
+  g.trep = v.rep;          // table t is the key of "signature" t: the identity
   g.max_tables = (uint32_t)count;
   g.chunks = chunks;
   g.key_bytes = 64;
   g.part = 0;
   g.nparts = 1;
   HIP_TRY(ctx, hipMemsetAsync(g.counters, 0, KG_COUNTERS * sizeof(uint32_t), st));
-  if (first == 0 && cap > count) HIP_TRY(ctx, hipMemsetAsync(base + off[2] + count, 0, cap - count, st));   // "no key": valid = 0
-  if (first == 0) k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, (uint32_t*)(base + off[3]), g.counters, (uint32_t)count);
-  else k_ks_iota<<<1, 256, 0, st>>>(0u, (uint32_t*)(base + off[3]), g.counters, (uint32_t)count);
+  if (first == 0 && cap > count) HIP_TRY(ctx, hipMemsetAsync(v.valid + count, 0, cap - count, st));   // "no key": valid = 0
+  if (first == 0) k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, v.rep, g.counters, (uint32_t)count);
+  else k_ks_iota<<<1, 256, 0, st>>>(0u, v.rep, g.counters, (uint32_t)count);
   HIP_TRY(ctx, hipGetLastError());
-  int rc = s2k_internal_key_chains(ctx, base + off[0] + first * 64, st, &g);
+  int rc = s2k_internal_key_chains(ctx, v.keys + first * 64, st, &g);
   if (rc) return rc;
   return s2k_internal_key_tables(ctx, st, &g, 0, 1, nullptr);
 }
 // the identity array of a set laid out for cap keys, alone: for buffers a set moves into (s2k_keyset_reserve)
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_identity(s2k_ctx* ctx, uint8_t* base, size_t cap, hipStream_t st, int chunks) {
-  size_t off[5];
-  (void)s2k_internal_keyset_bytes(cap, off, chunks);
-  k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, (uint32_t*)(base + off[3]), (uint32_t*)(base + off[4]), 0u);
+  const keyset_view v = s2k_internal_keyset_view(base, cap, chunks);
+  k_ks_iota<<<blocks_for(cap), 256, 0, st>>>((uint32_t)cap, v.rep, v.counters, 0u);
   HIP_TRY(ctx, hipGetLastError());
   return S2K_OK;
 }
@@ -1606,9 +1604,8 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_identity(s2k_ctx* 
 // (same stream, behind them)
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first,
                                                                          size_t count, uint4* joint, hipStream_t st) {
-  size_t off[5];
-  (void)s2k_internal_keyset_bytes(cap, off);
-  k_ks_joint<<<(unsigned)((count * KS_CHUNKS + 63) / 64), 64, 0, st>>>((uint32_t)count, (const uint4*)(base + off[1]) + first * (KS_SLOTS * 8),
+  const uint4* ktab = s2k_internal_keyset_view(base, cap).tables;
+  k_ks_joint<<<(unsigned)((count * KS_CHUNKS + 63) / 64), 64, 0, st>>>((uint32_t)count, ktab + first * (KS_SLOTS * 8),
                                                                        joint + first * KJ_KEY_QUADS);
   HIP_TRY(ctx, hipGetLastError());
   return S2K_OK;
@@ -1638,9 +1635,7 @@ static int keyset_build_joint_wide(s2k_ctx* ctx, const uint4* ktab, size_t n, ui
 // (keys first .. first + count - 1 of a set laid out for cap keys; scratch: s2k_internal_keyset_joint_scratch_bytes(count, w))
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size_t cap, size_t first,
                                                                               size_t count, int w, uint4* joint, uint4* scratch, hipStream_t st) {
-  size_t off[5];
-  (void)s2k_internal_keyset_bytes(cap, off);
-  const uint4* ktab = (const uint4*)(base + off[1]) + first * (KS_SLOTS * 8);
+  const uint4* ktab = s2k_internal_keyset_view(base, cap).tables + first * (KS_SLOTS * 8);
   if (w == 5) return keyset_build_joint_wide<5>(ctx, ktab, count, joint + first * kjw_geom<5>::KEY_QUADS, scratch, st);
   if (w == 6) return keyset_build_joint_wide<6>(ctx, ktab, count, joint + first * kjw_geom<6>::KEY_QUADS, scratch, st);
   return fail(ctx, S2K_ERR_ARG, "joint tables of digit width %d", w);
@@ -1657,8 +1652,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_reserve(s2k_ctx* c
 // costs a call nothing
 __attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t cap, size_t nkeys, size_t n,
                                                                    const uint32_t* d_kidx, hipStream_t st, key_groups* out, int chunks) {
-  size_t off[5];
-  (void)s2k_internal_keyset_bytes(cap, off, chunks);
+  const keyset_view v = s2k_internal_keyset_view(set_base, cap, chunks);
   int rc = s2k_internal_keyset_reserve(ctx, nkeys, n);   // (a no-op when the caller has reserved already)
   if (rc) return rc;
   const size_t np = (n + 63) & ~(size_t)63, kp = (nkeys + 63) & ~(size_t)63;
@@ -1679,17 +1673,17 @@ __attribute__((visibility("hidden"))) int s2k_internal_keyset_sort(s2k_ctx* ctx,
   k_ks_alloc<<<(unsigned)((nkeys + 256 * ALLOC_ITEMS - 1) / (256 * ALLOC_ITEMS)), 256, 0, st>>>((uint32_t)nkeys, cnt, base, counters);
   HIP_TRY(ctx, hipGetLastError());
   k_key_place<<<(unsigned)((n + 256 * PLACE_ITEMS - 1) / (256 * PLACE_ITEMS)), 256, 0, st>>>(
-      (uint32_t)n, slot_of, pos_of, base, false, (const uint32_t*)(set_base + off[3]), perm, ptab, left, counters);
+      (uint32_t)n, slot_of, pos_of, base, false, v.rep, perm, ptab, left, counters);
   HIP_TRY(ctx, hipGetLastError());
   *out = key_groups{};
   out->counters = counters;
   out->perm = perm;
   out->ptab = ptab;
   out->left = left;
-  out->ktab = (const uint4*)(set_base + off[1]);
+  out->ktab = v.tables;
   out->jtab = nullptr;
-  out->tinfo = set_base + off[2];
-  out->trep = (const uint32_t*)(set_base + off[3]);
+  out->tinfo = v.valid;
+  out->trep = v.rep;
   out->max_tables = (uint32_t)nkeys;
   out->chunks = chunks;
   out->key_bytes = 64;
