@@ -186,11 +186,7 @@ S2K_DEV pt29 dsm_complete29(const sc& u1, const sc& u2, const fe29& qx, const fe
   return acc;
 }
 
-// A worklist entry of the ECDSA flows is the signature's index, plus (batches below 2^30) a tag in the top bits:
-// WL_DOUBLE_GEN = the fast ladder found u2 Q == u1 G, both finite, in its final addition: R = 2 u1 G;
-// WL_DOUBLE_LAST = the plain ladder (generator part inside the kernel) found its sum equal to the last generator-table
-// entry it was about to add: R = 2 T_last[top digit of u1].
-constexpr uint32_t WL_TAG_LIMIT = 1u << 30, WL_INDEX_MASK = WL_TAG_LIMIT - 1u, WL_DOUBLE_GEN = 1u << 30, WL_DOUBLE_LAST = 2u << 30;
+// (the tags of a worklist entry, WL_*: engine_internal.h)
 
 // (`key`: the 64 bytes X || Y of the signature's public key)
 S2K_DEV uint8_t verify_complete29(size_t idx, const uint8_t* __restrict__ key, const uint8_t* __restrict__ dig,
@@ -316,7 +312,7 @@ k_verify_fallback_keyset(const uint32_t* __restrict__ wl_count, const uint32_t* 
 #endif
 constexpr int PREP_M = S2K_PREP_M;
 constexpr int PREP_WORDS = 17;
-enum { PF_OK = 1, PF_NEG1 = 2, PF_NEG2 = 4, PF_K1_B128 = 8, PF_K2_B128 = 16 };   // bit 128 of the odd half-scalars
+// (the flag word's bits, PF_*: engine_internal.h)
 
 S2K_DEV void ws_store_sc26(uint32_t* __restrict__ base, size_t stride, size_t i, const sc26& v) {
 #pragma unroll
@@ -467,12 +463,7 @@ S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const ui
 #ifndef S2K_JOINT_WAVES
 #define S2K_JOINT_WAVES 3
 #endif
-// The comb ladder: 145 VGPRs and three waves since a column adds its two entries to each other first; 4 here spills
-// (128 VGPRs, 23 spilled, 64 B scratch) and was timed no faster than the two-addition column it replaced.
-#ifndef S2K_COMB_WAVES
-#define S2K_COMB_WAVES 3
-#endif
-constexpr uint8_t VERDICT_PENDING = 2;   // k_verify_fast -> k_affine_finish
+// (the comb ladders' bound, S2K_COMB_WAVES, and VERDICT_PENDING: engine_internal.h)
 
 // Digits of an odd half scalar k < 2^129 in the order the per-key ladder consumes them.  As in
 // ds_init, digit i is nib_i = bits 4i+1 .. 4i+4 of k (signed value 2 nib_i - 15); digit i = 4c + j
@@ -2326,6 +2317,22 @@ __attribute__((visibility("hidden"))) void launch_ladder(const s2k_ctx* ctx, hip
     k_verify_fast<M><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count, \
                                                     w.wl, w.stride, out_pts, clk, kg);                                             \
     break;
+  // The comb ladders run in a kernel of their own that needs no lead point (comb_ladder.hip: k_verify_comb, same arguments);
+  // S2K_COMB_LEAD=1 brings back k_verify_fast<MODE_.._COMB>, =0 the new kernel where the build's default is the old one -
+  // read at every call, as S2K_KEY_FINISH_COMB is, so that a process can switch for A/B runs and for the tests that compare
+  // the two.  profiles/r20_comb_nolead_ab.txt.
+  if (mode == MODE_ECDSA_COMB || mode == MODE_SCHNORR_COMB) {
+    const char* lead = getenv("S2K_COMB_LEAD");
+    if (!(lead && *lead ? atoi(lead) != 0 : S2K_COMB_LEAD_DEFAULT != 0)) {
+      if (mode == MODE_ECDSA_COMB)
+        k_verify_comb<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count,
+                                                            w.wl, w.stride, out_pts, clk, kg);
+      else
+        k_verify_comb<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count,
+                                                           w.wl, w.stride, out_pts, clk, kg);
+      return;
+    }
+  }
   switch (mode) {
     S2K_LADDER(MODE_ECDSA)
     S2K_LADDER(MODE_SCHNORR)
@@ -2598,7 +2605,7 @@ const char* s2k_version(void) { return "secp256k1_voi_amd 0.4 (gfx950)"; }
 const char* s2k_build_config(void) {
   return "GT_BITS=" S2K_STR(S2K_GT_BITS) " GT_BITS_FIRST=" S2K_STR(S2K_GT_BITS_FIRST) " PREP_M=" S2K_STR(S2K_PREP_M)
          " QT_PACK=" S2K_STR(S2K_QT_PACK) " FAST_WAVES=" S2K_STR(S2K_FAST_WAVES) " STRIDE_PAD=" S2K_STR(S2K_STRIDE_PAD)
-         " ROW_MAX=" S2K_STR(S2K_ROW_MAX_DEFAULT) " QUAD_MAX=" S2K_STR(S2K_QUAD_MAX_DEFAULT)
+         " ROW_MAX=" S2K_STR(S2K_ROW_MAX_DEFAULT) " QUAD_MAX=" S2K_STR(S2K_QUAD_MAX_DEFAULT) " COMB_LEAD=" S2K_STR(S2K_COMB_LEAD_DEFAULT)
          " flags=[" S2K_BUILD_FLAGS "]";
 }
 const char* s2k_last_error(const s2k_ctx* ctx) { return ctx ? ctx->err : g_err; }

@@ -527,6 +527,9 @@ static_assert(KT_SLOTS == 72 && KT_W_SLOT == 9 && kt_geom<32>::SLOTS == 288, "ta
 // select +-E[idx], E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t, B_t = 2^(19 t) Q (the sign is the top tooth's; a negative top
 // tooth complements idx): 19 additions and 18 doublings per half, the doublings shared by the two halves - 38 additions and
 // 18 doublings per signature from the same 64 entries + lead pair (L + phi(L), L - phi(L), L = 2^115 Q) the window tables hold.
+// The default ladder, k_verify_comb (comb_ladder.hip), takes the lead as a digit instead - a' = a | 2^(L-1), the top tooth's
+// bit 18: sum_{i<L} (2 a'_i - 1) 2^i = k with no 2^L in front - and reads the 64 entries only; the lead pair stays in the table
+// for k_verify_fast<MODE_.._COMB> (S2K_COMB_LEAD=1).
 struct kc_geom {
   static constexpr int TEETH = 7, SPACING = 19, LEN = TEETH * SPACING;
   static constexpr int LEAD_LOG2 = LEN - SPACING + 1;   // 115: the ladder's 18 doublings make the lead 2^133 Q
@@ -674,6 +677,25 @@ enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_
        // MODE_SCHNORR_KEYED over the comb table (the lifted x-only keys of a call, or the X || Y keys of a comb key set)
        MODE_SCHNORR_COMB = 17 };
 constexpr uint32_t KVF_FORCE_WORKLIST = 0x80000000u;   // top bit of k_verify_fast's first argument (batches are below 2^31)
+// what the ladder kernels of engine.hip and comb_ladder.hip share:
+// the flag word of a signature's prepared scalars (k_scalar_prep, plane 16)
+enum { PF_OK = 1, PF_NEG1 = 2, PF_NEG2 = 4, PF_K1_B128 = 8, PF_K2_B128 = 16 };   // bit 128 of the odd half-scalars
+// A worklist entry of the ECDSA flows is the signature's index, plus (batches below 2^30) a tag in the top bits:
+// WL_DOUBLE_GEN = the fast ladder found u2 Q == u1 G, both finite, in its final addition: R = 2 u1 G;
+// WL_DOUBLE_LAST = the plain ladder (generator part inside the kernel) found its sum equal to the last generator-table
+// entry it was about to add: R = 2 T_last[top digit of u1].
+constexpr uint32_t WL_TAG_LIMIT = 1u << 30, WL_INDEX_MASK = WL_TAG_LIMIT - 1u, WL_DOUBLE_GEN = 1u << 30, WL_DOUBLE_LAST = 2u << 30;
+// The comb ladders: 145 VGPRs and three waves since a column adds its two entries to each other first; 4 here spills
+// (128 VGPRs, 23 spilled, 64 B scratch) and was timed no faster than the two-addition column it replaced.
+#ifndef S2K_COMB_WAVES
+#define S2K_COMB_WAVES 3
+#endif
+// Which kernel runs the comb ladders when S2K_COMB_LEAD is not set: 0 = k_verify_comb (comb_ladder.hip: no lead point, the
+// first round is one pair sum), 1 = k_verify_fast<MODE_.._COMB> (engine.hip).  s2k_build_config() names it.
+#ifndef S2K_COMB_LEAD_DEFAULT
+#define S2K_COMB_LEAD_DEFAULT 0
+#endif
+constexpr uint8_t VERDICT_PENDING = 2;   // a ladder kernel -> k_affine_finish
 constexpr int FIN_M = 16;                              // lanes per thread of k_affine_finish: its T argument is ceil(n / FIN_M)
 // The planes of ctx->ws for a batch of n (layout: WS_* in engine.hip; lane_ws_of), after s2k_internal_ensure_ws(ctx, n).
 struct lane_ws {
@@ -689,6 +711,13 @@ void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t c
 void launch_generator_part(const s2k_ctx* ctx, hipStream_t st, const lane_ws& w, uint32_t first, uint32_t end);
 void launch_ladder(const s2k_ctx* ctx, hipStream_t st, int mode, size_t n, uint32_t kvf, const uint8_t* pub, const uint8_t* rsig, const lane_ws& w,
                    uint8_t* out, uint8_t* out_pts, uint64_t* clk, const key_groups& kg);
+// comb_ladder.hip: the comb ladders without the lead point (the arguments of k_verify_fast); instantiated there for
+// false (ECDSA) and true (BIP-340), launched by launch_ladder alone
+template <bool SCHNORR>
+__global__ void k_verify_comb(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig,
+                              const uint32_t* __restrict__ prep, uint32_t* __restrict__ qt, uint32_t* __restrict__ fin, gt_view gt,
+                              uint8_t* __restrict__ out, uint32_t* __restrict__ wl_count, uint32_t* __restrict__ wl, size_t stride,
+                              uint8_t* __restrict__ out_pts, uint64_t* __restrict__ clk, key_groups kg);
 void launch_affine_finish(hipStream_t st, int mode, size_t n, uint32_t T, const uint8_t* rsig, const lane_ws& w, uint8_t* out, uint8_t* out_pts);
 void launch_verify_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
                             const uint8_t* s, uint32_t flags, uint8_t* out);

@@ -23,7 +23,7 @@
 //                  isomorphic by W; beta*x column
 //   k_key_chain<XONLY, KC_TEETH> / k_key_finish_comb_once   what an ECDSA or BIP-340 call builds instead by default, and a comb key set once: the same 64 entries per key
 //                  arranged as a signed 7-tooth comb (kc_geom), 7 bits of a half scalar per table addition - 38 additions and
-//                  18 doublings per signature (k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>); further down, beside kc_sets.  The finish kernel
+//                  18 doublings per signature (comb_ladder.hip: k_verify_comb, 37 and 18; k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>); further down, beside kc_sets.  The finish kernel
 //                  forms every cofactor before the first addition and writes each entry once; k_key_finish_comb, which parks
 //                  the sums in memory and fetches them back, stays behind S2K_KEY_FINISH_COMB=park (the same bytes)
 //
@@ -1277,7 +1277,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_group(s2k_ctx* ctx, s
   out->tinfo = tinfo;
   out->trep = trep;
   out->max_tables = (uint32_t)max_tables;
-  // ECDSA and BIP-340 verification calls: comb tables (k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>) unless the
+  // ECDSA and BIP-340 verification calls: comb tables (k_verify_comb; k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>) unless the
   // context asks for the window path; S2K_KEY_TABLES_SPLIT (the three kernels of the chunk tables, read at every call)
   // implies it
   const char* split = getenv("S2K_KEY_TABLES_SPLIT");

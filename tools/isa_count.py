@@ -16,6 +16,8 @@ those of the source:
   k_verify_fast<ECDSA_COMB>   round loop 19: a column (two additions, the entries added to each other first), the exit test,
                               the doubling (18)
   k_verify_fast<SCHNORR_KEYED> / <SCHNORR_COMB>   the BIP-340 ladders over the same tables: the loops of ECDSA_KEYED / ECDSA_COMB
+  k_verify_comb<false> / <true>   the comb ladders without the lead point (comb_ladder.hip; the default of ECDSA and BIP-340 calls): the
+                              first round peeled in front of the loop, round loop 18: the doubling, then a column (18 / 18)
   k_verify_row                table 7 | 32 windows x (doubling loop 4, two additions) | generator part GT_WINDOWS      (a wave per signature)
   k_verify_row_keyset / k_schnorr_row_keyset   chunk loop 32 (two additions each) | generator part GT_WINDOWS      (the same over a key set)
 
@@ -76,6 +78,14 @@ def disassemble(lib, mangled_prefix):
         raise RuntimeError("kernel %s* not found in %s" % (mangled_prefix, lib))
     finally:
         subprocess.run(["rm", "-rf", tmp])
+
+
+def has_kernel(lib, mangled_prefix):
+    try:
+        disassemble(lib, mangled_prefix)
+        return True
+    except RuntimeError:
+        return False
 
 
 class Cfg:
@@ -295,6 +305,30 @@ def comb(lib, mode=16, name="ECDSA_COMB"):
             "valu_per_trip": {"doubling": g.valu_in(dbl), "addition": column // 2, "column": column}, "instructions": len(g.ins)}
 
 
+def comb_nolead(lib, schnorr=False):
+    """k_verify_comb<false> (ECDSA) or <true> (BIP-340), comb_ladder.hip: the comb ladder without the lead point.  The first
+    round is peeled (one pair sum, straight-line code in front of the loop); the round loop runs 18 times with no loop inside
+    and no exit in its middle - the doubling, then the column - so every block of it weighs 18.  No branch stands between
+    the doubling and the column (the compiler interleaves them): valu_per_trip["round"] is the whole trip, ["column"] what is
+    left of it after the doubling of k_verify_fast<.._COMB> of the same library (the same inlined function), ["addition"]
+    half of that, as comb() reports it."""
+    g = Cfg(disassemble(lib, "_Z13k_verify_combILb%dEE" % (1 if schnorr else 0)))
+    name = "k_verify_comb<%s>" % ("true" if schnorr else "false")
+    top = g.top_level()
+    assert len(top) == 1, ("unexpected loop structure of " + name, [g.loops[k]["entries"] for k in top])
+    assert not g.children(top[0]), ("unexpected loops inside the round loop", g.children(top[0]))
+    rnd = g.loops[top[0]]["blocks"]
+    w = g.weights({top[0]: 18})
+    assert {w[b] for b in rnd} == {18}, ("trip weights of the round loop are not 18 / 18", sorted({w[b] for b in rnd}))
+    trip = g.valu_in(rnd)
+    dbl = comb(lib, 17 if schnorr else 16)["valu_per_trip"]["doubling"]
+    assert 3200 < trip < 4500, "the round (doubling and column) is not where it was looked for"
+    valu, mad = g.count(w)
+    return {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad,
+            "valu_per_trip": {"round": trip, "doubling": dbl, "column": trip - dbl, "addition": (trip - dbl) // 2},
+            "loop_trips": {"column": 18, "doubling": 18}, "instructions": len(g.ins)}
+
+
 def keyset(lib):
     """k_verify_fast<ECDSA_KEYSET>: the ladder over a key set's 32-chunk tables - one chunk loop (32) around the addition loop (2)"""
     g = Cfg(disassemble(lib, "_Z13k_verify_fastILi8EE"))
@@ -402,13 +436,17 @@ def generator_windows(lib):
 def static_counts(lib=DEFAULT_LIB, gt_windows=None):
     if gt_windows is None:
         gt_windows = generator_windows(lib)
-    return {"k_verify_fast": general(lib, gt_windows), "k_verify_fast_keyed": keyed(lib), "k_verify_fast_comb": comb(lib),
+    out = {"k_verify_fast": general(lib, gt_windows), "k_verify_fast_keyed": keyed(lib), "k_verify_fast_comb": comb(lib),
             "k_verify_fast_keyset": keyset(lib),
             "k_verify_fast_keyset_joint": keyset_joint(lib), "k_verify_fast_keyset_joint5": keyset_joint_wide(lib, 5),
             "k_verify_fast_keyset_joint6": keyset_joint_wide(lib, 6),
             "k_verify_fast_schnorr_keyed": keyed(lib, 6, "SCHNORR_KEYED"), "k_verify_fast_schnorr_comb": comb(lib, 17, "SCHNORR_COMB"),
             "k_verify_row": row_general(lib, gt_windows), "k_verify_row_keyset": row_keyset(lib, False, gt_windows),
             "k_schnorr_row_keyset": row_keyset(lib, True, gt_windows)}
+    if has_kernel(lib, "_Z13k_verify_combILb0EE"):      # (a library of before comb_ladder.hip, given for an A/B, has none)
+        out["k_verify_comb"] = comb_nolead(lib)
+        out["k_verify_comb_schnorr"] = comb_nolead(lib, True)
+    return out
 
 
 if __name__ == "__main__":
