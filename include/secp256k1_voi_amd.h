@@ -212,7 +212,8 @@ int s2k_ctx_last_keyed_ladder(s2k_ctx *ctx);
  * stats[0] signatures verified from per-key tables, [1] tables built, [2] signatures through the
  * general kernel, [3] signatures re-done by the complete-formula kernel.  All zero after a call that took the ladders of
  * small or mid-size batches (s2k_ctx_set_small_batch_max / s2k_ctx_set_mid_batch_max) and after a key-set call that took the
- * row ladder (s2k_ctx_set_keyset_small_batch_max): they neither group nor have a worklist. */
+ * row ladder (s2k_ctx_set_keyset_small_batch_max, s2k_ctx_set_keyset_comb_small_batch_max): they neither group nor have a
+ * worklist. */
 int s2k_ctx_key_grouping_stats(s2k_ctx *ctx, uint32_t stats[4]);
 /* State of S2K_KEYS_ADAPTIVE, without synchronising: out[0] consecutive observed calls that found no group, [1] calls
  * still to be verified without looking, [2] calls verified without looking so far, [3] calls that looked again after a
@@ -500,13 +501,23 @@ int s2k_ctx_set_mid_batch_max(s2k_ctx *ctx, uint32_t max_n);
  * table of the signature's key (k_verify_row_keyset / k_schnorr_row_keyset: 64 complete additions on the key's isomorphic
  * curve - b3 = 21 W^6 is a per-key field element there, pt29r_add_b3 -, then the generator part), instead of the chain of
  * launches and the lane-per-signature ladder of larger calls.  Sets of layout S2K_KEYSET_CHUNKS, JOINT, JOINT5 and JOINT6
- * take it (all keep the chunk table); S2K_KEYSET_COMB sets keep the lane-per-signature path at every size, as do calls with
- * S2K_ECDSA_FORCE_WORKLIST.  Same verdicts (tests/test_gpu_keyset_row.py). */
+ * take it (all keep the chunk table); S2K_KEYSET_COMB sets have a threshold of their own (below); calls with
+ * S2K_ECDSA_FORCE_WORKLIST keep the lane-per-signature path.  Same verdicts (tests/test_gpu_keyset_row.py). */
 int s2k_ctx_set_keyset_small_batch_max(s2k_ctx *ctx, uint32_t max_n);
+/* Small calls over a COMB key set, opt-in.  The same calls over an S2K_KEYSET_COMB set of up to max_n signatures (default 0 =
+ * never: such calls keep the lane-per-signature path unless the caller asks) run ONE launch with a wavefront per signature
+ * over the comb table of the signature's key (k_verify_row_comb / k_schnorr_row_comb).  A comb entry (x, y), affine on the
+ * key's isomorphic curve, is the projective point (x W : y : W^3) of secp256k1 - one product layer for the two entries of a
+ * column -, so the ladder runs on secp256k1 itself with no per-key constant: 37 complete additions, 18 doublings and 19
+ * conversions, 166 product layers against the chunk table's 257, then the generator part.  The by-index calls only; calls
+ * with S2K_ECDSA_FORCE_WORKLIST keep the lane-per-signature path.  Same verdicts (tests/test_gpu_keyset_comb_row.py). */
+int s2k_ctx_set_keyset_comb_small_batch_max(s2k_ctx *ctx, uint32_t max_n);
 /* What the last key-set verification call of the context enqueued: S2K_KEYSET_LADDER_LANE (a lane per signature),
- * S2K_KEYSET_LADDER_ROW (a wavefront per signature), -1 before any.  No synchronisation. */
+ * S2K_KEYSET_LADDER_ROW (a wavefront per signature on a chunk table), S2K_KEYSET_LADDER_ROW_COMB (a wavefront per signature
+ * on a comb table), -1 before any.  No synchronisation. */
 #define S2K_KEYSET_LADDER_LANE 0
 #define S2K_KEYSET_LADDER_ROW 1
+#define S2K_KEYSET_LADDER_ROW_COMB 2
 int s2k_ctx_last_keyset_ladder(s2k_ctx *ctx);
 /* Times of a ticket on the device's clock, for placement diagnostics (s2k_group_member_stats_ex): after
  * s2k_ctx_ticket_timing(ctx, 1) every submitted ticket records three moments on the device's clock: t0 = its first host-to-device
@@ -574,6 +585,7 @@ int s2k_group_set_key_grouping(s2k_group *g, int mode, uint32_t min_group, uint3
 int s2k_group_set_small_batch_max(s2k_group *g, uint32_t max_n);   /* s2k_ctx_set_small_batch_max on every member (a member's shard is what counts as the batch) */
 int s2k_group_set_mid_batch_max(s2k_group *g, uint32_t max_n);     /* s2k_ctx_set_mid_batch_max on every member */
 int s2k_group_set_keyset_small_batch_max(s2k_group *g, uint32_t max_n);   /* s2k_ctx_set_keyset_small_batch_max on every member */
+int s2k_group_set_keyset_comb_small_batch_max(s2k_group *g, uint32_t max_n);   /* s2k_ctx_set_keyset_comb_small_batch_max on every member */
 int s2k_group_ecdsa_verify_batch(s2k_group *g, size_t n, const uint8_t *pub_xy, const uint8_t *digest32, const uint8_t *r,
                                  const uint8_t *s, uint32_t flags, uint8_t *valid);
 int s2k_group_ecdsa_verify_batch_submit(s2k_group *g, size_t n, const uint8_t *pub_xy, const uint8_t *digest32,
@@ -1103,7 +1115,13 @@ enum {
    * (in[5], in[6]) affine with x1 != x2, in their lazy forms (one unit each), s1 = -1 when bit 0 of in[7] is set, s2 = -1 when
    * its bit 1 is (in[7] NULL: both +1).  out, out2 = affine x, y; flag = 0 when Z3 = 0 (E1 = +-E2, acc = +-(s1 E1 + s2 E2),
    * Z = 0).  reps == 0: once; reps >= 1: `reps` times the column with one jpt29_double behind it, as the ladder runs them. */
-  S2K_HP_JADD_PAIR
+  S2K_HP_JADD_PAIR,
+  /* a round of the wave-per-signature comb ladder (engine.hip: row_ladder_comb), through s2k_fp_op_batch_ex with the operands
+   * of PT29R_ADD_B3: Q = (d, e) is moved to y^2 = x^3 + 7 c^6 as there and comes back as the projective point (x c : y : c^3)
+   * of secp256k1 (fe29r.h: pt29r_pair_from_iso, both halves of the layer in turn); the accumulator starts at P = (a, b) and
+   * each repetition is acc = pt29r_add(pt29r_double(acc), Q): 2^reps P + (2^reps - 1) Q.  out, out2, flag, bit 0 of `lazy`
+   * and the repetition count as PT29R_ADD. */
+  S2K_HP_PT29R_COMB_STEP
 };
 int s2k_fp_op_batch_ex(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, size_t n, const uint8_t *const in[5],
                        uint8_t *out, uint8_t *out2, uint8_t *flag);

@@ -55,8 +55,8 @@ KEYSET_AUTO, KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6, KEYSET_C
  HP_FER_MUL, HP_FER_MUL_PLUS, HP_FER_MUL_ADD_MUL, HP_FER_SMALL, HP_PT29R_DBL, HP_PT29R_ADD, HP_FER_SWAPS,
  HP_SC26_MUL, HP_SC26_SQR, HP_SC26_TO_MONT, HP_SC26_TO_SC, HP_SC26_INV, HP_SC26_CHAIN,
  HP_SC_MONTMUL, HP_SC_TO_MONT, HP_SC_MONT_INV, HP_SC_ADD, HP_SC_NEG, HP_SC_REDUCE_ONCE, HP_SC_GT_HALF_N,
- HP_AFF_DBL, HP_AFF_ADD, HP_XYZZ_ADD_FIRST, HP_PT29R_ADD_B3, HP_JADD_PAIR) = range(52)
-KEYSET_LADDER_LANE, KEYSET_LADDER_ROW = 0, 1                     # s2k_ctx_last_keyset_ladder
+ HP_AFF_DBL, HP_AFF_ADD, HP_XYZZ_ADD_FIRST, HP_PT29R_ADD_B3, HP_JADD_PAIR, HP_PT29R_COMB_STEP) = range(53)
+KEYSET_LADDER_LANE, KEYSET_LADDER_ROW, KEYSET_LADDER_ROW_COMB = 0, 1, 2                  # s2k_ctx_last_keyset_ladder
 H2C_SSWU_RO, H2C_SSWU_NU = 0, 1        # s2k_hash_to_curve_batch: hash_to_curve (random oracle) / encode_to_curve (non-uniform)
 
 IDENTITY = bytes(65)
@@ -302,6 +302,7 @@ def load_library() -> C.CDLL:
     lib.s2k_group_set_small_batch_max.argtypes = [vp, u32]
     lib.s2k_group_set_mid_batch_max.argtypes = [vp, u32]
     lib.s2k_group_set_keyset_small_batch_max.argtypes = [vp, u32]
+    lib.s2k_group_set_keyset_comb_small_batch_max.argtypes = [vp, u32]
     lib.s2k_group_schnorr_batch_verify_rlc.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
     lib.s2k_group_multi_scalar_mult.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_group_keyset_create.argtypes = [vp, sz, vp, ci, vp]
@@ -416,6 +417,7 @@ def load_library() -> C.CDLL:
     lib.s2k_ctx_set_small_batch_max.argtypes = [vp, u32]
     lib.s2k_ctx_set_mid_batch_max.argtypes = [vp, u32]
     lib.s2k_ctx_set_keyset_small_batch_max.argtypes = [vp, u32]
+    lib.s2k_ctx_set_keyset_comb_small_batch_max.argtypes = [vp, u32]
     lib.s2k_ctx_last_keyset_ladder.argtypes = [vp]
     lib.s2k_ctx_create_ex.argtypes = [ci, ci, u32, C.POINTER(vp)]
     lib.s2k_set_generator_table_budget.argtypes = [sz]
@@ -478,6 +480,7 @@ EXPORTED_SYMBOLS = [
     "s2k_ctx_set_small_batch_max", "s2k_ctx_set_mid_batch_max", "s2k_ctx_create_ex", "s2k_set_generator_table_budget", "s2k_set_table_memory_budgets", "s2k_ctx_gt_info", "s2k_ctx_gt_note", "s2k_ctx_gt_wait",
     "s2k_group_create_ex", "s2k_debug_gt_swap_in_call",
     "s2k_ctx_set_keyset_small_batch_max", "s2k_ctx_last_keyset_ladder", "s2k_group_set_keyset_small_batch_max",
+    "s2k_ctx_set_keyset_comb_small_batch_max", "s2k_group_set_keyset_comb_small_batch_max",
     "s2k_ct_point_add", "s2k_ct_point_double", "s2k_ct_point_subtract", "s2k_ct_point_negate", "s2k_ct_point_conditional_negate",
     "s2k_ct_point_conditional_select", "s2k_ct_point_equal", "s2k_ct_point_is_identity", "s2k_ct_point_is_y_odd",
     "s2k_ct_scalar_op", "s2k_ct_scalar_conditional_select", "s2k_ct_scalar_conditional_negate", "s2k_ct_scalar_predicate",
@@ -1398,11 +1401,16 @@ class Engine(_TicketOwner):
 
     def set_keyset_small_batch_max(self, max_n: int):
         """key-set calls of up to max_n signatures take the wave-per-signature ladder over the set's tables
-        (s2k_ctx_set_keyset_small_batch_max; 0: never; comb sets never do)"""
+        (s2k_ctx_set_keyset_small_batch_max; 0: never; comb sets: set_keyset_comb_small_batch_max)"""
         self._check(self._lib.s2k_ctx_set_keyset_small_batch_max(self._h, int(max_n)))
 
+    def set_keyset_comb_small_batch_max(self, max_n: int):
+        """by-index calls over a KEYSET_COMB set of up to max_n signatures take the wave-per-signature ladder over the set's comb
+        tables (s2k_ctx_set_keyset_comb_small_batch_max; 0, what a new engine starts with: never)"""
+        self._check(self._lib.s2k_ctx_set_keyset_comb_small_batch_max(self._h, int(max_n)))
+
     def last_keyset_ladder(self) -> int:
-        """KEYSET_LADDER_LANE / KEYSET_LADDER_ROW: what the last key-set verification call enqueued; -1 before any."""
+        """KEYSET_LADDER_LANE / KEYSET_LADDER_ROW / KEYSET_LADDER_ROW_COMB: what the last key-set verification call enqueued; -1 before any."""
         return int(self._lib.s2k_ctx_last_keyset_ladder(self._h))
 
     def last_keyed_ladder(self) -> int:
@@ -1724,6 +1732,9 @@ class Group(_TicketOwner):
 
     def set_keyset_small_batch_max(self, max_n: int):
         self._check(self._lib.s2k_group_set_keyset_small_batch_max(self._h, int(max_n)))
+
+    def set_keyset_comb_small_batch_max(self, max_n: int):
+        self._check(self._lib.s2k_group_set_keyset_comb_small_batch_max(self._h, int(max_n)))
 
     def gt_wait(self) -> int:
         """block until every member's device has its wide generator tables (s2k_group_gt_wait); the smallest width in use"""

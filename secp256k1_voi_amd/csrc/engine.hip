@@ -405,7 +405,9 @@ __attribute__((visibility("hidden"))) uint32_t prep_lanes(size_t n) {
   return (uint32_t)(shared > wide ? shared : wide);
 }
 // The same for ONE signature, its own inversion, the result in 17 words (u1 | k1 | k2 | flags: the planes' layout): the
-// preparation wave of the wave-per-signature kernels (k_verify_row, k_recover_row).
+// preparation wave of the wave-per-signature kernels (k_verify_row, k_recover_row).  FLAT: the scalar products and the
+// inversion are expanded in place (sc26.h), which leaves the kernel without a private segment.
+template <bool FLAT = false>
 S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig,
                              const uint8_t* __restrict__ recid, uint32_t flags, uint32_t* __restrict__ out17) {
   sc x;
@@ -414,7 +416,17 @@ S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const ui
     x = sc_zero();
     x.v[0] = 1;
   }
-  const sc26 s_inv_m = sc26_mont_inv(sc26_to_mont(sc26_from_sc(x)));     // x^-1 * R
+  struct ops {
+    static S2K_DEV sc26 mm(const sc26& a, const sc26& b) {
+      if constexpr (FLAT) return sc26_montmul(a, b);
+      else return sc26_mm(a, b);
+    }
+    static S2K_DEV sc26 inv_of(const sc26& a) {           // a -> a^-1 * R
+      if constexpr (FLAT) return sc26_mont_inv_flat(sc26_to_mont_flat(a));
+      else return sc26_mont_inv(sc26_to_mont(a));
+    }
+  };
+  const sc26 s_inv_m = ops::inv_of(sc26_from_sc(x));     // x^-1 * R
   sc r, s;
   uint32_t e_raw[8];
   load_be32(r.v, rsig + i * 32);
@@ -428,11 +440,11 @@ S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const ui
   if (recid) {
     rid = recid[i];
     ok = ok && rid < 4 && (!(rid & 2u) || u256_lt(r.v, FE_P_MINUS_N));     // RecoverPoint (point_s11n.go:245-282)
-    u1 = sc26_to_sc(sc26_mm(sc26_from_sc(sc_neg(e)), s_inv_m));   // -e / r
-    u2 = sc26_to_sc(sc26_mm(sc26_from_sc(s), s_inv_m));           //  s / r
+    u1 = sc26_to_sc(ops::mm(sc26_from_sc(sc_neg(e)), s_inv_m));   // -e / r
+    u2 = sc26_to_sc(ops::mm(sc26_from_sc(s), s_inv_m));           //  s / r
   } else {
-    u1 = sc26_to_sc(sc26_mm(sc26_from_sc(e), s_inv_m));
-    u2 = sc26_to_sc(sc26_mm(sc26_from_sc(r), s_inv_m));
+    u1 = sc26_to_sc(ops::mm(sc26_from_sc(e), s_inv_m));
+    u2 = sc26_to_sc(ops::mm(sc26_from_sc(r), s_inv_m));
   }
   sc k1, k2;
   bool neg1, neg2;
@@ -1449,6 +1461,164 @@ k_verify_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kid
   if (lane == 0) out[sig] = verdict;
 }
 
+// ---- small calls over a COMB key set (S2K_KEYSET_COMB) ----
+// The comb's ladder doubles, and a doubling on the key's isomorphic curve would need the per-key constant as the addition
+// there does.  It is not run there: an affine entry (x, y) of y^2 = x^3 + 7 W^6 IS the projective point (x W : y : W^3) of
+// secp256k1 (pt29r_pair_from_iso, fe29r.h: one layer for the two entries of a column), and from then on the ladder is
+// pt29r_double and pt29r_add on secp256k1 itself - no b3, and no map back at the end.  37 additions of 3 layers, 18 doublings
+// of 2 and 19 conversions: 166 row-product layers on the key part, where row_ladder_keyset spends 64 x 4 + 1.
+// The key's W (one unit: a product's output) and W^3, formed once per signature
+struct row_comb_iso {
+  fer w, w3;
+};
+S2K_DEV row_comb_iso row_comb_iso_of(const uint4* __restrict__ kt, const fer_consts& k) {
+  row_comb_iso r;
+  r.w = ke_row_load(kt + (size_t)kc_geom::WENT * 8, kc_geom::W, k);
+  r.w3 = fer_mul(fer_mul(r.w, r.w, k), r.w, k);
+  return r;
+}
+// u * G + (+-k1) * Q + (+-k2) * lambda(Q), Q the key of the comb table kt (kc_geom): u | k1 | k2 | flags in the 17 words `p`
+// (LDS), the recoding that of k_verify_comb (comb_ladder.hip) - a' = (k >> 1) | 2^132 per half, tooth t its bits 19 t ..
+// 19 t + 18, column j the 7-bit index whose top bit is the sign; the LEAD slots are not read.  Column 18 starts the
+// accumulator as the sum of its two entries; rounds 17..0 double, add E1, add phi(E2).  `flip` changes both signs (BIP-340
+// over a key stored with odd Y).  Teeth, indices, signs and addresses are wave-uniform; the result is projective.
+S2K_DEV pt29r row_ladder_comb(const uint4* __restrict__ kt, fer w, fer w3, const uint32_t* p, bool flip, gt_view gt, const fer_consts& k) {
+  using G = kc_geom;
+  const fer one = k.j == 0 ? 1u : 0u;
+  const uint32_t pf = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[16]);
+  const bool neg1 = ((pf & PF_NEG1) != 0) != flip, neg2 = ((pf & PF_NEG2) != 0) != flip;
+  uint32_t t1[G::TEETH], t2[G::TEETH];
+  {
+    uint32_t k1[5], k2[5];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      k1[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[8 + i]);
+      k2[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[12 + i]);
+    }
+    k1[4] = (pf & PF_K1_B128) ? 1u : 0u;
+    k2[4] = (pf & PF_K2_B128) ? 1u : 0u;
+#pragma unroll
+    for (int t = 0; t < G::TEETH; ++t) {
+      const int bit = G::SPACING * t + 1, limb = bit >> 5, sh = bit & 31;      // (+ 1: a = k >> 1)
+      uint32_t v1 = k1[limb] >> sh, v2 = k2[limb] >> sh;
+      if (sh > 32 - G::SPACING) {
+        v1 |= k1[limb + 1] << (32 - sh);
+        v2 |= k2[limb + 1] << (32 - sh);
+      }
+      t1[t] = v1 & ((1u << G::SPACING) - 1u);
+      t2[t] = v2 & ((1u << G::SPACING) - 1u);
+    }
+    t1[G::TEETH - 1] |= 1u << (G::SPACING - 1);                                 // a' = a | 2^132: the lead, as a digit
+    t2[G::TEETH - 1] |= 1u << (G::SPACING - 1);
+  }
+  struct column {       // the two entries of a column as loaded: x of E1, beta x of E2, their y and whether each is negated
+    fer x1, y1, x2, y2;
+    bool n1, n2;
+  };
+  auto fetch = [&](int j) -> column {
+    uint32_t w1 = 0, w2 = 0;
+#pragma unroll
+    for (int t = 0; t < G::TEETH; ++t) {
+      w1 |= ((t1[t] >> j) & 1u) << t;
+      w2 |= ((t2[t] >> j) & 1u) << t;
+    }
+    const bool top1 = (w1 & 64u) != 0, top2 = (w2 & 64u) != 0;
+    const uint4 *e1 = kt + (size_t)((top1 ? w1 : ~w1) & 63u) * 8, *e2 = kt + (size_t)((top2 ? w2 : ~w2) & 63u) * 8;
+    column c;
+    c.x1 = ke_row_load(e1, 0u, k);
+    c.y1 = ke_row_load(e1, 1u, k);
+    c.x2 = ke_row_load(e2, 2u, k);
+    c.y2 = ke_row_load(e2, 1u, k);
+    c.n1 = neg1 != !top1;
+    c.n2 = neg2 != !top2;
+    return c;
+  };
+  auto entries = [&](const column& c, pt29r& e1, pt29r& e2) {
+    pt29r_pair_from_iso(c.x1, c.n1 ? fer_negate(c.y1, 1, k) : c.y1, c.x2, c.n2 ? fer_negate(c.y2, 1, k) : c.y2, w, w3, e1, e2, k);   // y [2]
+  };
+  column nx = fetch(G::SPACING - 1);
+  pt29r acc, e1, e2;
+  {
+    const column c = nx;
+    nx = fetch(G::SPACING - 2);                                     // in flight during the addition
+    entries(c, e1, e2);
+    acc = pt29r_add(e1, e2, k);
+  }
+#pragma unroll 1
+  for (int j = G::SPACING - 2; j >= 0; --j) {
+    const column c = nx;
+    if (j > 0) nx = fetch(j - 1);                                   // in flight during the round
+    acc = pt29r_double(acc, k);
+    entries(c, e1, e2);
+    acc = pt29r_add(acc, e1, k);
+    acc = pt29r_add(acc, e2, k);
+  }
+  uint32_t u[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) u[i] = p[i];
+  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
+#pragma unroll 1
+  for (uint32_t i = 0; i < gt.windows; ++i) {
+    pt29r q;
+    q.x = fer_from_words(g.x.v, k);
+    q.y = fer_from_words(g.y.v, k);
+    q.z = one;
+    if (i + 1 < gt.windows) g = gt_load(gt, i + 1, gt_next_digit(u, gt.bits));   // in flight during the addition
+    acc = pt29r_add(acc, q, k);
+  }
+  return acc;
+}
+
+// k_verify_row_keyset over a comb set: same block, same validity rules, the table stride is the comb's
+__global__ void __launch_bounds__(320)
+k_verify_row_comb(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint4* __restrict__ ktab,
+                  const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
+                  const uint8_t* __restrict__ ssig, uint32_t flags, gt_view gt, uint8_t* __restrict__ out) {
+  __shared__ uint32_t prep_s[4][20];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (wave == 4) {                                              // the preparation wave (nothing called: no private segment)
+    const uint32_t i = blockIdx.x * 4 + lane;
+    if (lane < 4 && i < n) scalar_prep_one<true>(i, dig, rsig, ssig, nullptr, flags, prep_s[lane]);
+    __syncthreads();
+    return;
+  }
+  const uint32_t sig = blockIdx.x * 4 + wave;
+  const fer_consts k = fer_setup(lane);
+  bool ok = false;
+  const uint4* kt = ktab;
+  row_comb_iso iso = {0u, 0u};
+  if (sig < n) {
+    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
+    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
+    if (ok) {                                                   // (wave-uniform)
+      kt = ktab + (size_t)key * (KC_SLOTS * 8);
+      iso = row_comb_iso_of(kt, k);
+    }
+  }
+  __syncthreads();
+  if (sig >= n) return;
+  const uint32_t* p = prep_s[wave];
+  if (!(ok && (p[16] & PF_OK))) {
+    if (lane == 0) out[sig] = 0;
+    return;
+  }
+  const pt29r acc = row_ladder_comb(kt, iso.w, iso.w3, p, false, gt, k);
+  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
+  uint8_t verdict = 0;
+  if (!fer_is_zero(acc.z, k)) {
+    uint32_t rw[8];
+    load_be32(rw, rsig + (size_t)sig * 32);
+    bool match = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(rw, k), acc.z, k), 1, k)), k);
+    if (u256_lt(rw, FE_P_MINUS_N)) {
+      uint32_t r2[8];
+      u256_add(r2, rw, SC_N);
+      match = match || fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(r2, k), acc.z, k), 1, k)), k);
+    }
+    verdict = match ? 1 : 0;
+  }
+  if (lane == 0) out[sig] = verdict;
+}
+
 // FOUR LANES per signature (pt29q.h: a point is X | Y | Z | Z on the lanes of a quad, a layer of the complete formulas one lane
 // product): the ladders for calls between the wave-per-signature kernels and the lane-per-signature ones - a
 // doubling is 550 dependent instructions where a lane needs 1 070, so a lone wave is through its 16 signatures in half the
@@ -1712,7 +1882,8 @@ S2K_DEV void schnorr_msg(const uint8_t* __restrict__ msgs, const uint64_t* __res
 }
 // parseSchnorrSignature (schnorr.go:420-449): r < p, s < n, e = H(r || P || m) mod n.
 // Returns ok; s and e as plain scalars.
-// (pk_i: the 32 bytes of item i's x-only key, wherever they live)
+// (pk_i: the 32 bytes of item i's x-only key, wherever they live; FLAT: the hash expanded in place, sha256.h)
+template <bool FLAT = false>
 S2K_DEV bool schnorr_parse_key(size_t i, const uint8_t* __restrict__ pk_i, const uint8_t* __restrict__ sig,
                                const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
                                sc& s_out, sc& e_out) {
@@ -1730,7 +1901,8 @@ S2K_DEV bool schnorr_parse_key(size_t i, const uint8_t* __restrict__ pk_i, const
   const uint8_t* m;
   uint32_t len;
   schnorr_msg(msgs, offs, msg_len, i, m, len);
-  bip340_challenge(dg, r_be, pk_be, m, len);
+  if constexpr (FLAT) bip340_challenge_flat(dg, r_be, pk_be, m, len);
+  else bip340_challenge(dg, r_be, pk_be, m, len);
   uint32_t e_raw[8];
 #pragma unroll
   for (int w = 0; w < 8; ++w) e_raw[w] = dg[7 - w];
@@ -1914,6 +2086,84 @@ k_schnorr_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ ki
   ok = ok && (p[16] & PF_OK);
   pt29r acc = pt29r_identity(k);
   if (ok) acc = row_ladder_keyset(kt, iso, p, flip, gt, k);     // (wave-uniform)
+  __syncthreads();
+  if (sig >= n) return;
+  // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
+  uint8_t verdict = 0;
+  if (ok && yr_s[wave][15] && !fer_is_zero(acc.z, k)) {
+    uint32_t rw[8];
+    load_be32(rw, sig64 + (size_t)sig * 64);
+    const fer xR = fer_from_words(rw, k), yR = k.j <= 8 ? yr_s[wave][k.j] : 0u;
+    const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
+    const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
+    verdict = (mx && my) ? 1 : 0;
+  }
+  if (lane == 0) out[sig] = verdict;
+}
+
+// k_schnorr_row_keyset over a comb set (row_ladder_comb): the same six waves and the same two barriers
+__global__ void __launch_bounds__(384)
+k_schnorr_row_comb(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint8_t* __restrict__ set_keys,
+                   const uint4* __restrict__ ktab, const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ sig64,
+                   const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len, gt_view gt,
+                   uint8_t* __restrict__ out) {
+  __shared__ uint32_t prep_s[4][20];
+  __shared__ uint32_t yr_s[4][16];          // y_r of the block's signatures, limb j at word j; word 15: r is an x of the curve
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (wave == 4) {                                              // the preparation wave (nothing called: no private segment)
+    const uint32_t i = blockIdx.x * 4 + lane;
+    if (lane < 4 && i < n) {
+      const uint32_t key = kidx[i];
+      sc s, e;
+      const bool ok = schnorr_parse_key<true>(i, set_keys + (size_t)(key < nkeys ? key : 0u) * 64, sig64, msgs, offs, msg_len, s, e);   // (r < p, s < n)
+      sc k1, k2;
+      bool neg1, neg2;
+      sc_split_glv_odd(sc_neg(e), k1, neg1, k2, neg2);          // schnorr.go:244
+      uint32_t* o = prep_s[lane];
+#pragma unroll
+      for (int w = 0; w < 8; ++w) o[w] = s.v[w];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) o[8 + w] = k1.v[w];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) o[12 + w] = k2.v[w];
+      o[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
+    }
+    __syncthreads();
+    __syncthreads();
+    return;
+  }
+  const fer_consts k = fer_setup(lane);
+  if (wave == 5) {                                              // the lifting wave: row i takes r of the block's signature i
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 4 + k.row;
+    uint32_t rw[8];
+    load_be32(rw, sig64 + (size_t)(i < n ? i : n - 1) * 64);
+    const fer c = fer_curve_rhs(fer_from_words(rw, k), k);
+    const fer y = fer_sqrt_chain(c, k);
+    const bool is_root = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);     // (row by row)
+    const fer y_even = fer_norm(fer_is_odd(y, k) ? fer_negate(y, 1, k) : y, k);
+    yr_s[k.row][k.j] = k.j == 15 ? (is_root ? 1u : 0u) : y_even;
+    __syncthreads();
+    return;
+  }
+  const uint32_t sig = blockIdx.x * 4 + wave;
+  bool ok = false, flip = false;
+  const uint4* kt = ktab;
+  row_comb_iso iso = {0u, 0u};
+  if (sig < n) {
+    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
+    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
+    if (ok) {                                                   // (wave-uniform)
+      kt = ktab + (size_t)key * (KC_SLOTS * 8);
+      iso = row_comb_iso_of(kt, k);
+      flip = (set_keys[(size_t)key * 64 + 63] & 1u) != 0;       // BIP-340 multiplies lift_x(X): the point with even Y
+    }
+  }
+  __syncthreads();
+  const uint32_t* p = prep_s[wave];
+  ok = ok && (p[16] & PF_OK);
+  pt29r acc = pt29r_identity(k);
+  if (ok) acc = row_ladder_comb(kt, iso.w, iso.w3, p, flip, gt, k);     // (wave-uniform)
   __syncthreads();
   if (sig >= n) return;
   // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
@@ -2422,6 +2672,10 @@ __attribute__((visibility("hidden"))) void launch_verify_row_keyset(const s2k_ct
   k_verify_row_keyset<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, ktab, tinfo, dig, r, s, flags, ctx->gt_call,
                                                                out);
 }
+__attribute__((visibility("hidden"))) void launch_verify_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
+                                   const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
+  k_verify_row_comb<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, ktab, tinfo, dig, r, s, flags, ctx->gt_call, out);
+}
 static void launch_schnorr_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
                                const uint64_t* offs, uint32_t msg_len, const uint32_t* prep, size_t stride, uint8_t* out) {
   if (!prep)
@@ -2434,6 +2688,12 @@ __attribute__((visibility("hidden"))) void launch_schnorr_row_keyset(const s2k_c
                                       uint32_t msg_len, uint8_t* out) {
   k_schnorr_row_keyset<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, set_keys, ktab, tinfo, sig, msgs, offs,
                                                                 msg_len, ctx->gt_call, out);
+}
+__attribute__((visibility("hidden"))) void launch_schnorr_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
+                                    const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
+                                    uint32_t msg_len, uint8_t* out) {
+  k_schnorr_row_comb<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, set_keys, ktab, tinfo, sig, msgs, offs,
+                                                              msg_len, ctx->gt_call, out);
 }
 static void launch_recover_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
                                const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
@@ -3661,6 +3921,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_pipe_slot(s2k_ctx* ctx, s
   sl.ctx->kt_comb = ctx->kt_comb;
   sl.ctx->row_max = ctx->row_max;
   sl.ctx->ks_row_max = ctx->ks_row_max;
+  sl.ctx->ks_comb_row_max = ctx->ks_comb_row_max;
   sl.ctx->quad_max = ctx->quad_max;
   sl.direct = host_pinned(valid, n);
   if (!sl.direct && sl.h_valid_bytes < n) {
@@ -3850,10 +4111,16 @@ int s2k_ctx_set_small_batch_max(s2k_ctx* ctx, uint32_t max_n) {
 }
 // ECDSA batches above that and up to max_n take the four-lanes-per-signature ladder (k_verify_quad); 0 switches it off.
 // Key-set calls of up to max_n signatures take the wave-per-signature ladder over the set's tables (k_verify_row_keyset /
-// k_schnorr_row_keyset); 0 switches it off.  Comb sets never take it.
+// k_schnorr_row_keyset); 0 switches it off.  Comb sets have the threshold below.
 int s2k_ctx_set_keyset_small_batch_max(s2k_ctx* ctx, uint32_t max_n) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   ctx->ks_row_max = max_n;
+  return S2K_OK;
+}
+// ... and over a COMB set (k_verify_row_comb / k_schnorr_row_comb), a threshold of its own: 0, the default, is never
+int s2k_ctx_set_keyset_comb_small_batch_max(s2k_ctx* ctx, uint32_t max_n) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  ctx->ks_comb_row_max = max_n;
   return S2K_OK;
 }
 int s2k_ctx_set_mid_batch_max(s2k_ctx* ctx, uint32_t max_n) {

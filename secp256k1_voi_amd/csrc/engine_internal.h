@@ -167,6 +167,7 @@ struct s2k_ctx {
   uint32_t quad_max = S2K_QUAD_MAX_DEFAULT;   // ... and up to this many the four-lanes-per-signature ladder (s2k_ctx_set_mid_batch_max)
   uint32_t row_max = S2K_ROW_MAX_DEFAULT;   // batches of up to this many signatures take the wave-per-signature ladder (s2k_ctx_set_small_batch_max)
   uint32_t ks_row_max = S2K_KS_ROW_MAX_DEFAULT;   // key-set calls of up to this many signatures take the row ladder over the set's tables (s2k_ctx_set_keyset_small_batch_max)
+  uint32_t ks_comb_row_max = 0;      // ... and those over a COMB set of up to this many k_verify_row_comb / k_schnorr_row_comb (s2k_ctx_set_keyset_comb_small_batch_max; 0: never)
   int ks_last = -1;                  // S2K_KEYSET_LADDER_* of the last key-set verification call (-1: none yet)
   int kg_mode = S2K_KEYS_ADAPTIVE;
   uint32_t kg_min_group = 0, kg_hash_bits = 0, kg_max_tables = KG_MAX_TABLES_DEFAULT;
@@ -732,6 +733,11 @@ void launch_verify_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size
 void launch_schnorr_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
                                const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
                                uint32_t msg_len, uint8_t* out);
+void launch_verify_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
+                            const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out);
+void launch_schnorr_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
+                             const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
+                             uint32_t msg_len, uint8_t* out);
 
 struct dev_buf {
   void* p = nullptr;

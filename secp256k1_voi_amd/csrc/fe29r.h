@@ -311,5 +311,17 @@ S2K_DEV pt29r pt29r_from_iso(const pt29r& p, fer w, fer w3, const fer_consts& k)
   r.y = p.y;
   return r;
 }
+// The same map for AFFINE points of that curve, before the ladder instead of behind it: (x, y) -> (x W : y : W^3) is a
+// projective point of secp256k1 itself, and what is added to it needs no per-key constant (pt29r_add takes any q.z).  One
+// layer carries the two entries of a comb column: x1 W in rows 0, 1, x2 W in rows 2, 3; the y stay as they are (up to two
+// units: a negated entry's), W^3 is formed once per signature.
+S2K_DEV void pt29r_pair_from_iso(fer x1, fer y1, fer x2, fer y2, fer w, fer w3, pt29r& e1, pt29r& e2, const fer_consts& k) {
+  const fer M = fer_mul(fer_sel2(k, x1, x2), w, k);                          // x1 W | x1 W | x2 W | x2 W
+  fer_halves(M, e1.x, e2.x);
+  e1.y = y1;
+  e2.y = y2;
+  e1.z = w3;
+  e2.z = w3;
+}
 
 }  // namespace s2k

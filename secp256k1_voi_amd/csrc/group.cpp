@@ -382,6 +382,18 @@ int s2k_group_set_keyset_small_batch_max(s2k_group* g, uint32_t max_n) {
   }
   return S2K_OK;
 }
+// (weak for the same reason)
+extern "C" int s2k_ctx_set_keyset_comb_small_batch_max(s2k_ctx* ctx, uint32_t max_n) __attribute__((weak));
+int s2k_group_set_keyset_comb_small_batch_max(s2k_group* g, uint32_t max_n) {
+  if (!g) return S2K_ERR_ARG;
+  if (!s2k_ctx_set_keyset_comb_small_batch_max) return gfail(g, S2K_ERR_ARG, "contexts without s2k_ctx_set_keyset_comb_small_batch_max");
+  group_wait_idle(g);
+  for (member* me : g->members) {
+    const int rc = s2k_ctx_set_keyset_comb_small_batch_max(me->ctx, max_n);
+    if (rc) return gfail(g, rc, "%s", s2k_last_error(me->ctx));
+  }
+  return S2K_OK;
+}
 
 int s2k_group_set_mid_batch_max(s2k_group* g, uint32_t max_n) {
   if (!g) return S2K_ERR_ARG;

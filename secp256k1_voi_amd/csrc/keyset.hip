@@ -303,18 +303,20 @@ int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, siz
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
-  if (n <= ctx->ks_row_max && ks->chunks != KC_TEETH && !(flags & (S2K_ECDSA_FORCE_WORKLIST | S2K_ECDSA_FORCE_COMPLETE))) {
-    // small calls: a wave per signature over the set's 32-chunk tables (k_verify_row_keyset), one launch; nothing is sorted
+  const bool comb = ks->chunks == KC_TEETH;
+  if (n <= (comb ? ctx->ks_comb_row_max : ctx->ks_row_max) && !(flags & (S2K_ECDSA_FORCE_WORKLIST | S2K_ECDSA_FORCE_COMPLETE))) {
+    // small calls: a wave per signature over the set's 32-chunk tables (k_verify_row_keyset) or, where the caller asked for it
+    // (s2k_ctx_set_keyset_comb_small_batch_max), over a comb set's tables (k_verify_row_comb), one launch; nothing is sorted
     // and nothing is left for a worklist
     const keyset_view v = s2k_internal_keyset_view(ks->base, ks->cap, ks->chunks);
-    ctx->ks_last = S2K_KEYSET_LADDER_ROW;
+    ctx->ks_last = comb ? S2K_KEYSET_LADDER_ROW_COMB : S2K_KEYSET_LADDER_ROW;
     ctx->kg_counters = nullptr;
     ctx->last_wl_count = nullptr;
     prof_mark(ctx, st, 0);
     prof_mark(ctx, st, 1);
     prof_mark(ctx, st, 2);
-    launch_verify_row_keyset(ctx, st, n, ks->n, (const uint32_t*)d_key_index, v.tables, v.valid,
-                             (const uint8_t*)d_dig, (const uint8_t*)d_r, (const uint8_t*)d_s, flags, (uint8_t*)d_valid);
+    (comb ? launch_verify_row_comb : launch_verify_row_keyset)(ctx, st, n, ks->n, (const uint32_t*)d_key_index, v.tables, v.valid,
+                                                               (const uint8_t*)d_dig, (const uint8_t*)d_r, (const uint8_t*)d_s, flags, (uint8_t*)d_valid);
     HIP_TRY(ctx, hipGetLastError());
     prof_mark(ctx, st, 3);
     prof_mark(ctx, st, 4);
@@ -770,14 +772,16 @@ int s2k_schnorr_verify_batch_keyset_device(s2k_ctx* ctx, const s2k_keyset* ks, s
   hipStream_t st = (hipStream_t)hip_stream;
   int rc = ctx_enter(ctx, st);
   if (rc) return rc;
-  if (n <= ctx->ks_row_max && ks->chunks != KC_TEETH) {
-    // small calls: a wave per signature over the set's 32-chunk tables (k_schnorr_row_keyset), one launch
+  const bool comb = ks->chunks == KC_TEETH;
+  if (n <= (comb ? ctx->ks_comb_row_max : ctx->ks_row_max)) {
+    // small calls: a wave per signature over the set's 32-chunk tables (k_schnorr_row_keyset) or, where the caller asked for it,
+    // over a comb set's tables (k_schnorr_row_comb), one launch
     const keyset_view v = s2k_internal_keyset_view(ks->base, ks->cap, ks->chunks);
-    ctx->ks_last = S2K_KEYSET_LADDER_ROW;
+    ctx->ks_last = comb ? S2K_KEYSET_LADDER_ROW_COMB : S2K_KEYSET_LADDER_ROW;
     ctx->kg_counters = nullptr;
     ctx->last_wl_count = nullptr;
-    launch_schnorr_row_keyset(ctx, st, n, ks->n, (const uint32_t*)d_key_index, v.keys, v.tables, v.valid, (const uint8_t*)d_sig, (const uint8_t*)d_msgs, (const uint64_t*)d_msg_offsets,
-                              (uint32_t)msg_len, (uint8_t*)d_valid);
+    (comb ? launch_schnorr_row_comb : launch_schnorr_row_keyset)(ctx, st, n, ks->n, (const uint32_t*)d_key_index, v.keys, v.tables, v.valid, (const uint8_t*)d_sig,
+                                                                 (const uint8_t*)d_msgs, (const uint64_t*)d_msg_offsets, (uint32_t)msg_len, (uint8_t*)d_valid);
     HIP_TRY(ctx, hipGetLastError());
     return ctx_leave(ctx, st);
   }

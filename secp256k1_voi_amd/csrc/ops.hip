@@ -567,6 +567,8 @@ k_pt29q_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
 //   FER_MUL a*b | FER_MUL_PLUS a*b+c | FER_MUL_ADD_MUL a*b+c*d | FER_SMALL 21 a  (out = row 0's result, flag = the rows agree)
 //   PT29R_DBL / PT29R_ADD: chained `reps` times like the quad forms
 //   PT29R_ADD_B3: pt29r_add_b3 on y^2 = x^3 + 7 c^6 (c = W), P and Q moved there and the sum moved back
+//   PT29R_COMB_STEP: a round of row_ladder_comb (engine.hip), `reps` times: acc = pt29r_add(pt29r_double(acc), Q) from acc = P on
+//                 secp256k1, Q moved to y^2 = x^3 + 7 c^6 and brought back as (x c : y : c^3) by pt29r_pair_from_iso
 //   FER_SWAPS: out[0..255] = what v_permlane16_swap / v_permlane32_swap make of the lane numbers (n >= 8)
 __global__ void __launch_bounds__(256)
 k_pt29r_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
@@ -661,9 +663,26 @@ k_pt29r_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
     w3 = fer_from_fe29(cw3, k);
     b3 = fer_small_norm(fer_mul(w3, w3, k), 21u, k);
   }
+  pt29r e1 = pt29r_identity(k), e2 = e1;
+  if (op == S2K_HP_PT29R_COMB_STEP) {
+    // c is W: P = (a, b) stays on secp256k1, Q goes to y^2 = x^3 + 7 W^6 by (x W^2, y W^3) and comes back as the ladder's
+    // entries do - the layer's two halves carry the same Q here, e1 and e2 take turns
+    const fe29 cw2 = fe29_sqr(cn), cw3 = fe29_mul(cw2, cn);
+    p.x = fe29_normalize_weak(a);
+    p.y = fe29_normalize_weak(b);
+    p.z = fe29_one();
+    if (fe29_is_zero(a) && fe29_is_zero(b)) p = pt29_identity();
+    const fer qx = fer_from_fe29(fe29_mul(d, cw2), k), qy = fer_from_fe29(fe29_mul(e, cw3), k);
+    if (!(fe29_is_zero(d) && fe29_is_zero(e))) pt29r_pair_from_iso(qx, qy, qx, qy, fer_from_fe29(cn, k), fer_from_fe29(cw3, k), e1, e2, k);
+  }
   p.y = fe29_lazy_form(p.y, lazy & 1u);        // y may come with two units
   pt29r rc = pt29r_from(p, k);
   const pt29r sc_ = pt29r_from(s, k);
+  if (op == S2K_HP_PT29R_COMB_STEP) {
+#pragma unroll 1
+    for (uint32_t i = 0; i < reps; ++i) rc = pt29r_add(pt29r_double(rc, k), (i & 1u) ? e2 : e1, k);
+    reps = 0;
+  }
 #pragma unroll 1
   for (uint32_t i = 0; i < reps; ++i)
     rc = op == S2K_HP_PT29R_DBL ? pt29r_double(rc, k) : op == S2K_HP_PT29R_ADD_B3 ? pt29r_add_b3(rc, sc_, b3, k) : pt29r_add(rc, sc_, k);
@@ -946,7 +965,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   if (impl != S2K_IMPL_FAST) return fail(ctx, S2K_ERR_ARG, "s2k_fp_op_batch_ex serves S2K_IMPL_FAST only (8x32: s2k_fp_op_batch)");
   const uint32_t reps = lazy >> 20;           // quad / row forms, SC26_CHAIN, AFF_*: bits 20.. of `lazy` = how often the operation is chained (0: once)
   lazy &= 0xfffffu;
-  if (op < 0 || op > S2K_HP_PT29R_ADD_B3) return fail(ctx, S2K_ERR_ARG, "bad op");
+  if (op < 0 || (op > S2K_HP_PT29R_ADD_B3 && op != S2K_HP_PT29R_COMB_STEP)) return fail(ctx, S2K_ERR_ARG, "bad op");   // (JADD_PAIR: s2k_fp_op_batch_ex8)
   if (op == S2K_HP_FER_SWAPS && n < 8) return fail(ctx, S2K_ERR_ARG, "S2K_HP_FER_SWAPS writes 256 bytes: n >= 8");
   if (n == 0) return S2K_OK;
   if (!in || !in[0] || !out) return fail(ctx, S2K_ERR_ARG, "null buffer");
@@ -965,7 +984,7 @@ int s2k_fp_op_batch_ex(s2k_ctx* ctx, uint32_t impl, int op, uint32_t lazy, size_
   HIP_TRY(ctx, dout.alloc(n * 32));
   if (out2) HIP_TRY(ctx, dout2.alloc(n * 32));
   if (flag) HIP_TRY(ctx, dflag.alloc(n));
-  if ((op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS) || op == S2K_HP_PT29R_ADD_B3)
+  if ((op >= S2K_HP_FER_MUL && op <= S2K_HP_FER_SWAPS) || op == S2K_HP_PT29R_ADD_B3 || op == S2K_HP_PT29R_COMB_STEP)
     k_pt29r_op<<<blocks_for(64 * n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);
   else if (op == S2K_HP_AFF_DBL || op == S2K_HP_AFF_ADD)
     k_aff_op<<<blocks_for(n), 256>>>(op, lazy, (uint32_t)n, reps ? reps : 1u, args, (uint8_t*)dout.p, (uint8_t*)dout2.p, (uint8_t*)dflag.p);

@@ -74,5 +74,27 @@ __device__ __noinline__ sc26 sc26_mont_inv(sc26 x) {
   return sc26_mm(sc26_from_sc(sc_modinv(sc26_to_sc(x))), sc26_from_limbs(SC26_R3));
 #endif
 }
+// sc26_to_mont and sc26_mont_inv with nothing called: a call of sc26_mm hands its second operand over in private memory
+// (the 40-byte stores in front of each call), so a kernel that is to own no private segment (k_verify_row_comb,
+// k_schnorr_row_comb) takes a copy of the inversion's code instead.
+S2K_DEV sc26 sc26_to_mont_flat(const sc26& a) { return sc26_montmul(a, sc26_from_limbs(SC26_R2)); }
+S2K_DEV sc26 sc26_mont_inv_flat(const sc26& x) {
+#if S2K_SC_INV_FERMAT
+  struct ops {
+    static __device__ __forceinline__ sc26 mul(const sc26& a, const sc26& b) { return sc26_montmul(a, b); }
+    static __device__ __forceinline__ sc26 sqn(sc26 a, int n) {
+#pragma unroll 1
+      for (int i = 0; i < n; ++i) a = sc26_montsqr(a);
+      return a;
+    }
+  };
+  return sc_inv_chain<sc26, ops>(x);
+#else
+  const sc c = sc26_to_sc(x);
+  sc r;
+  mi_modinv_words<false>(r.v, c.v);
+  return sc26_montmul(sc26_from_sc(r), sc26_from_limbs(SC26_R3));
+#endif
+}
 
 }  // namespace s2k

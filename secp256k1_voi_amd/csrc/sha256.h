@@ -60,8 +60,9 @@ S2K_DEV void sha256_compress(uint32_t st[8], const uint32_t w_in[16]) {
 
 // digest (8 big-endian words) of tag-block || r || pk || msg[0..len)
 // r_be, pk_be: the 8 big-endian words of each 32-byte string, most significant first.
-__device__ __noinline__ void bip340_challenge(uint32_t out[8], const uint32_t r_be[8], const uint32_t pk_be[8],
-                                               const uint8_t* __restrict__ msg, uint32_t len) {
+// (_flat: expanded in place, for a kernel that is to own no private segment - the call hands the word arrays over in memory)
+S2K_DEV void bip340_challenge_flat(uint32_t out[8], const uint32_t r_be[8], const uint32_t pk_be[8],
+                                   const uint8_t* __restrict__ msg, uint32_t len) {
   uint32_t st[8], w[16];
 #pragma unroll
   for (int i = 0; i < 8; ++i) st[i] = BIP340_CHALLENGE_MIDSTATE[i];
@@ -95,6 +96,10 @@ __device__ __noinline__ void bip340_challenge(uint32_t out[8], const uint32_t r_
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) out[i] = st[i];
+}
+__device__ __noinline__ void bip340_challenge(uint32_t out[8], const uint32_t r_be[8], const uint32_t pk_be[8],
+                                               const uint8_t* __restrict__ msg, uint32_t len) {
+  bip340_challenge_flat(out, r_be, pk_be, msg, len);
 }
 
 }  // namespace s2k

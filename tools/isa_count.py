@@ -20,6 +20,8 @@ those of the source:
                               first round peeled in front of the loop, round loop 18: the doubling, then a column (18 / 18)
   k_verify_row                table 7 | 32 windows x (doubling loop 4, two additions) | generator part GT_WINDOWS      (a wave per signature)
   k_verify_row_keyset / k_schnorr_row_keyset   chunk loop 32 (two additions each) | generator part GT_WINDOWS      (the same over a key set)
+  k_verify_row_comb / k_schnorr_row_comb       column 18 in front of the loop | round loop 18 (a doubling, two additions) | generator part
+                              GT_WINDOWS      (the same over a comb key set)
 
 This is what ties the roofline's instruction counts (profiles/r04_valu_counts.json, PMC) to the binary that is measured:
 tests/test_counts_cpu.py recounts the built library and compares, bench.py recounts the library it loaded.
@@ -374,6 +376,34 @@ def _flat_weights(g, trips):
     return w
 
 
+def _reach(edges, seed):
+    """the blocks of `seed` and everything that follows them along `edges` (g.succ: after them, g.pred: before them)"""
+    seen, stack = set(seed), list(seed)
+    while stack:
+        for y in edges[stack.pop()]:
+            if y not in seen:
+                seen.add(y)
+                stack.append(y)
+    return seen
+
+
+def _dominators(g):
+    """block -> the set of blocks on every path from the entry to it (itself included); blocks the entry does not reach
+    (padding behind the end) keep the full set"""
+    nb = len(g.blocks)
+    dom = [set(range(nb)) for _ in range(nb)]
+    dom[0] = {0}
+    changed = True
+    while changed:
+        changed = False
+        for b in range(1, nb):
+            if g.pred[b]:
+                new = set.intersection(*(dom[q] for q in g.pred[b])) | {b}
+                if new != dom[b]:
+                    dom[b], changed = new, True
+    return dom
+
+
 def _mads_in(g, body):
     return sum(1 for b in body for i in range(*g.blocks[b]) if g.ins[i][1].startswith("v_mad_u64_u32"))
 
@@ -426,6 +456,58 @@ def row_keyset(lib, schnorr=False, gt_windows=None):
     return out
 
 
+def row_comb(lib, schnorr=False, gt_windows=None):
+    """k_verify_row_comb / k_schnorr_row_comb, a wave per signature over a key set's COMB table: column 18 - a conversion and
+    one addition - is straight-line code in front of the round loop, which runs 18 times with no loop inside (a doubling, the
+    conversion of the column's two entries, two additions: every block of it weighs 18), then gt_windows generator
+    additions.  BIP-340: the lifting wave's squaring runs are counted apart, as row_keyset() does.
+    These kernels call nothing (they own no private segment), so the PREPARATION wave's code is in their text where the
+    siblings call it.  It belongs to no signature wave and is counted apart, as the lifting wave's runs are: that wave's
+    blocks are those on a path through its one loop - the scalar inversion's 20 division-step batches with the step loop
+    inside (ECDSA), the message blocks of the challenge hash (BIP-340) - that no path joins with the round loop
+    (valu_prep_wave: its straight-line code, the scalar products and the hash's first block; valu_prep_loop: the loop, per
+    trip).  What the siblings' preparation wave keeps in the kernel's text (loads, argument set-up, the split) stays in
+    their sum."""
+    if gt_windows is None:
+        gt_windows = generator_windows(lib)
+    name = "k_schnorr_row_comb" if schnorr else "k_verify_row_comb"
+    g = Cfg(disassemble(lib, "_Z18k_schnorr_row_comb" if schnorr else "_Z17k_verify_row_comb"))
+    top = g.top_level()
+    assert len(top) == (15 if schnorr else 3) and not any(g.children(k) for k in top[:-1]), ("unexpected loop structure of " + name, [g.loops[k]["entries"] for k in top])
+    rnd, gen, sq, prep = top[0], top[1], top[2:-1], top[-1]
+    rb, gb, pb = g.loops[rnd]["blocks"], g.loops[gen]["blocks"], g.loops[prep]["blocks"]
+    # a round is a doubling, a conversion and two additions (2 + 1 + 2 x 3 layers), a window one addition; the preparation's
+    # loop holds no field product at all
+    assert _mads_in(g, rb) > 2 * _mads_in(g, gb) and all(len(g.loops[k]["blocks"]) == 1 and _mads_in(g, g.loops[k]["blocks"]) == 15 for k in sq) and \
+        _mads_in(g, pb) < 15, "cannot tell the loops of %s apart" % name
+    trips = {k: 0 for k in range(len(g.loops))}                     # (the preparation's loop and what is inside it)
+    assert all(k in top or set(g.loops[k]["blocks"]) <= set(pb) for k in trips), "a loop inside another than the preparation's"
+    trips.update({rnd: 18, gen: gt_windows})
+    w = _flat_weights(g, trips)
+    assert {w[b] for b in rb} == {18}, ("trip weights of the round loop are not 18", sorted({w[b] for b in rb}))
+
+    # The wave's branch is divergent to the compiler, so its region stands in line with the others' (entered with an empty
+    # mask by them): the blocks dominated by the outermost dominator of its loop from which no round loop can follow.
+    dom = _dominators(g)
+    before_rounds = _reach(g.pred, rb)
+    head = g.loops[prep]["entries"][0]
+    guards = [d for d in range(len(g.blocks)) if d in dom[head] and d not in before_rounds]
+    assert guards, "no block of %s dominates the preparation wave's loop alone" % name
+    guard = [d for d in guards if all(d in dom[x] for x in guards)][0]
+    prep_wave = {b for b in range(len(g.blocks)) if guard in dom[b]}
+    assert set(pb) <= prep_wave and not prep_wave & (set(rb) | set(gb) | set().union(*(g.loops[k]["blocks"] for k in sq), set())), \
+        "the preparation wave of %s is not apart from the other waves" % name
+    for b in prep_wave:
+        w[b] = 0
+    valu, mad = g.count(w)
+    out = {"valu_instr_static": valu, "mad_u64_u32_per_verify": mad, "key_additions": 37, "key_doublings": 18, "generator_additions": gt_windows,
+           "valu_per_trip": {"round": g.valu_in(rb), "generator": g.valu_in(gb)}, "loop_trips": {"round": 18}, "instructions": len(g.ins),
+           "valu_prep_wave": g.valu_in(prep_wave - set(pb)), "valu_prep_loop": g.valu_in(pb)}
+    if schnorr:
+        out["valu_lift_wave"] = sum(t * g.valu_in(g.loops[k]["blocks"]) for t, k in zip(SQRT_CHAIN_TRIPS, sq))
+    return out
+
+
 def generator_windows(lib):
     """ceil(256 / window bits) of THIS library (s2k_generator_window_bits: a host function, no GPU needed)"""
     import ctypes
@@ -446,6 +528,9 @@ def static_counts(lib=DEFAULT_LIB, gt_windows=None):
     if has_kernel(lib, "_Z13k_verify_combILb0EE"):      # (a library of before comb_ladder.hip, given for an A/B, has none)
         out["k_verify_comb"] = comb_nolead(lib)
         out["k_verify_comb_schnorr"] = comb_nolead(lib, True)
+    if has_kernel(lib, "_Z17k_verify_row_comb"):        # (likewise: a library of before the comb row ladder)
+        out["k_verify_row_comb"] = row_comb(lib, False, gt_windows)
+        out["k_schnorr_row_comb"] = row_comb(lib, True, gt_windows)
     return out
 
 
