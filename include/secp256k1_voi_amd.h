@@ -698,7 +698,12 @@ int s2k_is_valid_signature_encoding_bip0066(const uint8_t *sig_with_sighash, siz
  * the verification ladder (RecoverPublicKey, ecdsa.go:244-282) and compared with the supplied one on the device
  * (PublicKey.Equal: the serialised points, secec.go:121-129); RejectMalleable applies before the recovery (ecdsa.go:212).
  * s2k_ecdsa_verify_encoded_batch_submit: the same without the wait at the end (s2k_wait; see
- * s2k_ecdsa_verify_batch_submit). */
+ * s2k_ecdsa_verify_batch_submit).
+ * PRECONDITION on the three offset arrays, of this call, its _submit form and the two key-set forms below: offsets never
+ * decrease (off[i] <= off[i + 1] for every i < n), and off[n] is the size of the blob in bytes (off[0] need not be 0: the
+ * bytes before it are not read).  The calls do NOT verify this: no scan of the 3 (n + 1) offsets is made.  A decreasing
+ * offset makes an item's length, and the byte count of a workgroup's stretch, wrap around: the device then reads outside
+ * the blob.  The caller must check offsets that come from an untrusted source. */
 int s2k_ecdsa_verify_encoded_batch(s2k_ctx *ctx, size_t n, const uint8_t *pubs, const uint64_t *pub_off,
                                    const uint8_t *digests, const uint64_t *dig_off, const uint8_t *sigs,
                                    const uint64_t *sig_off, int encoding, size_t digest_len, uint32_t flags,
@@ -732,6 +737,29 @@ int s2k_ecdsa_verify_encoded_batch_keyset_submit(s2k_ctx *ctx, const s2k_keyset 
                                                  const uint8_t *sigs, const uint64_t *sig_off, int encoding, size_t digest_len,
                                                  uint32_t flags, uint8_t *valid, s2k_ticket *ticket);
 int s2k_ctx_last_encoded_keyset_stats(s2k_ctx *ctx, uint64_t out[4]);
+/* Test hooks for the parse step of the encoded calls (ingest.hip).
+ * s2k_debug_parse_encoded runs, for the piece [first, first + cnt) of a batch of n_total items, the kernels the encoded calls
+ * run in front of their ladders - through the same launch helpers -, and no ladder: ks NULL: k_parse_encoded; else (a set with
+ * an index, as s2k_ecdsa_verify_encoded_batch_keyset asks) k_parse_encoded_keyset, k_decompress_list,
+ * k_decompress_list_close.  Blobs, offsets (n_total + 1 each), encoding, digest_len and flags as the encoded calls take them
+ * (S2K_ECDSA_BIP0066 implies 32-byte digests and low-s there as here); the piece's bytes go up where the offsets say.  Every
+ * output is filled with `sentinel` on the device before the launch and copied back whole afterwards, so the caller sees which
+ * rows were written: xy[n_total * 64], dg / r / s[n_total * 32], recid[n_total] (S2K_ENCODING_COMPACT_RECOVERABLE only, else
+ * NULL), and with a set found[cnt] (key index per item of the piece), list[cnt] (the decompression list: its first
+ * counters[3] entries are items of the batch, in no fixed order) and counters[8]: the call's four counters {hits of 33-byte
+ * keys, of 65-byte keys, roots of the pieces before, length of the list} read after k_decompress_list, then again after
+ * k_decompress_list_close.  new_call != 0 zeroes the counters first, as the start of a call does; 0 goes on counting: a
+ * second piece of the same call.  Unlike the encoded calls, the hook scans the offsets and refuses decreasing ones.
+ * Synchronous; uses the context's buffers and counters (s2k_ctx_last_encoded_keyset_stats reads them), so not for use beside
+ * calls in flight.
+ * s2k_debug_parse_encoded_caps: out = the bytes of LDS the parse kernels stage a workgroup's stretch of the key, digest and
+ * signature blob in; a stretch from lo to hi is staged when (hi - (lo & ~15)) + 16 <= the capacity, else read in place. */
+int s2k_debug_parse_encoded(s2k_ctx *ctx, const s2k_keyset *ks, size_t n_total, const uint8_t *pubs, const uint64_t *pub_off,
+                            const uint8_t *digests, const uint64_t *dig_off, const uint8_t *sigs, const uint64_t *sig_off,
+                            size_t first, size_t cnt, int encoding, size_t digest_len, uint32_t flags, int new_call,
+                            uint8_t sentinel, uint8_t *xy, uint8_t *dg, uint8_t *r, uint8_t *s, uint8_t *recid, uint32_t *found,
+                            uint32_t *list, uint32_t counters[8]);
+int s2k_debug_parse_encoded_caps(uint32_t out[3]);
 
 /* ---- BIP-340 Schnorr verification (batched) ---------------------------------------- */
 /* For each i < n: bitcoin.SchnorrPublicKey.Verify(msg_i, sig_i) for the x-only key pk_i

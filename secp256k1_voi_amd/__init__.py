@@ -285,6 +285,8 @@ def load_library() -> C.CDLL:
     lib.s2k_ecdsa_verify_encoded_batch_keyset.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, sz, u32, vp]
     lib.s2k_ecdsa_verify_encoded_batch_keyset_submit.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, ci, sz, u32, vp, C.POINTER(u64)]
     lib.s2k_ctx_last_encoded_keyset_stats.argtypes = [vp, C.POINTER(u64)]
+    lib.s2k_debug_parse_encoded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, sz, u32, ci, C.c_uint8, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.s2k_debug_parse_encoded_caps.argtypes = [vp]
     lib.s2k_wait.argtypes = [vp, u64]
     lib.s2k_poll.argtypes = [vp, u64]
     lib.s2k_wait_all.argtypes = [vp]
@@ -450,6 +452,7 @@ EXPORTED_SYMBOLS = [
     "s2k_parse_asn1_signature", "s2k_parse_compact_signature", "s2k_is_valid_signature_encoding_bip0066",
     "s2k_ecdsa_verify_encoded_batch",
     "s2k_ecdsa_verify_encoded_batch_keyset", "s2k_ecdsa_verify_encoded_batch_keyset_submit", "s2k_ctx_last_encoded_keyset_stats",
+    "s2k_debug_parse_encoded", "s2k_debug_parse_encoded_caps",
     "s2k_ecdsa_verify_batch_submit", "s2k_ecdsa_verify_encoded_batch_submit", "s2k_wait", "s2k_poll", "s2k_wait_all",
     "s2k_device_count", "s2k_group_create", "s2k_group_destroy", "s2k_group_size", "s2k_group_last_error",
     "s2k_group_set_key_grouping", "s2k_group_set_small_batch_max", "s2k_group_set_mid_batch_max", "s2k_group_ecdsa_verify_batch", "s2k_group_ecdsa_verify_batch_submit", "s2k_group_wait",
@@ -596,6 +599,15 @@ def pointset_geometry(window_bits: int) -> tuple:
     if load_library().s2k_pointset_geometry(int(window_bits), out.ctypes.data) != 0:
         raise ValueError("secp256k1: point-set digit width is 4 or 8")
     return tuple(int(x) for x in out)
+
+
+def parse_encoded_caps() -> tuple:
+    """(key, digest, signature) bytes of LDS the parse kernels of the encoded calls stage a workgroup's stretch of each blob in
+    (s2k_debug_parse_encoded_caps; no device)."""
+    out = np.zeros(3, dtype=np.uint32)
+    if load_library().s2k_debug_parse_encoded_caps(out.ctypes.data) != 0:
+        raise EngineError("s2k_debug_parse_encoded_caps failed")
+    return tuple(int(v) for v in out)
 
 
 def keyset_geometry(layout: int) -> tuple:
@@ -1072,6 +1084,33 @@ class Engine(_TicketOwner):
         o = (C.c_uint64 * 4)()
         self._check(self._lib.s2k_ctx_last_encoded_keyset_stats(self._h, o))
         return {"hits33": int(o[0]), "hits65": int(o[1]), "roots": int(o[2]), "delegated": int(o[3])}
+
+    def debug_parse_encoded(self, pubs, digests, sigs, first=0, cnt=None, encoding=ENCODING_ASN1, digest_len=0, reject_malleable=False,
+                            bip0066=False, keyset=None, new_call=True, sentinel=0xA5) -> dict:
+        """test hook (s2k_debug_parse_encoded): the parse step of the encoded calls for the piece [first, first + cnt) of the
+        batch, no ladder.  Lists of byte strings or (blob, offsets) pairs.  Returns the arrays of the WHOLE batch - xy (n, 64),
+        dg / r / s (n, 32), recid (n,) for the recoverable encoding - with `sentinel` in every byte the kernels did not write,
+        and over a key set found (cnt,), the decompression list, and the call's counters after k_decompress_list ("before")
+        and after k_decompress_list_close ("after") as dicts of hits33 / hits65 / roots / list."""
+        n, a, flags = self._encoded_keyset_args(pubs, digests, sigs, reject_malleable, bip0066, False)
+        cnt = n - first if cnt is None else cnt
+        o = dict(xy=np.zeros((n, 64), np.uint8), dg=np.zeros((n, 32), np.uint8), r=np.zeros((n, 32), np.uint8), s=np.zeros((n, 32), np.uint8))
+        recid = np.zeros(n, np.uint8) if encoding == ENCODING_COMPACT_RECOVERABLE else None
+        found, lst, ctr = np.zeros(max(cnt, 1), np.uint32), np.zeros(max(cnt, 1), np.uint32), np.zeros(8, np.uint32)
+        self._check(self._lib.s2k_debug_parse_encoded(self._h, keyset._k if keyset is not None else None, n, *(x.ctypes.data for x in a),
+                                                      int(first), int(cnt), int(encoding), int(digest_len), flags, 1 if new_call else 0,
+                                                      int(sentinel), o["xy"].ctypes.data, o["dg"].ctypes.data, o["r"].ctypes.data,
+                                                      o["s"].ctypes.data, None if recid is None else recid.ctypes.data, found.ctypes.data,
+                                                      lst.ctypes.data, ctr.ctypes.data))
+        if recid is not None:
+            o["recid"] = recid
+        if keyset is not None:
+            names = ("hits33", "hits65", "roots", "list")
+            o["before"] = dict(zip(names, (int(v) for v in ctr[:4])))
+            o["after"] = dict(zip(names, (int(v) for v in ctr[4:])))
+            o["found"] = found[:cnt]
+            o["list"] = lst[:o["before"]["list"]]
+        return o
 
     def ecdsa_verify_batch_device(self, n, d_pub_xy, d_digest32, d_r, d_s, d_valid, flags=0, stream=0):
         """Device-pointer form: integer device addresses, enqueued on `stream` (a hipStream_t value)."""

@@ -342,6 +342,56 @@ k_recovered_equals(uint32_t n, const uint8_t* __restrict__ xy, const uint8_t* __
   valid[i] = (ok[i] == 1 && diff == 0) ? 1 : 0;
 }
 
+// The launch lines of the parse step, written once: encoded_enqueue_inner, encoded_keyset_enqueue and s2k_debug_parse_encoded
+// all go through them.  pe_input: the three blobs and their offset arrays on the device (or in a page-locked block the device
+// reads), with the options of the call; pe_output: the arrays of the whole batch the piece's rows go to.
+struct pe_input {
+  const uint8_t* pubs;
+  const uint64_t* pub_off;
+  const uint8_t* digests;
+  const uint64_t* dig_off;
+  const uint8_t* sigs;
+  const uint64_t* sig_off;
+  int encoding;
+  size_t digest_len;
+  uint32_t flags;
+};
+struct pe_output {
+  uint8_t *xy, *dg, *r, *s;
+  uint8_t* recid;      // S2K_ENCODING_COMPACT_RECOVERABLE only, else null
+};
+// items [first, first + cnt) of the batch through k_parse_encoded
+int launch_parse_encoded(s2k_ctx* ctx, hipStream_t st, const pe_input& in, size_t first, size_t cnt, const pe_output& o) {
+  k_parse_encoded<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)first, (uint32_t)cnt, in.pubs, in.pub_off, in.digests, in.dig_off, in.sigs, in.sig_off,
+                                                  in.encoding, (uint32_t)in.digest_len, (in.flags & S2K_ECDSA_BIP0066) ? 1 : 0,
+                                                  (in.flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0, o.xy, o.dg, o.r, o.s, o.recid);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+// the same through k_parse_encoded_keyset: pk.found gets the piece's key indices, pk.list its compressed keys outside the set
+int launch_parse_encoded_keyset(s2k_ctx* ctx, hipStream_t st, const pe_input& in, size_t first, size_t cnt, const pe_output& o, const pe_keyset& pk) {
+  k_parse_encoded_keyset<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)first, (uint32_t)cnt, in.pubs, in.pub_off, in.digests, in.dig_off, in.sigs,
+                                                         in.sig_off, in.encoding, (uint32_t)in.digest_len, (in.flags & S2K_ECDSA_BIP0066) ? 1 : 0,
+                                                         (in.flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0, o.xy, o.dg, o.r, o.s, pk);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+// the roots of the piece's list (of at most cnt items), then the list joins the call's total
+int launch_decompress_list(s2k_ctx* ctx, hipStream_t st, size_t cnt, const pe_output& o, const pe_keyset& pk) {
+  k_decompress_list<<<fallback_blocks(ctx, cnt), 256, 0, st>>>(pk.list, pk.ctr, (uint32_t)cnt, o.xy, o.dg, o.r, o.s);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+int launch_decompress_list_close(s2k_ctx* ctx, hipStream_t st, const pe_keyset& pk) {
+  k_decompress_list_close<<<1, 1, 0, st>>>(pk.ctr);
+  HIP_TRY(ctx, hipGetLastError());
+  return S2K_OK;
+}
+// the set's index and validity bytes as the parse kernel takes them
+pe_keyset pe_keyset_of(const s2k_bykey_view& kv, uint32_t* found, uint32_t* list, uint32_t* ctr) {
+  return {{kv.slots, (uint32_t)(((uint64_t)1 << kv.log2_slots) - 1), kv.seed, kv.set.keys}, kv.set.valid, found, list, ctr};
+}
+
 }  // namespace
 
 extern "C" {
@@ -381,7 +431,6 @@ static int encoded_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pubs, co
                                  const uint64_t* dig_off, const uint8_t* sigs, const uint64_t* sig_off, int encoding, size_t digest_len,
                                  uint32_t flags, uint8_t* h_out, bool one_shot, const uint8_t** small_out = nullptr) {
   if (small_out) *small_out = nullptr;
-  const bool bip66 = (flags & S2K_ECDSA_BIP0066) != 0;
   const bool recoverable = encoding == S2K_ENCODING_COMPACT_RECOVERABLE;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t pub_bytes = pub_off[n], dig_bytes = dig_off[n], sig_bytes = sig_off[n];
@@ -396,6 +445,7 @@ static int encoded_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pubs, co
   uint8_t* io = (uint8_t*)ctx->io;
   rc = ctx_streams(ctx);
   if (rc) return rc;
+  const pe_output out = {io + o_xy, io + o_dg, io + o_r, io + o_s, recoverable ? io + o_id : nullptr};
   if (small_out && !one_shot && s2k_internal_small_call(ctx, n, flags) && pub_bytes + dig_bytes + sig_bytes <= ((size_t)1 << 20) &&
       (ctx->kg_mode == S2K_KEYS_ADAPTIVE || ctx->kg_mode == S2K_KEYS_OFF)) {
     const size_t sizes[7] = {pub_bytes, dig_bytes, sig_bytes, (n + 1) * 8, (n + 1) * 8, (n + 1) * 8, n};
@@ -408,11 +458,9 @@ static int encoded_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pubs, co
     memcpy(h[3], pub_off, (n + 1) * 8);
     memcpy(h[4], dig_off, (n + 1) * 8);
     memcpy(h[5], sig_off, (n + 1) * 8);
-    k_parse_encoded<<<(unsigned)((n + 255) / 256), 256, 0, ctx->s_comp>>>(
-        0u, (uint32_t)n, d[0], (const uint64_t*)d[3], d[1], (const uint64_t*)d[4], d[2], (const uint64_t*)d[5], encoding,
-        (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0, io + o_xy, io + o_dg, io + o_r, io + o_s,
-        recoverable ? io + o_id : nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    const pe_input in = {d[0], (const uint64_t*)d[3], d[1], (const uint64_t*)d[4], d[2], (const uint64_t*)d[5], encoding, digest_len, flags};
+    rc = launch_parse_encoded(ctx, ctx->s_comp, in, 0, n, out);
+    if (rc) return rc;
     if (recoverable) {
       rc = s2k_ecdsa_recover_batch_device(ctx, n, io + o_dg, io + o_r, io + o_s, io + o_id, 0u, io + o_rec, io + o_ok, ctx->s_comp);
       if (rc) return rc;
@@ -431,6 +479,8 @@ static int encoded_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pubs, co
   HIP_TRY(ctx, hipMemcpyAsync(io + o_po, pub_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_do, dig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_so, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
+  const pe_input in = {io + o_pub, (const uint64_t*)(io + o_po), io + o_dig, (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so),
+                       encoding, digest_len, flags};
   const size_t round = (size_t)3 * 4 * (size_t)ctx->cu_count * 64;
   // with key grouping on, every chunk groups (and builds tables) on its own, so fewer and larger chunks: two halves
   // (s2k_ecdsa_verify_batch does the same; three chunks of a 2^20 batch left under 6 signatures per key and chunk,
@@ -444,11 +494,8 @@ static int encoded_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pubs, co
     HIP_TRY(ctx, hipMemcpyAsync(io + o_sig + sig_off[lo], sigs + sig_off[lo], sig_off[hi] - sig_off[lo], hipMemcpyHostToDevice, ctx->s_copy));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_copied[k & 1], ctx->s_copy));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_comp, ctx->ev_copied[k & 1], 0));
-    k_parse_encoded<<<(unsigned)((cnt + 255) / 256), 256, 0, ctx->s_comp>>>(
-        (uint32_t)lo, (uint32_t)cnt, io + o_pub, (const uint64_t*)(io + o_po), io + o_dig, (const uint64_t*)(io + o_do), io + o_sig,
-        (const uint64_t*)(io + o_so), encoding, (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0,
-        io + o_xy, io + o_dg, io + o_r, io + o_s, recoverable ? io + o_id : nullptr);
-    HIP_TRY(ctx, hipGetLastError());
+    rc = launch_parse_encoded(ctx, ctx->s_comp, in, lo, cnt, out);
+    if (rc) return rc;
     if (recoverable) {
       // RecoverPublicKey (ecdsa.go:244-282) on the shared ladder, then k.Equal(q) on the device
       rc = s2k_ecdsa_recover_batch_device(ctx, cnt, io + o_dg + lo * 32, io + o_r + lo * 32, io + o_s + lo * 32, io + o_id + lo,
@@ -541,7 +588,6 @@ static int encoded_keyset_enqueue(s2k_ctx* ctx, const s2k_keyset* ks, const s2k_
                                   const uint64_t* pub_off, const uint8_t* digests, const uint64_t* dig_off, const uint8_t* sigs,
                                   const uint64_t* sig_off, int encoding, size_t digest_len, uint32_t flags, uint8_t* h_out, bool one_shot,
                                   uint64_t* delegated) {
-  const bool bip66 = (flags & S2K_ECDSA_BIP0066) != 0;
   const uint32_t vflags = flags & (S2K_ECDSA_REJECT_MALLEABLE | S2K_ECDSA_FORCE_WORKLIST);
   *delegated = 0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -570,8 +616,10 @@ static int encoded_keyset_enqueue(s2k_ctx* ctx, const s2k_keyset* ks, const s2k_
   HIP_TRY(ctx, hipMemcpyAsync(io + o_po, pub_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_do, dig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
   HIP_TRY(ctx, hipMemcpyAsync(io + o_so, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_copy));
-  const pe_keyset pk = {{kv.slots, (uint32_t)(((uint64_t)1 << kv.log2_slots) - 1), kv.seed, kv.set.keys}, kv.set.valid, (uint32_t*)ctx->ks_found,
-                        (uint32_t*)(io + o_list), ctx->ek_ctr};
+  const pe_keyset pk = pe_keyset_of(kv, (uint32_t*)ctx->ks_found, (uint32_t*)(io + o_list), ctx->ek_ctr);
+  const pe_input in = {io + o_pub, (const uint64_t*)(io + o_po), io + o_dig, (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so),
+                       encoding, digest_len, flags};
+  const pe_output out = {io + o_xy, io + o_dg, io + o_r, io + o_s, nullptr};
   int k = 0;
   for (size_t lo = 0; lo < n; lo += chunk, ++k) {
     const size_t cnt = n - lo < chunk ? n - lo : chunk, hi = lo + cnt;
@@ -581,26 +629,20 @@ static int encoded_keyset_enqueue(s2k_ctx* ctx, const s2k_keyset* ks, const s2k_
     HIP_TRY(ctx, hipEventRecord(ctx->ev_copied[k & 1], ctx->s_copy));
     HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_copied[k & 1], 0));
     if (s2k_internal_bykey_delegates(ctx, cnt, flags)) {
-      k_parse_encoded<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)lo, (uint32_t)cnt, io + o_pub, (const uint64_t*)(io + o_po), io + o_dig,
-                                                      (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so), encoding,
-                                                      (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0,
-                                                      io + o_xy, io + o_dg, io + o_r, io + o_s, nullptr);
-      HIP_TRY(ctx, hipGetLastError());
+      rc = launch_parse_encoded(ctx, st, in, lo, cnt, out);
+      if (rc) return rc;
       rc = s2k_ecdsa_verify_batch_device(ctx, cnt, io + o_xy + lo * 64, io + o_dg + lo * 32, io + o_r + lo * 32, io + o_s + lo * 32, vflags,
                                          io + o_v + lo, st);
       if (rc) return rc;
       *delegated += cnt;
       continue;
     }
-    k_parse_encoded_keyset<<<blocks_for(cnt), 256, 0, st>>>((uint32_t)lo, (uint32_t)cnt, io + o_pub, (const uint64_t*)(io + o_po), io + o_dig,
-                                                           (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so), encoding,
-                                                           (uint32_t)digest_len, bip66 ? 1 : 0, (flags & S2K_ECDSA_REJECT_MALLEABLE) ? 1 : 0,
-                                                           io + o_xy, io + o_dg, io + o_r, io + o_s, pk);
-    HIP_TRY(ctx, hipGetLastError());
-    k_decompress_list<<<fallback_blocks(ctx, cnt), 256, 0, st>>>(pk.list, pk.ctr, (uint32_t)cnt, io + o_xy, io + o_dg, io + o_r, io + o_s);
-    HIP_TRY(ctx, hipGetLastError());
-    k_decompress_list_close<<<1, 1, 0, st>>>(pk.ctr);
-    HIP_TRY(ctx, hipGetLastError());
+    rc = launch_parse_encoded_keyset(ctx, st, in, lo, cnt, out, pk);
+    if (rc) return rc;
+    rc = launch_decompress_list(ctx, st, cnt, out, pk);
+    if (rc) return rc;
+    rc = launch_decompress_list_close(ctx, st, pk);
+    if (rc) return rc;
     rc = s2k_internal_bykey_device(ctx, ks, cnt, io + o_xy + lo * 64, io + o_dg + lo * 32, io + o_r + lo * 32, io + o_s + lo * 32, vflags,
                                    io + o_v + lo, st, pk.found);
     if (rc) return rc;
@@ -696,6 +738,106 @@ int s2k_ctx_last_encoded_keyset_stats(s2k_ctx* ctx, uint64_t out[4]) {
     out[2] = (uint64_t)c[EK_ROOTS] + c[EK_LIST];
   }
   out[3] = ctx->ek_delegated;
+  return S2K_OK;
+}
+
+// Test hooks: the parse step of the encoded calls alone, its arrays copied back (see the header).
+int s2k_debug_parse_encoded_caps(uint32_t out[3]) {
+  if (!out) return S2K_ERR_ARG;
+  out[0] = PE_PUB_CAP;
+  out[1] = PE_DIG_CAP;
+  out[2] = PE_SIG_CAP;
+  return S2K_OK;
+}
+
+int s2k_debug_parse_encoded(s2k_ctx* ctx, const s2k_keyset* ks, size_t n_total, const uint8_t* pubs, const uint64_t* pub_off,
+                            const uint8_t* digests, const uint64_t* dig_off, const uint8_t* sigs, const uint64_t* sig_off, size_t first,
+                            size_t cnt, int encoding, size_t digest_len, uint32_t flags, int new_call, uint8_t sentinel, uint8_t* xy,
+                            uint8_t* dg, uint8_t* r, uint8_t* s, uint8_t* recid, uint32_t* found, uint32_t* list, uint32_t counters[8]) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  const size_t n = n_total;
+  if (!xy || !dg || !r || !s) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  int rc = encoded_check_args(ctx, n, pubs, pub_off, digests, dig_off, sigs, sig_off, encoding, &digest_len, &flags, xy);
+  if (rc) return rc;
+  const bool recoverable = encoding == S2K_ENCODING_COMPACT_RECOVERABLE;
+  if (cnt == 0 || first > n || cnt > n - first) return fail(ctx, S2K_ERR_ARG, "the piece is not inside the batch");
+  if (recoverable && !recid) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if (ks && (!found || !list || !counters)) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  // (a test hook can afford the scan the product leaves out: the offsets never decrease)
+  for (const uint64_t* off : {pub_off, dig_off, sig_off})
+    for (size_t i = 0; i < n; ++i)
+      if (off[i] > off[i + 1]) return fail(ctx, S2K_ERR_ARG, "offsets decrease");
+  s2k_bykey_view kv;
+  if (ks) {
+    rc = encoded_keyset_check(ctx, ks, encoding, flags, &kv);
+    if (rc) return rc;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ctx_streams(ctx);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
+  // the layout of encoded_enqueue_inner / encoded_keyset_enqueue: blobs, offsets, the output arrays of the whole batch, the list
+  const size_t pub_bytes = pub_off[n], dig_bytes = dig_off[n], sig_bytes = sig_off[n];
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_pub = 0, o_dig = o_pub + al(pub_bytes), o_sig = o_dig + al(dig_bytes), o_po = o_sig + al(sig_bytes),
+               o_do = o_po + al((n + 1) * 8), o_so = o_do + al((n + 1) * 8), o_xy = o_so + al((n + 1) * 8), o_dg = o_xy + al(n * 64),
+               o_r = o_dg + al(n * 32), o_s = o_r + al(n * 32), o_id = o_s + al(n * 32), o_list = o_id + al(n),
+               total = o_list + al(cnt * sizeof(uint32_t));
+  rc = ctx_reserve(ctx, &ctx->io, &ctx->io_bytes, total);
+  if (rc) return rc;
+  const size_t found_bytes = ((cnt + 63) & ~(size_t)63) * sizeof(uint32_t);
+  if (ks) {
+    rc = ctx_reserve(ctx, &ctx->ks_found, &ctx->ks_found_bytes, found_bytes);
+    if (rc) return rc;
+    if (!ctx->ek_ctr) {
+      HIP_TRY(ctx, hipMalloc((void**)&ctx->ek_ctr, 256));
+      new_call = 1;
+    }
+  }
+  uint8_t* io = (uint8_t*)ctx->io;
+  hipStream_t st = ctx->s_comp;
+  const size_t hi = first + cnt;
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_po, pub_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_do, dig_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_so, sig_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  // the piece's bytes, where the offsets say (what lies around them in the buffer is whatever an earlier call left)
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_pub + pub_off[first], pubs + pub_off[first], pub_off[hi] - pub_off[first], hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_dig + dig_off[first], digests + dig_off[first], dig_off[hi] - dig_off[first], hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(io + o_sig + sig_off[first], sigs + sig_off[first], sig_off[hi] - sig_off[first], hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(io + o_xy, sentinel, total - o_xy, st));
+  const pe_input in = {io + o_pub, (const uint64_t*)(io + o_po), io + o_dig, (const uint64_t*)(io + o_do), io + o_sig, (const uint64_t*)(io + o_so),
+                       encoding, digest_len, flags};
+  const pe_output out = {io + o_xy, io + o_dg, io + o_r, io + o_s, recoverable ? io + o_id : nullptr};
+  uint32_t c[2 * EK_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!ks) {
+    rc = launch_parse_encoded(ctx, st, in, first, cnt, out);
+    if (rc) return rc;
+  } else {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ks_found, sentinel, found_bytes, st));
+    if (new_call) HIP_TRY(ctx, hipMemsetAsync(ctx->ek_ctr, 0, EK_WORDS * sizeof(uint32_t), st));
+    const pe_keyset pk = pe_keyset_of(kv, (uint32_t*)ctx->ks_found, (uint32_t*)(io + o_list), ctx->ek_ctr);
+    rc = launch_parse_encoded_keyset(ctx, st, in, first, cnt, out, pk);
+    if (!rc) rc = launch_decompress_list(ctx, st, cnt, out, pk);
+    if (rc) {
+      s2k_internal_drain(ctx);
+      return rc;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpy(c, ctx->ek_ctr, EK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    rc = launch_decompress_list_close(ctx, st, pk);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpy(c + EK_WORDS, ctx->ek_ctr, EK_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(found, ctx->ks_found, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(list, io + o_list, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    memcpy(counters, c, sizeof c);
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipMemcpy(xy, io + o_xy, n * 64, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(dg, io + o_dg, n * 32, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(r, io + o_r, n * 32, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(s, io + o_s, n * 32, hipMemcpyDeviceToHost));
+  if (recoverable) HIP_TRY(ctx, hipMemcpy(recid, io + o_id, n, hipMemcpyDeviceToHost));
   return S2K_OK;
 }
 
