@@ -869,6 +869,24 @@ int s2k_multi_scalar_mult(s2k_ctx *ctx, size_t n, const uint8_t *k /* n*32 */, c
                           uint8_t *out /* 65 */);
 int s2k_multi_scalar_mult_device(s2k_ctx *ctx, size_t n, const void *d_k, const void *d_points, void *d_out65,
                                  void *hip_stream);
+/* Test hook for the bucket method behind the call above and both whole-batch verifiers (msm.hip): out = sum_i +-mag[i] * P[i]
+ * over nterms TERMS as the parse and split kernels would have left them - mags: 16 bytes each, big-endian, the whole range
+ * 0 .. 2^128 - 1 (the halves of the endomorphism split stay below 0xA2A9 * 2^112; only the raw coefficients of the whole-batch
+ * checks go beyond); points: 65-byte records 0x04 || X || Y of points on the curve, or all zero for an identity term (flag 0:
+ * the term is skipped); signs: NULL, or one byte per term, non-zero negates the point.  window_bits 0: the width the call chooses for
+ * nterms terms; 8, 12 or 16: that width at any size.  A small kernel of the hook fills the term arrays (msm_store_term), then
+ * the sort, the bucket pass, the reduction and the tail run as in the product.  geom[10] = {c, nw, nb, nslot, nkeys, L_A,
+ * nlanes, fold16, big, list_len}: window bits, windows, keys per slot, slots, keys (padded to a multiple of 256), list
+ * entries per range of the bucket pass and ranges (restated from the core's formulas for the one-part flow, not read back:
+ * S2K_MSM_SPLIT_WINDOW must be unset), 1 when the 16-bit reduction by row and column sums ran, the count of buckets spread over more than 8 ranges (k_msm_stitch's counter:
+ * it goes beyond the 4096 the queue holds) and the length of the sorted list.  offsets / list: both NULL, or offsets[nkeys_cap]
+ * with nkeys_cap >= nkeys + 1 and list[list_cap] with list_cap >= list_len: the sort's offset[0 .. nkeys] and list[0 ..
+ * list_len) (term index | 0x80000000 for a negative digit; key = window * nb + |digit| - 1; the order inside a key is not
+ * defined).  S2K_ERR_ARG: nterms == 0 or above 2^22, another window_bits, a point record that is neither, buffers too small.
+ * Synchronous; uses the context's multiscalar workspace, so not for use beside calls in flight. */
+int s2k_debug_msm_terms(s2k_ctx *ctx, size_t nterms, const uint8_t *mags /* nterms*16 */, const uint8_t *points /* nterms*65 */,
+                        const uint8_t *signs /* nterms or NULL */, int window_bits, uint8_t *out /* 65 */, uint32_t geom[10],
+                        uint32_t *offsets, size_t nkeys_cap, uint32_t *list, size_t list_cap);
 /* Many independent sums in one call: out[j] = sum of k[i] * P[i] over i in [seg_offsets[j], seg_offsets[j+1]) — for every j
  * the record Point.MultiScalarMultVartime(scalars[a:b], points[a:b]) gives (point_mul_multi.go:73-117), so exactly what
  * s2k_multi_scalar_mult returns for that slice.  ONLY the Vartime form: variable time (data-dependent digit additions and

@@ -352,6 +352,7 @@ def load_library() -> C.CDLL:
     lib.s2k_point_decode_batch.argtypes = [vp, sz, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult_device.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.s2k_debug_msm_terms.argtypes = [vp, sz, vp, vp, vp, ci, vp, vp, vp, sz, vp, sz]
     lib.s2k_multi_scalar_mult_segments.argtypes = [vp, sz, vp, vp, sz, vp, vp]
     lib.s2k_multi_scalar_mult_segments_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
     lib.s2k_debug_msm_segments_plan.argtypes = [sz, sz, vp, u32, C.c_uint64, vp, sz, vp, vp, vp, vp]
@@ -467,7 +468,7 @@ EXPORTED_SYMBOLS = [
     "s2k_schnorr_verify_batch_bisect", "s2k_schnorr_verify_batch_bisect_device",
     "s2k_scalar_base_mult_batch", "s2k_scalar_mult_batch", "s2k_double_scalar_mult_basepoint_batch",
     "s2k_point_add_batch", "s2k_point_double_batch", "s2k_point_decode_batch",
-    "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device",
+    "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device", "s2k_debug_msm_terms",
     "s2k_multi_scalar_mult_segments", "s2k_multi_scalar_mult_segments_device", "s2k_debug_msm_segments_plan",
     "s2k_pointset_create", "s2k_pointset_destroy", "s2k_pointset_size", "s2k_pointset_window_bits", "s2k_pointset_device_bytes",
     "s2k_pointset_geometry", "s2k_debug_pointset_entry", "s2k_debug_pointset_check_args",
@@ -1570,6 +1571,30 @@ class Engine(_TicketOwner):
         self._check(self._lib.s2k_multi_scalar_mult(self._h, n, scalars.ctypes.data if n else None,
                                                     points.ctypes.data if n else None, out.ctypes.data))
         return out.tobytes()
+
+    def debug_msm_terms(self, mags, points, signs=None, window_bits=0, dump=False) -> dict:
+        """test hook (s2k_debug_msm_terms): the multiscalar core on given terms - mags (n, 16) big-endian magnitudes, points
+        (n, 65) records (all zero: an identity term), signs (n,) non-zero negates, window_bits 0 / 8 / 12 / 16.  Returns out
+        (65 bytes), the geometry c / nw / nb / nslot / nkeys / L_A / nlanes / fold16, big (k_msm_stitch's counter of oversized
+        buckets) and list_len; with dump the sort's offset[0 .. nkeys] and list[0 .. list_len) as well."""
+        mags = _arr(mags, 16)
+        n = mags.shape[0]
+        points = _arr(points, 65, n)
+        if signs is not None:
+            signs = np.ascontiguousarray(signs, dtype=np.uint8).reshape(n)
+        out, geom = np.zeros(65, dtype=np.uint8), np.zeros(10, dtype=np.uint32)
+        offsets = np.zeros(9 * 32768 + 1, dtype=np.uint32) if dump else None          # (the largest key range: 16-bit windows)
+        lst = np.zeros(max(16 * n, 1), dtype=np.uint32) if dump else None             # (at most 16 windows per term)
+        self._check(self._lib.s2k_debug_msm_terms(self._h, n, mags.ctypes.data, points.ctypes.data,
+                                                  None if signs is None else signs.ctypes.data, int(window_bits), out.ctypes.data,
+                                                  geom.ctypes.data, None if offsets is None else offsets.ctypes.data,
+                                                  0 if offsets is None else offsets.size, None if lst is None else lst.ctypes.data,
+                                                  0 if lst is None else lst.size))
+        o = dict(zip(("c", "nw", "nb", "nslot", "nkeys", "L_A", "nlanes", "fold16", "big", "list_len"), (int(v) for v in geom)))
+        o["out"] = out.tobytes()
+        if dump:
+            o["offset"], o["list"] = offsets[:o["nkeys"] + 1], lst[:o["list_len"]]
+        return o
 
     def multi_scalar_mult_device(self, n, d_scalars, d_points, d_out65, stream=0):
         self._check(self._lib.s2k_multi_scalar_mult_device(self._h, int(n), d_scalars, d_points, d_out65, stream))

@@ -1066,7 +1066,8 @@ static uint32_t msm_lanes_target() {   // tuning hook: S2K_MSM_LANES overrides t
   return v;
 }
 // carve the MSM workspace for up to n terms (+ aux_bytes of scratch for the caller)
-int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m) {
+// (force_c: 0, or the window width a test asks for at any size - s2k_debug_msm_terms)
+int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m, uint32_t force_c = 0) {
   msm_geom& g = m.g;
   // window width: measured (tools/msm_sweep.py, MI355X, ms for 2^11 .. 2^20 inputs = twice as many terms):
   // 16-bit windows from 2^13 terms on: 0.83 0.75 0.75 0.76 0.78 0.80 0.89 1.01 1.31 1.95; 12-bit windows up to
@@ -1076,7 +1077,7 @@ int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m) {
     const char* e = getenv("S2K_MSM_C16_FROM_LOG2");
     return e ? atoi(e) : 13;
   }();
-  g.c = n >= ((size_t)1 << c16_from_log2) ? 16 : (n >= 256 ? 12 : 8);
+  g.c = force_c ? force_c : (n >= ((size_t)1 << c16_from_log2) ? 16 : (n >= 256 ? 12 : 8));
   g.nw = (SCALAR_BITS + g.c - 1) / g.c;
   g.nb = 1u << (g.c - 1);
   g.nslot = g.nw + 1;
@@ -1704,6 +1705,36 @@ k_rlc_mark_valid(uint32_t lo, uint32_t m, const uint8_t* __restrict__ s_flag, ui
   if (i < m) valid[lo + i] = s_flag[lo + i];
 }
 
+// Test hook (s2k_debug_msm_terms): given magnitudes, points and signs -> terms, as k_msm_parse and the whole-batch front ends
+// leave them.  flag 1: a point on the curve, 0: an all-zero record (the term is skipped), 2: anything else (status).
+__global__ void __launch_bounds__(256)
+k_msm_debug_fill(uint32_t n, const uint8_t* __restrict__ mags, const uint8_t* __restrict__ points, const uint8_t* __restrict__ signs,
+                 uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag, uint32_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* rec = points + i * 65;
+  uint8_t f = 0;
+  uint32_t x[8], y[8];
+  if (rec[0] == 0x04) {
+    load_be32_unaligned(x, rec + 1);
+    load_be32_unaligned(y, rec + 33);
+    f = xy_on_curve_words(x, y) ? 1 : 2;
+  } else {
+    for (int j = 0; j < 65; ++j)
+      if (rec[j]) f = 2;
+  }
+  if (f == 2) atomicOr(status, 1u);
+  flag[i] = f;
+  if (f != 1) return;
+  sc k = sc_zero();
+  const uint8_t* mg = mags + i * 16;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)      // big-endian bytes -> words, least significant first
+    k.v[w] = (uint32_t)mg[12 - 4 * w] << 24 | (uint32_t)mg[13 - 4 * w] << 16 | (uint32_t)mg[14 - 4 * w] << 8 | mg[15 - 4 * w];
+  msm_store_term(scw, ptw, n, i, k, x, y, signs && signs[i]);
+}
+constexpr size_t MSM_DEBUG_TERMS_MAX = (size_t)1 << 22;     // what the hook lays out: 64 MiB of magnitudes, 272 MiB of records
+
 }  // namespace
 
 // (engine_internal.h) the launches of one sum, n > 0 inputs; the caller has entered the context and synchronises
@@ -1816,6 +1847,77 @@ int s2k_multi_scalar_mult(s2k_ctx* ctx, size_t n, const uint8_t* scalars, const 
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(out65, d[2], 65, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
+  return S2K_OK;
+}
+
+// Test hook: the multiscalar core on given terms (see the header)
+int s2k_debug_msm_terms(s2k_ctx* ctx, size_t nterms, const uint8_t* mags, const uint8_t* points, const uint8_t* signs, int window_bits,
+                        uint8_t* out65, uint32_t geom[10], uint32_t* offsets, size_t nkeys_cap, uint32_t* list, size_t list_cap) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!mags || !points || !out65 || !geom) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  if ((offsets == nullptr) != (list == nullptr)) return fail(ctx, S2K_ERR_ARG, "offsets and list go together");
+  if (nterms == 0 || nterms > MSM_DEBUG_TERMS_MAX) return fail(ctx, S2K_ERR_ARG, "term count outside 1 .. 2^22");
+  if (window_bits != 0 && window_bits != 8 && window_bits != 12 && window_bits != 16)
+    return fail(ctx, S2K_ERR_ARG, "window_bits must be 0, 8, 12 or 16");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ctx_streams(ctx);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
+  const size_t n = nterms;
+  const size_t sizes[4] = {n * 16 + 16, n * 65 + 16, n + 16, 128};
+  uint8_t* d[4];
+  rc = ctx_stage(ctx, sizes, 4, d);
+  if (rc) return rc;
+  hipStream_t st = ctx->s_comp;
+  rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  msm_ws m;
+  rc = msm_setup(ctx, n, 0, m, (uint32_t)window_bits);
+  if (rc) return rc;
+  const msm_geom& g = m.g;
+  // (the key range is msm_setup's to say, so this refusal comes after the workspace has grown; nothing is enqueued yet)
+  if (offsets && nkeys_cap < m.nkeys + 1) return fail(ctx, S2K_ERR_ARG, "offsets buffer too small for the key range");
+  HIP_TRY(ctx, hipMemcpyAsync(d[0], mags, n * 16, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d[1], points, n * 65, hipMemcpyHostToDevice, st));
+  if (signs) HIP_TRY(ctx, hipMemcpyAsync(d[2], signs, n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
+  k_msm_debug_fill<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d[0], d[1], signs ? d[2] : nullptr, m.scw, m.ptw, m.flag, m.status);
+  HIP_TRY(ctx, hipGetLastError());
+  rc = msm_core(ctx, st, n, m, d[3]);
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  uint32_t h_status = 0, h_big = 0, h_total = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&h_status, m.status, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&h_big, m.big, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&h_total, m.offset + m.nkeys, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out65, d[3], 65, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  ctx->have_last = false;   // the stream has been synchronised: nothing of this context is in flight
+  if (h_status) return fail(ctx, S2K_ERR_ARG, "a point record is neither a point on the curve nor all zero");
+  // the geometry as msm_setup chose it.  L_A, nlanes and fold16 are NOT observed: they restate msm_core's formulas for the
+  // one-part flow (S2K_MSM_SPLIT_WINDOW unset) and read S2K_MSM_OLD_REDUCE afresh where the core caches it, so a change of
+  // msm_core has to be repeated here - the tests use them to know where range borders fall, the sums and the sort's arrays
+  // are what they check the core by
+  const size_t pairs = n * (size_t)g.nw, target = msm_lanes_target();
+  size_t la = (pairs + target - 1) / target;
+  if (la < MSM_L_MIN) la = MSM_L_MIN;
+  geom[0] = g.c;
+  geom[1] = g.nw;
+  geom[2] = g.nb;
+  geom[3] = g.nslot;
+  geom[4] = (uint32_t)m.nkeys;
+  geom[5] = (uint32_t)la;
+  geom[6] = (uint32_t)((pairs + la - 1) / la);
+  geom[7] = g.c == 16 && !getenv("S2K_MSM_OLD_REDUCE") && m.nslots + 1 > FOLD_END ? 1u : 0u;
+  geom[8] = h_big;
+  geom[9] = h_total;
+  if (offsets) {
+    if (h_total > list_cap) return fail(ctx, S2K_ERR_ARG, "list buffer too small for the sorted list");
+    HIP_TRY(ctx, hipMemcpy(offsets, m.offset, (m.nkeys + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (h_total) HIP_TRY(ctx, hipMemcpy(list, m.list, (size_t)h_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
   return S2K_OK;
 }
 
