@@ -800,7 +800,9 @@ int s2k_schnorr_verify_batch_keyset_submit(s2k_ctx *ctx, const s2k_keyset *ks, s
  * output; because the library mixes in operating-system randomness of its own, a reused or
  * predictable seed does not make the coefficients predictable.  It does not say which signature
  * fails — s2k_schnorr_verify_batch_bisect does.  The
- * reference has single verification only (schnorr.go:221); this is BASELINE config 4. */
+ * reference has single verification only (schnorr.go:221); this is BASELINE config 4.
+ * A refused call (S2K_ERR_ARG: a NULL buffer, n >= 2^28, msg_len >= 2^31 - in both forms before anything is staged
+ * or launched) leaves *all_valid = 0. */
 /* (Host-pointer forms of the whole-batch calls - this one, s2k_schnorr_verify_batch_bisect, s2k_multi_scalar_mult - are
  * synchronous: transfer, kernels, answer.  Two contexts on two host threads that take whole batches alternately overlap one's
  * transfer with the other's kernels; the library makes the phases of such calls take turns per device, so the two settle at
@@ -887,6 +889,37 @@ int s2k_multi_scalar_mult_device(s2k_ctx *ctx, size_t n, const void *d_k, const 
 int s2k_debug_msm_terms(s2k_ctx *ctx, size_t nterms, const uint8_t *mags /* nterms*16 */, const uint8_t *points /* nterms*65 */,
                         const uint8_t *signs /* nterms or NULL */, int window_bits, uint8_t *out /* 65 */, uint32_t geom[10],
                         uint32_t *offsets, size_t nkeys_cap, uint32_t *list, size_t list_cap);
+/* Test hooks for the two whole-batch verifiers (s2k_schnorr_batch_verify_rlc, s2k_ecdsa_batch_verify_rlc and their bisect
+ * calls): the ERROR POINT of a batch under a coefficient key that is taken as given.  key32 IS the PRF key of the
+ * coefficients (a_0 = 1, a_i = the low 128 bits of SHA-256(key32 || i as 8 bytes, big-endian)) - where the product derives it
+ * as SHA-256(seed32 || getrandom), these take it from the caller and no operating-system randomness enters, so the result is
+ * an exact, predictable group element: E = sum of a_i E_i over the items that are in the combination, with
+ *   BIP-340   E_i = s_i G - lift_x(r_i) - e_i lift_x(pk_i)
+ *   ECDSA     E_i = R_i - u1_i G - u2_i Q_i   (as s2k_ecdsa_batch_verify_rlc states it),
+ * the identity exactly for an item the per-signature call accepts.  NOT for production: a known key makes the check forgeable.
+ * form 0, the aggregated form: what the whole-batch calls run (keys grouped on the device under the context's
+ *   s2k_ctx_set_key_grouping hash_bits, one term pair per distinct key, the generator's term, the multiscalar core); it takes
+ *   the whole batch only: lo == 0 and cnt == n.
+ * form 1, the plain form: what the bisect calls run on a rejected batch - one term pair per item, the terms kept in the
+ *   context's save area, then the sum over the sub-range [lo, lo + cnt) of the batch alone (coefficients by the item's index
+ *   in the BATCH, not in the range), by the very functions the bisection runs.
+ * out: the affine record 0x04 || X || Y of E, or 65 zero bytes for the identity.  *status: the device status word as read
+ * back, non-zero when an item is out of the combination (an s, r or v out of range, an r or key that is no abscissa / point
+ * of the curve).  It is the PREPARATION's word and the preparation runs over the whole batch: in form 1 it covers all n items,
+ * not the sub-range (the sub-range step sets no status of its own).  in_comb (n bytes, or NULL): 1 for an item that took part
+ * in the sum, 0 for one that was left out - after the key terms in form 0; all n items in form 1 as well.
+ * S2K_ERR_ARG: a NULL pointer (msgs may be NULL when every message is empty), n == 0 or above 2^22, msg_len above 2^31 - 1, a
+ * form other than 0 and 1, a range that is empty or not inside the batch, (ECDSA) flags other than S2K_ECDSA_REJECT_MALLEABLE.
+ * Host pointers; synchronous; they use the context's staging buffer, its multiscalar workspace and its save area, so they are
+ * not for use beside calls in flight. */
+int s2k_debug_schnorr_rlc_point(s2k_ctx *ctx, size_t n, const uint8_t *pk /* n*32 */, const uint8_t *msgs,
+                                const uint64_t *msg_offsets, size_t msg_len, const uint8_t *sig /* n*64 */,
+                                const uint8_t *key32, int form, size_t lo, size_t cnt, uint8_t *out /* 65 */,
+                                uint32_t *status, uint8_t *in_comb /* n or NULL */);
+int s2k_debug_ecdsa_rlc_point(s2k_ctx *ctx, size_t n, const uint8_t *pub_xy /* n*64 */, const uint8_t *digest32 /* n*32 */,
+                              const uint8_t *r /* n*32 */, const uint8_t *s /* n*32 */, const uint8_t *recovery_id /* n */,
+                              uint32_t flags, const uint8_t *key32, int form, size_t lo, size_t cnt, uint8_t *out /* 65 */,
+                              uint32_t *status, uint8_t *in_comb /* n or NULL */);
 /* Many independent sums in one call: out[j] = sum of k[i] * P[i] over i in [seg_offsets[j], seg_offsets[j+1]) — for every j
  * the record Point.MultiScalarMultVartime(scalars[a:b], points[a:b]) gives (point_mul_multi.go:73-117), so exactly what
  * s2k_multi_scalar_mult returns for that slice.  ONLY the Vartime form: variable time (data-dependent digit additions and

@@ -353,6 +353,8 @@ def load_library() -> C.CDLL:
     lib.s2k_multi_scalar_mult.argtypes = [vp, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult_device.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.s2k_debug_msm_terms.argtypes = [vp, sz, vp, vp, vp, ci, vp, vp, vp, sz, vp, sz]
+    lib.s2k_debug_schnorr_rlc_point.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, ci, sz, sz, vp, vp, vp]
+    lib.s2k_debug_ecdsa_rlc_point.argtypes = [vp, sz, vp, vp, vp, vp, vp, u32, vp, ci, sz, sz, vp, vp, vp]
     lib.s2k_multi_scalar_mult_segments.argtypes = [vp, sz, vp, vp, sz, vp, vp]
     lib.s2k_multi_scalar_mult_segments_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp]
     lib.s2k_debug_msm_segments_plan.argtypes = [sz, sz, vp, u32, C.c_uint64, vp, sz, vp, vp, vp, vp]
@@ -469,6 +471,7 @@ EXPORTED_SYMBOLS = [
     "s2k_scalar_base_mult_batch", "s2k_scalar_mult_batch", "s2k_double_scalar_mult_basepoint_batch",
     "s2k_point_add_batch", "s2k_point_double_batch", "s2k_point_decode_batch",
     "s2k_multi_scalar_mult", "s2k_multi_scalar_mult_device", "s2k_debug_msm_terms",
+    "s2k_debug_schnorr_rlc_point", "s2k_debug_ecdsa_rlc_point",
     "s2k_multi_scalar_mult_segments", "s2k_multi_scalar_mult_segments_device", "s2k_debug_msm_segments_plan",
     "s2k_pointset_create", "s2k_pointset_destroy", "s2k_pointset_size", "s2k_pointset_window_bits", "s2k_pointset_device_bytes",
     "s2k_pointset_geometry", "s2k_debug_pointset_entry", "s2k_debug_pointset_check_args",
@@ -1595,6 +1598,35 @@ class Engine(_TicketOwner):
         if dump:
             o["offset"], o["list"] = offsets[:o["nkeys"] + 1], lst[:o["list_len"]]
         return o
+
+    def _debug_rlc_result(self, n, call, key32, form, lo, cnt):
+        key = np.frombuffer(bytes(key32), dtype=np.uint8)
+        if key.size != 32:
+            raise ValueError("key32 must be 32 bytes")
+        out, status, in_comb = np.zeros(65, dtype=np.uint8), C.c_uint32(0), np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(call(key.ctypes.data, int(form), int(lo), int(n - lo if cnt is None else cnt), out.ctypes.data, C.byref(status),
+                         in_comb.ctypes.data))
+        return {"out": out.tobytes(), "status": int(status.value), "in_comb": in_comb[:n]}
+
+    def debug_schnorr_rlc_point(self, pk32, msgs, sig64, key32: bytes, form: int = 0, lo: int = 0, cnt: int | None = None) -> dict:
+        """test hook (s2k_debug_schnorr_rlc_point): the error point of a BIP-340 batch under the coefficient key `key32`, taken
+        as given - form 0: the aggregated form of the whole batch, form 1: the plain form's sub-range [lo, lo + cnt) (cnt None:
+        to the end).  Returns out (65 bytes: the affine record, zero for the identity), status (the device status word) and
+        in_comb (n flags: the item took part in the sum).  `msgs`: a list of byte strings or an (n, L) uint8 array."""
+        pk32 = _arr(pk32, 32)
+        n = pk32.shape[0]
+        sig64 = _arr(sig64, 64, n)
+        m, offs, mlen, _keep = self._schnorr_msgs(msgs, n)       # (_keep: the message arrays live until the call returns)
+        return self._debug_rlc_result(n, lambda *rest: self._lib.s2k_debug_schnorr_rlc_point(
+            self._h, n, pk32.ctypes.data, m, offs, mlen, sig64.ctypes.data, *rest), key32, form, lo, cnt)
+
+    def debug_ecdsa_rlc_point(self, pub_xy, digest32, r, s, recovery_id, key32: bytes, form: int = 0, lo: int = 0,
+                              cnt: int | None = None, reject_malleable: bool = False) -> dict:
+        """test hook (s2k_debug_ecdsa_rlc_point): the same for a batch of recoverable ECDSA signatures"""
+        n, pub_xy, digest32, r, s, rid, _ = self._recoverable_args(pub_xy, digest32, r, s, recovery_id, bytes(32))
+        return self._debug_rlc_result(n, lambda *rest: self._lib.s2k_debug_ecdsa_rlc_point(
+            self._h, n, pub_xy.ctypes.data, digest32.ctypes.data, r.ctypes.data, s.ctypes.data, rid.ctypes.data,
+            REJECT_MALLEABLE if reject_malleable else 0, *rest), key32, form, lo, cnt)
 
     def multi_scalar_mult_device(self, n, d_scalars, d_points, d_out65, stream=0):
         self._check(self._lib.s2k_multi_scalar_mult_device(self._h, int(n), d_scalars, d_points, d_out65, stream))

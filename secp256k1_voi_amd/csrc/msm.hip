@@ -2140,6 +2140,54 @@ int s2k_schnorr_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pk
   return rlc_verdict(ctx, st, n, rlc_batch_bip340(d_pk, d_msgs, d_msg_offsets, msg_len, d_sig), seed32, all_valid);
 }
 
+// The kept terms of a batch in the plain form (the context's rlc_save): what a sub-range is gathered from, since the
+// sub-range runs re-carve the multiscalar workspace.  `leaf`: leaf_bytes of scratch behind them (the ECDSA leaf verifier's).
+struct rlc_saved {
+  size_t n;
+  uint32_t *scw, *ptw, *as;
+  uint8_t *flag, *leaf;
+};
+static size_t rlc_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+// terms, flags and a_i s_i planes of the plain form as rlc_run_full left them in `m` / `as` -> sv
+static int rlc_keep_terms(s2k_ctx* ctx, hipStream_t st, size_t n, const msm_ws& m, const uint32_t* as, size_t leaf_bytes, rlc_saved& sv) {
+  const size_t NS = 3 * n;
+  const size_t o_scw = 0, o_ptw = rlc_pad(NS * 4 * 4), o_flag = o_ptw + rlc_pad(NS * 16 * 4), o_as = o_flag + rlc_pad(n),
+               o_leaf = o_as + rlc_pad(n * 8 * 4), total = o_leaf + leaf_bytes;
+  int rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, total);
+  if (rc) return rc;
+  uint8_t* base = (uint8_t*)ctx->rlc_save;
+  sv.n = n;
+  sv.scw = (uint32_t*)(base + o_scw);
+  sv.ptw = (uint32_t*)(base + o_ptw);
+  sv.as = (uint32_t*)(base + o_as);
+  sv.flag = base + o_flag;
+  sv.leaf = base + o_leaf;
+  k_rlc_save<<<blocks_for(NS), 256, 0, st>>>((uint32_t)n, m.scw, m.ptw, m.flag, sv.scw, sv.ptw, sv.flag);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(sv.as, as, n * 8 * 4, hipMemcpyDeviceToDevice, st));
+  return S2K_OK;
+}
+// error point of the sub-range [lo, lo + cnt) of the kept batch: its 3 cnt terms gathered, its generator term summed, the
+// multiscalar core on 3 cnt + 2 terms; E on the host, the stream synchronised
+static int rlc_sub_range(s2k_ctx* ctx, hipStream_t st, const rlc_saved& sv, bool ecdsa, uint32_t lo, uint32_t cnt, uint8_t E[65]) {
+  msm_ws w;
+  const size_t N = 3 * (size_t)cnt + 2;
+  int r = msm_setup(ctx, N, 256 + RLC_SUM_BLOCKS * 32, w);
+  if (r) return r;
+  uint32_t* sum_part = (uint32_t*)w.aux;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, w.zero_bytes, st));
+  k_rlc_gather<<<blocks_for(3 * (size_t)cnt), 256, 0, st>>>(lo, cnt, (uint32_t)sv.n, sv.scw, sv.ptw, sv.flag, w.scw, w.ptw, w.flag);
+  k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>(cnt, sv.n, sv.as + lo, sum_part, w.scw, w.ptw, w.flag, N, N, 0u);
+  k_schnorr_rlc_sum<<<1, 256, 0, st>>>(cnt, sv.n, nullptr, sum_part, w.scw, w.ptw, w.flag, N, N, ecdsa ? 1u : 0u);
+  HIP_TRY(ctx, hipGetLastError());
+  uint8_t* d_out = (uint8_t*)w.status + 64;
+  r = msm_core(ctx, st, N, w, d_out);
+  if (r) return r;
+  HIP_TRY(ctx, hipMemcpyAsync(E, d_out, 65, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return S2K_OK;
+}
+
 // Per-signature verdicts at the price of the whole-batch check when (as usual) everything verifies:
 // one combination over the batch; if it is rejected, the failing signatures are located by
 // bisection on the kept terms (header).  stats (host, optional): [0] sub-range multiscalar
@@ -2153,11 +2201,10 @@ static int rlc_bisect(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& i
   // multiscalar floor (0.75 ms + preparation), per-signature verification 0.56 ms per 2^16 signatures.
   constexpr uint32_t LEAF = 1u << 17;
   constexpr size_t MAX_FAILING = 8;        // more failing ranges than this on one level: stop bisecting
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // The leaf verifier is the ground truth the combination is allowed to skip.  BIP-340: s2k_schnorr_verify_batch.  ECDSA: the
   // keys recovered by s2k_ecdsa_recover_batch_device into `leaf` (65-byte records, then the ok bytes; it lies behind the kept
   // terms in rlc_save, sized for the whole batch: once bisecting is abandoned a range can be any size) and k_ecdsa_rlc_leaf.
-  const size_t leaf_bytes = ecdsa ? pad(n * 65) + pad(n) : 0;
+  const size_t leaf_bytes = ecdsa ? rlc_pad(n * 65) + rlc_pad(n) : 0;
   uint8_t* leaf = nullptr;
   auto verify_each = [&](uint32_t lo, uint32_t cnt) -> int {
     if (stats) stats[1] += cnt;
@@ -2165,7 +2212,7 @@ static int rlc_bisect(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& i
       return s2k_schnorr_verify_batch_device(ctx, cnt, in.key + (size_t)lo * 32,
                                              in.msg_offsets ? in.msgs : (in.msgs ? in.msgs + (size_t)lo * in.msg_len : nullptr),
                                              in.msg_offsets ? in.msg_offsets + lo : nullptr, in.msg_len, in.sig + (size_t)lo * 64, 0, valid + lo, st);
-    uint8_t *rec = leaf, *okb = leaf + pad(n * 65);
+    uint8_t *rec = leaf, *okb = leaf + rlc_pad(n * 65);
     int r = s2k_ecdsa_recover_batch_device(ctx, cnt, in.dig + (size_t)lo * 32, in.r + (size_t)lo * 32, in.s + (size_t)lo * 32, in.recid + lo,
                                            0u, rec, okb, st);
     if (r) return r;
@@ -2201,38 +2248,17 @@ static int rlc_bisect(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& i
     if (rc) return rc;
   }
   // keep the terms: the sub-range runs re-carve the multiscalar workspace
-  const size_t NS = 3 * n;
-  const size_t o_scw = 0, o_ptw = pad(NS * 4 * 4), o_flag = o_ptw + pad(NS * 16 * 4), o_as = o_flag + pad(n),
-               o_leaf = o_as + pad(n * 8 * 4), total = o_leaf + leaf_bytes;
-  rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, total);
+  rlc_saved sv;
+  rc = rlc_keep_terms(ctx, st, n, m, as, leaf_bytes, sv);
   if (rc) return rc;
-  uint8_t* sv = (uint8_t*)ctx->rlc_save;
-  leaf = sv + o_leaf;
-  uint32_t *s_scw = (uint32_t*)(sv + o_scw), *s_ptw = (uint32_t*)(sv + o_ptw), *s_as = (uint32_t*)(sv + o_as);
-  uint8_t* s_flag = sv + o_flag;
-  k_rlc_save<<<blocks_for(NS), 256, 0, st>>>((uint32_t)n, m.scw, m.ptw, m.flag, s_scw, s_ptw, s_flag);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(s_as, as, n * 8 * 4, hipMemcpyDeviceToDevice, st));
+  leaf = sv.leaf;
+  const uint8_t* s_flag = sv.flag;
 
   // error point of a sub-range
   auto sub = [&](uint32_t lo, uint32_t cnt, uint8_t E[65]) -> int {
-    msm_ws w;
-    const size_t N = 3 * (size_t)cnt + 2;
-    int r = msm_setup(ctx, N, 256 + RLC_SUM_BLOCKS * 32, w);
-    if (r) return r;
-    uint32_t* sum_part = (uint32_t*)w.aux;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, w.zero_bytes, st));
-    k_rlc_gather<<<blocks_for(3 * (size_t)cnt), 256, 0, st>>>(lo, cnt, (uint32_t)n, s_scw, s_ptw, s_flag, w.scw, w.ptw, w.flag);
-    k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>(cnt, n, s_as + lo, sum_part, w.scw, w.ptw, w.flag, N, N, 0u);
-    k_schnorr_rlc_sum<<<1, 256, 0, st>>>(cnt, n, nullptr, sum_part, w.scw, w.ptw, w.flag, N, N, ecdsa ? 1u : 0u);
-    HIP_TRY(ctx, hipGetLastError());
-    uint8_t* d_out = (uint8_t*)w.status + 64;
-    r = msm_core(ctx, st, N, w, d_out);
-    if (r) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(E, d_out, 65, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (stats) stats[0] += 1;
-    return S2K_OK;
+    int r = rlc_sub_range(ctx, st, sv, ecdsa, lo, cnt, E);
+    if (r == S2K_OK && stats) stats[0] += 1;
+    return r;
   };
   struct range {
     uint32_t lo, cnt;
@@ -2302,6 +2328,8 @@ int s2k_schnorr_verify_batch_bisect(s2k_ctx* ctx, size_t n, const uint8_t* pk, c
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   if (n == 0) return S2K_OK;
   if (!pk || !sig || !valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  // before anything is staged: n * msg_len bytes would be reserved and copied from `msgs`
+  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
   uint8_t* d[5];
   hipStream_t st;
   s2k_phase_guard phase(ctx->device, n * 128);           // (two verifiers on two threads: engine_internal.h)
@@ -2341,11 +2369,14 @@ int s2k_schnorr_batch_verify_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pk, cons
                                  const uint8_t* seed32, int* all_valid) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
+  *all_valid = 0;       // (a refusal below leaves no verdict of an earlier call behind)
   if (n == 0) {
     *all_valid = 1;
     return S2K_OK;
   }
   if (!pk || !sig) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  // before anything is staged: n * msg_len bytes would be reserved and copied from `msgs`
+  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
   uint8_t* d[5];
   hipStream_t st;
   s2k_phase_guard phase(ctx->device, n * 128);           // (two verifiers on two threads: engine_internal.h)
@@ -2456,6 +2487,102 @@ int s2k_ecdsa_verify_recoverable_batch_bisect(s2k_ctx* ctx, size_t n, const uint
   HIP_TRY(ctx, hipStreamSynchronize(st));
   ctx->have_last = false;
   return S2K_OK;
+}
+
+// ---- test hooks: the error point of a whole-batch check under a GIVEN coefficient key (see the header) ----
+// (a staged, checked batch; the context entered).  form 0: what rlc_verdict runs, with the affine record of the bisect call's
+// first pass; form 1: the plain-form terms kept and the sub-range [lo, lo + cnt) summed, by the functions rlc_bisect runs.
+static int rlc_debug_point(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* key32, int form, size_t lo,
+                           size_t cnt, uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
+  rlc_key coeff;
+  for (int j = 0; j < 8; ++j)
+    coeff.w[j] = ((uint32_t)key32[4 * j] << 24) | ((uint32_t)key32[4 * j + 1] << 16) | ((uint32_t)key32[4 * j + 2] << 8) | key32[4 * j + 3];
+  msm_ws m;
+  uint32_t* as = nullptr;
+  uint8_t h[192];
+  const uint8_t* d_flag;
+  if (form == 0) {
+    int rc = rlc_run_full(ctx, st, n, in, key32, m, &as, h, RLC_AGGREGATED, coeff, false);
+    if (rc) return rc;
+    memcpy(status, h, 4);
+    memcpy(out65, h + 64, 65);
+    d_flag = m.flag;
+  } else {
+    int rc = rlc_run_full(ctx, st, n, in, key32, m, &as, h, RLC_PLAIN_TERMS_ONLY, coeff, false);
+    if (rc) return rc;
+    // the preparation's word, over the whole batch: the sub-range step re-carves the workspace and zeroes it
+    HIP_TRY(ctx, hipMemcpyAsync(status, m.status, 4, hipMemcpyDeviceToHost, st));
+    rlc_saved sv;
+    rc = rlc_keep_terms(ctx, st, n, m, as, 0, sv);
+    if (rc) return rc;
+    rc = rlc_sub_range(ctx, st, sv, in.scheme == RLC_ECDSA, (uint32_t)lo, (uint32_t)cnt, out65);
+    if (rc) return rc;
+    d_flag = sv.flag;
+  }
+  if (in_comb) HIP_TRY(ctx, hipMemcpyAsync(in_comb, d_flag, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return S2K_OK;
+}
+static int rlc_debug_check_args(s2k_ctx* ctx, size_t n, const void* key32, int form, size_t lo, size_t cnt, const void* out65,
+                                const void* status) {
+  if (!key32 || !out65 || !status) return fail(ctx, S2K_ERR_ARG, "null argument");
+  if (n == 0 || n > MSM_DEBUG_TERMS_MAX) return fail(ctx, S2K_ERR_ARG, "batch size outside 1 .. 2^22");
+  if (form != 0 && form != 1) return fail(ctx, S2K_ERR_ARG, "form must be 0 (aggregated) or 1 (plain, sub-range)");
+  if (form == 0 ? (lo != 0 || cnt != n) : (cnt == 0 || lo >= n || cnt > n - lo))
+    return fail(ctx, S2K_ERR_ARG, "range outside the batch (the aggregated form takes the whole batch only)");
+  return S2K_OK;
+}
+// enter, run, leave: every path behind ctx_enter goes through ctx_leave, a failed one with nothing left in flight
+static int rlc_debug_run(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* key32, int form, size_t lo,
+                         size_t cnt, uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
+  int rc = ctx_enter(ctx, st);
+  if (rc) return rc;
+  rc = rlc_debug_point(ctx, st, n, in, key32, form, lo, cnt, out65, status, in_comb);
+  if (rc) s2k_internal_drain(ctx);
+  const int left = ctx_leave(ctx, st);
+  if (rc == S2K_OK && left == S2K_OK) ctx->have_last = false;   // the stream has been synchronised
+  return rc ? rc : left;
+}
+
+int s2k_debug_schnorr_rlc_point(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets, size_t msg_len,
+                                const uint8_t* sig, const uint8_t* key32, int form, size_t lo, size_t cnt, uint8_t* out65,
+                                uint32_t* status, uint8_t* in_comb) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  if (!pk || !sig) return fail(ctx, S2K_ERR_ARG, "null buffer");
+  int rc = rlc_debug_check_args(ctx, n, key32, form, lo, cnt, out65, status);
+  if (rc) return rc;
+  if (msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
+  uint8_t* d[5];
+  hipStream_t st;
+  rc = stage_schnorr(ctx, n, pk, msgs, msg_offsets, msg_len, sig, d, &st);
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  return rlc_debug_run(ctx, st, n, rlc_batch_bip340(d[0], d[1], msg_offsets ? d[2] : nullptr, msg_len, d[3]), key32, form, lo, cnt,
+                       out65, status, in_comb);
+}
+
+int s2k_debug_ecdsa_rlc_point(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                              const uint8_t* recid, uint32_t flags, const uint8_t* key32, int form, size_t lo, size_t cnt,
+                              uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
+  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
+  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
+  if (rc) return rc;
+  rc = rlc_debug_check_args(ctx, n, key32, form, lo, cnt, out65, status);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
+  uint8_t* d[6];
+  hipStream_t st;
+  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
+  if (rc) {
+    s2k_internal_drain(ctx);
+    return rc;
+  }
+  return rlc_debug_run(ctx, st, n, rlc_batch_ecdsa(d[0], d[1], d[2], d[3], d[4], flags), key32, form, lo, cnt, out65, status, in_comb);
 }
 
 }  // extern "C"

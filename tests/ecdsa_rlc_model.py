@@ -56,6 +56,58 @@ def combination(items, coeffs):
     return acc
 
 
+def in_combination(Q, digest, r, s, v, reject_malleable=False):
+    """the item passes its own checks: ranges of r, s and v, low s under the flag, a point for (r, v), a key on the curve"""
+    if not (1 <= r < N and 1 <= s < N) or v > 3 or (reject_malleable and s > N // 2):
+        return False
+    return Q is not None and Q[0] < P and Q[1] < P and pyref.on_curve(Q) and recover_point(r, v) is not None
+
+
+def item_error_with(ar, Q, digest, r, s, v):
+    """item_error over another implementation of the group (schnorr_rlc_model.Arith)"""
+    u1, u2 = scalars(digest, r, s)
+    return ar.add(recover_point(r, v), neg(ar.add(ar.base_mult(u1), ar.mul(u2, Q))))
+
+
+OUT = "out of the combination"
+
+
+def checked_error(item, ar=None, reject_malleable=False, errors=None):
+    """E_i of an item that is in the combination, OUT for one that is not; kept in `errors` (a dict) by item and flag"""
+    import schnorr_rlc_model as SM
+    key = (item, reject_malleable)
+    if errors is None or key not in errors:
+        E = item_error_with(ar or SM.PURE, *item) if in_combination(*item, reject_malleable=reject_malleable) else OUT
+        if errors is None:
+            return E
+        errors[key] = E
+    return errors[key]
+
+
+def error_point(items, key32, lo=0, cnt=None, ar=None, reject_malleable=False, errors=None):
+    """(E, status): E = sum a_i R_i - (sum a_i u1_i) G - sum (a_i u2_i) Q_i = sum of a_i E_i over the items lo <= i < lo + cnt
+    that are in the combination, a_i = schnorr_rlc_model.coefficient(key32, i) by the index in the batch; status = some item
+    of the range is out of the combination.  errors: a dict that keeps E_i by item across calls (tiled batches)."""
+    import schnorr_rlc_model as SM
+    ar = ar or SM.PURE
+    cnt = len(items) - lo if cnt is None else cnt
+    acc, status = None, False
+    for i in range(lo, lo + cnt):
+        E = checked_error(items[i], ar, reject_malleable, errors)
+        if E is OUT:
+            status = True
+        elif E is not None:
+            acc = ar.add(acc, ar.mul(SM.coefficient(key32, i), E))
+    return acc, status
+
+
+def from_arrays(b):
+    """the items of an engine batch (a key that is no point stays a pair of integers)"""
+    val = lambda row: int.from_bytes(bytes(row), "big")
+    return [((val(b["pub"][i][:32]), val(b["pub"][i][32:])), bytes(b["digest"][i]), val(b["r"][i]), val(b["s"][i]), int(b["v"][i]))
+            for i in range(len(b["v"]))]
+
+
 def sign_recoverable(d, digest, k, high_s=False, base_mult=None):
     """(r, s, v) of the nonce k: v = parity of y(k G), flipped when s is negated, bit 1 set when x(k G) >= n"""
     R = base_mult(k) if base_mult else mul(k, G)

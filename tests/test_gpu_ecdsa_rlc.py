@@ -321,3 +321,93 @@ def test_refusals(eng, oracle, good512):
     res.value = 0
     assert rlc(0, a, 0) == 0 and res.value == 1                                     # the empty batch
     check_both(eng, b, np.ones(16, np.uint8))
+
+
+# ---- 8. the error point itself, under a given coefficient key (s2k_debug_ecdsa_rlc_point) ----
+# The verdicts above are one bit per batch or per item; the value the bisection computes with is E = sum a_i E_i,
+# E_i = R_i - u1_i G - u2_i Q_i, a_i by the item's index.  With the key given it is an exact group element: compared here with
+# ecdsa_rlc_model.error_point over the oracle's arithmetic, in the aggregated form (0) and in the plain form's sub-ranges (1).
+KEY = bytes(range(32, 64))
+
+
+class PointModel:
+    def __init__(self, oracle):
+        import schnorr_rlc_model as SM
+        self.ar, self.errors = SM.oracle_arith(oracle), {}
+
+    def point(self, b, lo=0, cnt=None, reject=False):
+        items = M.from_arrays(b)
+        E, status = M.error_point(items, KEY, lo, cnt, ar=self.ar, reject_malleable=reject, errors=self.errors)
+        flags = np.array([0 if M.checked_error(it, self.ar, reject, self.errors) is M.OUT else 1 for it in items], np.uint8)
+        return pyref.enc65(E), status, flags
+
+
+@pytest.fixture(scope="module")
+def pm(oracle):
+    return PointModel(oracle)
+
+
+def check_point(eng, pm, b, reject=False):
+    """both forms over the whole batch: the model's point, status and in-combination flags; returns the record"""
+    want, status, flags = pm.point(b, reject=reject)
+    any_out = not flags.all()
+    assert status == any_out
+    for form in (0, 1):
+        res = eng.debug_ecdsa_rlc_point(*args(b), KEY, form, reject_malleable=reject)
+        assert res["out"] == want, (form, res["out"].hex(), want.hex())
+        assert (res["status"] != 0) == status, (form, res["status"])
+        assert np.array_equal(res["in_comb"], flags), (form, np.nonzero(res["in_comb"] != flags)[0][:10])
+    return want
+
+
+def test_error_point_every_position_in_turn(eng, oracle, pm, good512):
+    n = 257
+    good = tiled(good512, n)
+    assert check_point(eng, pm, good) == bytes(65)
+    seen = set()
+    for i in range(n):
+        b = copy(good)
+        b["digest"][i, 31 - i % 32] ^= 1 << (i % 8)
+        want = check_point(eng, pm, b)
+        assert want != bytes(65) and want not in seen, i
+        seen.add(want)
+
+
+@pytest.mark.parametrize("what", list(DAMAGES) + ["high s under the flag"])
+def test_error_point_of_each_way_to_be_bad(eng, oracle, pm, good512, what):
+    n, i = 300, 150
+    b = tiled(good512, n)
+    reject = what == "high s under the flag"
+    if reject:
+        put(b["s"], i, N - as_int(b["s"][i]))
+        b["v"][i] ^= 1
+    else:
+        DAMAGES[what](b, i)
+    assert truth(oracle, b, [i], reject)[0] == 0
+    want = check_point(eng, pm, b, reject)
+    out = not M.in_combination(*M.from_arrays(b)[i], reject_malleable=reject)
+    assert (want == bytes(65)) == out, what            # left out: the status word alone rejects the batch
+
+
+def test_error_point_of_sub_ranges(eng, oracle, pm, good512):
+    n = 300
+    b = tiled(good512, n)
+    for i in (0, 149, 150, 299):
+        b["digest"][i, 5] ^= 0x40
+    put(b["r"], 77, 0)                                  # out of the combination
+    whole, status, flags = pm.point(b)
+    assert status and flags.sum() == n - 1 and whole != bytes(65)
+    got = {}
+    for lo, cnt in ((0, 150), (150, 150), (0, 1), (299, 1), (1, 298), (149, 2), (0, 300), (77, 1), (78, 71)):
+        res = eng.debug_ecdsa_rlc_point(*args(b), KEY, 1, lo, cnt)
+        want, in_range, _ = pm.point(b, lo, cnt)
+        assert res["out"] == want, (lo, cnt)
+        # the status word is the preparation's, over the whole batch: item 77 is out whether the range holds it or not
+        assert res["status"] != 0 and in_range == (lo <= 77 < lo + cnt), (lo, cnt)
+        assert np.array_equal(res["in_comb"], flags)
+        got[lo, cnt] = res["out"]
+    assert got[77, 1] == bytes(65) == got[78, 71]
+    assert oracle.point_add(got[0, 150], got[150, 150]) == got[0, 300] == whole
+    assert eng.debug_ecdsa_rlc_point(*args(b), KEY, 0)["out"] == whole
+    put(b["r"], 77, as_int(tiled(good512, n)["r"][77]))
+    assert eng.debug_ecdsa_rlc_point(*args(b), KEY, 1, 150, 150)["status"] == 0
