@@ -340,13 +340,48 @@ int s2k_keyset_valid_keys(s2k_keyset *ks, uint8_t *valid /* s2k_keyset_size byte
  *   fills more than half of the free device memory (2^16 keys at S2K_KEYSET_JOINT5 are 56 GB) cannot grow this way -
  *   S2K_ERR_NOMEM, the set intact - and should be given its capacity at creation.  capacity <= s2k_keyset_capacity: S2K_OK, nothing changes.  The
  *   index is rebuilt when it has fewer than 2 * capacity slots.
- * Threading: as s2k_keyset_destroy and s2k_keyset_index_create - no call or ticket that uses the set may be in progress.
- * Not provided: removing keys. */
+ * Threading: as s2k_keyset_destroy and s2k_keyset_index_create - no call or ticket that uses the set may be in progress. */
 int s2k_keyset_create_cap(s2k_ctx *ctx, size_t n_keys, const uint8_t *pub_xy, int layout, size_t capacity, s2k_keyset **out);
 size_t s2k_keyset_capacity(const s2k_keyset *ks);
 int s2k_keyset_reserve(s2k_keyset *ks, size_t capacity);
 int s2k_keyset_append(s2k_keyset *ks, size_t n_new, const uint8_t *pub_xy /* n_new*64, host */, uint32_t *first_index /* may be NULL */);
 int s2k_keyset_append_device(s2k_keyset *ks, size_t n_new, const void *d_pub_xy /* n_new*64 */, uint32_t *first_index);
+/* Replacing and removing keys in place.  s2k_keyset_replace[_device] overwrites the live rows slots[0 .. m-1] of a set with the
+ * keys pub_xy[0 .. m-1] (X || Y, 64 bytes each; host memory, or device memory of the set's device - `slots` is host memory in
+ * both forms).  THE CONTRACT: after a successful call the set behaves, bit for bit, like a set created whole with
+ * s2k_keyset_create_cap from the key list K' of the same layout and capacity, K'[slots[j]] = pub_xy[j] and every other row
+ * unchanged - in every call that takes a set (by index, by key bytes, encoded, ECDSA and BIP-340, small and large, every
+ * layout), in s2k_keyset_valid_keys, in s2k_keyset_lookup* and in the occupied count of s2k_keyset_index_info.  A signature
+ * whose key index names a replaced row is verified under the new key.  A duplicate of the old key elsewhere in the set takes
+ * over the lookup's answer for those bytes, and a new key that duplicates a held one answers with the lower of the two rows:
+ * the index is built anew over the live rows, at the number of slots and with the seed it has.
+ * s2k_keyset_remove is s2k_keyset_replace with 64 zero bytes per slot.  (0, 0) is no point of the curve: the row is what
+ *   NewPublicKey (secec.go:188-216) would have refused - its validity byte 0, every signature under it false, never an answer
+ *   of the 33-byte and valid-x-only lookups (the 64-byte lookup of 64 zero bytes finds it, as it finds any row by its bytes).
+ * s2k_keyset_size, s2k_keyset_capacity and every other row's index are unchanged; no device address moves.  The library keeps
+ * no list of free slots: which rows are free to be reused is the caller's bookkeeping (an LRU, epochs, ...).
+ * Cost: the tables of the m keys - built, m at a time up to a bounded piece, in a staging set (at most 2 GiB, or the cap of
+ *   s2k_set_table_memory_budgets where that is smaller; a piece is at least one key) and moved to their rows by one copy kernel
+ *   per piece - and the index build.  The launches follow the pieces, not m and not how scattered the slots are.  The device
+ *   form reads its m * 64 key bytes back once (the pairs are sorted by slot on the host).
+ * S2K_ERR_ARG, before anything is touched: a NULL argument with m > 0; a slot >= s2k_keyset_size (the rows size .. capacity - 1
+ *   are s2k_keyset_append's); the same slot twice in one call.  m == 0: S2K_OK.
+ * Failure: everything the call allocates (staging, build scratch, the new index table) is allocated before the first byte of
+ *   the set changes, so S2K_ERR_NOMEM leaves the set exactly as it was.  A device failure once rows are being written leaves
+ *   the rows named by the call undefined; the index is then built over the rows as they are, and a set whose index cannot be
+ *   rebuilt keeps its tables and loses its index (s2k_keyset_index_create makes another).
+ * Threading and ordering: as s2k_keyset_append - synchronous, on the null stream, the device idle before and after; not beside
+ *   a call or ticket that uses the set. */
+int s2k_keyset_replace(s2k_keyset *ks, size_t m, const uint32_t *slots /* m, host */, const uint8_t *pub_xy /* m*64, host */);
+int s2k_keyset_replace_device(s2k_keyset *ks, size_t m, const uint32_t *slots /* m, HOST */, const void *d_pub_xy /* m*64 */);
+int s2k_keyset_remove(s2k_keyset *ks, size_t m, const uint32_t *slots /* m, host */);
+/* Test hooks of the above, pure host functions.  s2k_debug_keyset_replace_plan: the argument checks and the order a call with
+ * these slots over a set of n_live keys works in - S2K_ERR_ARG as the call; order[j] (m words, may be NULL) = the position in
+ * `slots` of the j-th smallest slot; *n_pieces (may be NULL) = the pieces of at most piece_keys slots (0: one piece).
+ * s2k_debug_keyset_replace_piece: every later call of the process works in pieces of `keys` keys (0: the automatic size). */
+int s2k_debug_keyset_replace_plan(size_t n_live, size_t m, const uint32_t *slots, size_t piece_keys, uint32_t *order /* m */,
+                                  uint64_t *n_pieces);
+int s2k_debug_keyset_replace_piece(size_t keys);
 int s2k_ecdsa_verify_batch_keyset(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint32_t *key_index /* n */,
                                   const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
 int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_key_index /* n uint32 */,
@@ -654,6 +689,10 @@ int s2k_group_keyset_create_cap(s2k_group *g, size_t n_keys, const uint8_t *pub_
 size_t s2k_group_keyset_capacity(const s2k_group_keyset *gks);
 int s2k_group_keyset_reserve(s2k_group_keyset *gks, size_t capacity);
 int s2k_group_keyset_append(s2k_group_keyset *gks, size_t n_new, const uint8_t *pub_xy /* n_new*64, host */, uint32_t *first_index);
+/* s2k_keyset_replace / s2k_keyset_remove on every member's set (host keys), on the members' threads; the size does not move.
+ * A refusal is every member's, before anything is touched; the first failing member's code is returned. */
+int s2k_group_keyset_replace(s2k_group_keyset *gks, size_t m, const uint32_t *slots /* m, host */, const uint8_t *pub_xy /* m*64, host */);
+int s2k_group_keyset_remove(s2k_group_keyset *gks, size_t m, const uint32_t *slots /* m, host */);
 int s2k_group_ecdsa_verify_batch_keyset(s2k_group *g, const s2k_group_keyset *gks, size_t n, const uint32_t *key_index,
                                         const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags,
                                         uint8_t *valid);

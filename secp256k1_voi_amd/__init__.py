@@ -246,6 +246,11 @@ def load_library() -> C.CDLL:
     lib.s2k_keyset_reserve.argtypes = [vp, sz]
     lib.s2k_keyset_append.argtypes = [vp, sz, vp, C.POINTER(u32)]
     lib.s2k_keyset_append_device.argtypes = [vp, sz, vp, C.POINTER(u32)]
+    lib.s2k_keyset_replace.argtypes = [vp, sz, vp, vp]
+    lib.s2k_keyset_replace_device.argtypes = [vp, sz, vp, vp]
+    lib.s2k_keyset_remove.argtypes = [vp, sz, vp]
+    lib.s2k_debug_keyset_replace_plan.argtypes = [sz, sz, vp, sz, vp, vp]
+    lib.s2k_debug_keyset_replace_piece.argtypes = [sz]
     lib.s2k_keyset_layout.argtypes = [vp]
     lib.s2k_keyset_destroy.argtypes = [vp]
     lib.s2k_keyset_destroy.restype = None
@@ -313,6 +318,8 @@ def load_library() -> C.CDLL:
     lib.s2k_group_keyset_capacity.restype = sz
     lib.s2k_group_keyset_reserve.argtypes = [vp, sz]
     lib.s2k_group_keyset_append.argtypes = [vp, sz, vp, C.POINTER(u32)]
+    lib.s2k_group_keyset_replace.argtypes = [vp, sz, vp, vp]
+    lib.s2k_group_keyset_remove.argtypes = [vp, sz, vp]
     lib.s2k_group_keyset_destroy.argtypes = [vp]
     lib.s2k_group_keyset_destroy.restype = None
     lib.s2k_group_keyset_size.argtypes = [vp]
@@ -445,6 +452,7 @@ EXPORTED_SYMBOLS = [
     "s2k_ecdsa_verify_batch", "s2k_ecdsa_verify_batch_device", "s2k_ecdsa_workspace_bytes", "s2k_ctx_device_bytes",
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_keyset_create_cap", "s2k_keyset_capacity", "s2k_keyset_reserve", "s2k_keyset_append", "s2k_keyset_append_device",
+    "s2k_keyset_replace", "s2k_keyset_replace_device", "s2k_keyset_remove", "s2k_debug_keyset_replace_plan", "s2k_debug_keyset_replace_piece",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_keyset_index_geometry", "s2k_keyset_index_create", "s2k_keyset_index_info", "s2k_keyset_lookup", "s2k_keyset_lookup_device",
     "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device", "s2k_ecdsa_verify_batch_keyset_bykey_submit",
@@ -463,6 +471,7 @@ EXPORTED_SYMBOLS = [
     "s2k_group_member_stats", "s2k_group_schnorr_batch_verify_rlc", "s2k_group_multi_scalar_mult",
     "s2k_group_keyset_create", "s2k_group_keyset_destroy", "s2k_group_keyset_size", "s2k_group_keyset_layout", "s2k_group_keyset_device_bytes",
     "s2k_group_keyset_create_cap", "s2k_group_keyset_capacity", "s2k_group_keyset_reserve", "s2k_group_keyset_append",
+    "s2k_group_keyset_replace", "s2k_group_keyset_remove",
     "s2k_group_ecdsa_verify_batch_keyset", "s2k_group_ecdsa_verify_batch_keyset_submit",
     "s2k_schnorr_verify_batch", "s2k_schnorr_verify_batch_device",
     "s2k_schnorr_verify_batch_keyset", "s2k_schnorr_verify_batch_keyset_device", "s2k_schnorr_verify_batch_keyset_submit",
@@ -631,6 +640,35 @@ def keyset_index_geometry(n_keys: int, log2_slots: int = 0) -> tuple:
             load_library().s2k_keyset_index_geometry(int(n_keys), int(log2_slots), out.ctypes.data) != 0:
         raise ValueError(f"no key-set index of {n_keys} keys in 2^{log2_slots} slots")
     return int(out[0]), int(out[1])
+
+
+def _slots(slots) -> np.ndarray:
+    """row numbers of a key set -> contiguous uint32 array (ValueError for what is no list of uint32 values)"""
+    a = np.asarray(slots)
+    if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError("secp256k1: slots are uint32 row numbers")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+
+
+def keyset_replace_plan(n_live: int, slots, piece_keys: int = 0) -> dict:
+    """The host-side plan of KeySet.replace / remove (s2k_debug_keyset_replace_plan; no device): the argument checks
+    (EngineError for a slot >= n_live or one named twice), `order` - the positions in `slots` in ascending order of the slot -
+    and the number of pieces of at most piece_keys slots (0: one piece)."""
+    lib = load_library()
+    slots = _slots(slots)
+    m = slots.shape[0]
+    order = np.zeros(m, dtype=np.uint32)
+    pieces = C.c_uint64(0)
+    rc = lib.s2k_debug_keyset_replace_plan(int(n_live), m, slots.ctypes.data if m else None, int(piece_keys), order.ctypes.data if m else None,
+                                           C.addressof(pieces))
+    if rc:
+        raise EngineError(f"s2k error {rc}: {lib.s2k_last_error(None).decode()}")
+    return dict(order=order, pieces=int(pieces.value))
+
+
+def debug_keyset_replace_piece(keys: int) -> None:
+    """Test knob (s2k_debug_keyset_replace_piece): KeySet.replace / remove work in pieces of `keys` keys; 0: automatic."""
+    load_library().s2k_debug_keyset_replace_piece(int(keys))
 
 
 def msm_segments_plan(n: int, offsets, piece_terms: int = 0, crossover: int = 0, arrays: bool = True) -> dict:
@@ -1983,6 +2021,20 @@ class GroupKeySet:
                                                                 C.byref(first)))
         return int(first.value)
 
+    def replace(self, slots, pub_xy):
+        """s2k_group_keyset_replace: the live rows `slots` of every member's set overwritten with the keys pub_xy (host)"""
+        slots, pub_xy = _slots(slots), _arr(pub_xy, 64)
+        m = slots.shape[0]
+        if pub_xy.nbytes != m * 64:
+            raise ValueError("secp256k1: len(slots) * 64 != len(pub_xy)")
+        self._grp._check(self._grp._lib.s2k_group_keyset_replace(self._k, m, slots.ctypes.data if m else None, pub_xy.ctypes.data if m else None))
+
+    def remove(self, slots):
+        """s2k_group_keyset_remove: the live rows `slots` of every member's set made "no key" """
+        slots = _slots(slots)
+        m = slots.shape[0]
+        self._grp._check(self._grp._lib.s2k_group_keyset_remove(self._k, m, slots.ctypes.data if m else None))
+
     def layout(self) -> int:
         return int(self._grp._lib.s2k_group_keyset_layout(self._k))
 
@@ -2112,6 +2164,34 @@ class KeySet:
         n = pub_xy.shape[0]
         self._check_own(self._eng._lib.s2k_keyset_append(self._k, n, pub_xy.ctypes.data if n else None, C.byref(first)))
         return int(first.value)
+
+    def replace(self, slots, pub_xy):
+        """The live rows `slots` (uint32, each below len(), none twice) overwritten with the keys pub_xy (len(slots) x 64 bytes:
+        host bytes / arrays, or a torch uint8 tensor on the set's device) - s2k_keyset_replace[_device].  Afterwards the set is,
+        in every call, the set created whole from the changed key list; len(), capacity() and every other row's index stay, and
+        the set's index follows.  Which rows are free to reuse is the caller's bookkeeping.  No call or ticket that uses the set
+        may be in progress."""
+        slots = _slots(slots)
+        m = slots.shape[0]
+        if hasattr(pub_xy, "data_ptr") and hasattr(pub_xy, "is_cuda"):
+            t = pub_xy
+            if not t.is_cuda or t.element_size() != 1 or t.numel() != m * 64:
+                raise ValueError("secp256k1: a device tensor of len(slots) x 64 bytes")
+            t = t.contiguous()
+            self._check_own(self._eng._lib.s2k_keyset_replace_device(self._k, m, slots.ctypes.data if m else None, t.data_ptr() if m else None))
+            return
+        pub_xy = _arr(pub_xy, 64)
+        if pub_xy.nbytes != m * 64:
+            raise ValueError("secp256k1: len(slots) * 64 != len(pub_xy)")
+        self._check_own(self._eng._lib.s2k_keyset_replace(self._k, m, slots.ctypes.data if m else None, pub_xy.ctypes.data if m else None))
+
+    def remove(self, slots):
+        """The live rows `slots` made "no key" (s2k_keyset_remove: replace with 64 zero bytes each): every signature under them
+        verifies false, valid_keys() says 0 and the lookups of valid keys never answer them.  The rows stay rows: len() does not
+        move, and replace() puts a key back."""
+        slots = _slots(slots)
+        m = slots.shape[0]
+        self._check_own(self._eng._lib.s2k_keyset_remove(self._k, m, slots.ctypes.data if m else None))
 
     def layout(self) -> int:
         """The layout the set has: KEYSET_CHUNKS, KEYSET_JOINT, KEYSET_JOINT5, KEYSET_JOINT6 or KEYSET_COMB (s2k_keyset_layout)."""

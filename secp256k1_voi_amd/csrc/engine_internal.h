@@ -633,6 +633,12 @@ int s2k_internal_keyset_build_joint_wide(s2k_ctx* ctx, const uint8_t* base, size
 int s2k_internal_keyset_reserve(s2k_ctx* ctx, size_t nkeys, size_t n);
 int s2k_internal_keyset_sort(s2k_ctx* ctx, const uint8_t* set_base, size_t cap, size_t nkeys, size_t n, const uint32_t* d_kidx, hipStream_t st,
                              key_groups* out, int chunks = KS_CHUNKS);
+// replacing rows of a set (keyset_replace.hip; s2k_keyset_replace, keyset.hip): the host plan of a call (s2k_debug_keyset_replace_plan),
+// the keys of a piece for a layout, and the rows 0 .. count - 1 of a staging set moved to the rows d_slots[] of the set
+int s2k_internal_keyset_replace_plan(size_t n_live, size_t m, const uint32_t* slots, size_t piece_keys, uint32_t* order, uint64_t* n_pieces);
+size_t s2k_internal_keyset_replace_piece(int chunks, int jw);
+int s2k_internal_keyset_scatter_rows(const uint8_t* stage, size_t stage_cap, const uint4* stage_joint, uint8_t* base, size_t cap, uint4* joint,
+                                     int jw, int chunks, const uint32_t* d_slots, size_t count);
 
 // the index of a key set, key bytes -> key index (keyset_index.hip; the table and its probe loops: keyset_index.h).  Enqueue
 // only.  build: inserts the keys first .. first + count - 1; `slots` (2^log2_slots words of 64 bits) all ones and `info`

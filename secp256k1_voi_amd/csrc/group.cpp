@@ -509,6 +509,8 @@ extern "C" int s2k_keyset_create_cap(s2k_ctx* ctx, size_t n_keys, const uint8_t*
 extern "C" size_t s2k_keyset_capacity(const s2k_keyset* ks) __attribute__((weak));
 extern "C" int s2k_keyset_reserve(s2k_keyset* ks, size_t capacity) __attribute__((weak));
 extern "C" int s2k_keyset_append(s2k_keyset* ks, size_t n_new, const uint8_t* pub_xy, uint32_t* first_index) __attribute__((weak));
+extern "C" int s2k_keyset_replace(s2k_keyset* ks, size_t m, const uint32_t* slots, const uint8_t* pub_xy) __attribute__((weak));
+extern "C" int s2k_keyset_remove(s2k_keyset* ks, size_t m, const uint32_t* slots) __attribute__((weak));
 int s2k_group_keyset_create(s2k_group* g, size_t n_keys, const uint8_t* pub_xy, int layout, s2k_group_keyset** out) {
   return s2k_group_keyset_create_cap(g, n_keys, pub_xy, layout, 0, out);
 }
@@ -585,6 +587,20 @@ int s2k_group_keyset_append(s2k_group_keyset* gks, size_t n_new, const uint8_t* 
   if (first_index) *first_index = (uint32_t)gks->n_keys;
   gks->n_keys += n_new;
   return S2K_OK;
+}
+// s2k_keyset_replace / s2k_keyset_remove on every member's set: the count does not move.  (A slot the members refuse they all
+// refuse, before anything is touched; after a device failure on one member its set differs from the others'.)
+int s2k_group_keyset_replace(s2k_group_keyset* gks, size_t m, const uint32_t* slots, const uint8_t* pub_xy) {
+  if (!gks) return S2K_ERR_ARG;
+  if (!s2k_keyset_replace) return gfail(gks->group, S2K_ERR_ARG, "contexts without s2k_keyset_replace");
+  if (m && (!slots || !pub_xy)) return gfail(gks->group, S2K_ERR_ARG, "null argument");
+  return m ? group_keyset_each(gks, "replace", [=](s2k_keyset* ks) { return s2k_keyset_replace(ks, m, slots, pub_xy); }) : S2K_OK;
+}
+int s2k_group_keyset_remove(s2k_group_keyset* gks, size_t m, const uint32_t* slots) {
+  if (!gks) return S2K_ERR_ARG;
+  if (!s2k_keyset_remove) return gfail(gks->group, S2K_ERR_ARG, "contexts without s2k_keyset_remove");
+  if (m && !slots) return gfail(gks->group, S2K_ERR_ARG, "null argument");
+  return m ? group_keyset_each(gks, "remove", [=](s2k_keyset* ks) { return s2k_keyset_remove(ks, m, slots); }) : S2K_OK;
 }
 // layout and device memory of the set on the group's first member (the members hold the same set; with S2K_KEYSET_AUTO a
 // member short of memory may have fallen back to chunk tables on its own)

@@ -351,14 +351,20 @@ int s2k_keyset_index_geometry(size_t n_keys, uint32_t log2_slots, uint64_t out[2
 }
 // A fresh index of the keys 0 .. nkeys - 1 of the set in 2^lg slots: allocated, filled and read back on the null stream
 // (synchronous).  The set is not touched: the caller puts the table in (keyset_index_adopt).
-static int keyset_index_make(const s2k_keyset* ks, size_t nkeys, uint32_t lg, uint64_t seed, uint64_t** out_slots, uint32_t h[S2K_KSI_INFO_WORDS]) {
-  const size_t nslots = (size_t)1 << lg, bytes = nslots * sizeof(uint64_t);
-  uint64_t* slots = nullptr;
-  hipError_t e = hipMalloc((void**)&slots, bytes + S2K_KSI_INFO_WORDS * sizeof(uint32_t));
+// (its two halves apart for s2k_keyset_replace, which allocates before it writes a row and fills afterwards: keyset_index_alloc,
+// and keyset_index_fill, which frees the table when it fails)
+static int keyset_index_alloc(uint32_t lg, uint64_t** out_slots) {
+  const size_t bytes = ((size_t)1 << lg) * sizeof(uint64_t);
+  hipError_t e = hipMalloc((void**)out_slots, bytes + S2K_KSI_INFO_WORDS * sizeof(uint32_t));
   if (e != hipSuccess) {
     (void)hipGetLastError();
+    *out_slots = nullptr;
     return fail(nullptr, S2K_ERR_NOMEM, "key-set index of %zu bytes: %s", bytes, hipGetErrorString(e));
   }
+  return S2K_OK;
+}
+static int keyset_index_fill(const s2k_keyset* ks, size_t nkeys, uint32_t lg, uint64_t seed, uint64_t* slots, uint32_t h[S2K_KSI_INFO_WORDS]) {
+  const size_t nslots = (size_t)1 << lg, bytes = nslots * sizeof(uint64_t);
   uint32_t* info = reinterpret_cast<uint32_t*>(slots + nslots);
   const keyset_view v = s2k_internal_keyset_view(ks->base, ks->cap, ks->chunks);
   int rc = S2K_OK;
@@ -372,8 +378,14 @@ static int keyset_index_make(const s2k_keyset* ks, size_t nkeys, uint32_t lg, ui
   if (rc) {
     (void)hipDeviceSynchronize();
     (void)hipFree(slots);
-    return rc;
   }
+  return rc;
+}
+static int keyset_index_make(const s2k_keyset* ks, size_t nkeys, uint32_t lg, uint64_t seed, uint64_t** out_slots, uint32_t h[S2K_KSI_INFO_WORDS]) {
+  uint64_t* slots = nullptr;
+  int rc = keyset_index_alloc(lg, &slots);
+  if (rc == S2K_OK) rc = keyset_index_fill(ks, nkeys, lg, seed, slots, h);
+  if (rc) return rc;
   *out_slots = slots;
   return S2K_OK;
 }
@@ -553,6 +565,111 @@ int s2k_keyset_reserve(s2k_keyset* ks, size_t capacity) {
   if (ks->index && ((uint64_t)1 << ks->index_log2) < 2 * (uint64_t)capacity) return keyset_index_rebuild(ks, ks->n);
   return S2K_OK;
 }
+// ---------------------------------------------------------------------------------------
+// Replacing keys.  The table kernels build table t at row t of a contiguous range, so the new keys' tables are built in a
+// STAGING SET - buffers laid out as a set of `piece` keys is, built as a creation of that many keys is - and
+// k_ks_scatter_rows (keyset_replace.hip) moves its rows to their slots; a call with more slots than a piece runs piece after
+// piece through the same buffers, the (slot, key) pairs in ascending order of the slot.  The launches follow the pieces, never
+// the slots.  The index is not patched - a slot of its table belongs to one 64-byte string forever (keyset_index.h) - but
+// built anew over the rows 0 .. n - 1, at the geometry and the seed it has, into a table allocated, like everything else the
+// call needs, before the first byte of the set changes.  As the append: the null stream, the device idle before and after.
+// ---------------------------------------------------------------------------------------
+// (src: m keys in the order of `slots`, host or device memory; null: 64 zero bytes each - no point of the curve)
+static int keyset_replace(s2k_keyset* ks, size_t m, const uint32_t* slots, const void* src, bool on_device, bool remove) {
+  if (!ks) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (m == 0) return S2K_OK;
+  if (!slots || (!src && !remove)) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  uint32_t* order = new (std::nothrow) uint32_t[m];
+  uint32_t* sorted = new (std::nothrow) uint32_t[m];
+  uint8_t* keys = (uint8_t*)calloc(m, 64);
+  uint8_t *stage = nullptr, *d_slots = nullptr;
+  uint4 *stage_joint = nullptr, *scratch = nullptr;
+  uint64_t* table = nullptr;
+  auto done = [&](int rc) {
+    (void)hipFree(stage);
+    (void)hipFree(stage_joint);
+    (void)hipFree(scratch);
+    (void)hipFree(d_slots);
+    (void)hipFree(table);
+    free(keys);
+    delete[] sorted;
+    delete[] order;
+    return rc;
+  };
+  if (!order || !sorted || !keys) return done(fail(nullptr, S2K_ERR_NOMEM, "out of host memory"));
+  int rc = s2k_internal_keyset_replace_plan(ks->n, m, slots, 0, order, nullptr);
+  if (rc) return done(rc);
+  size_t piece = s2k_internal_keyset_replace_piece(ks->chunks, ks->joint ? ks->jw : 0);
+  if (piece > m) piece = m;
+  if (hipSetDevice(ks->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)      // (the rule of s2k_keyset_destroy: no call that uses the set is in progress)
+    return done(fail(nullptr, S2K_ERR_HIP, "key-set replace: the device of the set"));
+  if (src && on_device) {
+    // (sorted on the host like a caller's host keys: m * 64 bytes come back once)
+    uint8_t* given = (uint8_t*)malloc(m * 64);
+    if (!given) return done(fail(nullptr, S2K_ERR_NOMEM, "out of host memory"));
+    const hipError_t e = hipMemcpy(given, src, m * 64, hipMemcpyDeviceToHost);
+    for (size_t j = 0; j < m && e == hipSuccess; ++j) memcpy(keys + j * 64, given + (size_t)order[j] * 64, 64);
+    free(given);
+    if (e != hipSuccess) return done(fail(nullptr, S2K_ERR_HIP, "copy of the keys failed"));
+  } else if (src) {
+    for (size_t j = 0; j < m; ++j) memcpy(keys + j * 64, (const uint8_t*)src + (size_t)order[j] * 64, 64);
+  }
+  for (size_t j = 0; j < m; ++j) sorted[j] = slots[order[j]];
+  // everything the call allocates, before the first byte of the set changes
+  size_t off[5];
+  const size_t stage_bytes = s2k_internal_keyset_bytes(piece, off, ks->chunks);
+  const size_t joint_bytes = ks->joint ? s2k_internal_keyset_joint_bytes(piece, ks->jw) : 0;
+  const size_t scratch_bytes = ks->joint ? s2k_internal_keyset_joint_scratch_bytes(piece, ks->jw) : 0;
+  hipError_t e = hipMalloc((void**)&stage, stage_bytes);
+  if (e == hipSuccess && joint_bytes) e = hipMalloc((void**)&stage_joint, joint_bytes);
+  if (e == hipSuccess && scratch_bytes) e = hipMalloc((void**)&scratch, scratch_bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_slots, m * sizeof(uint32_t));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return done(fail(nullptr, S2K_ERR_NOMEM, "key-set replace: %zu bytes of staging for %zu keys a piece: %s", stage_bytes + joint_bytes + scratch_bytes,
+                     piece, hipGetErrorString(e)));
+  }
+  if (ks->index && (rc = keyset_index_alloc(ks->index_log2, &table)) != S2K_OK) return done(rc);
+  if (hipMemcpy(d_slots, sorted, m * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+    return done(fail(nullptr, S2K_ERR_HIP, "copy of the slots failed"));
+  const keyset_view sv = s2k_internal_keyset_view(stage, piece, ks->chunks);
+  bool touched = false;
+  for (size_t first = 0; first < m && rc == S2K_OK; first += piece) {
+    const size_t count = m - first < piece ? m - first : piece;
+    if (hipMemcpy(sv.keys, keys + first * 64, count * 64, hipMemcpyHostToDevice) != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "copy of the keys failed");
+    if (rc == S2K_OK) rc = s2k_internal_keyset_build(nullptr, stage, piece, 0, count, nullptr, ks->chunks);
+    if (rc == S2K_OK && ks->joint)
+      rc = ks->jw == 4 ? s2k_internal_keyset_build_joint(nullptr, stage, piece, 0, count, stage_joint, nullptr)
+                       : s2k_internal_keyset_build_joint_wide(nullptr, stage, piece, 0, count, ks->jw, stage_joint, scratch, nullptr);
+    // (a build that failed has written staging only: the set is as it was)
+    if (rc == S2K_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set replace: the table build failed");
+    if (rc) break;
+    touched = true;
+    rc = s2k_internal_keyset_scatter_rows(stage, piece, stage_joint, ks->base, ks->cap, ks->joint, ks->jw, ks->chunks, (const uint32_t*)d_slots + first, count);
+    if (rc == S2K_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(nullptr, S2K_ERR_HIP, "key-set replace: moving the rows failed");
+  }
+  // the index of the rows as they are now - also after a failure that left some of them written - or, failing that, none
+  if (ks->index && touched) {
+    (void)hipGetLastError();
+    uint32_t h[S2K_KSI_INFO_WORDS] = {0, 0, 0, 0};
+    const int irc = keyset_index_fill(ks, ks->n, ks->index_log2, ks->index_seed, table, h);
+    if (irc == S2K_OK) keyset_index_adopt(ks, table, ks->index_log2, ks->index_seed, h);
+    else {
+      (void)hipFree(ks->index);
+      ks->index = nullptr;
+      if (rc == S2K_OK) rc = irc;
+    }
+    table = nullptr;      // (adopted, or freed by the fill that failed)
+  }
+  return done(rc);
+}
+int s2k_keyset_replace(s2k_keyset* ks, size_t m, const uint32_t* slots, const uint8_t* pub_xy) {
+  return keyset_replace(ks, m, slots, pub_xy, false, false);
+}
+int s2k_keyset_replace_device(s2k_keyset* ks, size_t m, const uint32_t* slots, const void* d_pub_xy) {
+  return keyset_replace(ks, m, slots, d_pub_xy, true, false);
+}
+int s2k_keyset_remove(s2k_keyset* ks, size_t m, const uint32_t* slots) { return keyset_replace(ks, m, slots, nullptr, false, true); }
 int s2k_keyset_index_info(const s2k_keyset* ks, uint64_t out[4]) {
   if (!ks || !out) return fail(nullptr, S2K_ERR_ARG, "null argument");
   out[0] = ks->index ? (uint64_t)1 << ks->index_log2 : 0;
