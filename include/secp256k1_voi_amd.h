@@ -712,7 +712,9 @@ size_t s2k_ecdsa_workspace_bytes(size_t n);
  * settings (s2k_ctx_set_key_grouping): the resident generator tables (40 GiB), the per-signature workspace above, and -
  * with the grouping on, the default, for n >= 256 - the grouping arrays and the per-key table buffer (n / min_group
  * tables of 9 KiB, at most max_tables: 2.4 GB at n = 2^20, 38 GB at 2^24, whether or not keys repeat).  The multi-scalar and BIP-340
- * batch entry points keep a workspace of their own on top (about 1.4 KB per term).  Size HBM by this, not by
+ * batch entry points keep a workspace of their own on top (about 1.4 KB per term), and the verification calls that take
+ * messages (s2k_ecdsa_verify_messages_batch*) a digest buffer of 32 n bytes, allocated on the first such call: neither is
+ * counted here, and what this function returns for given settings is what it always returned.  Size HBM by this, not by
  * s2k_ecdsa_workspace_bytes alone, when several contexts share a device. */
 size_t s2k_ctx_device_bytes(const s2k_ctx *ctx, size_t n);
 
@@ -1252,6 +1254,82 @@ int s2k_fp_op_batch_ex8(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, uint
  * Serves splitGLV (point_mul_glv.go:59); impl must be S2K_IMPL_FAST. */
 int s2k_fn_split_glv_batch_ex(s2k_ctx *ctx, uint32_t impl, size_t n, const uint8_t *k, uint8_t *k1, uint8_t *k2,
                               uint8_t *signs);
+
+/* ---- SHA-2 message digests on the device, and ECDSA verification from messages -------- */
+/* The reference's ECDSA callers start from a message and a hash: h := sha256.Sum256(m); pk.Verify(h[:], sig, opts).  The
+ * calls above take h; these take m and hash on the device (one lane per message), so no per-item work is left on the host.
+ *   S2K_HASH_SHA256   SHA-256(m)
+ *   S2K_HASH_SHA256D  SHA-256(SHA-256(m)), Bitcoin's message hash: one more compression
+ *   S2K_HASH_SHA512   SHA-512(m); a verification call uses its leftmost 32 bytes, which is what the reference's hashToScalar
+ *                     does with a hash longer than the order (secec/ecdsa.go:477-486)
+ * Messages follow the convention of s2k_schnorr_verify_batch: n strings of msg_len bytes each (msg_offsets == NULL), or one
+ * blob with msg_offsets[n + 1] byte offsets (any lengths, zero included; msg_offsets[0] need not be 0).  Every message is
+ * shorter than 2^31 bytes.
+ *
+ * s2k_digest_batch: out[i * out_len .. + out_len) = the digest of message i.  out_len is 32 - the whole SHA-256 / SHA-256d
+ * digest, or the leftmost 32 bytes of SHA-512 - or 64 with S2K_HASH_SHA512, the whole digest.  This is the digest the
+ * verification calls take: the encoded, recovery, whole-batch and group calls have no messages form of their own and are
+ * reached as s2k_digest_batch_device followed by the existing call on the same stream, without a host round trip.
+ * _device: device pointers, chained on the caller's stream like the other *_device forms; does not synchronise.
+ *
+ * s2k_ecdsa_verify_messages_batch[_device/_submit], ..._keyset[_device], ..._keyset_bykey[_device]: the arguments of
+ * s2k_ecdsa_verify_batch[...] and its key-set forms with digest32 replaced by (alg, msgs, msg_offsets, msg_len).  Each runs
+ * the digest kernel into a buffer of the context (32 bytes per item, allocated on the first such call and kept), then the
+ * unchanged path of its digest sibling on the same stream: valid[i] is bit for bit what the sibling gives on the digests of
+ * the messages, on every ladder its dispatch picks, and s2k_ctx_key_grouping_stats / s2k_ctx_last_keyset_ladder read as
+ * after the sibling.  _submit: messages, offsets, keys and signatures must stay alive until s2k_wait, like the other inputs.
+ *
+ * S2K_ERR_ARG before anything is launched, outputs untouched, for every form: an unknown alg, a NULL buffer with n > 0,
+ * msg_len >= 2^31, an out_len other than the above, n >= 2^30, and whatever the digest sibling refuses (a key set of another
+ * context, S2K_ECDSA_FORCE_COMPLETE over a key set, ...).  n == 0 succeeds and writes nothing.
+ * The HOST forms scan the offsets and refuse, the same way, offsets that decrease and items of 2^31 bytes or more.
+ * PRECONDITION of the _device forms, as for s2k_schnorr_verify_batch_device: the offsets on the device never decrease, every
+ * item is shorter than 2^31 bytes and msg_offsets[n] is within the blob.  They cannot check this without a round trip and do
+ * not: a decreasing offset makes the device read outside the blob.
+ *
+ * Cost: lanes of a wavefront with different block counts run to the longest of them, so a batch with one very long message
+ * is slow, not wrong; there is no second kernel for it.  Out of scope here: messages forms of the encoded, recovery,
+ * whole-batch and group calls (see above), other hash functions, tagged hashes (BIP-340's challenge is computed by the
+ * Schnorr calls), and a cooperative kernel for single huge messages.
+ * s2k_ctx_device_bytes does not count the 32 n bytes of the digest buffer.
+ *
+ * Test hooks.  s2k_debug_digest_caps: out[0] = the bytes of LDS a workgroup stages the stretch of its 256 messages in; a
+ * stretch at addresses [lo, hi) is staged when (hi - (lo & ~15)) + 16 <= that capacity, else read in place.
+ * s2k_debug_digest_strided: s2k_digest_batch with rows out_stride (out_len .. 4096) bytes apart; out[n * out_stride] goes to
+ * the device as the caller filled it and comes back whole, so the bytes between the rows show that they were not written. */
+#define S2K_HASH_SHA256 0
+#define S2K_HASH_SHA256D 1
+#define S2K_HASH_SHA512 2
+int s2k_digest_batch(s2k_ctx *ctx, int alg, size_t n, const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                     uint8_t *out /* n*out_len */, size_t out_len);
+int s2k_digest_batch_device(s2k_ctx *ctx, int alg, size_t n, const void *d_msgs, const void *d_msg_offsets, size_t msg_len,
+                            void *d_out, size_t out_len, void *hip_stream);
+int s2k_ecdsa_verify_messages_batch(s2k_ctx *ctx, size_t n, const uint8_t *pub_xy /* n*64 */, int alg, const uint8_t *msgs,
+                                    const uint64_t *msg_offsets, size_t msg_len, const uint8_t *r /* n*32 */,
+                                    const uint8_t *s /* n*32 */, uint32_t flags, uint8_t *valid /* n */);
+int s2k_ecdsa_verify_messages_batch_device(s2k_ctx *ctx, size_t n, const void *d_pub_xy, int alg, const void *d_msgs,
+                                           const void *d_msg_offsets, size_t msg_len, const void *d_r, const void *d_s,
+                                           uint32_t flags, void *d_valid, void *hip_stream);
+int s2k_ecdsa_verify_messages_batch_submit(s2k_ctx *ctx, size_t n, const uint8_t *pub_xy, int alg, const uint8_t *msgs,
+                                           const uint64_t *msg_offsets, size_t msg_len, const uint8_t *r, const uint8_t *s,
+                                           uint32_t flags, uint8_t *valid, s2k_ticket *ticket);
+int s2k_ecdsa_verify_messages_batch_keyset(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint32_t *key_index /* n */,
+                                           int alg, const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                                           const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
+int s2k_ecdsa_verify_messages_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_key_index,
+                                                  int alg, const void *d_msgs, const void *d_msg_offsets, size_t msg_len,
+                                                  const void *d_r, const void *d_s, uint32_t flags, void *d_valid,
+                                                  void *hip_stream);
+int s2k_ecdsa_verify_messages_batch_keyset_bykey(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint8_t *pub_xy, int alg,
+                                                 const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                                                 const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
+int s2k_ecdsa_verify_messages_batch_keyset_bykey_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_pub_xy,
+                                                        int alg, const void *d_msgs, const void *d_msg_offsets, size_t msg_len,
+                                                        const void *d_r, const void *d_s, uint32_t flags, void *d_valid,
+                                                        void *hip_stream);
+int s2k_debug_digest_caps(uint32_t out[1]);
+int s2k_debug_digest_strided(s2k_ctx *ctx, int alg, size_t n, const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
+                             uint8_t *out /* n*out_stride */, size_t out_len, size_t out_stride);
 
 /* ---- introspection used by the tests ------------------------------------------------ */
 /* Copies generator-table entry T_i[d] (X‖Y big-endian) to out64.  Layout: DESIGN.md §3. */

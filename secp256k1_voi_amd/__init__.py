@@ -42,6 +42,7 @@ BIP0066 = 2
 FORCE_COMPLETE = 0x80000000
 FORCE_WORKLIST = 0x40000000
 ENCODING_ASN1, ENCODING_COMPACT, ENCODING_COMPACT_RECOVERABLE = 0, 1, 2
+HASH_SHA256, HASH_SHA256D, HASH_SHA512 = 0, 1, 2    # S2K_HASH_*: the digest of the calls that take messages
 
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_NEG, OP_INV, OP_SQRT = range(7)
 IMPL_COMPLETE, IMPL_FAST = 0, 1
@@ -292,6 +293,17 @@ def load_library() -> C.CDLL:
     lib.s2k_ctx_last_encoded_keyset_stats.argtypes = [vp, C.POINTER(u64)]
     lib.s2k_debug_parse_encoded.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, sz, ci, sz, u32, ci, C.c_uint8, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.s2k_debug_parse_encoded_caps.argtypes = [vp]
+    lib.s2k_digest_batch.argtypes = [vp, ci, sz, vp, vp, sz, vp, sz]
+    lib.s2k_digest_batch_device.argtypes = [vp, ci, sz, vp, vp, sz, vp, sz, vp]
+    lib.s2k_debug_digest_caps.argtypes = [vp]
+    lib.s2k_debug_digest_strided.argtypes = [vp, ci, sz, vp, vp, sz, vp, sz, sz]
+    lib.s2k_ecdsa_verify_messages_batch.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp]
+    lib.s2k_ecdsa_verify_messages_batch_device.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, vp]
+    lib.s2k_ecdsa_verify_messages_batch_submit.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, C.POINTER(u64)]
+    lib.s2k_ecdsa_verify_messages_batch_keyset.argtypes = [vp, vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp]
+    lib.s2k_ecdsa_verify_messages_batch_keyset_device.argtypes = [vp, vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, vp]
+    lib.s2k_ecdsa_verify_messages_batch_keyset_bykey.argtypes = [vp, vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp]
+    lib.s2k_ecdsa_verify_messages_batch_keyset_bykey_device.argtypes = [vp, vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, vp]
     lib.s2k_wait.argtypes = [vp, u64]
     lib.s2k_poll.argtypes = [vp, u64]
     lib.s2k_wait_all.argtypes = [vp]
@@ -464,6 +476,10 @@ EXPORTED_SYMBOLS = [
     "s2k_ecdsa_verify_encoded_batch",
     "s2k_ecdsa_verify_encoded_batch_keyset", "s2k_ecdsa_verify_encoded_batch_keyset_submit", "s2k_ctx_last_encoded_keyset_stats",
     "s2k_debug_parse_encoded", "s2k_debug_parse_encoded_caps",
+    "s2k_digest_batch", "s2k_digest_batch_device", "s2k_debug_digest_caps", "s2k_debug_digest_strided",
+    "s2k_ecdsa_verify_messages_batch", "s2k_ecdsa_verify_messages_batch_device", "s2k_ecdsa_verify_messages_batch_submit",
+    "s2k_ecdsa_verify_messages_batch_keyset", "s2k_ecdsa_verify_messages_batch_keyset_device",
+    "s2k_ecdsa_verify_messages_batch_keyset_bykey", "s2k_ecdsa_verify_messages_batch_keyset_bykey_device",
     "s2k_ecdsa_verify_batch_submit", "s2k_ecdsa_verify_encoded_batch_submit", "s2k_wait", "s2k_poll", "s2k_wait_all",
     "s2k_device_count", "s2k_group_create", "s2k_group_destroy", "s2k_group_size", "s2k_group_last_error",
     "s2k_group_set_key_grouping", "s2k_group_set_small_batch_max", "s2k_group_set_mid_batch_max", "s2k_group_ecdsa_verify_batch", "s2k_group_ecdsa_verify_batch_submit", "s2k_group_wait",
@@ -621,6 +637,47 @@ def parse_encoded_caps() -> tuple:
     if load_library().s2k_debug_parse_encoded_caps(out.ctypes.data) != 0:
         raise EngineError("s2k_debug_parse_encoded_caps failed")
     return tuple(int(v) for v in out)
+
+
+def digest_caps() -> int:
+    """Bytes of LDS the digest kernel stages a workgroup's stretch of messages in (s2k_debug_digest_caps; no device)."""
+    out = np.zeros(1, dtype=np.uint32)
+    if load_library().s2k_debug_digest_caps(out.ctypes.data) != 0:
+        raise EngineError("s2k_debug_digest_caps failed")
+    return int(out[0])
+
+
+def _messages(msgs, n=None):
+    """Messages as the calls that hash on the device take them: a list of byte strings, a (blob, offsets) pair - blob a bytes
+    object or uint8 array, offsets n + 1 byte offsets into it, used as they are - or an (n, L) uint8 array of fixed-length
+    messages.  Returns (n, blob address or None, offsets address or None, msg_len, arrays to keep alive)."""
+    if isinstance(msgs, tuple) and len(msgs) == 2 and isinstance(msgs[1], (np.ndarray, list)):
+        blob, offs = msgs
+        if isinstance(blob, (bytes, bytearray, memoryview)):
+            blob = np.frombuffer(bytes(blob) or b"\0", dtype=np.uint8)
+        elif not (isinstance(blob, np.ndarray) and blob.dtype == np.uint8 and blob.flags["C_CONTIGUOUS"]):
+            blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        if not (isinstance(offs, np.ndarray) and offs.dtype == np.uint64 and offs.flags["C_CONTIGUOUS"]):
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if offs.shape[0] < 1:
+            raise ValueError("offsets: n + 1 entries are needed")
+        m, keep = offs.shape[0] - 1, [blob, offs]
+        ret = (blob.ctypes.data if blob.size else None, offs.ctypes.data, 0)
+    elif isinstance(msgs, (list, tuple)):
+        offs = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(bytes(x) for x in msgs) or b"\0", dtype=np.uint8)
+        m, keep = len(msgs), [blob, offs]
+        ret = (blob.ctypes.data, offs.ctypes.data, 0)
+    else:
+        a = msgs if (isinstance(msgs, np.ndarray) and msgs.dtype == np.uint8 and msgs.flags["C_CONTIGUOUS"]) else np.ascontiguousarray(msgs, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("fixed-length messages: an (n, L) uint8 array is needed")
+        m, keep = a.shape[0], [a]
+        ret = (a.ctypes.data if a.size else None, None, a.shape[1])
+    if n is not None and m != n:
+        raise ValueError(f"length mismatch: expected {n} messages, got {m}")
+    return (m,) + ret + (keep,)
 
 
 def keyset_geometry(layout: int) -> tuple:
@@ -1158,6 +1215,102 @@ class Engine(_TicketOwner):
         """Device-pointer form: integer device addresses, enqueued on `stream` (a hipStream_t value)."""
         self._check(self._lib.s2k_ecdsa_verify_batch_device(self._h, int(n), d_pub_xy, d_digest32, d_r, d_s,
                                                             int(flags), d_valid, stream))
+
+    # ---- SHA-2 digests on the device, and ECDSA verification from messages (digest.hip) ----------
+    def digest_batch(self, msgs, alg: int = HASH_SHA256, out_len: int = 32, out_stride: int = 0, out=None) -> np.ndarray:
+        """s2k_digest_batch: (n, out_len) digests of the messages (`msgs`: a list of byte strings, a (blob, offsets) pair or an
+        (n, L) uint8 array); alg HASH_SHA256 / HASH_SHA256D / HASH_SHA512, out_len 32 or, with HASH_SHA512, 64.
+        out_stride (test hook s2k_debug_digest_strided): rows that far apart in `out`, an (n, out_stride) uint8 array that
+        goes to the device as it is and comes back with only the first out_len bytes of each row written."""
+        n, blob, offs, mlen, keep = _messages(msgs)
+        if out_stride:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape == (n, out_stride)):
+                raise ValueError("out: a contiguous (n, out_stride) uint8 array is needed")
+            self._check(self._lib.s2k_debug_digest_strided(self._h, int(alg), n, blob, offs, mlen, out.ctypes.data, int(out_len), int(out_stride)))
+            return out
+        res = np.zeros((n, int(out_len)), dtype=np.uint8)
+        self._check(self._lib.s2k_digest_batch(self._h, int(alg), n, blob, offs, mlen, res.ctypes.data, int(out_len)))
+        return res
+
+    def digest_batch_device(self, alg, n, d_msgs, d_msg_offsets, msg_len, d_out, out_len=32, stream=0):
+        self._check(self._lib.s2k_digest_batch_device(self._h, int(alg), int(n), d_msgs, d_msg_offsets, int(msg_len), d_out, int(out_len), stream))
+
+    @staticmethod
+    def _ecdsa_flags(reject_malleable, force_complete=False, force_worklist=False):
+        return (REJECT_MALLEABLE if reject_malleable else 0) | (FORCE_COMPLETE if force_complete else 0) | (FORCE_WORKLIST if force_worklist else 0)
+
+    def ecdsa_verify_messages_batch(self, pub_xy, msgs, r, s, alg: int = HASH_SHA256, reject_malleable: bool = False,
+                                    force_complete: bool = False, force_worklist: bool = False) -> np.ndarray:
+        """ecdsa_verify_batch on the digests of `msgs`, hashed on the device (s2k_ecdsa_verify_messages_batch); host buffers."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        pub_xy, s = _arr(pub_xy, 64, n), _arr(s, 32, n)
+        _, blob, offs, mlen, keep = _messages(msgs, n)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch(self._h, n, pub_xy.ctypes.data, int(alg), blob, offs, mlen, r.ctypes.data, s.ctypes.data,
+                                                              self._ecdsa_flags(reject_malleable, force_complete, force_worklist), out.ctypes.data))
+        return out
+
+    def ecdsa_verify_messages_batch_submit(self, pub_xy, msgs, r, s, alg: int = HASH_SHA256, out=None, reject_malleable: bool = False) -> "Ticket":
+        """s2k_ecdsa_verify_messages_batch_submit: as ecdsa_verify_batch_submit (contiguous uint8 arrays are used as they are;
+        everything, the messages included, is kept alive by the ticket)."""
+        arrs = []
+        for a, w in ((pub_xy, 64), (r, 32), (s, 32)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"]):
+                a = _arr(a, w)
+            arrs.append(a.reshape(-1, w))
+        n = arrs[1].shape[0]
+        if arrs[0].shape[0] != n or arrs[2].shape[0] != n:
+            raise ValueError(f"length mismatch: expected {n} items")
+        _, blob, offs, mlen, keep = _messages(msgs, n)
+        out = _out_array(out, n)
+        t = C.c_uint64(0)
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_submit(self._h, n, arrs[0].ctypes.data, int(alg), blob, offs, mlen, arrs[1].ctypes.data,
+                                                                     arrs[2].ctypes.data, REJECT_MALLEABLE if reject_malleable else 0,
+                                                                     out.ctypes.data, C.byref(t)))
+        return self._hold(int(t.value), out, arrs + keep)
+
+    def ecdsa_verify_messages_batch_device(self, n, d_pub_xy, alg, d_msgs, d_msg_offsets, msg_len, d_r, d_s, d_valid, flags=0, stream=0):
+        """Device-pointer form (s2k_ecdsa_verify_messages_batch_device): d_msg_offsets None for n messages of msg_len bytes."""
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_device(self._h, int(n), d_pub_xy, int(alg), d_msgs, d_msg_offsets, int(msg_len),
+                                                                     d_r, d_s, int(flags), d_valid, stream))
+
+    def ecdsa_verify_messages_batch_keyset(self, keyset, key_index, msgs, r, s, alg: int = HASH_SHA256, reject_malleable: bool = False,
+                                           force_worklist: bool = False) -> np.ndarray:
+        """ecdsa_verify_batch_keyset on the digests of `msgs`, hashed on the device; host buffers."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        s = _arr(s, 32, n)
+        ki = np.ascontiguousarray(key_index, dtype=np.uint32).reshape(-1)
+        if ki.shape[0] != n:
+            raise ValueError(f"length mismatch: expected {n} key indices, got {ki.shape[0]}")
+        _, blob, offs, mlen, keep = _messages(msgs, n)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_keyset(self._h, keyset._k, n, ki.ctypes.data, int(alg), blob, offs, mlen, r.ctypes.data,
+                                                                     s.ctypes.data, self._ecdsa_flags(reject_malleable, False, force_worklist),
+                                                                     out.ctypes.data))
+        return out
+
+    def ecdsa_verify_messages_batch_keyset_device(self, keyset, n, d_key_index, alg, d_msgs, d_msg_offsets, msg_len, d_r, d_s, d_valid, flags=0, stream=0):
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_keyset_device(self._h, keyset._k, int(n), d_key_index, int(alg), d_msgs, d_msg_offsets,
+                                                                            int(msg_len), d_r, d_s, int(flags), d_valid, stream))
+
+    def ecdsa_verify_messages_batch_bykey(self, keyset, pub_xy, msgs, r, s, alg: int = HASH_SHA256, reject_malleable: bool = False,
+                                          force_worklist: bool = False) -> np.ndarray:
+        """ecdsa_verify_batch_bykey on the digests of `msgs`, hashed on the device; host buffers."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        pub_xy, s = _arr(pub_xy, 64, n), _arr(s, 32, n)
+        _, blob, offs, mlen, keep = _messages(msgs, n)
+        out = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_keyset_bykey(self._h, keyset._k, n, pub_xy.ctypes.data, int(alg), blob, offs, mlen,
+                                                                           r.ctypes.data, s.ctypes.data,
+                                                                           self._ecdsa_flags(reject_malleable, False, force_worklist), out.ctypes.data))
+        return out
+
+    def ecdsa_verify_messages_batch_bykey_device(self, keyset, n, d_pub_xy, alg, d_msgs, d_msg_offsets, msg_len, d_r, d_s, d_valid, flags=0, stream=0):
+        self._check(self._lib.s2k_ecdsa_verify_messages_batch_keyset_bykey_device(self._h, keyset._k, int(n), d_pub_xy, int(alg), d_msgs, d_msg_offsets,
+                                                                                  int(msg_len), d_r, d_s, int(flags), d_valid, stream))
 
     def schnorr_verify_batch(self, pk32, msgs, sig64, force_complete: bool = False) -> np.ndarray:
         """BIP-340: valid bits for n (x-only key, message, 64-byte signature) triples.

@@ -125,6 +125,8 @@ struct s2k_ctx {
   size_t seg_host_bytes = 0;
   void* h2c_dev = nullptr;      // hashing to the curve (h2c.hip): status word and DST_prime on the device, allocated on its first call
   void* h2c_host = nullptr;     // ... and the pinned host block both travel through
+  void* msg_digest = nullptr;   // the verification calls that take messages (digest.hip): 32 bytes per item, what k_digest_messages
+  size_t msg_digest_bytes = 0;  // writes and the digest call behind it reads; allocated on the first such call
   void* rlc_save = nullptr;     // kept terms of a rejected whole-batch check (BIP-340, recoverable ECDSA) while its failing
                                 // signatures are located; the ECDSA leaf verifier's recovered keys
   size_t rlc_save_bytes = 0;

@@ -18,10 +18,11 @@ def be_gt(a, b):
     return anyd & (a[rows, first] > b[first])
 
 
-def synth_batch(eng, n, n_keys, seed, key_idx=None):
+def synth_batch(eng, n, n_keys, seed, key_idx=None, digest=None):
     """Valid low-s ECDSA signatures built with the engine's own batched primitives
     (scalar_base_mult, Fn inverse/mul/add); returns uint8 arrays pub (n,64), digest, r, s.
-    Signature i is made with key key_idx[i] (default i mod n_keys)."""
+    Signature i is made with key key_idx[i] (default i mod n_keys).  digest: (n,32) digests to sign (the hashes of a
+    caller's messages) instead of random ones."""
     rng = np.random.default_rng(seed)
 
     def rand_scalars(m):
@@ -34,7 +35,7 @@ def synth_batch(eng, n, n_keys, seed, key_idx=None):
     Q = eng.scalar_base_mult_batch(d)[:, 1:]
     key_idx = np.arange(n) % n_keys if key_idx is None else np.asarray(key_idx)
     k = rand_scalars(n)
-    digest = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    digest = rng.integers(0, 256, size=(n, 32), dtype=np.uint8) if digest is None else np.ascontiguousarray(digest, dtype=np.uint8).reshape(n, 32)
     Rp = eng.scalar_base_mult_batch(k)
     zero = np.zeros((n, 32), np.uint8)
     r, _ = eng.fn_op_batch(OP_ADD, Rp[:, 1:33], zero)          # x(R) mod n
