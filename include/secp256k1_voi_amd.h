@@ -382,6 +382,32 @@ int s2k_keyset_remove(s2k_keyset *ks, size_t m, const uint32_t *slots /* m, host
 int s2k_debug_keyset_replace_plan(size_t n_live, size_t m, const uint32_t *slots, size_t piece_keys, uint32_t *order /* m */,
                                   uint64_t *n_pieces);
 int s2k_debug_keyset_replace_piece(size_t keys);
+/* Test hook: the tables of key `key` of a set read back, entries first .. first + count - 1 of one section, into `out` (host
+ * memory).  Synchronous, on the null stream; the calling rules of s2k_keyset_valid_keys (not beside a call that uses the set).
+ * Every table entry of a key is a point m * Q of the key Q on the key's isomorphic curve: for the affine (x, y) of m * Q what
+ * is stored is (W^2 x, W^3 y), and where there is a third column beta W^2 x, with W the one Z all entries of the key share.
+ * Limb-stored entries are read with the loaders of the ladders (ke_load*, je_load) and fully reduced; every coordinate is 32
+ * big-endian bytes.
+ *   section 0, the shared scale: count must be 1; out = 32 bytes, W (element W_SLOT of the window geometry's scratch, element
+ *     W of entry WENT of a comb set).
+ *   section 1, the base table: 96 bytes per entry, X || Y || beta X - but for the lead pair, which has no beta column (no
+ *     ladder takes the endomorphism of a starting point): its last 32 bytes are zero.  S2K_KEYSET_CHUNKS, _JOINT, _JOINT5, _JOINT6: the
+ *     32-chunk table, 258 entries - entry 8 c + a = (2 a + 1) 16^c Q for c < 32, a < 8, then the lead pair L + phi(L),
+ *     L - phi(L) with L = 2^128 Q at 256 and 257.  S2K_KEYSET_COMB: 66 entries - E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t,
+ *     B_t = 2^(19 t) Q, for idx < 64, then the lead pair from L = 2^115 Q.
+ *   section 2, the joint table: 64 bytes per entry, X || Y.  S2K_KEYSET_JOINT: 4096 entries, entry 128 c + 2 (8 a + b) + s =
+ *     E_a + (-1)^s phi(E_b), E_a = (2 a + 1) 16^c Q.  S2K_KEYSET_JOINT5 / _JOINT6 (W = 5 / 6 bits, POS = 26 / 22 positions,
+ *     NE = 16 / 32 odd multiples): POS * 2 NE^2 + 2 entries, entry 2 NE^2 i + 2 (NE a + b) + s = (2 a + 1) B_i +
+ *     (-1)^s phi((2 b + 1) B_i), B_i = 2^(W i) Q, then the lead pair 2^(W POS) Q +- phi(2^(W POS) Q).  A wide entry comes as
+ *     the eight 32-bit words per coordinate it is stored as, most significant first and NOT reduced: the ladder takes them
+ *     for canonical, and a test is what checks that.  S2K_KEYSET_CHUNKS and _COMB have no section 2.
+ * S2K_ERR_ARG, `out` untouched and nothing launched: a NULL argument; key >= s2k_keyset_size; a section the layout does not
+ * have; first + count beyond the section; count != 1 in section 0.  count == 0 (sections 1 and 2): S2K_OK.  The rows of a key
+ * that is no valid public key are returned as they are: their content is unspecified. */
+int s2k_debug_keyset_entries(s2k_keyset *ks, size_t key, int section, size_t first, size_t count, uint8_t *out /* host */);
+/* The entries section `section` of the set's layout has (1 / 258 or 66 / 4096, 13314 or 45058), a pure host function:
+ * S2K_ERR_ARG, *entries untouched, for a NULL argument or a section the layout does not have. */
+int s2k_debug_keyset_section_entries(const s2k_keyset *ks, int section, size_t *entries);
 int s2k_ecdsa_verify_batch_keyset(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const uint32_t *key_index /* n */,
                                   const uint8_t *digest32, const uint8_t *r, const uint8_t *s, uint32_t flags, uint8_t *valid);
 int s2k_ecdsa_verify_batch_keyset_device(s2k_ctx *ctx, const s2k_keyset *ks, size_t n, const void *d_key_index /* n uint32 */,

@@ -252,6 +252,8 @@ def load_library() -> C.CDLL:
     lib.s2k_keyset_remove.argtypes = [vp, sz, vp]
     lib.s2k_debug_keyset_replace_plan.argtypes = [sz, sz, vp, sz, vp, vp]
     lib.s2k_debug_keyset_replace_piece.argtypes = [sz]
+    lib.s2k_debug_keyset_entries.argtypes = [vp, sz, ci, sz, sz, vp]
+    lib.s2k_debug_keyset_section_entries.argtypes = [vp, ci, C.POINTER(sz)]
     lib.s2k_keyset_layout.argtypes = [vp]
     lib.s2k_keyset_destroy.argtypes = [vp]
     lib.s2k_keyset_destroy.restype = None
@@ -465,6 +467,7 @@ EXPORTED_SYMBOLS = [
     "s2k_keyset_create", "s2k_keyset_create_ex", "s2k_keyset_layout", "s2k_keyset_geometry", "s2k_keyset_destroy", "s2k_keyset_size", "s2k_keyset_device_bytes", "s2k_keyset_valid_keys",
     "s2k_keyset_create_cap", "s2k_keyset_capacity", "s2k_keyset_reserve", "s2k_keyset_append", "s2k_keyset_append_device",
     "s2k_keyset_replace", "s2k_keyset_replace_device", "s2k_keyset_remove", "s2k_debug_keyset_replace_plan", "s2k_debug_keyset_replace_piece",
+    "s2k_debug_keyset_entries", "s2k_debug_keyset_section_entries",
     "s2k_ecdsa_verify_batch_keyset", "s2k_ecdsa_verify_batch_keyset_device", "s2k_ecdsa_verify_batch_keyset_submit",
     "s2k_keyset_index_geometry", "s2k_keyset_index_create", "s2k_keyset_index_info", "s2k_keyset_lookup", "s2k_keyset_lookup_device",
     "s2k_ecdsa_verify_batch_keyset_bykey", "s2k_ecdsa_verify_batch_keyset_bykey_device", "s2k_ecdsa_verify_batch_keyset_bykey_submit",
@@ -2359,6 +2362,21 @@ class KeySet:
     def valid_keys(self) -> np.ndarray:
         out = np.zeros(len(self), dtype=np.uint8)
         self._eng._check(self._eng._lib.s2k_keyset_valid_keys(self._k, out.ctypes.data))
+        return out
+
+    def debug_entries(self, key: int, section: int, first: int = 0, count: int | None = None) -> np.ndarray:
+        """test hook (s2k_debug_keyset_entries): entries first .. first + count - 1 (None: to the end of the section) of the
+        tables of key `key`, read with the ladders' loaders.  Section 0: the key's shared scale W, a (1, 32) array; section 1:
+        the base table, (count, 96) = X || Y || beta X; section 2: the joint table, (count, 64) = X || Y.  Coordinates are 32
+        big-endian bytes, reduced - but for the wide joint layouts, whose stored words come as they are.  The sections' sizes
+        (s2k_debug_keyset_section_entries) and what each entry is: include/secp256k1_voi_amd.h.  Whatever the library refuses -
+        a section the layout lacks, a range past its end - raises EngineError."""
+        if count is None:
+            total = C.c_size_t(0)
+            self._check_own(self._eng._lib.s2k_debug_keyset_section_entries(self._k, int(section), C.byref(total)))
+            count = max(int(total.value) - int(first), 0)     # (a `first` past the end: the library refuses it below)
+        out = np.zeros((int(count), {0: 32, 1: 96}.get(int(section), 64)), dtype=np.uint8)
+        self._check_own(self._eng._lib.s2k_debug_keyset_entries(self._k, int(key), int(section), int(first), int(count), out.ctypes.data))
         return out
 
     def index_create(self, log2_slots: int = 0):

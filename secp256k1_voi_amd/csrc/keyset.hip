@@ -1,6 +1,8 @@
 // keyset.hip — key sets (s2k_keyset_*): the set and its index, growing it, and the verification entry points over it, by key
 // index and by key bytes, synchronous and as tickets.  The kernels, their launchers, the context and the ticket plumbing are
-// engine.hip's (engine_internal.h); the table builds and the sort keyed.hip's; the index's kernels keyset_index.hip's.
+// engine.hip's (engine_internal.h); the table builds and the sort keyed.hip's; the index's kernels keyset_index.hip's.  Two small
+// kernels live here: k_ks_expand_x (the x-only keys of a BIP-340 call by index) and k_ks_debug_entries (the test hook
+// s2k_debug_keyset_entries: a set's tables read back).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -11,6 +13,7 @@
 
 #include "engine_internal.h"
 #include "keyset_index.h"
+#include "lane_tables.h"
 
 using namespace s2k;
 
@@ -201,6 +204,102 @@ int s2k_keyset_valid_keys(s2k_keyset* ks, uint8_t* valid) {
   const keyset_view v = s2k_internal_keyset_view(ks->base, ks->cap, ks->chunks);
   HIP_TRY(nullptr, hipSetDevice(ks->device));
   HIP_TRY(nullptr, hipMemcpy(valid, v.valid, ks->n, hipMemcpyDeviceToHost));
+  return S2K_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Test hook (s2k_debug_keyset_entries): the tables of one key read back entry by entry, through the loaders the ladders read
+// them with (ke_load / ke_load3, je_load), reduced and big-endian; a wide joint entry as the eight words per coordinate it
+// is stored as.  No kernel of the library is involved: one thread per entry of the range, null stream.
+// ---------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+enum { KSD_SCALE = 0, KSD_BASE = 1, KSD_JOINT4 = 2, KSD_JOINTW = 3 };
+static_assert(kjw_geom<5>::EQ == kjw_geom<6>::EQ, "one entry size for both wide layouts: KSD_JOINTW steps by it whatever the width");
+// entries of a section of the set's layout (0: the layout has no such section)
+size_t ksd_section_entries(const s2k_keyset* ks, int section) {
+  const int jw = ks->joint ? ks->jw : 0;
+  if (section == 0) return 1;
+  if (section == 1) return ks->chunks == KC_TEETH ? kc_geom::ENTRIES : kt_geom<KS_CHUNKS>::ENTRIES;
+  if (section == 2 && jw) return jw == 6 ? kjw_geom<6>::LEAD + 2 : jw == 5 ? kjw_geom<5>::LEAD + 2 : (size_t)KS_CHUNKS * KJ_PER_CHUNK;
+  return 0;
+}
+__device__ __forceinline__ void ksd_store(uint8_t* o, const fe29& v) {
+  uint32_t w[8];
+  fe29_to_words(w, fe29_normalize(v));
+  store_be32_unaligned(o, w);
+}
+// src: the first entry of the range (KSD_SCALE: the entry that holds W, `elem` its element); out: count * 32 / 96 / 64 / 64 bytes
+__global__ void __launch_bounds__(64)
+k_ks_debug_entries(int kind, const uint4* __restrict__ src, uint32_t count, int elem, uint8_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= count) return;
+  if (kind == KSD_SCALE) {
+    ksd_store(out, ke_load(src, elem));
+  } else if (kind == KSD_BASE) {
+    fe29 x, y, bx;
+    ke_load3(src + (size_t)i * 8, x, y, bx);
+    ksd_store(out + (size_t)i * 96, x);
+    ksd_store(out + (size_t)i * 96 + 32, y);
+    ksd_store(out + (size_t)i * 96 + 64, bx);
+  } else if (kind == KSD_JOINT4) {
+    fe29 x, y;
+    je_load(src + (size_t)i * KJ_ENTRY_QUADS, x, y);
+    ksd_store(out + (size_t)i * 64, x);
+    ksd_store(out + (size_t)i * 64 + 32, y);
+  } else {
+    // (what jw_load cuts into limbs: the words themselves, most significant first - canonical or not is the caller's to see)
+    const uint4* e = src + (size_t)i * kjw_geom<5>::EQ;
+    const uint4 a = e[0], b = e[1], c = e[2], d = e[3];
+    const uint32_t xw[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, yw[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+    store_be32_unaligned(out + (size_t)i * 64, xw);
+    store_be32_unaligned(out + (size_t)i * 64 + 32, yw);
+  }
+}
+}  // namespace
+extern "C" {
+int s2k_debug_keyset_section_entries(const s2k_keyset* ks, int section, size_t* entries) {
+  if (!ks || !entries) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  const size_t n = ksd_section_entries(ks, section);
+  if (!n) return fail(nullptr, S2K_ERR_ARG, "the layout of the key set has no section %d", section);
+  *entries = n;
+  return S2K_OK;
+}
+int s2k_debug_keyset_entries(s2k_keyset* ks, size_t key, int section, size_t first, size_t count, uint8_t* out) {
+  if (!ks || !out) return fail(nullptr, S2K_ERR_ARG, "null argument");
+  if (key >= ks->n) return fail(nullptr, S2K_ERR_ARG, "key %zu of a set of %zu", key, ks->n);
+  const bool comb = ks->chunks == KC_TEETH;
+  const int jw = ks->joint ? ks->jw : 0;
+  const size_t entries = ksd_section_entries(ks, section), out_bytes = section == 0 ? 32 : section == 1 ? 96 : 64;
+  if (!entries) return fail(nullptr, S2K_ERR_ARG, "the layout of the key set has no section %d", section);
+  if (first > entries || count > entries - first) return fail(nullptr, S2K_ERR_ARG, "entries %zu + %zu of a section of %zu", first, count, entries);
+  if (section == 0 && count != 1) return fail(nullptr, S2K_ERR_ARG, "section 0 is one value");
+  if (count == 0) return S2K_OK;
+  const uint4* kt = s2k_internal_keyset_view(ks->base, ks->cap, ks->chunks).tables + key * (size_t)(comb ? KC_SLOTS : KS_SLOTS) * 8;
+  using GS = kt_geom<KS_CHUNKS>;
+  const uint4* src;
+  int kind, elem = 0;
+  if (section == 0) {
+    kind = KSD_SCALE;
+    src = kt + (size_t)(comb ? kc_geom::WENT : GS::SCR + GS::W_SLOT / 3) * 8;
+    elem = comb ? kc_geom::W : GS::W_SLOT % 3;
+  } else if (section == 1) {
+    kind = KSD_BASE;
+    src = kt + first * 8;
+  } else if (jw == 4) {
+    kind = KSD_JOINT4;
+    src = ks->joint + key * KJ_KEY_QUADS + first * KJ_ENTRY_QUADS;
+  } else {
+    kind = KSD_JOINTW;
+    src = ks->joint + key * (jw == 6 ? kjw_geom<6>::KEY_QUADS : kjw_geom<5>::KEY_QUADS) + first * kjw_geom<5>::EQ;
+  }
+  HIP_TRY(nullptr, hipSetDevice(ks->device));
+  dev_buf o;
+  HIP_TRY(nullptr, o.alloc(count * out_bytes));
+  k_ks_debug_entries<<<(unsigned)((count + 63) / 64), 64>>>(kind, src, (uint32_t)count, elem, (uint8_t*)o.p);
+  HIP_TRY(nullptr, hipGetLastError());
+  HIP_TRY(nullptr, hipDeviceSynchronize());
+  HIP_TRY(nullptr, hipMemcpy(out, o.p, count * out_bytes, hipMemcpyDeviceToHost));
   return S2K_OK;
 }
 
