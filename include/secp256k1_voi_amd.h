@@ -1262,7 +1262,7 @@ enum {
    * its bit 1 is (in[7] NULL: both +1).  out, out2 = affine x, y; flag = 0 when Z3 = 0 (E1 = +-E2, acc = +-(s1 E1 + s2 E2),
    * Z = 0).  reps == 0: once; reps >= 1: `reps` times the column with one jpt29_double behind it, as the ladder runs them. */
   S2K_HP_JADD_PAIR,
-  /* a round of the wave-per-signature comb ladder (engine.hip: row_ladder_comb), through s2k_fp_op_batch_ex with the operands
+  /* a round of the wave-per-signature comb ladder (small_call.hip: row_ladder_comb), through s2k_fp_op_batch_ex with the operands
    * of PT29R_ADD_B3: Q = (d, e) is moved to y^2 = x^3 + 7 c^6 as there and comes back as the projective point (x c : y : c^3)
    * of secp256k1 (fe29r.h: pt29r_pair_from_iso, both halves of the layer in turn); the accumulator starts at P = (a, b) and
    * each repetition is acc = pt29r_add(pt29r_double(acc), Q): 2^reps P + (2^reps - 1) Q.  out, out2, flag, bit 0 of `lazy`

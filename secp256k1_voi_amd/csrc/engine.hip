@@ -1,5 +1,8 @@
-// engine.hip — gfx950 kernels and the C-ABI of include/secp256k1_voi_amd.h (the generator tables: gtable.hip; key sets and the
-// entry points over them: keyset.hip).
+// engine.hip — the lane-per-signature kernels (k_scalar_prep, k_generator_part, k_verify_fast, k_affine_finish, k_schnorr_prep),
+// the complete-formula fallback and worklist kernels, the context, and the ECDSA, BIP-340, recovery and point call flows of
+// include/secp256k1_voi_amd.h.  Elsewhere: the kernels of calls too small for a lane per signature (small_call.hip); host
+// staging, tickets and page-locked memory (pipeline.hip); the generator tables (gtable.hip); key sets and the entry points
+// over them (keyset.hip).
 //
 // One lane per signature / per point; every lane of a wave runs the same instruction
 // stream (complete formulas, fixed windows), so there is no divergence on secret- or
@@ -13,7 +16,6 @@
 #include <new>
 
 #include <sys/random.h>
-#include <unistd.h>
 
 #include <atomic>
 #include <chrono>
@@ -29,13 +31,11 @@
 #include "xyzz29.h"
 #include "lane_tables.h"
 #include "pt29.h"
-#include "fe29r.h"
-#include "pt29q.h"
 #include "complete_path.h"
 #include "point.h"
 #include "sc.h"
 #include "sc26.h"
-#include "sha256.h"
+#include "sig_prep.h"
 
 using namespace s2k;
 
@@ -403,60 +403,6 @@ k_scalar_prep(uint32_t n, uint32_t T, const uint8_t* __restrict__ dig, const uin
 __attribute__((visibility("hidden"))) uint32_t prep_lanes(size_t n) {
   const size_t shared = (n + PREP_M - 1) / PREP_M, wide = n < ((size_t)1 << 16) ? n : ((size_t)1 << 16);
   return (uint32_t)(shared > wide ? shared : wide);
-}
-// The same for ONE signature, its own inversion, the result in 17 words (u1 | k1 | k2 | flags: the planes' layout): the
-// preparation wave of the wave-per-signature kernels (k_verify_row, k_recover_row).  FLAT: the scalar products and the
-// inversion are expanded in place (sc26.h), which leaves the kernel without a private segment.
-template <bool FLAT = false>
-S2K_DEV void scalar_prep_one(size_t i, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig,
-                             const uint8_t* __restrict__ recid, uint32_t flags, uint32_t* __restrict__ out17) {
-  sc x;
-  load_be32(x.v, (recid ? rsig : ssig) + i * 32);      // the value whose inverse is needed
-  if (!(sc_is_canonical_raw(x.v) && !sc_is_zero(x))) {   // (rejected below)
-    x = sc_zero();
-    x.v[0] = 1;
-  }
-  struct ops {
-    static S2K_DEV sc26 mm(const sc26& a, const sc26& b) {
-      if constexpr (FLAT) return sc26_montmul(a, b);
-      else return sc26_mm(a, b);
-    }
-    static S2K_DEV sc26 inv_of(const sc26& a) {           // a -> a^-1 * R
-      if constexpr (FLAT) return sc26_mont_inv_flat(sc26_to_mont_flat(a));
-      else return sc26_mont_inv(sc26_to_mont(a));
-    }
-  };
-  const sc26 s_inv_m = ops::inv_of(sc26_from_sc(x));     // x^-1 * R
-  sc r, s;
-  uint32_t e_raw[8];
-  load_be32(r.v, rsig + i * 32);
-  load_be32(s.v, ssig + i * 32);
-  load_be32(e_raw, dig + i * 32);
-  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-  if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);
-  const sc e = sc_reduce_once(e_raw);
-  sc u1, u2;
-  uint32_t rid = 0;
-  if (recid) {
-    rid = recid[i];
-    ok = ok && rid < 4 && (!(rid & 2u) || u256_lt(r.v, FE_P_MINUS_N));     // RecoverPoint (point_s11n.go:245-282)
-    u1 = sc26_to_sc(ops::mm(sc26_from_sc(sc_neg(e)), s_inv_m));   // -e / r
-    u2 = sc26_to_sc(ops::mm(sc26_from_sc(s), s_inv_m));           //  s / r
-  } else {
-    u1 = sc26_to_sc(ops::mm(sc26_from_sc(e), s_inv_m));
-    u2 = sc26_to_sc(ops::mm(sc26_from_sc(r), s_inv_m));
-  }
-  sc k1, k2;
-  bool neg1, neg2;
-  sc_split_glv_odd(u2, k1, neg1, k2, neg2);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) out17[w] = u1.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) out17[8 + w] = k1.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) out17[12 + w] = k2.v[w];
-  out17[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0) |
-              ((rid & 3u) << 8);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1110,711 +1056,6 @@ k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
 }
 
 // ---------------------------------------------------------------------------------------
-// Small batches: ONE WAVE PER SIGNATURE (round 5).  A call of up to a few thousand signatures - the reference's own
-// shape is a loop of single Verify calls, BASELINE config 1 verifies 1024 - leaves the chip empty whatever the kernel: what
-// it costs is the latency of one lane's ladder, 261 k dependent instructions, 0.7 ms for 64 signatures as for 8192
-// (bench.py batch_sweep).  Here the ladder runs in the row arithmetic of fe29r.h (a field element = one register, one limb
-// per lane of a 16-lane row, the four products of a formula layer in the four rows of the wave): the same signed-odd-digit
-// GLV ladder as k_verify_fast - table {1,3,..,15} Q, 32 windows of four doublings and two additions, the generator part from
-// the resident tables - on the COMPLETE projective formulas (pt29r_add / pt29r_double: no exceptional case, so no worklist
-// and no second kernel), ~70 k instructions of one wave per signature.  Digits, table indices and generator-table addresses
-// are wave-uniform.  Verdicts are those of the other paths (same preparation kernel, same accept rule ecdsa.go:392-470).
-// ---------------------------------------------------------------------------------------
-// limb j (lane j of every row) of a 256-bit value given as eight little-endian words every lane holds
-S2K_DEV fer fer_from_words(const uint32_t w[8], const fer_consts& k) {
-  const uint32_t bit = 29u * k.j, idx = bit >> 5, sh = bit & 31u;
-  uint32_t lo = 0, hi = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    lo = idx == (uint32_t)i ? w[i] : lo;
-    hi = idx + 1 == (uint32_t)i ? w[i] : hi;
-  }
-  const uint64_t v = ((uint64_t)hi << 32) | lo;
-  return k.j <= 8 ? ((uint32_t)(v >> sh) & F29_M) : 0u;       // (limb 8: bits 232..255, 24 of them)
-}
-// value == 0 (mod p), the same answer in every lane
-S2K_DEV bool fer_is_zero(fer a, const fer_consts& k) { return fe29_is_zero(fer_to_fe29(fer_norm(a, k))); }
-
-// canonical value odd?  (the same answer in every lane of a row)
-S2K_DEV bool fer_is_odd(fer a, const fer_consts& k) { return (fe29_normalize(fer_to_fe29(fer_norm(a, k))).n[0] & 1u) != 0; }
-S2K_DEV fer fer_sqr_n(fer a, int n, const fer_consts& k) {
-#pragma unroll 1
-  for (int i = 0; i < n; ++i) a = fer_mul(a, a, k);
-  return a;
-}
-// a^((p+1)/4): the chain of fe29_sqrt (Sqrt, internal/field/field_sqrt_ratio.go:14), row by row - four roots per wave
-S2K_DEV fer fer_sqrt_chain(fer a, const fer_consts& k) {
-  const fer x2 = fer_mul(fer_mul(a, a, k), a, k);
-  const fer x3 = fer_mul(fer_mul(x2, x2, k), a, k);
-  const fer x6 = fer_mul(fer_sqr_n(x3, 3, k), x3, k);
-  const fer x9 = fer_mul(fer_sqr_n(x6, 3, k), x3, k);
-  const fer x11 = fer_mul(fer_sqr_n(x9, 2, k), x2, k);
-  const fer x22 = fer_mul(fer_sqr_n(x11, 11, k), x11, k);
-  const fer x44 = fer_mul(fer_sqr_n(x22, 22, k), x22, k);
-  const fer x88 = fer_mul(fer_sqr_n(x44, 44, k), x44, k);
-  const fer x176 = fer_mul(fer_sqr_n(x88, 88, k), x88, k);
-  const fer x220 = fer_mul(fer_sqr_n(x176, 44, k), x44, k);
-  const fer x223 = fer_mul(fer_sqr_n(x220, 3, k), x3, k);
-  fer t = fer_mul(fer_sqr_n(x223, 23, k), x22, k);
-  t = fer_mul(fer_sqr_n(t, 6, k), x2, k);
-  return fer_sqr_n(t, 2, k);
-}
-// x^3 + 7
-S2K_DEV fer fer_curve_rhs(fer x, const fer_consts& k) {
-  const fer seven = k.j == 0 ? 7u : 0u;
-  return fer_mul_plus(fer_mul(x, x, k), x, seven, k);
-}
-
-// The wave-per-signature kernels.  A block is four signature waves and one PREPARATION wave: lanes 0..3 of the
-// fifth wave run the scalar arithmetic of the block's four signatures (s^-1, u1, u2, the odd GLV split: one lane's chain of
-// 55 us) into LDS while the signature waves do what does not depend on it - key checks, square roots, the key's table -, then
-// the block meets at one barrier.  One launch per call.
-//
-// row_table: the table of the key in LDS, one 256-byte line per coordinate of an entry (lane l of the wave at word l) - x, y,
-// z and lambda's x (beta * x) of (2j + 1) Q, j < 8; an entry is three loads at a wave-uniform offset.
-S2K_DEV void row_table(const pt29r& Q1, uint32_t (*tab)[8][64], const fer_consts& k, uint32_t lane) {
-  const fer beta = fer_from_words(FE_BETA, k);
-  const pt29r D = pt29r_double(Q1, k);
-  pt29r cur = Q1;
-#pragma unroll 1
-  for (int j = 0; j < 8; ++j) {
-    if (j) cur = pt29r_add(cur, D, k);
-    tab[0][j][lane] = cur.x;
-    tab[1][j][lane] = fer_norm(cur.y, k);
-    tab[2][j][lane] = cur.z;
-    tab[3][j][lane] = fer_mul(cur.x, beta, k);
-  }
-}
-// u * G + k1 * Q + k2 * lambda(Q) for ONE signature on the whole wave, Q's table in `tab`, u | k1 | k2 | flags in the 17 words
-// `p` (LDS): 32 x (4 doublings + 2 additions) on the complete formulas, then the generator part from the resident tables (no
-// entry is the identity, no digit is special).  The result is projective.
-S2K_DEV pt29r row_ladder(uint32_t (*tab)[8][64], const uint32_t* p, gt_view gt, const fer_consts& k, uint32_t lane) {
-  const fer one = k.j == 0 ? 1u : 0u;
-  const uint32_t pf = p[16];
-  // |k1|, |k2| odd, < 2^129 (sc_split_glv_odd)
-  sc k1 = sc_zero(), k2 = sc_zero();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    k1.v[w] = p[8 + w];
-    k2.v[w] = p[12 + w];
-  }
-  k1.v[4] = (pf & PF_K1_B128) ? 1u : 0u;
-  k2.v[4] = (pf & PF_K2_B128) ? 1u : 0u;
-  const bool neg1 = pf & PF_NEG1, neg2 = pf & PF_NEG2;
-  digit_stream d1 = ds_init(k1), d2 = ds_init(k2);
-  auto entry_of = [&](uint32_t w, bool lam, bool sneg) -> pt29r {   // the entry of digit w (signed odd: 2w - 15), or its image
-    const bool neg = sneg != (w < 8u);                              // under the endomorphism, negated with the scalar's sign
-    const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w < 8u) ? (7u - w) : (w - 8u)));
-    pt29r a;
-    a.x = tab[lam ? 3 : 0][e][lane];
-    a.y = tab[1][e][lane];
-    a.z = tab[2][e][lane];
-    if (neg) a.y = fer_negate(a.y, 1, k);                           // [2]: the addition normalises y
-    return a;
-  };
-  pt29r acc = pt29r_add(entry_of(8u, false, neg1), entry_of(8u, true, neg2), k);   // the top digits are +1 (w = 8)
-#pragma unroll 1
-  for (int i = 31; i >= 0; --i) {
-    const uint32_t w1 = ds_next(d1), w2 = ds_next(d2);
-    const pt29r a1 = entry_of(w1, false, neg1), a2 = entry_of(w2, true, neg2);   // (in flight during the doublings)
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) acc = pt29r_double(acc, k);
-    acc = pt29r_add(acc, a1, k);
-    acc = pt29r_add(acc, a2, k);
-  }
-  uint32_t u[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) u[w] = p[w];
-  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-#pragma unroll 1
-  for (uint32_t w = 0; w < gt.windows; ++w) {
-    pt29r q;
-    q.x = fer_from_words(g.x.v, k);
-    q.y = fer_from_words(g.y.v, k);
-    q.z = one;
-    if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));   // in flight during the addition
-    acc = pt29r_add(acc, q, k);
-  }
-  return acc;
-}
-// a^(p-2), the chain of fe29_inv (Invert, internal/field/field_invert.go:11), in row products
-S2K_DEV fer fer_inv_chain(fer a, const fer_consts& k) {
-  const fer x2 = fer_mul(fer_mul(a, a, k), a, k);
-  const fer x3 = fer_mul(fer_mul(x2, x2, k), a, k);
-  const fer x6 = fer_mul(fer_sqr_n(x3, 3, k), x3, k);
-  const fer x9 = fer_mul(fer_sqr_n(x6, 3, k), x3, k);
-  const fer x11 = fer_mul(fer_sqr_n(x9, 2, k), x2, k);
-  const fer x22 = fer_mul(fer_sqr_n(x11, 11, k), x11, k);
-  const fer x44 = fer_mul(fer_sqr_n(x22, 22, k), x22, k);
-  const fer x88 = fer_mul(fer_sqr_n(x44, 44, k), x44, k);
-  const fer x176 = fer_mul(fer_sqr_n(x88, 88, k), x88, k);
-  const fer x220 = fer_mul(fer_sqr_n(x176, 44, k), x44, k);
-  const fer x223 = fer_mul(fer_sqr_n(x220, 3, k), x3, k);
-  fer t = fer_mul(fer_sqr_n(x223, 23, k), x22, k);
-  t = fer_mul(fer_sqr_n(t, 5, k), a, k);
-  t = fer_mul(fer_sqr_n(t, 3, k), x2, k);
-  return fer_mul(fer_sqr_n(t, 2, k), a, k);
-}
-
-// PublicKey.Verify (secec/ecdsa.go:171, 392-470) with one WAVEFRONT per signature: the small-batch ladder
-__global__ void __launch_bounds__(320)
-k_verify_row(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-             const uint8_t* __restrict__ ssig, uint32_t flags, gt_view gt, uint8_t* __restrict__ out) {
-  __shared__ uint32_t tab_all[4][4][8][64];
-  __shared__ uint32_t prep_s[4][20];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) scalar_prep_one(i, dig, rsig, ssig, nullptr, flags, prep_s[lane]);
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  const fer_consts k = fer_setup(lane);
-  bool ok = sig < n;
-  if (ok) {
-    uint32_t xw[8], yw[8];
-    load_be32(xw, pub + (size_t)sig * 64);
-    load_be32(yw, pub + (size_t)sig * 64 + 32);
-    ok = fe_is_canonical_raw(xw) && fe_is_canonical_raw(yw);
-    pt29r Q1;
-    Q1.x = fer_from_words(xw, k);
-    Q1.y = fer_from_words(yw, k);
-    Q1.z = k.j == 0 ? 1u : 0u;
-    // y^2 == x^3 + 7 (point_s11n.go:298-307)
-    ok = ok && fer_is_zero(fer_add(fer_mul(Q1.y, Q1.y, k), fer_negate(fer_curve_rhs(Q1.x, k), 1, k)), k);
-    if (ok) row_table(Q1, tab_all[wave], k, lane);              // (wave-uniform)
-  }
-  __syncthreads();
-  if (sig >= n) return;
-  const uint32_t* p = prep_s[wave];
-  if (!(ok && (p[16] & PF_OK))) {
-    if (lane == 0) out[sig] = 0;
-    return;
-  }
-  const pt29r acc = row_ladder(tab_all[wave], p, gt, k, lane);
-  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
-  uint8_t verdict = 0;
-  if (!fer_is_zero(acc.z, k)) {
-    uint32_t rw[8];
-    load_be32(rw, rsig + (size_t)sig * 32);
-    bool match = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(rw, k), acc.z, k), 1, k)), k);
-    if (u256_lt(rw, FE_P_MINUS_N)) {
-      uint32_t r2[8];
-      u256_add(r2, rw, SC_N);
-      match = match || fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(r2, k), acc.z, k), 1, k)), k);
-    }
-    verdict = match ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
-}
-
-// ---- small calls over a KEY SET: the wave-per-signature ladder on the set's 32-chunk tables ----
-// Every layout but the comb keeps {1,3,..,15} 16^c Q, c < 32, and the lead pair L +- phi(L), L = 16^32 Q, per key
-// (kt_geom<32>): the key part of a signature is 64 table additions, no doubling, no table build, no curve check.  The entries
-// are AFFINE points of the key's isomorphic curve y^2 = x^3 + 7 W^6 (one shared Z = W per key, keyed.hip), and the complete
-// addition contains the curve constant: pt29r_add_b3 with b3 = 21 W^6, formed once per signature.  The sum goes back to
-// secp256k1 by pt29r_from_iso and takes the generator part as row_ladder does.
-// limb j (lane j of every row) of element `which` (0: x, 1: y, 2: beta x) of the 128-byte entry at e (lane_tables.h: ke_store3)
-S2K_DEV fer ke_row_load(const uint4* __restrict__ e, uint32_t which, const fer_consts& k) {
-  const uint32_t v = reinterpret_cast<const uint32_t*>(e)[k.j < 8 ? which * 8u + k.j : 24u + which];   // (lanes 9..15: limb 8's word)
-  return k.j <= 8 ? v : 0u;
-}
-struct row_iso {       // of the signature's key: W, W^3, 21 W^6
-  fer w, w3, b3;
-};
-S2K_DEV row_iso row_iso_of(const uint4* __restrict__ kt, const fer_consts& k) {
-  using G = kt_geom<KS_CHUNKS>;
-  row_iso r;
-  r.w = ke_row_load(kt + (size_t)(G::SCR + G::W_SLOT / 3) * 8, G::W_SLOT % 3, k);
-  r.w3 = fer_mul(fer_mul(r.w, r.w, k), r.w, k);
-  r.b3 = fer_small_norm(fer_mul(r.w3, r.w3, k), 21u, k);
-  return r;
-}
-// u * G + (+-k1) * Q + (+-k2) * lambda(Q), Q the key of table kt: u | k1 | k2 | flags in the 17 words `p` (LDS), the digits those
-// of k_verify_fast<MODE_ECDSA_KEYSET> (nibble c of (k - 1) / 2 selects +-(2j + 1) 16^c Q, the lead pair first).  `flip`
-// changes both signs (BIP-340 over a key stored with odd Y).  Digits and addresses are wave-uniform; the result is projective.
-S2K_DEV pt29r row_ladder_keyset(const uint4* __restrict__ kt, const row_iso& iso, const uint32_t* p, bool flip, gt_view gt,
-                                const fer_consts& k) {
-  using G = kt_geom<KS_CHUNKS>;
-  const fer one = k.j == 0 ? 1u : 0u;
-  const uint32_t pf = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[16]);
-  const bool neg1 = ((pf & PF_NEG1) != 0) != flip, neg2 = ((pf & PF_NEG2) != 0) != flip;
-  uint32_t a[4], b[4];       // (k1 - 1) / 2, (k2 - 1) / 2: 128 bits each
-  {
-    uint32_t k1[5], k2[5];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      k1[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[8 + w]);
-      k2[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[12 + w]);
-    }
-    k1[4] = (pf & PF_K1_B128) ? 1u : 0u;
-    k2[4] = (pf & PF_K2_B128) ? 1u : 0u;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      a[w] = (k1[w] >> 1) | (k1[w + 1] << 31);
-      b[w] = (k2[w] >> 1) | (k2[w + 1] << 31);
-    }
-  }
-  auto entry_of = [&](uint32_t c, uint32_t w, bool lam, bool sneg) -> pt29r {   // digit w (signed odd: 2w - 15) of chunk c
-    const bool neg = sneg != (w < 8u);
-    const uint4* e = kt + (size_t)(c * 8u + ((w < 8u) ? (7u - w) : (w - 8u))) * 8;
-    pt29r r;
-    r.x = ke_row_load(e, lam ? 2u : 0u, k);
-    r.y = ke_row_load(e, 1u, k);
-    r.z = one;
-    if (neg) r.y = fer_negate(r.y, 1, k);                           // [2]: the addition normalises y
-    return r;
-  };
-  pt29r acc;
-  {
-    const uint4* e = kt + (size_t)(neg1 == neg2 ? G::LEAD : G::LEAD + 1) * 8;   // +-(L +- phi(L))
-    acc.x = ke_row_load(e, 0u, k);
-    acc.y = ke_row_load(e, 1u, k);
-    acc.z = one;
-    if (neg1) acc.y = fer_negate(acc.y, 1, k);
-  }
-  pt29r a1 = entry_of(0u, a[0] & 15u, false, neg1), a2 = entry_of(0u, b[0] & 15u, true, neg2);
-#pragma unroll 1
-  for (uint32_t c = 0; c < (uint32_t)KS_CHUNKS; ++c) {
-    const pt29r c1 = a1, c2 = a2;
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      a[w] = (a[w] >> 4) | (a[w + 1] << 28);
-      b[w] = (b[w] >> 4) | (b[w + 1] << 28);
-    }
-    a[3] >>= 4;
-    b[3] >>= 4;
-    if (c + 1 < (uint32_t)KS_CHUNKS) {                              // in flight during the additions
-      a1 = entry_of(c + 1, a[0] & 15u, false, neg1);
-      a2 = entry_of(c + 1, b[0] & 15u, true, neg2);
-    }
-    acc = pt29r_add_b3(acc, c1, iso.b3, k);
-    acc = pt29r_add_b3(acc, c2, iso.b3, k);
-  }
-  acc = pt29r_from_iso(acc, iso.w, iso.w3, k);
-  uint32_t u[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) u[w] = p[w];
-  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-#pragma unroll 1
-  for (uint32_t w = 0; w < gt.windows; ++w) {
-    pt29r q;
-    q.x = fer_from_words(g.x.v, k);
-    q.y = fer_from_words(g.y.v, k);
-    q.z = one;
-    if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));   // in flight during the addition
-    acc = pt29r_add(acc, q, k);
-  }
-  return acc;
-}
-
-// k_verify_row over a key set: the signature names its key by index; an index outside the set or a key the set marks invalid
-// gives 0 without touching a table.  The block's preparation wave is the critical path in front of the ladder here (there is
-// no table build to hide it behind); the signature waves form W^3 and 21 W^6 meanwhile.
-__global__ void __launch_bounds__(320)
-k_verify_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint4* __restrict__ ktab,
-                    const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-                    const uint8_t* __restrict__ ssig, uint32_t flags, gt_view gt, uint8_t* __restrict__ out) {
-  __shared__ uint32_t prep_s[4][20];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) scalar_prep_one(i, dig, rsig, ssig, nullptr, flags, prep_s[lane]);
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  const fer_consts k = fer_setup(lane);
-  bool ok = false;
-  const uint4* kt = ktab;
-  row_iso iso = {0u, 0u, 0u};
-  if (sig < n) {
-    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
-    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
-    if (ok) {                                                   // (wave-uniform)
-      kt = ktab + (size_t)key * (KS_SLOTS * 8);
-      iso = row_iso_of(kt, k);
-    }
-  }
-  __syncthreads();
-  if (sig >= n) return;
-  const uint32_t* p = prep_s[wave];
-  if (!(ok && (p[16] & PF_OK))) {
-    if (lane == 0) out[sig] = 0;
-    return;
-  }
-  const pt29r acc = row_ladder_keyset(kt, iso, p, false, gt, k);
-  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
-  uint8_t verdict = 0;
-  if (!fer_is_zero(acc.z, k)) {
-    uint32_t rw[8];
-    load_be32(rw, rsig + (size_t)sig * 32);
-    bool match = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(rw, k), acc.z, k), 1, k)), k);
-    if (u256_lt(rw, FE_P_MINUS_N)) {
-      uint32_t r2[8];
-      u256_add(r2, rw, SC_N);
-      match = match || fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(r2, k), acc.z, k), 1, k)), k);
-    }
-    verdict = match ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
-}
-
-// ---- small calls over a COMB key set (S2K_KEYSET_COMB) ----
-// The comb's ladder doubles, and a doubling on the key's isomorphic curve would need the per-key constant as the addition
-// there does.  It is not run there: an affine entry (x, y) of y^2 = x^3 + 7 W^6 IS the projective point (x W : y : W^3) of
-// secp256k1 (pt29r_pair_from_iso, fe29r.h: one layer for the two entries of a column), and from then on the ladder is
-// pt29r_double and pt29r_add on secp256k1 itself - no b3, and no map back at the end.  37 additions of 3 layers, 18 doublings
-// of 2 and 19 conversions: 166 row-product layers on the key part, where row_ladder_keyset spends 64 x 4 + 1.
-// The key's W (one unit: a product's output) and W^3, formed once per signature
-struct row_comb_iso {
-  fer w, w3;
-};
-S2K_DEV row_comb_iso row_comb_iso_of(const uint4* __restrict__ kt, const fer_consts& k) {
-  row_comb_iso r;
-  r.w = ke_row_load(kt + (size_t)kc_geom::WENT * 8, kc_geom::W, k);
-  r.w3 = fer_mul(fer_mul(r.w, r.w, k), r.w, k);
-  return r;
-}
-// u * G + (+-k1) * Q + (+-k2) * lambda(Q), Q the key of the comb table kt (kc_geom): u | k1 | k2 | flags in the 17 words `p`
-// (LDS), the recoding that of k_verify_comb (comb_ladder.hip) - a' = (k >> 1) | 2^132 per half, tooth t its bits 19 t ..
-// 19 t + 18, column j the 7-bit index whose top bit is the sign; the LEAD slots are not read.  Column 18 starts the
-// accumulator as the sum of its two entries; rounds 17..0 double, add E1, add phi(E2).  `flip` changes both signs (BIP-340
-// over a key stored with odd Y).  Teeth, indices, signs and addresses are wave-uniform; the result is projective.
-S2K_DEV pt29r row_ladder_comb(const uint4* __restrict__ kt, fer w, fer w3, const uint32_t* p, bool flip, gt_view gt, const fer_consts& k) {
-  using G = kc_geom;
-  const fer one = k.j == 0 ? 1u : 0u;
-  const uint32_t pf = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[16]);
-  const bool neg1 = ((pf & PF_NEG1) != 0) != flip, neg2 = ((pf & PF_NEG2) != 0) != flip;
-  uint32_t t1[G::TEETH], t2[G::TEETH];
-  {
-    uint32_t k1[5], k2[5];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      k1[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[8 + i]);
-      k2[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)p[12 + i]);
-    }
-    k1[4] = (pf & PF_K1_B128) ? 1u : 0u;
-    k2[4] = (pf & PF_K2_B128) ? 1u : 0u;
-#pragma unroll
-    for (int t = 0; t < G::TEETH; ++t) {
-      const int bit = G::SPACING * t + 1, limb = bit >> 5, sh = bit & 31;      // (+ 1: a = k >> 1)
-      uint32_t v1 = k1[limb] >> sh, v2 = k2[limb] >> sh;
-      if (sh > 32 - G::SPACING) {
-        v1 |= k1[limb + 1] << (32 - sh);
-        v2 |= k2[limb + 1] << (32 - sh);
-      }
-      t1[t] = v1 & ((1u << G::SPACING) - 1u);
-      t2[t] = v2 & ((1u << G::SPACING) - 1u);
-    }
-    t1[G::TEETH - 1] |= 1u << (G::SPACING - 1);                                 // a' = a | 2^132: the lead, as a digit
-    t2[G::TEETH - 1] |= 1u << (G::SPACING - 1);
-  }
-  struct column {       // the two entries of a column as loaded: x of E1, beta x of E2, their y and whether each is negated
-    fer x1, y1, x2, y2;
-    bool n1, n2;
-  };
-  auto fetch = [&](int j) -> column {
-    uint32_t w1 = 0, w2 = 0;
-#pragma unroll
-    for (int t = 0; t < G::TEETH; ++t) {
-      w1 |= ((t1[t] >> j) & 1u) << t;
-      w2 |= ((t2[t] >> j) & 1u) << t;
-    }
-    const bool top1 = (w1 & 64u) != 0, top2 = (w2 & 64u) != 0;
-    const uint4 *e1 = kt + (size_t)((top1 ? w1 : ~w1) & 63u) * 8, *e2 = kt + (size_t)((top2 ? w2 : ~w2) & 63u) * 8;
-    column c;
-    c.x1 = ke_row_load(e1, 0u, k);
-    c.y1 = ke_row_load(e1, 1u, k);
-    c.x2 = ke_row_load(e2, 2u, k);
-    c.y2 = ke_row_load(e2, 1u, k);
-    c.n1 = neg1 != !top1;
-    c.n2 = neg2 != !top2;
-    return c;
-  };
-  auto entries = [&](const column& c, pt29r& e1, pt29r& e2) {
-    pt29r_pair_from_iso(c.x1, c.n1 ? fer_negate(c.y1, 1, k) : c.y1, c.x2, c.n2 ? fer_negate(c.y2, 1, k) : c.y2, w, w3, e1, e2, k);   // y [2]
-  };
-  column nx = fetch(G::SPACING - 1);
-  pt29r acc, e1, e2;
-  {
-    const column c = nx;
-    nx = fetch(G::SPACING - 2);                                     // in flight during the addition
-    entries(c, e1, e2);
-    acc = pt29r_add(e1, e2, k);
-  }
-#pragma unroll 1
-  for (int j = G::SPACING - 2; j >= 0; --j) {
-    const column c = nx;
-    if (j > 0) nx = fetch(j - 1);                                   // in flight during the round
-    acc = pt29r_double(acc, k);
-    entries(c, e1, e2);
-    acc = pt29r_add(acc, e1, k);
-    acc = pt29r_add(acc, e2, k);
-  }
-  uint32_t u[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) u[i] = p[i];
-  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-#pragma unroll 1
-  for (uint32_t i = 0; i < gt.windows; ++i) {
-    pt29r q;
-    q.x = fer_from_words(g.x.v, k);
-    q.y = fer_from_words(g.y.v, k);
-    q.z = one;
-    if (i + 1 < gt.windows) g = gt_load(gt, i + 1, gt_next_digit(u, gt.bits));   // in flight during the addition
-    acc = pt29r_add(acc, q, k);
-  }
-  return acc;
-}
-
-// k_verify_row_keyset over a comb set: same block, same validity rules, the table stride is the comb's
-__global__ void __launch_bounds__(320)
-k_verify_row_comb(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint4* __restrict__ ktab,
-                  const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-                  const uint8_t* __restrict__ ssig, uint32_t flags, gt_view gt, uint8_t* __restrict__ out) {
-  __shared__ uint32_t prep_s[4][20];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave (nothing called: no private segment)
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) scalar_prep_one<true>(i, dig, rsig, ssig, nullptr, flags, prep_s[lane]);
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  const fer_consts k = fer_setup(lane);
-  bool ok = false;
-  const uint4* kt = ktab;
-  row_comb_iso iso = {0u, 0u};
-  if (sig < n) {
-    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
-    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
-    if (ok) {                                                   // (wave-uniform)
-      kt = ktab + (size_t)key * (KC_SLOTS * 8);
-      iso = row_comb_iso_of(kt, k);
-    }
-  }
-  __syncthreads();
-  if (sig >= n) return;
-  const uint32_t* p = prep_s[wave];
-  if (!(ok && (p[16] & PF_OK))) {
-    if (lane == 0) out[sig] = 0;
-    return;
-  }
-  const pt29r acc = row_ladder_comb(kt, iso.w, iso.w3, p, false, gt, k);
-  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
-  uint8_t verdict = 0;
-  if (!fer_is_zero(acc.z, k)) {
-    uint32_t rw[8];
-    load_be32(rw, rsig + (size_t)sig * 32);
-    bool match = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(rw, k), acc.z, k), 1, k)), k);
-    if (u256_lt(rw, FE_P_MINUS_N)) {
-      uint32_t r2[8];
-      u256_add(r2, rw, SC_N);
-      match = match || fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(fer_from_words(r2, k), acc.z, k), 1, k)), k);
-    }
-    verdict = match ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
-}
-
-// FOUR LANES per signature (pt29q.h: a point is X | Y | Z | Z on the lanes of a quad, a layer of the complete formulas one lane
-// product): the ladders for calls between the wave-per-signature kernels and the lane-per-signature ones - a
-// doubling is 550 dependent instructions where a lane needs 1 070, so a lone wave is through its 16 signatures in half the
-// time, at twice the instructions per signature.  Behind the preparation kernels (one lane per signature).
-// quad_double_mult: u G + k1 Q + k2 lambda(Q) for the quad's signature, Q = (qx, qy) affine and on the curve; u | k1 | k2 | flags
-// from the preparation's planes.  The key's table - (2j + 1) Q, j < 8, projective - lives in LDS, tab[entry][limb][lane]: the
-// lanes of a quad hold x | y | z | beta * x of the entry (lane 3's copy of z is not read by an addition; lambda's image reads its
-// x from there).  Returns this lane's coordinate of the result.
-S2K_DEV fe29 quad_double_mult(const fe29& qx, const fe29& qy, uint32_t (*tab)[9][64], const uint32_t* __restrict__ prep, size_t stride,
-                              uint32_t sig, uint32_t pf, gt_view gt, uint32_t lane) {
-  const uint32_t q = lane & 3u;
-  const fe29 beta = fe29_from_words(FE_BETA), one = fe29_one();
-  {
-    fe29 cur = fe29_pick(q >= 2, fe29_pick(q == 1, qx, qy), one);                  // x | y | 1 | 1
-    const fe29 D = pt29q_double(cur, q);
-#pragma unroll 1
-    for (int j = 0; j < 8; ++j) {
-      if (j) cur = pt29q_add(cur, D, q);
-      const fe29 bx = fe29_mul(fe29_qperm<S2K_QP(0, 0, 0, 0)>(cur), beta);
-      const fe29 st = fe29_pick(q == 3, cur, bx);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) tab[j][i][lane] = st.n[i];
-    }
-  }
-  // |k1|, |k2| odd, < 2^129
-  sc k1 = sc_zero(), k2 = sc_zero();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    k1.v[w] = prep[(size_t)(8 + w) * stride + sig];
-    k2.v[w] = prep[(size_t)(12 + w) * stride + sig];
-  }
-  k1.v[4] = (pf & PF_K1_B128) ? 1u : 0u;
-  k2.v[4] = (pf & PF_K2_B128) ? 1u : 0u;
-  const bool neg1 = pf & PF_NEG1, neg2 = pf & PF_NEG2;
-  digit_stream d1 = ds_init(k1), d2 = ds_init(k2);
-  const uint32_t col3 = lane | 3u;
-  auto entry_of = [&](uint32_t w, bool lam, bool sneg) -> fe29 {   // this lane's coordinate of the entry of digit w (2w - 15)
-    const bool neg = sneg != (w < 8u);
-    const uint32_t e = (w < 8u) ? (7u - w) : (w - 8u);
-    const uint32_t col = (lam && q == 0) ? col3 : lane;            // lambda's image: x from the quad's fourth slot
-    fe29 a;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.n[i] = tab[e][i][col];
-    return fe29_normalize_weak(fe29_cond_negate1(a, neg && q == 1));
-  };
-  fe29 acc = pt29q_add(entry_of(8u, false, neg1), entry_of(8u, true, neg2), q);     // the top digits are +1 (w = 8)
-#pragma unroll 1
-  for (int i = 31; i >= 0; --i) {
-    const uint32_t w1 = ds_next(d1), w2 = ds_next(d2);
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) acc = pt29q_double(acc, q);
-    acc = pt29q_add(acc, entry_of(w1, false, neg1), q);
-    acc = pt29q_add(acc, entry_of(w2, true, neg2), q);
-  }
-  uint32_t u[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) u[w] = prep[(size_t)w * stride + sig];
-  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-#pragma unroll 1
-  for (uint32_t w = 0; w < gt.windows; ++w) {
-    const fe29 qc = fe29_pick(q >= 2, fe29_pick(q == 1, fe29_from_words(g.x.v), fe29_from_words(g.y.v)), one);
-    if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));
-    acc = pt29q_add(acc, qc, q);
-  }
-  return acc;
-}
-
-// PublicKey.Verify (secec/ecdsa.go:171, 392-470), four lanes per signature; behind k_scalar_prep
-__global__ void __launch_bounds__(256)
-k_verify_quad(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig, const uint32_t* __restrict__ prep,
-              gt_view gt, uint8_t* __restrict__ out, size_t stride) {
-  __shared__ uint32_t tab_all[4][8][9][64];
-  const uint32_t lane = threadIdx.x & 63u, q = lane & 3u;
-  const uint32_t sig0 = (blockIdx.x * 256 + threadIdx.x) >> 2;
-  const bool live = sig0 < n;
-  const uint32_t sig = live ? sig0 : n - 1;                     // (idle quads redo the last signature: no divergence, no store)
-  const uint32_t pf = prep[(size_t)16 * stride + sig];
-  uint32_t xw[8], yw[8];
-  load_be32(xw, pub + (size_t)sig * 64);
-  load_be32(yw, pub + (size_t)sig * 64 + 32);
-  bool ok = (pf & PF_OK) && fe_is_canonical_raw(xw) && fe_is_canonical_raw(yw);
-  fe29 qx = fe29_from_words(xw), qy = fe29_from_words(yw);
-  {   // y^2 == x^3 + 7 (point_s11n.go:298-307); an invalid key is replaced by G, its verdict is 0
-    fe29 rhs = fe29_mul(fe29_sqr(qx), qx);
-    rhs.n[0] += 7;
-    if (!fe29_eq(fe29_sqr(qy), rhs)) ok = false;
-    if (!ok) {
-      qx = fe29_from_words(FE_GX);
-      qy = fe29_from_words(FE_GY);
-    }
-  }
-  const fe29 acc = quad_double_mult(qx, qy, tab_all[threadIdx.x >> 6], prep, stride, sig, pf, gt, lane);
-  // ---- verdict: R != infinity and x(R) mod n == r (ecdsa.go:450-465), x(R) = X / Z ----
-  const pt29 R = pt29q_gather(acc);
-  uint8_t verdict = 0;
-  if (ok && !fe29_is_zero(R.z)) {
-    uint32_t rw[8];
-    load_be32(rw, rsig + (size_t)sig * 32);
-    bool match = fe29_eq(R.x, fe29_mul(fe29_from_words(rw), R.z));
-    if (u256_lt(rw, FE_P_MINUS_N)) {
-      uint32_t r2[8];
-      u256_add(r2, rw, SC_N);
-      match = match || fe29_eq(R.x, fe29_mul(fe29_from_words(r2), R.z));
-    }
-    verdict = match ? 1 : 0;
-  }
-  if (live && q == 0) out[sig] = verdict;
-}
-
-// SchnorrPublicKey.Verify (schnorr.go:221-253), four lanes per signature; behind k_schnorr_prep.  The two lifts - of the key and of
-// r, the point R would have to be - run side by side on the lanes of the quad (lanes 0, 2: the key; lanes 1, 3: r), one chain of
-// lane products; valid iff s G - e P is finite and equals (r, even y), compared projectively.
-__global__ void __launch_bounds__(256)
-k_schnorr_quad(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig64, const uint32_t* __restrict__ prep,
-               gt_view gt, uint8_t* __restrict__ out, size_t stride) {
-  __shared__ uint32_t tab_all[4][8][9][64];
-  const uint32_t lane = threadIdx.x & 63u, q = lane & 3u;
-  const uint32_t sig0 = (blockIdx.x * 256 + threadIdx.x) >> 2;
-  const bool live = sig0 < n;
-  const uint32_t sig = live ? sig0 : n - 1;
-  const uint32_t pf = prep[(size_t)16 * stride + sig];
-  uint32_t xw[8], rw[8];
-  load_be32(xw, pk + (size_t)sig * 32);
-  load_be32(rw, sig64 + (size_t)sig * 64);
-  bool ok = (pf & PF_OK) && fe_is_canonical_raw(xw);            // (PF_OK: r < p, s < n)
-  fe29 xP = fe29_from_words(xw);
-  const fe29 xR = fe29_from_words(rw);
-  const fe29 xin = fe29_pick((q & 1u) != 0, xP, xR);
-  fe29 c = fe29_mul(fe29_sqr(xin), xin);
-  c.n[0] += 7;
-  fe29 y;
-  const bool has = fe29_sqrt(y, c);
-  y = fe29_normalize(y);
-  y = fe29_pick((y.n[0] & 1u) != 0, y, fe29_normalize_weak(fe29_negate(y, 1)));       // the even root
-  const int hasP = __builtin_amdgcn_mov_dpp(has ? 1 : 0, S2K_QP(0, 0, 0, 0), 0xF, 0xF, true);
-  const int hasR = __builtin_amdgcn_mov_dpp(has ? 1 : 0, S2K_QP(1, 1, 1, 1), 0xF, 0xF, true);
-  ok = ok && hasP && hasR;
-  fe29 yP = fe29_qperm<S2K_QP(0, 0, 0, 0)>(y);
-  const fe29 yR = fe29_qperm<S2K_QP(1, 1, 1, 1)>(y);
-  if (!ok) {                                                    // keep the arithmetic on the curve; the verdict is 0
-    xP = fe29_from_words(FE_GX);
-    yP = fe29_from_words(FE_GY);
-  }
-  const fe29 acc = quad_double_mult(xP, yP, tab_all[threadIdx.x >> 6], prep, stride, sig, pf, gt, lane);
-  const pt29 R = pt29q_gather(acc);
-  uint8_t verdict = 0;
-  if (ok && !fe29_is_zero(R.z))
-    verdict = (fe29_eq(R.x, fe29_mul(xR, R.z)) && fe29_eq(R.y, fe29_mul(yR, R.z))) ? 1 : 0;
-  if (live && q == 0) out[sig] = verdict;
-}
-
-// RecoverPublicKey (ecdsa.go:244-282), four lanes per item; between k_scalar_prep (u1 = -e/r, u2 = s/r, the id in the flags) and
-// k_affine_finish<MODE_RECOVER>, which gets the Jacobian triple (X Z, Y Z^2, Z) it expects.  Items without a key: ok = 0 (their
-// record was zeroed before).
-__global__ void __launch_bounds__(256)
-k_recover_quad(uint32_t n, const uint8_t* __restrict__ rsig, const uint32_t* __restrict__ prep, gt_view gt, uint32_t* __restrict__ fin,
-               uint8_t* __restrict__ out, size_t stride) {
-  __shared__ uint32_t tab_all[4][8][9][64];
-  const uint32_t lane = threadIdx.x & 63u, q = lane & 3u;
-  const uint32_t sig0 = (blockIdx.x * 256 + threadIdx.x) >> 2;
-  const bool live = sig0 < n;
-  const uint32_t sig = live ? sig0 : n - 1;
-  const uint32_t pf = prep[(size_t)16 * stride + sig];
-  const uint32_t rid = (pf >> 8) & 3u;
-  uint32_t xw[8];
-  load_be32(xw, rsig + (size_t)sig * 32);
-  bool ok = (pf & PF_OK) != 0;                                  // (r, s in range, id < 4, r + n < p where the id asks for it)
-  if (ok && (rid & 2u)) u256_add(xw, xw, SC_N);
-  fe29 qx = fe29_from_words(xw);
-  fe29 c = fe29_mul(fe29_sqr(qx), qx);
-  c.n[0] += 7;
-  fe29 qy;
-  ok = fe29_sqrt(qy, c) && ok;
-  qy = fe29_normalize(qy);
-  qy = fe29_pick(((qy.n[0] & 1u) != 0) != ((rid & 1u) != 0), qy, fe29_normalize_weak(fe29_negate(qy, 1)));
-  if (!ok) {
-    qx = fe29_from_words(FE_GX);
-    qy = fe29_from_words(FE_GY);
-  }
-  const fe29 acc = quad_double_mult(qx, qy, tab_all[threadIdx.x >> 6], prep, stride, sig, pf, gt, lane);
-  const pt29 R = pt29q_gather(acc);
-  const bool finite = !fe29_is_zero(R.z);                       // identity: NewPublicKeyFromPoint fails (secec.go:206-209)
-  if (live && q == 0) {
-    if (ok && finite) {
-      const fe29 zz = fe29_sqr(R.z);
-      fq_store(fin, stride, sig, 0, fe29_mul(R.x, R.z));
-      fq_store(fin, stride, sig, 1, fe29_mul(R.y, zz));
-      fq_store(fin, stride, sig, 2, R.z);
-      out[sig] = VERDICT_PENDING;
-    } else {
-      out[sig] = 0;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
 // Affine epilogue of the BIP-340 and recovery paths.  Both need x/Z^2, y/Z^3 of the ladder's
 // result (the reference inverts per point: XBytes / IsYOdd, point_s11n.go:119-134); here one
 // thread takes FIN_M pending lanes (strided, so loads coalesce), multiplies their Z together,
@@ -1870,52 +1111,6 @@ k_affine_finish(uint32_t n, uint32_t T, const uint8_t* __restrict__ rsig, uint32
 // ---------------------------------------------------------------------------------------
 // BIP-340: scalar preparation (no inversion needed: R = s*G + (-e)*P) and complete fallback
 // ---------------------------------------------------------------------------------------
-S2K_DEV void schnorr_msg(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-                         size_t i, const uint8_t*& m, uint32_t& len) {
-  if (offs) {
-    m = msgs + offs[i];
-    len = (uint32_t)(offs[i + 1] - offs[i]);
-  } else {
-    m = msgs + i * (size_t)msg_len;
-    len = msg_len;
-  }
-}
-// parseSchnorrSignature (schnorr.go:420-449): r < p, s < n, e = H(r || P || m) mod n.
-// Returns ok; s and e as plain scalars.
-// (pk_i: the 32 bytes of item i's x-only key, wherever they live; FLAT: the hash expanded in place, sha256.h)
-template <bool FLAT = false>
-S2K_DEV bool schnorr_parse_key(size_t i, const uint8_t* __restrict__ pk_i, const uint8_t* __restrict__ sig,
-                               const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-                               sc& s_out, sc& e_out) {
-  uint32_t r_le[8], pk_le[8];
-  load_be32(r_le, sig + i * 64);
-  load_be32(s_out.v, sig + i * 64 + 32);
-  load_be32(pk_le, pk_i);
-  bool ok = fe_is_canonical_raw(r_le) && sc_is_canonical_raw(s_out.v);
-  uint32_t r_be[8], pk_be[8], dg[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    r_be[w] = r_le[7 - w];
-    pk_be[w] = pk_le[7 - w];
-  }
-  const uint8_t* m;
-  uint32_t len;
-  schnorr_msg(msgs, offs, msg_len, i, m, len);
-  if constexpr (FLAT) bip340_challenge_flat(dg, r_be, pk_be, m, len);
-  else bip340_challenge(dg, r_be, pk_be, m, len);
-  uint32_t e_raw[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) e_raw[w] = dg[7 - w];
-  e_out = sc_reduce_once(e_raw);
-  if (!ok) s_out = sc_zero();
-  return ok;
-}
-S2K_DEV bool schnorr_parse(size_t i, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
-                           const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-                           sc& s_out, sc& e_out) {
-  return schnorr_parse_key(i, pk + i * 32, sig, msgs, offs, msg_len, s_out, e_out);
-}
-
 __global__ void __launch_bounds__(256)
 k_schnorr_prep(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
                const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
@@ -1937,246 +1132,6 @@ k_schnorr_prep(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __rest
 #pragma unroll
   for (int w = 0; w < 4; ++w) prep[(size_t)(12 + w) * stride + i] = k2.v[w];
   prep[(size_t)16 * stride + i] = f;
-}
-
-// SchnorrPublicKey.Verify (schnorr.go:221-253) with one WAVEFRONT per signature (small batches; the block's fifth
-// wave hashes the challenges and splits -e meanwhile).  lift_x of the key and of r - the point R would have to be - run as
-// ONE chain of row products (rows 0, 1: the key; rows 2, 3: r): the signature is valid iff s G - e P is the point (r, even
-// y), compared projectively, so there is no inversion.
-// FUSED: five waves as described; the hashing makes that instance a 248-register kernel (two waves per SIMD), enough for up
-// to 1024 signatures (1280 waves).  !FUSED (larger calls): four waves behind k_schnorr_prep, whose planes they read - 62 registers.
-template <bool FUSED>
-__global__ void __launch_bounds__(FUSED ? 320 : 256)
-k_schnorr_row(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig64, const uint8_t* __restrict__ msgs,
-              const uint64_t* __restrict__ offs, uint32_t msg_len, const uint32_t* __restrict__ prep, size_t stride, gt_view gt,
-              uint8_t* __restrict__ out) {
-  __shared__ uint32_t tab_all[4][4][8][64];
-  __shared__ uint32_t prep_s[4][20];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if constexpr (!FUSED) {
-    const uint32_t i = blockIdx.x * 4 + wave;
-    if (lane < 17 && i < n) prep_s[wave][lane] = prep[(size_t)lane * stride + i];
-  }
-  if (FUSED && wave == 4) {                                     // the preparation wave (k_schnorr_prep for four signatures)
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) {
-      sc s, e;
-      const bool ok = schnorr_parse(i, pk, sig64, msgs, offs, msg_len, s, e);     // (r < p, s < n)
-      sc k1, k2;
-      bool neg1, neg2;
-      sc_split_glv_odd(sc_neg(e), k1, neg1, k2, neg2);          // schnorr.go:244
-      uint32_t* o = prep_s[lane];
-#pragma unroll
-      for (int w = 0; w < 8; ++w) o[w] = s.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[8 + w] = k1.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[12 + w] = k2.v[w];
-      o[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
-    }
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  const fer_consts k = fer_setup(lane);
-  bool ok = sig < n;
-  fer xR = 0, yR = 0;
-  if (ok) {
-    uint32_t xw[8], rw[8];
-    load_be32(xw, pk + (size_t)sig * 32);
-    load_be32(rw, sig64 + (size_t)sig * 64);
-    ok = fe_is_canonical_raw(xw);
-    const fer xP = fer_from_words(xw, k);
-    xR = fer_from_words(rw, k);
-    const fer c = fer_curve_rhs(fer_sel2(k, xP, xR), k);
-    const fer y = fer_sqrt_chain(c, k);
-    const bool is_root = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);     // (row by row)
-    const bool odd = fer_is_odd(y, k);
-    const fer y_even = fer_norm(odd ? fer_negate(y, 1, k) : y, k);
-    const uint64_t roots = __builtin_amdgcn_ballot_w64(is_root);
-    ok = ok && (roots & 1u) && ((roots >> 32) & 1u);            // both lifts exist (lane 0: the key, lane 32: r)
-    pt29r Q1;
-    Q1.x = xP;
-    fer_halves(y_even, Q1.y, yR);
-    Q1.z = k.j == 0 ? 1u : 0u;
-    if (ok) row_table(Q1, tab_all[wave], k, lane);              // (wave-uniform)
-  }
-  __syncthreads();
-  if (sig >= n) return;
-  const uint32_t* p = prep_s[wave];
-  if (!(ok && (p[16] & PF_OK))) {
-    if (lane == 0) out[sig] = 0;
-    return;
-  }
-  const pt29r acc = row_ladder(tab_all[wave], p, gt, k, lane);
-  // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
-  uint8_t verdict = 0;
-  if (!fer_is_zero(acc.z, k)) {
-    const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
-    const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
-    verdict = (mx && my) ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
-}
-
-// k_schnorr_row over a key set (row_ladder_keyset above).  The key needs no lift - the set holds X || Y, an odd stored Y flips
-// both half scalars' signs as in k_verify_fast's key-set modes - but r does: one square-root chain per signature, about as
-// long as the ladder itself.  It runs BESIDE the ladder: the block's sixth wave lifts the four r of the block in its four
-// rows while the signature waves run; they read y_r (even) from LDS for the verdict only, behind a second barrier.  The
-// fifth wave hashes the four challenges (over the set's X) and splits -e, as in k_schnorr_row<true>.
-__global__ void __launch_bounds__(384)
-k_schnorr_row_keyset(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint8_t* __restrict__ set_keys,
-                     const uint4* __restrict__ ktab, const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ sig64,
-                     const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len, gt_view gt,
-                     uint8_t* __restrict__ out) {
-  __shared__ uint32_t prep_s[4][20];
-  __shared__ uint32_t yr_s[4][16];          // y_r of the block's signatures, limb j at word j; word 15: r is an x of the curve
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) {
-      const uint32_t key = kidx[i];
-      sc s, e;
-      const bool ok = schnorr_parse_key(i, set_keys + (size_t)(key < nkeys ? key : 0u) * 64, sig64, msgs, offs, msg_len, s, e);   // (r < p, s < n)
-      sc k1, k2;
-      bool neg1, neg2;
-      sc_split_glv_odd(sc_neg(e), k1, neg1, k2, neg2);          // schnorr.go:244
-      uint32_t* o = prep_s[lane];
-#pragma unroll
-      for (int w = 0; w < 8; ++w) o[w] = s.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[8 + w] = k1.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[12 + w] = k2.v[w];
-      o[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
-    }
-    __syncthreads();
-    __syncthreads();
-    return;
-  }
-  const fer_consts k = fer_setup(lane);
-  if (wave == 5) {                                              // the lifting wave: row i takes r of the block's signature i
-    __syncthreads();
-    const uint32_t i = blockIdx.x * 4 + k.row;
-    uint32_t rw[8];
-    load_be32(rw, sig64 + (size_t)(i < n ? i : n - 1) * 64);
-    const fer c = fer_curve_rhs(fer_from_words(rw, k), k);
-    const fer y = fer_sqrt_chain(c, k);
-    const bool is_root = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);     // (row by row)
-    const fer y_even = fer_norm(fer_is_odd(y, k) ? fer_negate(y, 1, k) : y, k);
-    yr_s[k.row][k.j] = k.j == 15 ? (is_root ? 1u : 0u) : y_even;
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  bool ok = false, flip = false;
-  const uint4* kt = ktab;
-  row_iso iso = {0u, 0u, 0u};
-  if (sig < n) {
-    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
-    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
-    if (ok) {                                                   // (wave-uniform)
-      kt = ktab + (size_t)key * (KS_SLOTS * 8);
-      iso = row_iso_of(kt, k);
-      flip = (set_keys[(size_t)key * 64 + 63] & 1u) != 0;       // BIP-340 multiplies lift_x(X): the point with even Y
-    }
-  }
-  __syncthreads();
-  const uint32_t* p = prep_s[wave];
-  ok = ok && (p[16] & PF_OK);
-  pt29r acc = pt29r_identity(k);
-  if (ok) acc = row_ladder_keyset(kt, iso, p, flip, gt, k);     // (wave-uniform)
-  __syncthreads();
-  if (sig >= n) return;
-  // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
-  uint8_t verdict = 0;
-  if (ok && yr_s[wave][15] && !fer_is_zero(acc.z, k)) {
-    uint32_t rw[8];
-    load_be32(rw, sig64 + (size_t)sig * 64);
-    const fer xR = fer_from_words(rw, k), yR = k.j <= 8 ? yr_s[wave][k.j] : 0u;
-    const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
-    const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
-    verdict = (mx && my) ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
-}
-
-// k_schnorr_row_keyset over a comb set (row_ladder_comb): the same six waves and the same two barriers
-__global__ void __launch_bounds__(384)
-k_schnorr_row_comb(uint32_t n, uint32_t nkeys, const uint32_t* __restrict__ kidx, const uint8_t* __restrict__ set_keys,
-                   const uint4* __restrict__ ktab, const uint8_t* __restrict__ tinfo, const uint8_t* __restrict__ sig64,
-                   const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len, gt_view gt,
-                   uint8_t* __restrict__ out) {
-  __shared__ uint32_t prep_s[4][20];
-  __shared__ uint32_t yr_s[4][16];          // y_r of the block's signatures, limb j at word j; word 15: r is an x of the curve
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave (nothing called: no private segment)
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) {
-      const uint32_t key = kidx[i];
-      sc s, e;
-      const bool ok = schnorr_parse_key<true>(i, set_keys + (size_t)(key < nkeys ? key : 0u) * 64, sig64, msgs, offs, msg_len, s, e);   // (r < p, s < n)
-      sc k1, k2;
-      bool neg1, neg2;
-      sc_split_glv_odd(sc_neg(e), k1, neg1, k2, neg2);          // schnorr.go:244
-      uint32_t* o = prep_s[lane];
-#pragma unroll
-      for (int w = 0; w < 8; ++w) o[w] = s.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[8 + w] = k1.v[w];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o[12 + w] = k2.v[w];
-      o[16] = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
-    }
-    __syncthreads();
-    __syncthreads();
-    return;
-  }
-  const fer_consts k = fer_setup(lane);
-  if (wave == 5) {                                              // the lifting wave: row i takes r of the block's signature i
-    __syncthreads();
-    const uint32_t i = blockIdx.x * 4 + k.row;
-    uint32_t rw[8];
-    load_be32(rw, sig64 + (size_t)(i < n ? i : n - 1) * 64);
-    const fer c = fer_curve_rhs(fer_from_words(rw, k), k);
-    const fer y = fer_sqrt_chain(c, k);
-    const bool is_root = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);     // (row by row)
-    const fer y_even = fer_norm(fer_is_odd(y, k) ? fer_negate(y, 1, k) : y, k);
-    yr_s[k.row][k.j] = k.j == 15 ? (is_root ? 1u : 0u) : y_even;
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  bool ok = false, flip = false;
-  const uint4* kt = ktab;
-  row_comb_iso iso = {0u, 0u};
-  if (sig < n) {
-    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)kidx[sig]);
-    ok = key < nkeys && tinfo[key < nkeys ? key : 0u] != 0;
-    if (ok) {                                                   // (wave-uniform)
-      kt = ktab + (size_t)key * (KC_SLOTS * 8);
-      iso = row_comb_iso_of(kt, k);
-      flip = (set_keys[(size_t)key * 64 + 63] & 1u) != 0;       // BIP-340 multiplies lift_x(X): the point with even Y
-    }
-  }
-  __syncthreads();
-  const uint32_t* p = prep_s[wave];
-  ok = ok && (p[16] & PF_OK);
-  pt29r acc = pt29r_identity(k);
-  if (ok) acc = row_ladder_comb(kt, iso.w, iso.w3, p, flip, gt, k);     // (wave-uniform)
-  __syncthreads();
-  if (sig >= n) return;
-  // R = s G - e P is finite, x(R) = r and y(R) is even: X = r Z and Y = y_r Z with Z != 0
-  uint8_t verdict = 0;
-  if (ok && yr_s[wave][15] && !fer_is_zero(acc.z, k)) {
-    uint32_t rw[8];
-    load_be32(rw, sig64 + (size_t)sig * 64);
-    const fer xR = fer_from_words(rw, k), yR = k.j <= 8 ? yr_s[wave][k.j] : 0u;
-    const bool mx = fer_is_zero(fer_add(acc.x, fer_negate(fer_mul(xR, acc.z, k), 1, k)), k);
-    const bool my = fer_is_zero(fer_add(fer_norm(acc.y, k), fer_negate(fer_mul(yR, acc.z, k), 1, k)), k);
-    verdict = (mx && my) ? 1 : 0;
-  }
-  if (lane == 0) out[sig] = verdict;
 }
 
 // SchnorrPublicKey.Verify (schnorr.go:221-253) with complete formulas
@@ -2216,71 +1171,6 @@ k_schnorr_fallback(const uint32_t* __restrict__ wl_count, const uint32_t* __rest
   for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
     size_t idx = all_n ? w : wl[w];
     out[idx] = schnorr_verify_complete(idx, pk, sig, msgs, offs, msg_len, gt, qt, stride);
-  }
-}
-
-// RecoverPublicKey (ecdsa.go:244-282) with one WAVEFRONT per item (small batches; the block's fifth wave computes
-// u1 = -e/r, u2 = s/r meanwhile): R = (r or r + n, the root of the asked parity) by a chain of row products, Q = u1 G + u2 R
-// on the complete formulas, 1/Z by the inversion chain in row products, the 65-byte record written by the wave.  Items
-// without a key get ok = 0 and the zero record.
-__global__ void __launch_bounds__(320)
-k_recover_row(uint32_t n, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig,
-              const uint8_t* __restrict__ recid, gt_view gt, uint8_t* __restrict__ out, uint8_t* __restrict__ out_pts) {
-  __shared__ uint32_t tab_all[4][4][8][64];
-  __shared__ uint32_t prep_s[4][20];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (wave == 4) {                                              // the preparation wave
-    const uint32_t i = blockIdx.x * 4 + lane;
-    if (lane < 4 && i < n) scalar_prep_one(i, dig, rsig, ssig, recid, 0u, prep_s[lane]);
-    __syncthreads();
-    return;
-  }
-  const uint32_t sig = blockIdx.x * 4 + wave;
-  const fer_consts k = fer_setup(lane);
-  bool ok = sig < n;
-  if (ok) {
-    const uint32_t rid = recid[sig];
-    uint32_t xw[8];
-    load_be32(xw, rsig + (size_t)sig * 32);
-    if (rid & 2u) u256_add(xw, xw, SC_N);                       // (that r + n < p holds is the preparation wave's check)
-    pt29r Q1;
-    Q1.x = fer_from_words(xw, k);
-    Q1.z = k.j == 0 ? 1u : 0u;
-    const fer c = fer_curve_rhs(Q1.x, k);
-    const fer y = fer_sqrt_chain(c, k);
-    ok = fer_is_zero(fer_add(fer_mul(y, y, k), fer_negate(c, 1, k)), k);
-    Q1.y = fer_norm(fer_is_odd(y, k) != ((rid & 1u) != 0) ? fer_negate(y, 1, k) : y, k);
-    if (ok) row_table(Q1, tab_all[wave], k, lane);              // (wave-uniform)
-  }
-  __syncthreads();
-  if (sig >= n) return;
-  uint8_t* rec = out_pts + (size_t)sig * 65;
-  auto no_key = [&]() {                                         // ok = 0 and the zero record (RecoverPublicKey's error)
-    rec[lane] = 0;
-    if (lane == 0) {
-      rec[64] = 0;
-      out[sig] = 0;
-    }
-  };
-  const uint32_t* p = prep_s[wave];
-  if (!(ok && (p[16] & PF_OK))) {                               // (r, s in range, id < 4, r + n < p where the id asks for it)
-    no_key();
-    return;
-  }
-  const pt29r acc = row_ladder(tab_all[wave], p, gt, k, lane);
-  if (fer_is_zero(acc.z, k)) {                                  // identity: NewPublicKeyFromPoint fails (secec.go:206-209)
-    no_key();
-    return;
-  }
-  const fer zi = fer_inv_chain(acc.z, k);
-  uint32_t xw[8], yw[8];
-  fe29_to_words(xw, fe29_normalize(fer_to_fe29(fer_mul(acc.x, zi, k))));
-  fe29_to_words(yw, fe29_normalize(fer_to_fe29(fer_mul(fer_norm(acc.y, k), zi, k))));
-  if (lane == 0) {
-    rec[0] = 0x04;
-    store_be32_unaligned(rec + 1, xw);
-    store_be32_unaligned(rec + 33, yw);
-    out[sig] = 1;
   }
 }
 
@@ -2549,8 +1439,8 @@ __attribute__((visibility("hidden"))) void prof_mark(s2k_ctx* ctx, hipStream_t s
 // One launcher per kernel: it enqueues on the stream it is given and does nothing else (error checks, events and profiling
 // marks stay with the flows).  `ctx` gives the call's generator table (gt_call) and the worklist kernels' grid.
 // launch_scalar_prep: signatures [first, first + count) on `lanes` lanes (the planes are linear in the signature index: a piece
-// is the same kernel on shifted pointers); launch_ladder: the only place that names an instantiation of k_verify_fast;
-// launch_schnorr_row: prep == nullptr is k_schnorr_row<true>, whose fifth wave prepares.
+// is the same kernel on shifted pointers); launch_ladder: the only place that names an instantiation of k_verify_fast.
+// The launchers of the wave-per-signature and four-lanes-per-signature kernels: small_call.hip.
 __attribute__((visibility("hidden"))) void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t count, uint32_t lanes, const uint8_t* dig, const uint8_t* r,
                                const uint8_t* s, const uint8_t* recid, uint32_t flags) {
   k_scalar_prep<<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)count, lanes, dig + first * 32, r + first * 32, s + first * 32,
@@ -2662,51 +1552,6 @@ static void launch_point_fallback(const s2k_ctx* ctx, hipStream_t st, bool all, 
   else
     k_point_fallback<false><<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, u1, u2, pts65, out65, ctx->gt_call, w.qt,
                                                                      w.stride, status);
-}
-static void launch_verify_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
-                              uint32_t flags, uint8_t* out) {
-  k_verify_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, pub, dig, r, s, flags, ctx->gt_call, out);
-}
-__attribute__((visibility("hidden"))) void launch_verify_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
-                                     const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
-  k_verify_row_keyset<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, ktab, tinfo, dig, r, s, flags, ctx->gt_call,
-                                                               out);
-}
-__attribute__((visibility("hidden"))) void launch_verify_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
-                                   const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
-  k_verify_row_comb<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, ktab, tinfo, dig, r, s, flags, ctx->gt_call, out);
-}
-static void launch_schnorr_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
-                               const uint64_t* offs, uint32_t msg_len, const uint32_t* prep, size_t stride, uint8_t* out) {
-  if (!prep)
-    k_schnorr_row<true><<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, nullptr, 0, ctx->gt_call, out);
-  else
-    k_schnorr_row<false><<<(unsigned)((n + 3) / 4), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, prep, stride, ctx->gt_call, out);
-}
-__attribute__((visibility("hidden"))) void launch_schnorr_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
-                                      const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
-                                      uint32_t msg_len, uint8_t* out) {
-  k_schnorr_row_keyset<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, set_keys, ktab, tinfo, sig, msgs, offs,
-                                                                msg_len, ctx->gt_call, out);
-}
-__attribute__((visibility("hidden"))) void launch_schnorr_row_comb(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,
-                                    const uint4* ktab, const uint8_t* tinfo, const uint8_t* sig, const uint8_t* msgs, const uint64_t* offs,
-                                    uint32_t msg_len, uint8_t* out) {
-  k_schnorr_row_comb<<<(unsigned)((n + 3) / 4), 384, 0, st>>>((uint32_t)n, (uint32_t)nkeys, kidx, set_keys, ktab, tinfo, sig, msgs, offs,
-                                                              msg_len, ctx->gt_call, out);
-}
-static void launch_recover_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
-                               const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
-  k_recover_row<<<(unsigned)((n + 3) / 4), 320, 0, st>>>((uint32_t)n, dig, r, s, recid, ctx->gt_call, ok, pub65);
-}
-static void launch_verify_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* r, const lane_ws& w, uint8_t* out) {
-  k_verify_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, pub, r, w.prep, ctx->gt_call, out, w.stride);
-}
-static void launch_schnorr_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const lane_ws& w, uint8_t* out) {
-  k_schnorr_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, pk, sig, w.prep, ctx->gt_call, out, w.stride);
-}
-static void launch_recover_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* r, const lane_ws& w, uint8_t* out) {
-  k_recover_quad<<<(unsigned)((n + 63) / 64), 256, 0, st>>>((uint32_t)n, r, w.prep, ctx->gt_call, w.fin, out, w.stride);
 }
 
 // Front end of the grouped flows (ECDSA and BIP-340 verification): everything up to the ladders.
@@ -3436,44 +2281,6 @@ int s2k_ecdsa_recover_batch_device(s2k_ctx* ctx, size_t n, const void* d_dig, co
   return ctx_leave(ctx, st);
 }
 
-}  // extern "C"
-// Small synchronous calls from host memory (up to the small-batch threshold, s2k_ctx_set_small_batch_max): the inputs are
-// copied by the CPU into a page-locked block that the kernels read in place, and the kernels write the results there - no
-// DMA transfer at all.  The five transfers of a 1024-signature call cost 45 us of its 0.23 ms, more than its 160 KB take
-// either way.  `count` pieces of `sizes[i]` bytes, 256-byte aligned; host[i] / dev[i]: the same piece as the CPU and as the
-// device address it.  (Synchronous entry points only: the block is free again when the call returns.)
-__attribute__((visibility("hidden"))) int s2k_internal_small_block(s2k_ctx* ctx, const size_t* sizes, int count, uint8_t** host, uint8_t** dev) {
-  size_t total = 0;
-  for (int i = 0; i < count; ++i) total += (sizes[i] + 255) & ~(size_t)255;
-  if (total > ctx->h_small_bytes) {
-    if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-    ctx->h_small = ctx->d_small = nullptr;
-    ctx->h_small_bytes = 0;
-    const size_t want = (total + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    void *h = nullptr, *d = nullptr;
-    HIP_TRY(ctx, hipHostMalloc(&h, want, hipHostMallocDefault));
-    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipHostFree(h);
-      return fail(ctx, S2K_ERR_HIP, "hipHostGetDevicePointer failed for the small-call block");
-    }
-    ctx->h_small = (uint8_t*)h;
-    ctx->d_small = (uint8_t*)d;
-    ctx->h_small_bytes = want;
-  }
-  size_t off = 0;
-  for (int i = 0; i < count; ++i) {
-    host[i] = ctx->h_small + off;
-    dev[i] = ctx->d_small + off;
-    off += (sizes[i] + 255) & ~(size_t)255;
-  }
-  return S2K_OK;
-}
-__attribute__((visibility("hidden"))) bool s2k_internal_small_call(const s2k_ctx* ctx, size_t n, uint32_t flags) {
-  static const bool off = [] { const char* v = getenv("S2K_SMALL_CALLS_DMA"); return v && atoi(v) != 0; }();   // (A/B knob)
-  return !off && n <= ctx->row_max && !(flags & (S2K_ECDSA_FORCE_COMPLETE | S2K_ECDSA_FORCE_WORKLIST));
-}
-extern "C" {
 int s2k_ecdsa_recover_batch(s2k_ctx* ctx, size_t n, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
                             const uint8_t* recid, uint32_t flags, uint8_t* pub65, uint8_t* ok) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
@@ -3605,57 +2412,6 @@ int s2k_schnorr_verify_batch_device(s2k_ctx* ctx, size_t n, const void* d_pk, co
 // host-to-device copy of chunk j+1 runs on its own stream while chunk j is verified: for pageable
 // callers' memory the copy costs about half as much as the verification, so most of it hides.
 // Staging buffers and streams live in the context (no hipMalloc per call).
-// page-locked host memory the runtime can copy from asynchronously (hipHostMalloc or hipHostRegister)
-static bool host_pinned_at(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();          // an ordinary malloc'ed pointer: "invalid value", not an error of ours
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
-}
-// (first AND last byte: a buffer registered for fewer bytes than the call reads must not take the asynchronous path)
-static bool host_pinned(const void* p, size_t bytes) {
-  return host_pinned_at(p) && (bytes < 2 || host_pinned_at((const uint8_t*)p + bytes - 1));
-}
-void* s2k_host_alloc(size_t bytes) {
-  void* p = nullptr;
-  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  return p;
-}
-void s2k_host_free(void* p) {
-  if (p) (void)hipHostFree(p);
-}
-int s2k_host_register(void* p, size_t bytes) {
-  if (!p || !bytes) return fail(nullptr, S2K_ERR_ARG, "s2k_host_register: null buffer");
-  // Whole pages only.  The runtime pins and, on unregister, unmaps PAGES: registering a block of the C heap takes the
-  // neighbouring blocks of its first and last page along.  Seen on ROCm 7.2 / MI355X: four small malloc'ed arrays
-  // registered and unregistered, the allocator hands the same pages out again as part of a 2 MB block, and a plain
-  // pageable hipMemcpy from that block dies with a GPU memory access fault (tests/test_gpu_round3.py history).
-  const size_t page = (size_t)sysconf(_SC_PAGESIZE);
-  if (((uintptr_t)p % page) || (bytes % page))
-    return fail(nullptr, S2K_ERR_ARG, "s2k_host_register: buffer must start on a page boundary and cover whole pages (%zu bytes): "
-                                      "register memory that owns its pages (mmap, aligned_alloc), or use s2k_host_alloc", page);
-  hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(nullptr, S2K_ERR_HIP, "hipHostRegister: %s", hipGetErrorString(e));
-  }
-  return S2K_OK;
-}
-int s2k_host_unregister(void* p) {
-  if (!p) return fail(nullptr, S2K_ERR_ARG, "s2k_host_unregister: null buffer");
-  hipError_t e = hipHostUnregister(p);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(nullptr, S2K_ERR_HIP, "hipHostUnregister: %s", hipGetErrorString(e));
-  }
-  return S2K_OK;
-}
-
 // Everything of a host-buffer verification except the final wait: copies in, kernels, verdicts to h_out (host memory; the
 // copy is asynchronous when h_out is page-locked).  All work ends on ctx->s_comp.  one_shot: the batch is not cut into
 // chunks (submit / wait: the other slot's batch is what this one's transfer hides behind, and ONE grouped call sees every
@@ -3677,7 +2433,8 @@ static int verify_batch_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pub
   // grouping and the per-key tables start on them, and the digests and signatures cross PCIe meanwhile (the scalar
   // preparation on the second stream waits for them).  From pageable memory a copy is staged by the runtime and the
   // same order measured slower than two independent halves (9.0 against 8.4-8.6 ms per 2^20), which stay the path there.
-  const bool pinned = host_pinned(pub, n * 64) && host_pinned(dig, n * 32) && host_pinned(r, n * 32) && host_pinned(s, n * 32);
+  const bool pinned = s2k_internal_host_pinned(pub, n * 64) && s2k_internal_host_pinned(dig, n * 32) && s2k_internal_host_pinned(r, n * 32) &&
+                      s2k_internal_host_pinned(s, n * 32);
   // (submit / wait, one_shot: no pieces - the other tickets' kernels are what the transfer hides behind, and the ticket runs
   // one compute stream; measured 5.07 against 5.13 ms per 2^20 with the pieces.  S2K_SUBMIT_ARRIVALS=1: measurement knob)
   static const bool submit_arrivals = [] { const char* v = getenv("S2K_SUBMIT_ARRIVALS"); return v && atoi(v) != 0; }();
@@ -3734,16 +2491,6 @@ static int verify_batch_enqueue_inner(s2k_ctx* ctx, size_t n, const uint8_t* pub
   HIP_TRY(ctx, hipMemcpyAsync(h_out, d_valid, n, hipMemcpyDeviceToHost, ctx->s_comp));
   return S2K_OK;
 }
-// An error return leaves copies from (and to) caller-owned memory in flight on the context's streams: wait for them before the
-// caller may free or unregister that memory (the message of the error is kept).
-}  // extern "C"
-__attribute__((visibility("hidden"))) void s2k_internal_drain(s2k_ctx* ctx) {
-  if (ctx->s_copy) (void)hipStreamSynchronize(ctx->s_copy);
-  if (ctx->s_aux) (void)hipStreamSynchronize(ctx->s_aux);
-  if (ctx->s_comp) (void)hipStreamSynchronize(ctx->s_comp);
-  (void)hipGetLastError();
-}
-extern "C" {
 static int verify_batch_enqueue(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
                                 const uint8_t* s, uint32_t flags, uint8_t* h_out, bool one_shot) {
   const int rc = verify_batch_enqueue_inner(ctx, n, pub, dig, r, s, flags, h_out, one_shot);
@@ -3786,266 +2533,6 @@ int s2k_ecdsa_verify_batch(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uin
   return S2K_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// submit / wait: the host-pointer entry points without the wait at their end.  The reference's caller holds its data in
-// host memory (secec/ecdsa.go:171-228) and a synchronous call pays transfer and compute in series: 7.1 ms from pinned
-// memory, 8.2 from pageable against 4.9 ms resident per 2^20 signatures (round 3).  Here the context owns child contexts
-// ("slots": own workspaces and staging buffers; the 40 GiB generator tables are shared per device) that take the submitted
-// batches in turn.  The children run on the PARENT's streams, in two lanes: even tickets on the parent's own two compute
-// streams, odd tickets on a second pair, one copy stream for all.  Within a lane the kernels of consecutive tickets follow
-// each other in stream order, each ticket with the two-stream overlap of a resident call (grouping and tables beside
-// preparation and generator part); the lanes run beside each other as two resident contexts do (worth 3 %); a ticket's
-// 160 MiB cross PCIe (3.0 ms) on the copy stream beside the kernels of the tickets before it.  Up to four tickets are in
-// flight (per lane one computing, one arriving); a fifth submit first retires the oldest one (its verdicts are delivered;
-// a later s2k_wait on its ticket returns at once).
-// (Earlier forms gave every ticket streams of its own so that one ticket's grouping and tables could run beside another's
-// ladder.  They do not: the keyed ladder holds 4 x 128 of a SIMD's 512 VGPRs, so the other ticket's kernels crawl, its
-// empty tail launches - 161 VGPRs a wave - wait milliseconds for room, and nine streams on the runtime's hardware queues
-// serialise at random.  5.2-5.7 ms per batch against 4.7-4.9 this way; profiles/r04_pipeline_timeline.txt.)
-// ---------------------------------------------------------------------------------------
-}  // extern "C"
-static void pipe_note_failure(s2k_ctx* ctx, uint64_t ticket, int rc) {
-  const unsigned i = ctx->pipe_failed_n++ % 8u;
-  ctx->pipe_failed[i] = ticket;
-  ctx->pipe_failed_rc[i] = rc;
-}
-// waits for the slot's batch and delivers its verdicts; the slot is free afterwards
-__attribute__((visibility("hidden"))) int s2k_internal_pipe_retire(s2k_ctx* ctx, s2k_ctx::pipe_slot& sl) {
-  if (!sl.ticket) return S2K_OK;
-  int rc = S2K_OK;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(sl.done) != hipSuccess) {
-    rc = fail(ctx, S2K_ERR_HIP, "ticket %llu: the batch did not complete: %s", (unsigned long long)sl.ticket,
-              hipGetErrorString(hipGetLastError()));
-    s2k_internal_drain(sl.ctx);
-  } else if (!sl.direct) {
-    memcpy(sl.dst, sl.h_valid, sl.n);
-  }
-  if (rc == S2K_OK && sl.timed) {                    // s2k_ctx_ticket_timing: transfer and whole-ticket time on the device's clock
-    float h2d = 0, all = 0;
-    // (t_copied sits on the copy stream behind the ticket's transfers; with more streams in the process than hardware queues
-    // its marker can still be waiting in a shared queue when the ticket's verdicts are there - eight members on one device
-    // showed it: then it is waited for, the copies themselves are long done)
-    const hipError_t e0 = hipEventSynchronize(sl.t_end);
-    hipError_t e1 = hipEventElapsedTime(&h2d, sl.t_begin, sl.t_copied);
-    if (e1 == hipErrorNotReady) {
-      (void)hipGetLastError();
-      (void)hipEventSynchronize(sl.t_copied);
-      e1 = hipEventElapsedTime(&h2d, sl.t_begin, sl.t_copied);
-    }
-    const hipError_t e2 = hipEventElapsedTime(&all, sl.t_begin, sl.t_end);
-    const unsigned i = ctx->pipe_times_n++ % 8u;
-    ctx->pipe_times_ticket[i] = sl.ticket;
-    if (e0 == hipSuccess && e1 == hipSuccess && e2 == hipSuccess) {
-      ctx->pipe_times_ms[i][0] = h2d;
-      ctx->pipe_times_ms[i][1] = all;
-    } else {                                           // no times for this ticket: the runtime's codes, negated, say why
-      (void)hipGetLastError();
-      ctx->pipe_times_ms[i][0] = -(float)(e1 != hipSuccess ? e1 : e0);
-      ctx->pipe_times_ms[i][1] = -(float)(e2 != hipSuccess ? e2 : e0);
-    }
-  }
-  sl.timed = false;
-  sl.ticket = 0;
-  return rc;
-}
-// the slot the next ticket runs on, free, with its child context and landing buffer in place
-__attribute__((visibility("hidden"))) int s2k_internal_pipe_slot(s2k_ctx* ctx, size_t n, uint8_t* valid, s2k_ctx::pipe_slot** out) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  s2k_ctx::pipe_slot& sl = ctx->pipe[ctx->pipe_next % s2k_ctx::PIPE_SLOTS];
-  if (sl.ticket) {                                   // every slot holds a batch: the oldest one (this slot's) is retired first
-    const uint64_t t = sl.ticket;
-    const int rc = s2k_internal_pipe_retire(ctx, sl);
-    if (rc) pipe_note_failure(ctx, t, rc);           // (reported by s2k_wait on that ticket)
-  }
-  if (!sl.ctx) {
-    // first use of the slot.  All or nothing: a failure anywhere leaves the slot as it was found (no child context, no
-    // event), so that the next submit tries again from the start instead of running on a half-built slot.
-    int rc = ctx_streams(ctx);                        // the parent's three streams carry every ticket
-    if (rc == S2K_OK) rc = ctx_aux_streams(ctx);
-    if (rc) return rc;
-    const bool odd_lane = (ctx->pipe_next & 1u) != 0;   // (PIPE_SLOTS is even: a slot always serves the same lane)
-    static const bool one_lane = [] { const char* v = getenv("S2K_SUBMIT_ONE_LANE"); return v && atoi(v) != 0; }();   // measurement knob
-    if (odd_lane && !one_lane && !(ctx->lane1_comp && ctx->lane1_aux)) {   // the second lane's two streams: both or neither
-      hipStream_t a = nullptr, b = nullptr;
-      if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&b, hipStreamNonBlocking) != hipSuccess) {
-        const hipError_t e = hipGetLastError();
-        if (a) (void)hipStreamDestroy(a);
-        if (b) (void)hipStreamDestroy(b);
-        return fail(ctx, S2K_ERR_HIP, "submit: streams of the second lane: %s", hipGetErrorString(e));
-      }
-      ctx->lane1_comp = a;
-      ctx->lane1_aux = b;
-    }
-    s2k_ctx* child = nullptr;
-    rc = s2k_ctx_create_ex(ctx->device, ctx->gt_fixed, 0, &child);   // the parent's table width, explicit or automatic
-    if (rc) return fail(ctx, rc, "submit: child context: %s", s2k_last_error(nullptr));
-    child->s_copy = ctx->s_copy;
-    child->s_comp = (odd_lane && !one_lane) ? ctx->lane1_comp : ctx->s_comp;
-    child->s_aux = (odd_lane && !one_lane) ? ctx->lane1_aux : ctx->s_aux;
-    child->streams_shared = true;
-    rc = ctx_streams(child);                          // (its events)
-    if (rc == S2K_OK) rc = ctx_aux_streams(child);
-    hipEvent_t done = nullptr;
-    if (rc == S2K_OK && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
-      snprintf(child->err, sizeof child->err, "hipEventCreate: %s", hipGetErrorString(hipGetLastError()));
-      rc = S2K_ERR_HIP;
-    }
-    if (rc) {
-      rc = fail(ctx, rc, "submit: child context: %s", child->err);
-      s2k_ctx_destroy(child);                         // (streams_shared: the parent's streams stay)
-      return rc;
-    }
-    sl.ctx = child;
-    sl.done = done;
-  }
-  if (ctx->pipe_timing && !sl.t_begin) {              // timing events on demand; a failure only means no times for this slot
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    bool ok = true;
-    for (int i = 0; i < 3 && ok; ++i) ok = hipEventCreate(&e[i]) == hipSuccess;
-    if (ok) {
-      sl.t_begin = e[0];
-      sl.t_copied = e[1];
-      sl.t_end = e[2];
-    } else {
-      (void)hipGetLastError();
-      for (int i = 0; i < 3; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  }
-  sl.timed = ctx->pipe_timing && sl.t_begin && hipEventRecord(sl.t_begin, ctx->s_copy) == hipSuccess;
-  // the child verifies with the parent's settings of the moment
-  sl.ctx->kg_mode = ctx->kg_mode;
-  sl.ctx->parent = ctx;
-  sl.ctx->kg_min_group = ctx->kg_min_group;
-  sl.ctx->kg_hash_bits = ctx->kg_hash_bits;
-  sl.ctx->kg_max_tables = ctx->kg_max_tables;
-  sl.ctx->kt_comb = ctx->kt_comb;
-  sl.ctx->row_max = ctx->row_max;
-  sl.ctx->ks_row_max = ctx->ks_row_max;
-  sl.ctx->ks_comb_row_max = ctx->ks_comb_row_max;
-  sl.ctx->quad_max = ctx->quad_max;
-  sl.direct = host_pinned(valid, n);
-  if (!sl.direct && sl.h_valid_bytes < n) {
-    if (sl.h_valid) (void)hipHostFree(sl.h_valid);
-    sl.h_valid = nullptr;
-    sl.h_valid_bytes = 0;
-    const size_t want = (n + 4095) & ~(size_t)4095;
-    HIP_TRY(ctx, hipHostMalloc((void**)&sl.h_valid, want, hipHostMallocDefault));
-    sl.h_valid_bytes = want;
-  }
-  sl.dst = valid;
-  sl.n = n;
-  *out = &sl;
-  return S2K_OK;
-}
-__attribute__((visibility("hidden"))) void s2k_internal_pipe_issue(s2k_ctx* ctx, s2k_ctx::pipe_slot* sl, s2k_ticket* ticket) {
-  // s2k_ctx_ticket_timing: t_begin (s2k_internal_pipe_slot) and t_copied bracket the ticket's transfers on the copy stream; the
-  // compute stream WAITS for t_copied before t_end is recorded behind the verdicts, so that first copy start <= last copy end
-  // <= verdicts holds on the device's clock however the runtime multiplexes the streams onto hardware queues (eight members on
-  // one device: a marker could be processed after another stream's later one).  Costs the ticket nothing
-  // while the timing is off.
-  if (sl->timed)
-    sl->timed = hipEventRecord(sl->t_copied, ctx->s_copy) == hipSuccess && hipStreamWaitEvent(sl->ctx->s_comp, sl->t_copied, 0) == hipSuccess &&
-                hipEventRecord(sl->t_end, sl->ctx->s_comp) == hipSuccess;
-  if (hipEventRecord(sl->done, sl->ctx->s_comp) != hipSuccess) {    // behind the ticket's last operation (on its lane's stream)
-    // no event to wait on: the ticket is made to finish here, so that s2k_wait finds it done (or reports this failure)
-    const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(sl->ctx->s_comp);
-    (void)fail(ctx, S2K_ERR_HIP, "submit: hipEventRecord: %s", hipGetErrorString(e));
-  }
-  sl->ticket = ctx->pipe_next++;
-  *ticket = sl->ticket;
-}
-__attribute__((visibility("hidden"))) bool s2k_internal_host_pinned(const void* p, size_t bytes) { return host_pinned(p, bytes); }
-
-// Staging around a device form (engine_internal.h: stage_part).  The inputs of a call up, on `st` ...
-static int stage_copies_in(s2k_ctx* ctx, const stage_part* parts, int count, uint8_t* const* d, hipStream_t st) {
-  for (int i = 0; i < count; ++i)
-    if (parts[i].src && parts[i].bytes) HIP_TRY(ctx, hipMemcpyAsync(d[i], parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, st));
-  return S2K_OK;
-}
-// ... and its results back (landing: where a ticket's verdicts go instead of the caller's array; null: to the parts' own dst)
-static int stage_copies_out(s2k_ctx* ctx, const stage_part* parts, int count, uint8_t* const* d, hipStream_t st, void* landing) {
-  for (int i = 0; i < count; ++i)
-    if (parts[i].dst) HIP_TRY(ctx, hipMemcpyAsync(landing ? landing : parts[i].dst, d[i], parts[i].bytes, hipMemcpyDeviceToHost, st));
-  return S2K_OK;
-}
-__attribute__((visibility("hidden"))) int s2k_internal_staged_call(s2k_ctx* ctx, const stage_part* parts, int count, size_t phase_bytes,
-                                                                   bool small, const stage_run& run) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ctx_streams(ctx);
-  if (rc) return rc;
-  size_t sizes[STAGE_MAX_PARTS];
-  uint8_t *h[STAGE_MAX_PARTS], *d[STAGE_MAX_PARTS];
-  for (int i = 0; i < count; ++i) sizes[i] = parts[i].reserve;
-  hipStream_t st = ctx->s_comp;
-  if (small) {                                             // (s2k_internal_small_block: no DMA transfers)
-    rc = s2k_internal_small_block(ctx, sizes, count, h, d);
-    if (rc) return rc;
-    for (int i = 0; i < count; ++i)
-      if (parts[i].src && parts[i].bytes) memcpy(h[i], parts[i].src, parts[i].bytes);
-    rc = run(ctx, d, st);
-    if (rc) {
-      s2k_internal_drain(ctx);
-      return rc;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    for (int i = 0; i < count; ++i)
-      if (parts[i].dst) memcpy(parts[i].dst, h[i], parts[i].bytes);
-    ctx->have_last = false;
-    return S2K_OK;
-  }
-  // staged in the context's buffers on its compute stream (no allocation per call)
-  rc = ctx_stage(ctx, sizes, count, d);
-  if (rc) return rc;
-  rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  s2k_phase_guard phase(ctx->device, phase_bytes);         // (two verifiers on two threads: engine_internal.h)
-  rc = stage_copies_in(ctx, parts, count, d, st);
-  if (rc) return rc;
-  HIP_TRY(ctx, phase.landed(st));
-  rc = run(ctx, d, st);
-  if (rc) {
-    s2k_internal_drain(ctx);
-    return rc;
-  }
-  rc = stage_copies_out(ctx, parts, count, d, st, nullptr);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  ctx->have_last = false;
-  return S2K_OK;
-}
-__attribute__((visibility("hidden"))) int s2k_internal_staged_submit(s2k_ctx* ctx, size_t n, uint8_t* valid, const stage_part* parts, int count,
-                                                                     const stage_run& run, s2k_ticket* ticket) {
-  s2k_ctx::pipe_slot* sl = nullptr;
-  int rc = s2k_internal_pipe_slot(ctx, n, valid, &sl);
-  if (rc) return rc;
-  if (n) {
-    s2k_ctx* c = sl->ctx;
-    auto enqueue = [&]() -> int {
-      size_t sizes[STAGE_MAX_PARTS];
-      uint8_t* d[STAGE_MAX_PARTS];
-      for (int i = 0; i < count; ++i) sizes[i] = parts[i].reserve;
-      int rc2 = ctx_stage(c, sizes, count, d);
-      if (rc2 == S2K_OK) rc2 = stage_copies_in(c, parts, count, d, c->s_copy);
-      if (rc2) return rc2;
-      HIP_TRY(c, hipEventRecord(c->ev_copied[0], c->s_copy));
-      HIP_TRY(c, hipStreamWaitEvent(c->s_comp, c->ev_copied[0], 0));
-      rc2 = run(c, d, c->s_comp);
-      if (rc2) return rc2;
-      return stage_copies_out(c, parts, count, d, c->s_comp, sl->direct ? valid : sl->h_valid);
-    };
-    rc = enqueue();
-    if (rc) {
-      s2k_internal_drain(c);
-      return fail(ctx, rc, "%s", c->err);
-    }
-  }
-  s2k_internal_pipe_issue(ctx, sl, ticket);
-  return S2K_OK;
-}
-
-extern "C" {
 int s2k_ecdsa_verify_batch_submit(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
                                   const uint8_t* s, uint32_t flags, uint8_t* valid, s2k_ticket* ticket) {
   if (!ctx || !ticket) return fail(ctx, S2K_ERR_ARG, "null argument");
@@ -4061,47 +2548,6 @@ int s2k_ecdsa_verify_batch_submit(s2k_ctx* ctx, size_t n, const uint8_t* pub, co
   }
   s2k_internal_pipe_issue(ctx, sl, ticket);
   return S2K_OK;
-}
-
-int s2k_wait(s2k_ctx* ctx, s2k_ticket ticket) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (ticket == 0 || ticket >= ctx->pipe_next) return fail(ctx, S2K_ERR_ARG, "s2k_wait: ticket %llu was never issued", (unsigned long long)ticket);
-  for (s2k_ctx::pipe_slot& sl : ctx->pipe)
-    if (sl.ticket == ticket) return s2k_internal_pipe_retire(ctx, sl);
-  for (unsigned i = 0; i < 8; ++i)                    // retired by a later submit: its verdicts are delivered (or it failed then)
-    if (ctx->pipe_failed[i] == ticket) return fail(ctx, ctx->pipe_failed_rc[i], "ticket %llu failed when it was retired", (unsigned long long)ticket);
-  return S2K_OK;
-}
-
-// S2K_OK: the ticket's verdicts are delivered (as s2k_wait); S2K_PENDING: still in flight.  Never blocks.
-int s2k_poll(s2k_ctx* ctx, s2k_ticket ticket) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (ticket == 0 || ticket >= ctx->pipe_next) return fail(ctx, S2K_ERR_ARG, "s2k_poll: ticket %llu was never issued", (unsigned long long)ticket);
-  for (s2k_ctx::pipe_slot& sl : ctx->pipe)
-    if (sl.ticket == ticket) {
-      HIP_TRY(ctx, hipSetDevice(ctx->device));
-      const hipError_t e = hipEventQuery(sl.done);
-      if (e == hipErrorNotReady) {
-        (void)hipGetLastError();
-        return S2K_PENDING;
-      }
-      return s2k_internal_pipe_retire(ctx, sl);
-    }
-  return s2k_wait(ctx, ticket);                       // retired earlier
-}
-
-int s2k_wait_all(s2k_ctx* ctx) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  int rc = S2K_OK;
-  for (;;) {                                          // oldest first
-    s2k_ctx::pipe_slot* oldest = nullptr;
-    for (s2k_ctx::pipe_slot& sl : ctx->pipe)
-      if (sl.ticket && (!oldest || sl.ticket < oldest->ticket)) oldest = &sl;
-    if (!oldest) break;
-    const int r1 = s2k_internal_pipe_retire(ctx, *oldest);
-    if (r1 && !rc) rc = r1;
-  }
-  return rc;
 }
 
 // Batches of up to max_n signatures take the wave-per-signature ladder (k_verify_row); 0 switches it off.
@@ -4128,23 +2574,6 @@ int s2k_ctx_set_mid_batch_max(s2k_ctx* ctx, uint32_t max_n) {
   if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
   ctx->quad_max = max_n;
   return S2K_OK;
-}
-// Per-ticket times on the device's clock (for placement diagnostics, s2k_group_member_stats_ex): enable, submit, wait, ask.
-int s2k_ctx_ticket_timing(s2k_ctx* ctx, int enable) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  ctx->pipe_timing = enable != 0;
-  return S2K_OK;
-}
-int s2k_ticket_times(s2k_ctx* ctx, s2k_ticket ticket, double ms[2]) {
-  if (!ctx || !ms) return fail(ctx, S2K_ERR_ARG, "null argument");
-  for (unsigned i = 0; i < 8; ++i)
-    if (ticket && ctx->pipe_times_ticket[i] == ticket) {
-      ms[0] = ctx->pipe_times_ms[i][0];
-      ms[1] = ctx->pipe_times_ms[i][1];
-      return S2K_OK;
-    }
-  ms[0] = ms[1] = 0;
-  return S2K_PENDING;      // not retired yet, timing was off, or more than eight tickets ago
 }
 
 int s2k_schnorr_verify_batch(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs,

@@ -84,7 +84,7 @@ S2K_DEV void store_be32_unaligned(uint8_t* p, const uint32_t in[8]) {
   }
 }
 
-// Largest batch the wave-per-signature ladders (k_verify_row / k_schnorr_row / k_recover_row, engine.hip) take: above it the
+// Largest batch the wave-per-signature ladders (k_verify_row / k_schnorr_row / k_recover_row, small_call.hip) take: above it the
 // lane-per-signature kernels win (profiles/r05_small_batch_ab.txt, ECDSA: 0.19 against 0.68 ms up to 1024 signatures - one wave
 // per SIMD -, 0.41 against 0.7-1.1 at 4096, 0.71 against 1.08 at 8192, 1.31 against 1.10 at 16384 device-resident; from host
 // memory 0.28 against 0.74 ms at 1024, 0.50 against 0.75 at 4096, 0.77 against 0.78 at 8192).
@@ -134,7 +134,7 @@ struct s2k_ctx {
   // stream, events that chain them (created on first use)
   void* io = nullptr;
   size_t io_bytes = 0;
-  // small synchronous host calls (ctx_small_block, engine.hip): a page-locked block the kernels read and write in place
+  // small synchronous host calls (s2k_internal_small_block, pipeline.hip): a page-locked block the kernels read and write in place
   uint8_t* h_small = nullptr;
   uint8_t* d_small = nullptr;   // the same block as the device addresses it
   size_t h_small_bytes = 0;
@@ -369,17 +369,17 @@ int s2k_internal_msm_enqueue(s2k_ctx* ctx, hipStream_t st, size_t n, const void*
                              uint32_t** d_status);
 int s2k_internal_msm_reserve(s2k_ctx* ctx, size_t n);
 
-// submit / wait plumbing (engine.hip), shared with the encoded entry point (ingest.hip)
+// submit / wait plumbing (pipeline.hip), shared by the entry points that issue tickets (engine.hip, keyset.hip, digest.hip, ingest.hip)
 int s2k_internal_pipe_slot(s2k_ctx* ctx, size_t n, uint8_t* valid, s2k_ctx::pipe_slot** out);   // free slot for the next ticket
 int s2k_internal_pipe_retire(s2k_ctx* ctx, s2k_ctx::pipe_slot& sl);                             // wait + deliver verdicts
 void s2k_internal_pipe_issue(s2k_ctx* ctx, s2k_ctx::pipe_slot* sl, uint64_t* ticket);
 void s2k_internal_drain(s2k_ctx* ctx);                                                          // after an error: nothing left in flight
 bool s2k_internal_host_pinned(const void* p, size_t bytes);
-// small synchronous host calls without DMA transfers (engine.hip: ctx_small_block)
+// small synchronous host calls without DMA transfers (pipeline.hip)
 bool s2k_internal_small_call(const s2k_ctx* ctx, size_t n, uint32_t flags);
 int s2k_internal_small_block(s2k_ctx* ctx, const size_t* sizes, int count, uint8_t** host, uint8_t** dev);
 
-// Staging around a device form, for the host-pointer entry points that move their arrays whole (engine.hip).  A part is one
+// Staging around a device form, for the host-pointer entry points that move their arrays whole (pipeline.hip).  A part is one
 // array: `reserve` bytes of the context's staging buffer, of which `bytes` come from `src` before the device form runs (an
 // input; nothing is copied for a null src or no bytes) or go to `dst` after it (a result).  `run` enqueues the device form on
 // the staged pointers d[0 .. count) and the stream it is given, for the context it is given.
@@ -674,7 +674,8 @@ bool s2k_internal_bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags);
 int s2k_internal_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig, const void* d_r,
                               const void* d_s, uint32_t flags, void* d_valid, hipStream_t st, const uint32_t* d_found);
 
-// ---- engine.hip, for the key-set flows (keyset.hip): ladder modes, the lane workspace, stage-timing marks and launchers ----
+// ---- engine.hip and small_call.hip, for each other and for the key-set flows (keyset.hip): ladder modes, the lane workspace,
+// stage-timing marks and launchers ----
 enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_ECDSA_KEYED = 4, MODE_ECDSA_LEFT = 5,
        MODE_SCHNORR_KEYED = 6, MODE_SCHNORR_LEFT = 7, MODE_ECDSA_KEYSET = 8, MODE_ECDSA_KEYSET_JOINT = 9,
        MODE_ECDSA_KEYSET_JOINT5 = 10, MODE_ECDSA_KEYSET_JOINT6 = 11,
@@ -736,6 +737,17 @@ void launch_schnorr_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8
                          uint32_t msg_len);
 void launch_schnorr_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
                              const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out);
+// small_call.hip: the wave-per-signature kernels (launch_schnorr_row: prep == nullptr is k_schnorr_row<true>, whose fifth wave
+// prepares; else the planes of launch_schnorr_prep) and the four-lanes-per-signature kernels, behind the preparation kernels
+void launch_verify_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                       uint32_t flags, uint8_t* out);
+void launch_schnorr_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
+                        const uint64_t* offs, uint32_t msg_len, const uint32_t* prep, size_t stride, uint8_t* out);
+void launch_recover_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
+                        const uint8_t* recid, uint8_t* ok, uint8_t* pub65);
+void launch_verify_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* r, const lane_ws& w, uint8_t* out);
+void launch_schnorr_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pk, const uint8_t* sig, const lane_ws& w, uint8_t* out);
+void launch_recover_quad(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* r, const lane_ws& w, uint8_t* out);
 void launch_verify_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint4* ktab,
                               const uint8_t* tinfo, const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out);
 void launch_schnorr_row_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, size_t nkeys, const uint32_t* kidx, const uint8_t* set_keys,

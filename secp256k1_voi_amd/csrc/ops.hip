@@ -567,7 +567,7 @@ k_pt29q_op(int op, uint32_t lazy, uint32_t n, uint32_t reps, hp_args args, uint8
 //   FER_MUL a*b | FER_MUL_PLUS a*b+c | FER_MUL_ADD_MUL a*b+c*d | FER_SMALL 21 a  (out = row 0's result, flag = the rows agree)
 //   PT29R_DBL / PT29R_ADD: chained `reps` times like the quad forms
 //   PT29R_ADD_B3: pt29r_add_b3 on y^2 = x^3 + 7 c^6 (c = W), P and Q moved there and the sum moved back
-//   PT29R_COMB_STEP: a round of row_ladder_comb (engine.hip), `reps` times: acc = pt29r_add(pt29r_double(acc), Q) from acc = P on
+//   PT29R_COMB_STEP: a round of row_ladder_comb (small_call.hip), `reps` times: acc = pt29r_add(pt29r_double(acc), Q) from acc = P on
 //                 secp256k1, Q moved to y^2 = x^3 + 7 c^6 and brought back as (x c : y : c^3) by pt29r_pair_from_iso
 //   FER_SWAPS: out[0..255] = what v_permlane16_swap / v_permlane32_swap make of the lane numbers (n >= 8)
 __global__ void __launch_bounds__(256)

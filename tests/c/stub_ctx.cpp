@@ -4,7 +4,7 @@
 // A stub context keeps a worker thread - the "device": a submitted ticket completes 0-2 ms later ON THAT THREAD, which is
 // also the thread that writes the verdicts (as the DMA engine does), so a caller that reads them before s2k_wait is a
 // reported race.  The verdict of an item is a fixed function of its FIRST input byte, so the driver can check every shard
-// of every batch.  Four tickets in flight per context, the fifth submit retires the oldest, as engine.hip does.
+// of every batch.  Four tickets in flight per context, the fifth submit retires the oldest, as pipeline.hip does.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>

@@ -35,7 +35,7 @@ def ptr_add_b3(P1, P2, b3):
 
 
 def iso_consts(w):
-    """W (one unit, all rows) -> W, W^3, b3 = 21 W^6 as the kernels form them once per signature (engine.hip: row_iso_of)"""
+    """W (one unit, all rows) -> W, W^3, b3 = 21 W^6 as the kernels form them once per signature (small_call.hip: row_iso_of)"""
     w3 = F.fer_mul(F.fer_mul(w, w), w)
     b3 = F.fer_small_norm(F.fer_mul(w3, w3), F.lane_const(lambda j, r: 21))
     return w, w3, b3

@@ -1,4 +1,4 @@
-"""Lane-level model of pt29r_pair_from_iso (csrc/fe29r.h) and of the key part of row_ladder_comb (engine.hip), in the style of
+"""Lane-level model of pt29r_pair_from_iso (csrc/fe29r.h) and of the key part of row_ladder_comb (small_call.hip), in the style of
 tests/fer_b3_model.py and on top of tests/fer_model.py: the wave-per-signature ladder over a COMB key table.  An entry of
 such a table is an affine point (x, y) of the key's isomorphic curve y^2 = x^3 + 7 W^6; (x W : y : W^3) is that point on
 secp256k1 itself, so the ladder doubles and adds there (fer_model.ptr_double / ptr_add) and carries no per-key constant.  The
@@ -11,7 +11,7 @@ LEAD_BIT = TEETH * SPACING - 1          # bit 132 of a' = bit 18 of the top toot
 
 
 def comb_consts(w):
-    """W (one unit, all rows) -> W, W^3 as the kernels form them once per signature (engine.hip: row_comb_iso_of)"""
+    """W (one unit, all rows) -> W, W^3 as the kernels form them once per signature (small_call.hip: row_comb_iso_of)"""
     return w, F.fer_mul(F.fer_mul(w, w), w)
 
 

@@ -1,4 +1,4 @@
-"""The wave-per-signature ladder over a COMB key set (engine.hip: k_verify_row_comb / k_schnorr_row_comb) in the BUILT library,
+"""The wave-per-signature ladder over a COMB key set (small_call.hip: k_verify_row_comb / k_schnorr_row_comb) in the BUILT library,
 against its chunk-table siblings from the same disassembly (tools/isa_count.py on the shipped code object): 37 additions of
 three layers, 18 doublings of two and 19 conversions - 166 row-product layers on the key part - must come to fewer VALU
 instructions per signature wave than k_verify_row_keyset's 64 additions of four layers and the map back (257).  The layer

@@ -4,8 +4,8 @@ test_fe29_model.py.
 
   * bounds: every formula is run on upper bounds of its operands' limbs at their stated invariants; no 32-bit limb,
     64-bit column sum or negate() bias may overflow, and the invariants are closed under the formulas' own chaining;
-  * call sites: every fe29_eq / fe29_is_zero / fe29_normalize / fe29_inv_gcd of engine.hip, keyed.hip and msm.hip has
-    a row with its modelled operand bound (fe29_normalize_weak's input contract: limbs < 2^32 - 2^18);
+  * call sites: every fe29_eq / fe29_is_zero / fe29_normalize / fe29_inv_gcd of engine.hip, small_call.hip, keyed.hip and
+    msm.hip has a row with its modelled operand bound (fe29_normalize_weak's input contract: limbs < 2^32 - 2^18);
   * drift guard: the calls each model makes are compared with the calls of the C++ body it restates;
   * non-vacuity: one-token mutations of the source that the bounds must reject;
   * lazy budgets: the operand codes of s2k_fp_op_batch_ex (ops.hip, fe29_lazy_form) each formula accepts, which the
@@ -591,33 +591,36 @@ FER1 = B.units(1)                                         # fe29r.h: fer_norm / 
 
 # (file, text of the call as the source has it, how often, check)
 CALL_SITES = [
-    ("engine.hip", "fe29_eq(fe29_sqr(qy), rhs)", 3, lambda: eq(PROD, RHS)),
+    ("engine.hip", "fe29_eq(fe29_sqr(qy), rhs)", 2, lambda: eq(PROD, RHS)),
     ("engine.hip", "fe29_is_zero(acc.z)", 4, lambda: is_zero(COORD)),
     ("engine.hip", "fe29_eq(acc.x, fe29_mul(fe29_from_words(r.v), acc.z))", 1, lambda: eq(COORD, PROD)),
     ("engine.hip", "fe29_eq(acc.x, fe29_mul(fe29_from_words(r2), acc.z))", 1, lambda: eq(COORD, PROD)),
-    ("engine.hip", "qy = fe29_normalize(qy)", 3, lambda: normalize(PROD)),        # fe29_sqrt's root, or words
+    ("engine.hip", "qy = fe29_normalize(qy)", 2, lambda: normalize(PROD)),        # fe29_sqrt's root, or words
     ("engine.hip", "fe29_is_zero(q.z)", 1, lambda: is_zero(COORD)),
     ("engine.hip", "fe29_is_zero(acc.x)", 1, lambda: is_zero(COORD)),
     ("engine.hip", "fe29_eq(acc.x, fe29_mul(fe29_from_words(rw), zz))", 1, lambda: eq(COORD, PROD)),
     ("engine.hip", "fe29_eq(acc.x, fe29_mul(fe29_from_words(r2), zz))", 1, lambda: eq(COORD, PROD)),
-    ("engine.hip", "fe29_is_zero(fer_to_fe29(fer_norm(a, k)))", 1, lambda: is_zero(FER1)),
-    ("engine.hip", "fe29_normalize(fer_to_fe29(fer_norm(a, k)))", 1, lambda: normalize(FER1)),
-    ("engine.hip", "fe29_is_zero(R.z)", 3, lambda: is_zero(COORD)),
-    ("engine.hip", "fe29_eq(R.x, fe29_mul(fe29_from_words(rw), R.z))", 1, lambda: eq(COORD, PROD)),
-    ("engine.hip", "fe29_eq(R.x, fe29_mul(fe29_from_words(r2), R.z))", 1, lambda: eq(COORD, PROD)),
-    ("engine.hip", "y = fe29_normalize(y)", 2, lambda: normalize(PROD)),
-    ("engine.hip", "fe29_eq(R.x, fe29_mul(xR, R.z))", 1, lambda: eq(COORD, PROD)),
-    ("engine.hip", "fe29_eq(R.y, fe29_mul(yR, R.z))", 1, lambda: eq(COORD, PROD)),
+    ("engine.hip", "y = fe29_normalize(y)", 1, lambda: normalize(PROD)),
     ("engine.hip", "fe29_inv_gcd(acc)", 1, lambda: inv_gcd(PROD)),
     ("engine.hip", "fe29_normalize(fe29_mul(fe29_mul(fq_load(fin, stride, i, 1), zi2), zi))", 1, lambda: normalize(PROD)),
     ("engine.hip", "fe29_normalize(x)", 1, lambda: normalize(PROD)),
     ("engine.hip", "fe29_eq(x, fe29_from_words(rw))", 1, lambda: eq(PROD, CANON)),
-    ("engine.hip", "fe29_normalize(fer_to_fe29(fer_mul(acc.x, zi, k)))", 1, lambda: normalize(FER1)),
-    ("engine.hip", "fe29_normalize(fer_to_fe29(fer_mul(fer_norm(acc.y, k), zi, k)))", 1, lambda: normalize(FER1)),
     ("engine.hip", "fe29_is_zero(p.z)", 1, lambda: is_zero(COORD)),
     ("engine.hip", "fe29_inv_gcd(fe29_normalize_weak(p.z))", 1, lambda: inv_gcd(NW)),
     ("engine.hip", "fe29_normalize(fe29_mul(p.x, zi))", 1, lambda: normalize(PROD)),
     ("engine.hip", "fe29_normalize(fe29_mul(p.y, zi))", 1, lambda: normalize(PROD)),
+    ("small_call.hip", "fe29_eq(fe29_sqr(qy), rhs)", 1, lambda: eq(PROD, RHS)),                 # k_verify_quad
+    ("small_call.hip", "qy = fe29_normalize(qy)", 1, lambda: normalize(PROD)),                   # k_recover_quad: fe29_sqrt's root
+    ("small_call.hip", "fe29_is_zero(fer_to_fe29(fer_norm(a, k)))", 1, lambda: is_zero(FER1)),
+    ("small_call.hip", "fe29_normalize(fer_to_fe29(fer_norm(a, k)))", 1, lambda: normalize(FER1)),
+    ("small_call.hip", "fe29_is_zero(R.z)", 3, lambda: is_zero(COORD)),
+    ("small_call.hip", "fe29_eq(R.x, fe29_mul(fe29_from_words(rw), R.z))", 1, lambda: eq(COORD, PROD)),
+    ("small_call.hip", "fe29_eq(R.x, fe29_mul(fe29_from_words(r2), R.z))", 1, lambda: eq(COORD, PROD)),
+    ("small_call.hip", "y = fe29_normalize(y)", 1, lambda: normalize(PROD)),                     # k_schnorr_quad
+    ("small_call.hip", "fe29_eq(R.x, fe29_mul(xR, R.z))", 1, lambda: eq(COORD, PROD)),
+    ("small_call.hip", "fe29_eq(R.y, fe29_mul(yR, R.z))", 1, lambda: eq(COORD, PROD)),
+    ("small_call.hip", "fe29_normalize(fer_to_fe29(fer_mul(acc.x, zi, k)))", 1, lambda: normalize(FER1)),
+    ("small_call.hip", "fe29_normalize(fer_to_fe29(fer_mul(fer_norm(acc.y, k), zi, k)))", 1, lambda: normalize(FER1)),
     ("keyed.hip", "qy = fe29_normalize(qy)", 1, lambda: normalize(PROD)),
     ("keyed.hip", "fe29_eq(fe29_sqr(qy), rhs)", 1, lambda: eq(PROD, RHS)),
     ("keyed.hip", "fe29_inv_gcd(pre)", 2, lambda: inv_gcd(PROD)),
@@ -645,7 +648,7 @@ def source(name):
 
 
 def test_call_site_table_is_complete():
-    for f in ("engine.hip", "gtable.hip", "keyed.hip", "msm.hip", "aff29.h"):
+    for f in ("engine.hip", "small_call.hip", "gtable.hip", "keyed.hip", "msm.hip", "aff29.h"):
         rows = [r for r in CALL_SITES if r[0] == f]
         s = source(f)
         assert len(ROOTS.findall(s)) == sum(r[2] for r in rows), f"{f}: a call of fe29_eq / is_zero / normalize / inv_gcd has no row"

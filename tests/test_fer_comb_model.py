@@ -1,4 +1,4 @@
-"""The wave-per-signature ladder over a comb key table (csrc/fe29r.h: pt29r_pair_from_iso; engine.hip: row_ladder_comb) on the
+"""The wave-per-signature ladder over a comb key table (csrc/fe29r.h: pt29r_pair_from_iso; small_call.hip: row_ladder_comb) on the
 lane-level model tests/fer_comb_model.py: the entry conversion against big-integer arithmetic, limb bounds at the top of what
 the ladder feeds each formula, and the whole key part - column 18 as a pair sum, 18 rounds of doubling and two additions -
 against +-k1 Q +- k2 lambda(Q) for random half scalars and the recoding's corners.  No GPU; the compiled functions run in

@@ -1,4 +1,4 @@
-"""Small calls over a COMB key set: the wave-per-signature ladder on the set's comb tables (engine.hip: row_ladder_comb,
+"""Small calls over a COMB key set: the wave-per-signature ladder on the set's comb tables (small_call.hip: row_ladder_comb,
 k_verify_row_comb, k_schnorr_row_comb; fe29r.h: pt29r_pair_from_iso - an entry (x, y) of y^2 = x^3 + 7 W^6 is (x W : y : W^3) on
 secp256k1), opt-in through set_keyset_comb_small_batch_max.
 

@@ -1,4 +1,4 @@
-"""Small calls over a key set: the wave-per-signature ladder on the set's 32-chunk tables (engine.hip: k_verify_row_keyset,
+"""Small calls over a key set: the wave-per-signature ladder on the set's 32-chunk tables (small_call.hip: k_verify_row_keyset,
 k_schnorr_row_keyset; fe29r.h: pt29r_add_b3 on the key's isomorphic curve y^2 = x^3 + 7 W^6).
 
 Every verdict is compared three ways: with the CPU oracle's on the expanded keys (pyref / the oracle's schnorr_verify for

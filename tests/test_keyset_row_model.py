@@ -1,4 +1,4 @@
-"""The addition the wave-per-signature key-set ladder runs (csrc/fe29r.h: pt29r_add_b3, pt29r_from_iso; engine.hip:
+"""The addition the wave-per-signature key-set ladder runs (csrc/fe29r.h: pt29r_add_b3, pt29r_from_iso; small_call.hip:
 row_ladder_keyset) on the lane-level model tests/fer_b3_model.py: values against big-integer arithmetic on the key's
 isomorphic curve y^2 = x^3 + 7 W^6, limb bounds at the top of what the ladder feeds it, and the whole ladder - lead pair, 64
 digit additions, the map back, the generator part - against u1 G + u2 Q for the recoding's corner scalars.  No GPU; the

@@ -408,7 +408,7 @@ def _mads_in(g, body):
     return sum(1 for b in body for i in range(*g.blocks[b]) if g.ins[i][1].startswith("v_mad_u64_u32"))
 
 
-SQRT_CHAIN_TRIPS = [3, 3, 2, 11, 22, 44, 88, 44, 3, 23, 6, 2]      # fer_sqrt_chain's squaring runs (engine.hip), in order
+SQRT_CHAIN_TRIPS = [3, 3, 2, 11, 22, 44, 88, 44, 3, 23, 6, 2]      # fer_sqrt_chain's squaring runs (small_call.hip), in order
 
 
 def row_general(lib, gt_windows=None):
