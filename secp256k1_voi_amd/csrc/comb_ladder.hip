@@ -1,6 +1,6 @@
 // comb_ladder.hip — the comb ladders of the grouped ECDSA and BIP-340 calls and of comb key sets, in a kernel of their own:
 // k_verify_comb<false> runs where k_verify_fast<MODE_ECDSA_COMB> ran, k_verify_comb<true> where <MODE_SCHNORR_COMB> did
-// (engine.hip: launch_ladder; S2K_COMB_LEAD=1 brings those two back).  Same tables (kc_geom, keyed.hip), same arguments,
+// (lane_kernels.hip: launch_ladder; S2K_COMB_LEAD=1 brings those two back).  Same tables (kc_geom, keyed.hip), same arguments,
 // same verdicts; what differs is how the ladder starts.
 //
 // The recoding.  An odd half scalar k < 2^129 over the comb's L = 133 digit positions (7 teeth, 19 bits apart):
@@ -23,7 +23,7 @@
 
 using namespace s2k;
 
-// MODE_ECDSA_COMB (SCHNORR = false) / MODE_SCHNORR_COMB (true) of k_verify_fast (engine.hip, where the arguments, the lane
+// MODE_ECDSA_COMB (SCHNORR = false) / MODE_SCHNORR_COMB (true) of k_verify_fast (verify_fast.h, where the arguments, the lane
 // mapping and the verdict rules are described): lane idx of the launch's part handles signature kg.perm[idx] on the comb
 // table kg.ptab[idx]; the generator part u1 G comes from kg.gp (k_generator_part).
 template <bool SCHNORR>
@@ -164,7 +164,7 @@ k_verify_comb(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
     acc = jpt29_add(acc, q);
   }
 
-  // ---- verdict ---- (the rules of k_verify_fast, engine.hip: Z = 0 first seen in the final addition of two finite points
+  // ---- verdict ---- (the rules of k_verify_fast, verify_fast.h: Z = 0 first seen in the final addition of two finite points
   // is decided here - X3 != 0: opposite points, R is the identity; X3 = 0: equal points, the worklist kernel doubles u1 G -,
   // every other zero goes to the worklist untagged)
   uint8_t verdict = 0;
@@ -222,7 +222,7 @@ k_verify_comb(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8
   }
 }
 
-// the two instantiations launch_ladder (engine.hip) launches
+// the two instantiations launch_ladder (lane_kernels.hip) launches
 template __global__ void k_verify_comb<false>(uint32_t, const uint8_t*, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*, gt_view, uint8_t*,
                                               uint32_t*, uint32_t*, size_t, uint8_t*, uint64_t*, key_groups);
 template __global__ void k_verify_comb<true>(uint32_t, const uint8_t*, const uint8_t*, const uint32_t*, uint32_t*, uint32_t*, gt_view, uint8_t*,

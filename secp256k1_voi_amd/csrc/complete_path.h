@@ -1,5 +1,5 @@
 // complete_path.h — device functions of the COMPLETE path: 8x32 field (fe.h), projective RCB
-// formulas (point.h), the reference's algorithm shape.  Used by the fallback kernels of engine.hip
+// formulas (point.h), the reference's algorithm shape.  Used by the kernels of fallback.hip
 // (lanes the fast Jacobian kernel cannot decide, S2K_ECDSA_FORCE_COMPLETE) and by the Point /
 // Scalar entry points of ops.hip.
 #pragma once

@@ -1,8 +1,15 @@
-// engine.hip — the lane-per-signature kernels (k_scalar_prep, k_generator_part, k_verify_fast, k_affine_finish, k_schnorr_prep),
-// the complete-formula fallback and worklist kernels, the context, and the ECDSA, BIP-340, recovery and point call flows of
-// include/secp256k1_voi_amd.h.  Elsewhere: the kernels of calls too small for a lane per signature (small_call.hip); host
-// staging, tickets and page-locked memory (pipeline.hip); the generator tables (gtable.hip); key sets and the entry points
-// over them (keyset.hip).
+// engine.hip — host code only: the context, the settings, the lane workspace, and the ECDSA, BIP-340, recovery and point call
+// flows of include/secp256k1_voi_amd.h.  No kernel and no launch is in this file (tests/test_ladder_units_cpu.py).  Elsewhere:
+//   verify_fast.h        the ladder kernel k_verify_fast<MODE>, one lane per signature
+//   ladder_ecdsa.hip, ladder_schnorr.hip, fallback.hip   its instantiations, every MODE_* in one of them
+//   lane_kernels.hip     k_scalar_prep, k_schnorr_prep, k_hot_prep, k_generator_part, k_affine_finish and their launchers;
+//                        launch_ladder
+//   fallback.hip         the complete-formula and worklist kernels and their launchers
+//   comb_ladder.hip      the comb ladders without the lead point
+//   small_call.hip       the kernels of calls too small for a lane per signature
+//   pipeline.hip         host staging, tickets and page-locked memory
+//   gtable.hip           the generator tables
+//   keyset.hip           key sets and the entry points over them
 //
 // One lane per signature / per point; every lane of a wave runs the same instruction
 // stream (complete formulas, fixed windows), so there is no divergence on secret- or
@@ -39,1390 +46,6 @@
 
 using namespace s2k;
 
-// one signature, complete formulas only (secec/ecdsa.go:392-470)
-S2K_DEV uint8_t verify_complete(size_t idx, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig,
-                                const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, uint32_t flags,
-                                gt_view gt, uint32_t* __restrict__ qt, size_t stride) {
-  sc r, s;
-  uint32_t e_raw[8];
-  apt q;
-  load_be32(r.v, rsig + idx * 32);
-  load_be32(s.v, ssig + idx * 32);
-  load_be32(e_raw, dig + idx * 32);
-  load_be32(q.x.v, pub + idx * 64);
-  load_be32(q.y.v, pub + idx * 64 + 32);
-
-  // ParseCompactSignature range checks (s11n.go:129-144) + verify step 1 (ecdsa.go:400)
-  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-  if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);   // ecdsa.go:212
-  // NewPublicKey: canonical coordinates on the curve (point_s11n.go:187-201)
-  ok = ok && fe_is_canonical_raw(q.x.v) && fe_is_canonical_raw(q.y.v) && apt_on_curve(q);
-
-  sc e = sc_reduce_once(e_raw);                    // hashToScalar (ecdsa.go:477-486)
-  sc s_inv_m = sc_mont_inv(sc_to_mont(s));         // s^-1 * R
-  sc u1 = sc_montmul(e, s_inv_m);                  // e / s   (plain)
-  sc u2 = sc_montmul(r, s_inv_m);                  // r / s
-
-  pt rg = pt_base_mul(gt, u1.v);
-  pt rq = pt_mul_glv(u2, q, qt, stride, idx);
-  pt R = pt_add_complete(rg, rq);                  // point_mul_glv.go:316
-
-  ok = ok && !pt_is_identity(R);                   // ecdsa.go:450
-  // x(R) mod n == r  <=>  X == r*Z  or  (r + n < p and X == (r + n)*Z)   (ecdsa.go:459-465)
-  fe rf;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rf.v[i] = r.v[i];
-  bool match = fe_eq(R.x, fe_mul(rf, R.z));
-  if (u256_lt(r.v, FE_P_MINUS_N)) {
-    fe r2;
-    u256_add(r2.v, r.v, SC_N);
-    match = match || fe_eq(R.x, fe_mul(r2, R.z));
-  }
-  return (ok && match) ? 1 : 0;
-}
-
-// every lane through the complete path (S2K_ECDSA_FORCE_COMPLETE; also the round-1 baseline kernel)
-__global__ void __launch_bounds__(256)
-k_ecdsa_verify(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig,
-               const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, uint32_t flags,
-               uint8_t* __restrict__ out, gt_view gt, uint32_t* __restrict__ qt, size_t stride) {
-  size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n) return;
-  out[idx] = verify_complete(idx, pub, dig, rsig, ssig, flags, gt, qt, stride);
-}
-
-// ---------------------------------------------------------------------------------------
-// The worklist verifier: one signature with COMPLETE formulas on the 9x29 field (pt29.h: the
-// Renes-Costello-Batina addition, mixed addition and doubling, point_projective.go:24,123,208).
-// Same verdict as verify_complete for every input (tests run both), about a third of its cost:
-// lanes whose Jacobian ladder hit an exceptional case are re-done at close to the fast path's own
-// speed, so a batch crafted to send EVERY lane here (u1*G + u2*Q = infinity; anyone with a key
-// pair can mint those) costs a small multiple of a normal batch instead of serialising on the
-// 8x32 reference-shaped path.
-// Ladder: odd GLV halves (sc_split_glv_odd), signed odd digits, projective table of the 8 odd
-// multiples {1,3,..,15}*Q in planes [entry*27 + limb][lane] of the lane's table region; the
-// lambda-half multiplies X by beta at the lookup.
-// ---------------------------------------------------------------------------------------
-S2K_DEV void p29_store(uint32_t* __restrict__ qt, size_t stride, size_t lane, int entry, const pt29& p) {
-  uint32_t* b = qt + (size_t)(entry * 27) * stride + lane;
-#pragma unroll
-  for (int w = 0; w < 9; ++w) {
-    b[(size_t)w * stride] = p.x.n[w];
-    b[(size_t)(9 + w) * stride] = p.y.n[w];
-    b[(size_t)(18 + w) * stride] = p.z.n[w];
-  }
-}
-S2K_DEV pt29 p29_load(const uint32_t* __restrict__ qt, size_t stride, size_t lane, uint32_t entry) {
-  const uint32_t* b = qt + (size_t)(entry * 27) * stride + lane;
-  pt29 p;
-#pragma unroll
-  for (int w = 0; w < 9; ++w) {
-    p.x.n[w] = b[(size_t)w * stride];
-    p.y.n[w] = b[(size_t)(9 + w) * stride];
-    p.z.n[w] = b[(size_t)(18 + w) * stride];
-  }
-  return p;
-}
-static_assert(QT_ENTRIES * 27 <= 8 * 8 * 4, "projective 9x29 table must fit in the lane's table region");
-
-// u1*G + u2*Q (Q affine, on the curve) with complete formulas: the projective result (X : Y : Z)
-S2K_DEV pt29 dsm_complete29(const sc& u1, const sc& u2, const fe29& qx, const fe29& qy, gt_view gt,
-                            uint32_t* __restrict__ qt, size_t stride, size_t idx) {
-  sc k1, k2;
-  bool neg1, neg2;
-  sc_split_glv_odd(u2, k1, neg1, k2, neg2);
-
-  // table of odd multiples (projective): T[j] = (2j + 1) Q
-  pt29 q1;
-  q1.x = qx;
-  q1.y = qy;
-  q1.z = fe29_one();
-  {
-    pt29 q2 = pt29_double(q1), cur = q1;
-    p29_store(qt, stride, idx, 0, cur);
-#pragma unroll 1
-    for (int j = 1; j < QT_ENTRIES; ++j) {
-      cur = pt29_add(cur, q2);
-      p29_store(qt, stride, idx, j, cur);
-    }
-  }
-  const fe29 beta = fe29_from_words(FE_BETA);
-  digit_stream d1 = ds_init(k1), d2 = ds_init(k2);
-  // top digits are +1: acc = s1 * Q + s2 * lambda Q
-  pt29 acc = q1;
-  acc.y = fe29_cond_negate1(qy, neg1);
-  acc.y = fe29_normalize_weak(acc.y);
-  {
-    fe29 bx = fe29_mul(qx, beta);
-    acc = pt29_add_mixed(acc, bx, fe29_normalize_weak(fe29_cond_negate1(qy, neg2)));
-  }
-#pragma unroll 1
-  for (int i = 31; i >= 0; --i) {
-#pragma unroll 1
-    for (int j = 0; j < 4; ++j) acc = pt29_double(acc);
-    uint32_t w1 = ds_next(d1), w2 = ds_next(d2);
-#pragma unroll 1
-    for (int t = 0; t < 2; ++t) {
-      uint32_t w = t ? w2 : w1;
-      bool neg = (t ? neg2 : neg1) != (w < 8u);
-      uint32_t entry = (w < 8u) ? (7u - w) : (w - 8u);
-      pt29 a = p29_load(qt, stride, idx, entry);
-      if (t) a.x = fe29_mul(a.x, beta);
-      a.y = fe29_normalize_weak(fe29_cond_negate1(a.y, neg));
-      acc = pt29_add(acc, a);
-    }
-  }
-  // generator part (complete mixed additions; no table entry is the identity)
-  {
-    uint32_t u[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) u[w] = u1.v[w];
-#pragma unroll 1
-    for (uint32_t w = 0; w < gt.windows; ++w) {
-      apt g = gt_load(gt, w, gt_next_digit(u, gt.bits));
-      acc = pt29_add_mixed(acc, fe29_from_words(g.x.v), fe29_from_words(g.y.v));
-    }
-  }
-  return acc;
-}
-
-// (the tags of a worklist entry, WL_*: engine_internal.h)
-
-// (`key`: the 64 bytes X || Y of the signature's public key)
-S2K_DEV uint8_t verify_complete29(size_t idx, const uint8_t* __restrict__ key, const uint8_t* __restrict__ dig,
-                                  const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, uint32_t flags,
-                                  gt_view gt, uint32_t* __restrict__ qt, size_t stride, size_t lane,
-                                  uint32_t tag = 0) {
-  // idx: the signature; lane: the table column this thread may use (the worklist kernel passes the worklist
-  // POSITION, not the signature: the keyed ladder queues signatures in key order, and columns picked by
-  // signature would scatter a wave's table accesses over 64 cache lines: 47 ms instead of 20 for a batch
-  // that is queued whole)
-  sc r, s;
-  uint32_t e_raw[8];
-  apt q;
-  load_be32(r.v, rsig + idx * 32);
-  load_be32(s.v, ssig + idx * 32);
-  load_be32(e_raw, dig + idx * 32);
-  load_be32(q.x.v, key);
-  load_be32(q.y.v, key + 32);
-  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-  if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);
-  ok = ok && fe_is_canonical_raw(q.x.v) && fe_is_canonical_raw(q.y.v);
-  if (!ok) {   // keep the arithmetic well defined; the verdict is already "invalid"
-    q.x = fe_from_limbs(FE_GX);
-    q.y = fe_from_limbs(FE_GY);
-    s = sc_zero();
-    s.v[0] = 1;
-  }
-  fe29 qx = fe29_from_words(q.x.v), qy = fe29_from_words(q.y.v);
-  {
-    fe29 rhs = fe29_mul(fe29_sqr(qx), qx);
-    rhs.n[0] += 7;
-    if (!fe29_eq(fe29_sqr(qy), rhs)) {   // not on the curve (point_s11n.go:298-307)
-      ok = false;
-      qx = fe29_from_words(FE_GX);
-      qy = fe29_from_words(FE_GY);
-    }
-  }
-  sc e = sc_reduce_once(e_raw);
-  sc26 s_inv_m = sc26_mont_inv(sc26_to_mont(sc26_from_sc(s)));   // s^-1 * R (safegcd, modinv30.h)
-  sc u1 = sc26_to_sc(sc26_mm(sc26_from_sc(e), s_inv_m)), u2 = sc26_to_sc(sc26_mm(sc26_from_sc(r), s_inv_m));
-  pt29 acc;
-  if (tag == WL_DOUBLE_GEN) {
-    // the fast ladder has established u2 Q == u1 G (engine.hip, k_verify_fast: verdict): R = 2 u1 G, from the resident
-    // tables with the complete formulas - no ladder
-    acc.x = fe29_zero();
-    acc.y = fe29_one();
-    acc.z = fe29_zero();
-    uint32_t u[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) u[w] = u1.v[w];
-#pragma unroll 1
-    for (uint32_t w = 0; w < gt.windows; ++w) {
-      apt g = gt_load(gt, w, gt_next_digit(u, gt.bits));
-      acc = pt29_add_mixed(acc, fe29_from_words(g.x.v), fe29_from_words(g.y.v));
-    }
-    acc = pt29_double(acc);
-  } else if (tag == WL_DOUBLE_LAST) {
-    uint32_t u[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) u[w] = u1.v[w];
-    uint32_t digit = 0;
-#pragma unroll 1
-    for (uint32_t w = 0; w < gt.windows; ++w) digit = gt_next_digit(u, gt.bits);
-    apt g = gt_load(gt, gt.windows - 1, digit);
-    acc.x = fe29_from_words(g.x.v);
-    acc.y = fe29_from_words(g.y.v);
-    acc.z = fe29_one();
-    acc = pt29_double(acc);
-  } else {
-    acc = dsm_complete29(u1, u2, qx, qy, gt, qt, stride, lane);
-  }
-  ok = ok && !fe29_is_zero(acc.z);                   // ecdsa.go:450
-  // x(R) mod n == r  <=>  X == r*Z  or  (r + n < p and X == (r + n)*Z)   (ecdsa.go:459-465)
-  bool match = fe29_eq(acc.x, fe29_mul(fe29_from_words(r.v), acc.z));
-  if (u256_lt(r.v, FE_P_MINUS_N)) {
-    uint32_t r2[8];
-    u256_add(r2, r.v, SC_N);
-    match = match || fe29_eq(acc.x, fe29_mul(fe29_from_words(r2), acc.z));
-  }
-  return (ok && match) ? 1 : 0;
-}
-
-// the lanes the fast kernel could not decide (final Z = 0): a short worklist, normally empty
-__global__ void __launch_bounds__(256)
-k_verify_fallback(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, const uint8_t* __restrict__ pub,
-                  const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig,
-                  uint32_t flags, uint8_t* __restrict__ out, gt_view gt, uint32_t* __restrict__ qt,
-                  size_t stride) {
-  uint32_t count = *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    const uint32_t e = wl[w];
-    const size_t idx = e & WL_INDEX_MASK;
-    out[idx] = verify_complete29(idx, pub + idx * 64, dig, rsig, ssig, flags, gt, qt, stride, w, e & ~WL_INDEX_MASK);
-  }
-}
-// the same for a batch verified against a key set: the key of signature idx is keys[kidx[idx]]
-__global__ void __launch_bounds__(256)
-k_verify_fallback_keyset(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, const uint8_t* __restrict__ keys,
-                         const uint32_t* __restrict__ kidx, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-                         const uint8_t* __restrict__ ssig, uint32_t flags, uint8_t* __restrict__ out, gt_view gt,
-                         uint32_t* __restrict__ qt, size_t stride) {
-  uint32_t count = *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    const uint32_t e = wl[w];
-    const size_t idx = e & WL_INDEX_MASK;
-    out[idx] = verify_complete29(idx, keys + (size_t)kidx[idx] * 64, dig, rsig, ssig, flags, gt, qt, stride, w, e & ~WL_INDEX_MASK);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Fast path, kernel 1: scalar preparation with batched inversion.
-// Each thread owns PREP_M signatures (i = t, t+T, t+2T, ...): one inversion mod n (safegcd
-// division steps, modinv30.h; the reference's Scalar.Invert is a Fermat chain,
-// scalar_invert.go:11) is shared by PREP_M signatures through Montgomery's trick, 3 extra
-// multiplications each, instead of one inversion per signature as in verify (ecdsa.go:428).
-// PREP_M trades inversions against waves: measured at 2^20 (tools/ab_prep.sh) 2: 413, 3: 340,
-// 4: 285, 6: 276, 8: 299, 16: 356, 32: 450 us (with the Fermat chain: 16: 466 us).
-// Out per signature (word-major, coalesced):
-//   u1 (8 words), |k1|, |k2| (4 words each; u2 = +-k1 +- k2*lambda), flag word.
-// ---------------------------------------------------------------------------------------
-#ifndef S2K_PREP_M
-#define S2K_PREP_M 6
-#endif
-constexpr int PREP_M = S2K_PREP_M;
-constexpr int PREP_WORDS = 17;
-// (the flag word's bits, PF_*: engine_internal.h)
-
-S2K_DEV void ws_store_sc26(uint32_t* __restrict__ base, size_t stride, size_t i, const sc26& v) {
-#pragma unroll
-  for (int w = 0; w < 10; ++w) base[(size_t)w * stride + i] = v.n[w];
-}
-S2K_DEV sc26 ws_load_sc26(const uint32_t* __restrict__ base, size_t stride, size_t i) {
-  sc26 r;
-#pragma unroll
-  for (int w = 0; w < 10; ++w) r.n[w] = base[(size_t)w * stride + i];
-  return r;
-}
-
-// recid != nullptr selects public-key recovery (RecoverPublicKey, ecdsa.go:244-282): the shared
-// inversion is of r instead of s, and u1 = -e/r, u2 = s/r.
-__global__ void __launch_bounds__(64)
-k_scalar_prep(uint32_t n, uint32_t T, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-              const uint8_t* __restrict__ ssig, const uint8_t* __restrict__ recid, uint32_t flags,
-              uint32_t* __restrict__ prep, uint32_t* __restrict__ pref, uint32_t* __restrict__ smont, size_t stride) {
-  uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= T) return;
-  // products run on the lazy 10x26 Montgomery form (sc26.h); pref/smont are 10-word planes
-  sc26 one_m = sc26_from_limbs(SC26_ONE_M);
-  sc26 acc = one_m;
-#pragma unroll 1
-  for (int j = 0; j < PREP_M; ++j) {
-    size_t i = (size_t)t + (size_t)j * T;
-    if (i >= n) break;
-    sc s;
-    load_be32(s.v, (recid ? rsig : ssig) + i * 32);   // the value whose inverse is needed
-    bool ok_s = sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-    if (!ok_s) {   // keep the shared product invertible; the signature is rejected below
-      s = sc_zero();
-      s.v[0] = 1;
-    }
-    sc26 sm = sc26_to_mont(sc26_from_sc(s));
-    ws_store_sc26(smont, stride, i, sm);
-    acc = sc26_mm(acc, sm);
-    ws_store_sc26(pref, stride, i, acc);
-  }
-  sc26 inv = sc26_mont_inv(acc);
-#pragma unroll 1
-  for (int j = PREP_M - 1; j >= 0; --j) {
-    size_t i = (size_t)t + (size_t)j * T;
-    if (i >= n) continue;
-    sc26 sm = ws_load_sc26(smont, stride, i);
-    sc26 prev = j > 0 ? ws_load_sc26(pref, stride, i - T) : one_m;
-    sc26 s_inv_m = sc26_mm(inv, prev);             // s_i^-1 * R
-    inv = sc26_mm(inv, sm);
-    sc r, s;
-    uint32_t e_raw[8];
-    load_be32(r.v, rsig + i * 32);
-    load_be32(s.v, ssig + i * 32);
-    load_be32(e_raw, dig + i * 32);
-    bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-    if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);
-    sc e = sc_reduce_once(e_raw);
-    sc u1, u2;
-    uint32_t rid = 0;
-    if (recid) {
-      rid = recid[i];
-      // RecoverPoint (point_s11n.go:245-282): id in [0,3]; bit 1 means x = r + n, which must stay < p
-      ok = ok && rid < 4 && (!(rid & 2u) || u256_lt(r.v, FE_P_MINUS_N));
-      u1 = sc26_to_sc(sc26_mm(sc26_from_sc(sc_neg(e)), s_inv_m));   // -e / r
-      u2 = sc26_to_sc(sc26_mm(sc26_from_sc(s), s_inv_m));           //  s / r
-    } else {
-      u1 = sc26_to_sc(sc26_mm(sc26_from_sc(e), s_inv_m));
-      u2 = sc26_to_sc(sc26_mm(sc26_from_sc(r), s_inv_m));
-    }
-    sc k1, k2;
-    bool neg1, neg2;
-    sc_split_glv_odd(u2, k1, neg1, k2, neg2);          // both halves odd, < 2^129
-    uint32_t f = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) |
-                 (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0) | ((rid & 3u) << 8);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) prep[(size_t)w * stride + i] = u1.v[w];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) prep[(size_t)(8 + w) * stride + i] = k1.v[w];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) prep[(size_t)(12 + w) * stride + i] = k2.v[w];
-    prep[(size_t)16 * stride + i] = f;
-  }
-}
-
-// Lanes of k_scalar_prep for n signatures: PREP_M signatures share a lane's inversion where that saves instructions that
-// matter (2^20: a third of the kernel), but a call that cannot fill the chip anyway is better off with the latency of fewer
-// signatures per lane - up to 2^16 lanes (a wave on every SIMD) are used before signatures start to share one (94 us for six in
-// a row, 55 for one).
-__attribute__((visibility("hidden"))) uint32_t prep_lanes(size_t n) {
-  const size_t shared = (n + PREP_M - 1) / PREP_M, wide = n < ((size_t)1 << 16) ? n : ((size_t)1 << 16);
-  return (uint32_t)(shared > wide ? shared : wide);
-}
-
-// ---------------------------------------------------------------------------------------
-// Fast path, kernel 2: per-lane table, ladder, generator part, final comparison.
-// Per-lane table {1,3,..,15}*Q brought to one common Z (no inversion): build A_j = A_{j-1} + 2Q
-// on the curve isomorphic by C = Z(2Q), remember H_j (Z_j = Z_{j-1} H_j), then scale entry j
-// by (H_{j+1}...H_7)^{2,3}.  The ladder then only ever adds affine points (8 M + 3 S); its
-// result has the true Z = Z_ladder * Z_7 * C.
-// Table storage: tb_* (lane_tables.h).  Z_7 * C and the results handed to k_affine_finish go to the lane's
-// "fin" elements.
-// ---------------------------------------------------------------------------------------
-
-// Waves per SIMD the joint-table key-set ladder is built for.  Measured (tools/gpu_joint_waves.sh, same box, two runs each):
-// 3 waves (150 VGPRs, no spills) 1.743 / 1.746 ms, 4 waves (128 VGPRs, 21 spilled) 1.733 / 1.743 ms - the kernel is at the
-// clock the chip gives it (1.89-2.02 GHz under 8 GB of table fetches per launch) either way; 3 stays.
-#ifndef S2K_JOINT_WAVES
-#define S2K_JOINT_WAVES 3
-#endif
-// (the comb ladders' bound, S2K_COMB_WAVES, and VERDICT_PENDING: engine_internal.h)
-
-// Digits of an odd half scalar k < 2^129 in the order the per-key ladder consumes them.  As in
-// ds_init, digit i is nib_i = bits 4i+1 .. 4i+4 of k (signed value 2 nib_i - 15); digit i = 4c + j
-// belongs to chunk c = 2^(16c) Q and round j, and the ladder runs round 3 first, chunks upwards: its
-// nibble goes to place (3 - j) * 8 + c from the top of a 128-bit stream.
-struct digit_stream4 {
-  uint32_t w[4];
-};
-S2K_DEV digit_stream4 ds4_init_chunked(const sc& k_odd) {
-  digit_stream4 d;
-  d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0;
-#pragma unroll
-  for (int i = 0; i < 32; ++i) {
-    const int bit = 4 * i + 1, limb = bit >> 5, sh = bit & 31;
-    uint32_t nib = k_odd.v[limb] >> sh;
-    if (sh > 28) nib |= k_odd.v[limb + 1] << (32 - sh);
-    nib &= 15u;
-    const int c = i >> 2, j = i & 3, pos = 124 - 4 * ((3 - j) * 8 + c);
-    d.w[pos >> 5] |= nib << (pos & 31);
-  }
-  return d;
-}
-S2K_DEV uint32_t ds4_next(digit_stream4& d) {
-  uint32_t nib = d.w[3] >> 28;
-  d.w[3] = (d.w[3] << 4) | (d.w[2] >> 28);
-  d.w[2] = (d.w[2] << 4) | (d.w[1] >> 28);
-  d.w[1] = (d.w[1] << 4) | (d.w[0] >> 28);
-  d.w[0] <<= 4;
-  return nib;
-}
-
-// MODE_ECDSA:   pub = n x 64 (X||Y), rsig = n x 32 (r);      accept iff x(R) mod n == r
-// MODE_SCHNORR: pub = n x 32 (x-only key, BIP-340), rsig = n x 64 signatures (r at offset 0);
-//               P = lift_x(pub) (NewSchnorrPublicKey, schnorr.go:257-275), accept iff R != inf,
-//               y(R) even and x(R) == r (verifySchnorrSignatureR, schnorr.go:451-478)
-// MODE_RECOVER: pub unused, rsig = n x 32 (r); the point is R = RecoverPoint(r, id) with the id
-//               from the prep flag word; out = ok bytes, out_pts = n x 65 records of
-//               Q = (-e/r) G + (s/r) R (RecoverPublicKey, ecdsa.go:244-282)
-// MODE_POINT:   pub = n x 64 (X||Y), rsig unused; out_pts = n x 65 records of u1*G + u2*P with
-//               u1 and the split u2 taken from the prep planes as they are
-//               (DoubleScalarMultBasepointVartime, point_mul_glv.go:307; k_hot_prep)
-// MODE_ECDSA_KEYED / MODE_ECDSA_LEFT: MODE_ECDSA after the batch has been grouped by public key
-//               (keyed.hip).  Lane idx < *kg.counters[...] handles signature perm[idx]: inputs, prep
-//               planes and the verdict are the signature's, workspace columns are the lane's.
-//               KEYED lanes take their points from the key's precomputed affine table (table ptab[idx],
-//               no per-lane table, 12 doublings); LEFT lanes are the general path for the rest.
-// MODE_ECDSA_COMB: MODE_ECDSA_KEYED over the comb tables an ECDSA call builds by default (keyed.hip: k_key_chain on the comb's
-//               geometry, k_key_finish_comb): the same 64 entries per key serve 7 bits of a half scalar per addition.
-// MODE_SCHNORR_KEYED / MODE_SCHNORR_LEFT: the same for BIP-340 (tables of the lifted x-only keys); results go
-//               to k_affine_finish in the SIGNATURE's fin column.
-// MODE_SCHNORR_COMB: MODE_SCHNORR_KEYED over comb tables.  kg.key_bytes == 32: the tables of a call's lifted x-only keys;
-//               kg.key_bytes == 64: a comb key set (S2K_KEYSET_COMB), pub = the set's X || Y keys - an odd Y flips both half
-//               scalars' signs, as in the MODE_SCHNORR_KEYSET modes.
-// Waves per SIMD the register allocator must leave room for.  Measured (2^20 signatures):
-// unbounded (240 VGPRs, 2 waves) 11.08 ms; 3 waves (168 VGPRs, no spills) 10.89 ms; 4 waves
-// (128 VGPRs, 96 spilled) 11.45 ms.
-#ifndef S2K_FAST_WAVES
-#define S2K_FAST_WAVES 3
-#endif
-// ---------------------------------------------------------------------------------------
-// Grouped flow only: the generator part u1*G of every signature, on its own.  It needs nothing but
-// the prepared u1, so it runs on the second stream, after the scalar preparation and beside the
-// grouping and per-key table kernels (which are latency or memory bound and leave the multipliers
-// idle); the ladders then finish with one Jacobian + Jacobian addition instead of GT_WINDOWS mixed ones.
-// Out: (X, Y, Z) in three "fin"-format elements per SIGNATURE (gp planes).  A degenerate addition
-// on the way (or u1 = 0) leaves Z = 0, which the ladder's final addition passes on to the worklist.
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_generator_part(uint32_t first, uint32_t n, const uint32_t* __restrict__ prep, gt_view gt,
-                 uint32_t* __restrict__ gp, size_t stride) {
-  size_t idx = (size_t)first + (size_t)blockIdx.x * 256 + threadIdx.x;   // signatures [first, n)
-  if (idx >= n) return;
-  uint32_t u[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) u[w] = prep[(size_t)w * stride + idx];
-  apt g = gt_load(gt, 0, gt_next_digit(u, gt.bits));
-  const fe29 ax = fe29_from_words(g.x.v), ay = fe29_from_words(g.y.v);
-  xyzz29 xa = xyzz29_from_affine(ax, ay);                                            // XYZZ additions, as in the keyed ladder
-  g = gt_load(gt, 1, gt_next_digit(u, gt.bits));
-  if (gt.windows > 1) {   // the first addition: both points affine
-    const fe29 gx = fe29_from_words(g.x.v), gy = fe29_from_words(g.y.v);
-    if (gt.windows > 2) g = gt_load(gt, 2, gt_next_digit(u, gt.bits));
-    xa = xyzz29_add_affine_first(ax, ay, gx, gy);
-  }
-#pragma unroll 1
-  for (uint32_t w = 2; w < gt.windows; ++w) {
-    const fe29 gx = fe29_from_words(g.x.v), gy = fe29_from_words(g.y.v);
-    if (w + 1 < gt.windows) g = gt_load(gt, w + 1, gt_next_digit(u, gt.bits));   // in flight during this addition
-    xa = xyzz29_add_affine(xa, gx, gy);
-  }
-  // (two entries in flight instead of one halve the kernel's waiting - SQ_WAIT_ANY 87 M -> 46 M wave cycles - and change
-  // neither its duration nor the step's: three waves per SIMD cover it; profiles/r06_wait_shares.txt)
-  const jpt29 acc = xyzz29_to_jacobian(xa);
-  fq_store(gp, stride, idx, 0, acc.x);
-  fq_store(gp, stride, idx, 1, acc.y);
-  fq_store(gp, stride, idx, 2, acc.z);
-}
-
-template <int MODE>
-#ifdef S2K_FAST_MAX_WAVES   // experiment: cap the occupancy (leaves VGPRs for a kernel of another stream to run beside the ladder)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S2K_FAST_MAX_WAVES, S2K_FAST_MAX_WAVES)))
-#else
-// (The ladders over per-key tables hold no per-lane table state and come out at 126 VGPRs: four waves per SIMD.  That is
-// the allocator's doing under a bound of three, and it is fragile: a rare branch that kept the accumulator alive across the
-// final addition took 152, and asking for four waves outright spills - 26 VGPRs for <ECDSA_KEYED>, 28 for the key-set
-// ladder, which stays at 142 VGPRs and three waves.  tests/test_counts_cpu.py watches the instruction counts; the
-// resource usage is printed by tools/kernel_regs.sh.)
-__global__ void __launch_bounds__(256, (MODE == MODE_ECDSA_KEYSET_JOINT || MODE == MODE_ECDSA_KEYSET_JOINT5 || MODE == MODE_ECDSA_KEYSET_JOINT6 ||
-                                        MODE == MODE_SCHNORR_KEYSET_JOINT || MODE == MODE_SCHNORR_KEYSET_JOINT5 || MODE == MODE_SCHNORR_KEYSET_JOINT6)
-                                           ? S2K_JOINT_WAVES : (MODE == MODE_ECDSA_COMB || MODE == MODE_SCHNORR_COMB) ? S2K_COMB_WAVES : S2K_FAST_WAVES)
-#endif
-k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig,
-              const uint32_t* __restrict__ prep, uint32_t* __restrict__ qt, uint32_t* __restrict__ fin,
-              gt_view gt, uint8_t* __restrict__ out, uint32_t* __restrict__ wl_count,
-              uint32_t* __restrict__ wl, size_t stride, uint8_t* __restrict__ out_pts, uint64_t* __restrict__ clk,
-              key_groups kg) {
-  constexpr bool SKS = MODE >= MODE_SCHNORR_KEYSET && MODE <= MODE_SCHNORR_KEYSET_JOINT6;   // BIP-340 over a key set
-  constexpr int KM = SKS ? MODE - 4 : MODE;                  // the key-set layout, as its ECDSA mode
-  constexpr bool JOINT = KM == MODE_ECDSA_KEYSET_JOINT;      // ... over its joint tables: one addition per digit position
-  constexpr int JW = KM == MODE_ECDSA_KEYSET_JOINT5 ? 5 : KM == MODE_ECDSA_KEYSET_JOINT6 ? 6 : 4;
-  constexpr bool JOINTW = JW > 4;                            // ... over joint tables of 5- or 6-bit digits (kjw_geom: 26 / 22 positions)
-  constexpr bool KEYSET = KM == MODE_ECDSA_KEYSET || JOINT || JOINTW;   // KEYED over a key set's 32-chunk tables: no doublings at all
-  constexpr bool COMB = MODE == MODE_ECDSA_COMB || MODE == MODE_SCHNORR_COMB;   // KEYED over the comb table of the key
-  constexpr bool KEYED = MODE == MODE_ECDSA_KEYED || MODE == MODE_SCHNORR_KEYED || KEYSET || COMB;
-  constexpr bool GROUPED = KEYED || MODE == MODE_ECDSA_LEFT || MODE == MODE_SCHNORR_LEFT;
-  constexpr bool ECDSA = MODE == MODE_ECDSA || MODE == MODE_ECDSA_KEYED || MODE == MODE_ECDSA_LEFT || (KEYSET && !SKS) || MODE == MODE_ECDSA_COMB;
-  const bool force_wl = (n_and_flags & KVF_FORCE_WORKLIST) != 0;
-  const uint32_t n = n_and_flags & ~KVF_FORCE_WORKLIST;
-  size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;         // lane: workspace column
-  size_t sig = idx;                                            // signature: input / prep / verdict column
-  uint32_t lanes = n;
-  if constexpr (GROUPED) {
-    uint32_t lo = 0, hi = kg.counters[KEYED ? KG_NKEYED : KG_NLEFT];
-    if (KEYED && kg.nparts > 1) {                              // two-part flow: this launch takes one side of the split
-      const uint32_t sp = kg.counters[KG_SPLIT_LANE];
-      if (kg.part) lo = sp;
-      else hi = sp;
-    }
-    idx += lo;
-    if (idx >= hi) return;
-    lanes = hi - lo;
-    sig = (KEYED ? kg.perm : kg.left)[idx];
-  } else {
-    if (idx >= n) return;
-  }
-  // effective shader clock of this launch (bench.py roofline): wave 0 of workgroup 0 stamps the
-  // shader cycle counter and the constant-rate wall clock when it starts and when it ends
-  // (and wave 0 of the LAST workgroup, which runs in the launch's final round: the clock sags under power
-  // over the 8 ms of a launch)
-  const bool stamp = clk != nullptr && (blockIdx.x == 0 || blockIdx.x == (lanes - 1) / 256) && threadIdx.x < 64;
-  uint64_t t0c = 0, t0w = 0;
-  if (stamp) {
-    t0c = __builtin_readcyclecounter();
-    t0w = __builtin_amdgcn_s_memrealtime();
-  }
-  uint32_t pf = prep[(size_t)16 * stride + sig];
-  bool ok;
-  fe29 qx, qy;
-  if constexpr (KEYED) {
-    ok = (pf & PF_OK) && kg.tinfo[kg.ptab[idx]];      // the key was validated when its table was built
-  } else if constexpr (MODE == MODE_RECOVER) {
-    uint32_t xw[8];
-    load_be32(xw, rsig + idx * 32);
-    ok = (pf & PF_OK) != 0;
-    if (ok && (pf & 0x200u)) u256_add(xw, xw, SC_N);   // x = r + n (< p, checked by the prep kernel)
-    if (!ok) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) xw[i] = FE_GX[i];
-    }
-    qx = fe29_from_words(xw);
-    fe29 rhs = fe29_mul(fe29_sqr(qx), qx);
-    rhs.n[0] += 7;
-    bool has = fe29_sqrt(qy, rhs);                      // SetCompressedBytes (point_s11n.go:152-169)
-    if (!has) {
-      ok = false;
-      qx = fe29_from_words(FE_GX);
-      qy = fe29_from_words(FE_GY);
-    }
-    qy = fe29_normalize(qy);
-    bool want_odd = (pf & 0x100u) != 0;
-    qy = fe29_select(((qy.n[0] & 1u) != 0) != want_odd, qy, fe29_normalize_weak(fe29_negate(qy, 1)));
-  } else if constexpr (ECDSA || MODE == MODE_POINT) {
-    apt q;
-    load_be32(q.x.v, pub + sig * 64);
-    load_be32(q.y.v, pub + sig * 64 + 32);
-    ok = (pf & PF_OK) && fe_is_canonical_raw(q.x.v) && fe_is_canonical_raw(q.y.v);
-    if (!ok) {   // keep the arithmetic on the curve; the verdict is already "invalid"
-      q.x = fe_from_limbs(FE_GX);
-      q.y = fe_from_limbs(FE_GY);
-    }
-    qx = fe29_from_words(q.x.v);
-    qy = fe29_from_words(q.y.v);
-    // y^2 == x^3 + 7 (point_s11n.go:298-307)
-    fe29 rhs = fe29_mul(fe29_sqr(qx), qx);
-    rhs.n[0] += 7;
-    bool on = fe29_eq(fe29_sqr(qy), rhs);
-    if (!on) {
-      ok = false;
-      qx = fe29_from_words(FE_GX);
-      qy = fe29_from_words(FE_GY);
-    }
-  } else {
-    uint32_t xw[8];
-    load_be32(xw, pub + sig * 32);
-    ok = (pf & PF_OK) && fe_is_canonical_raw(xw);
-    if (!ok) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) xw[i] = FE_GX[i];
-    }
-    qx = fe29_from_words(xw);
-    fe29 rhs = fe29_mul(fe29_sqr(qx), qx);
-    rhs.n[0] += 7;                                    // [1] (+7 on limb 0)
-    bool has = fe29_sqrt(qy, rhs);
-    if (!has) {   // not an x-coordinate of the curve
-      ok = false;
-      qx = fe29_from_words(FE_GX);
-      qy = fe29_from_words(FE_GY);
-    }
-    qy = fe29_normalize(qy);
-    qy = fe29_select((qy.n[0] & 1u) != 0, qy, fe29_normalize_weak(fe29_negate(qy, 1)));   // even y
-  }
-  bool neg1 = pf & PF_NEG1, neg2 = pf & PF_NEG2;
-  if constexpr (SKS) {
-    // BIP-340 multiplies P = lift_x(x), the point with EVEN y; the set holds the key as its caller gave it (X || Y): an odd Y
-    // means P = -Q, i.e. both half scalars change sign (`pub`: the set's key array)
-    const bool y_odd = (pub[(size_t)kg.ptab[idx] * 64 + 63] & 1u) != 0;
-    neg1 = neg1 != y_odd;
-    neg2 = neg2 != y_odd;
-  }
-  if constexpr (MODE == MODE_SCHNORR_COMB) {
-    // a comb key set holds X || Y as well (the same flip); the tables of a call are those of the lifted keys: nothing to do.
-    // One mode for both: the test is uniform over the launch
-    if (kg.key_bytes == 64) {
-      const bool y_odd = (pub[(size_t)kg.ptab[idx] * 64 + 63] & 1u) != 0;
-      neg1 = neg1 != y_odd;
-      neg2 = neg2 != y_odd;
-    }
-  }
-
-  // ---- table ----
-  if constexpr (!KEYED) {
-    jpt29 a0;
-    a0.x = qx;
-    a0.y = qy;
-    a0.z = fe29_one();
-    jpt29 d = jpt29_double(a0);                      // x [1] y [2] z [1]
-    fe29 c2 = fe29_sqr(d.z);
-    fe29 c3 = fe29_mul(c2, d.z);
-    const fe29 dx = d.x, dy = d.y;                   // the affine addend on the isomorphic curve
-    jpt29 cur;
-    cur.x = fe29_mul(qx, c2);
-    cur.y = fe29_mul(qy, c3);
-    cur.z = fe29_one();
-    tb_store(qt, stride, idx, 0, TB_X, cur.x);
-    tb_store(qt, stride, idx, 0, TB_Y, cur.y);
-#pragma unroll 1
-    for (int j = 1; j < QT_ENTRIES; ++j) {
-      fe29 h;
-      cur = jpt29_add_affine(cur, dx, dy, &h);
-      tb_store(qt, stride, idx, j, TB_X, cur.x);
-      tb_store(qt, stride, idx, j, TB_Y, cur.y);
-      tb_store(qt, stride, idx, j, TB_BX, h);          // H_j, replaced by beta * x_j below
-    }
-    fq_store(fin, stride, idx, TB_ZC_ELEM, fe29_mul(cur.z, d.z));   // Z_7 * C
-    fe29 prev_x = cur.x;
-    const fe29 beta = fe29_from_words(FE_BETA);
-    fe29 rr = fe29_one();
-#pragma unroll 1
-    for (int j = QT_ENTRIES - 2; j >= 0; --j) {
-      rr = fe29_mul(rr, tb_load(qt, stride, idx, j + 1, TB_BX));
-      tb_store(qt, stride, idx, j + 1, TB_BX, fe29_mul(prev_x, beta));
-      fe29 r2 = fe29_sqr(rr);
-      fe29 r3 = fe29_mul(r2, rr);
-      prev_x = fe29_mul(tb_load(qt, stride, idx, j, TB_X), r2);
-      fe29 y = fe29_mul(tb_load(qt, stride, idx, j, TB_Y), r3);
-      tb_store(qt, stride, idx, j, TB_X, prev_x);
-      tb_store(qt, stride, idx, j, TB_Y, y);
-    }
-    tb_store(qt, stride, idx, 0, TB_BX, fe29_mul(prev_x, beta));
-  }
-
-  // ---- ladder over |k1|, |k2| ----
-  sc k1 = sc_zero(), k2 = sc_zero();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    k1.v[w] = prep[(size_t)(8 + w) * stride + sig];
-    k2.v[w] = prep[(size_t)(12 + w) * stride + sig];
-  }
-  k1.v[4] = (pf & PF_K1_B128) ? 1u : 0u;   // odd by construction (sc_split_glv_odd): the signed
-  k2.v[4] = (pf & PF_K2_B128) ? 1u : 0u;   // odd-digit recoding is exact, no final correction
-  jpt29 acc;
-  if constexpr (COMB) {
-    // The comb ladder (kc_geom, engine_internal.h).  k = 2^133 + sum_{i<133} b_i 2^i, b_i = 2 a_i - 1, a = k >> 1 (k odd,
-    // < 2^129: a has 128 bits).  Column j (18 down to 0) of a half is the bits a_(19 t + j) of the seven teeth t: the top
-    // tooth gives the sign, the lower six (complemented under a negative top tooth) the entry
-    // E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t.  A round is one doubling (none in front of the first round) and the two
-    // halves' additions: 38 additions and 18 doublings.  The lead 2^133 Q = 2^18 * 2^115 Q goes in first, for both halves at
-    // once (L +- phi(L), as in the window ladder).
-    // All in Jacobian coordinates, a round's two entries added to each other first: 19 * 20 + 18 * 7 = 506 products (two
-    // mixed additions a round: 19 * 22 + 18 * 7 = 544).  XYZZ additions (10 in 9 reductions) would want an XYZZ
-    // doubling (6 M + 3 S = 9: 542 products) or the change of form around every single doubling (4 products a round: 578),
-    // and a fourth coordinate in registers; jacobian29.h's pair is the one the general ladder runs and the models bound.
-    // Z = 0 is sticky through all of it (Z3 = Z1 H h, Z3 = Y Z) and ends on the worklist exactly as before.
-    using G = kc_geom;
-    const uint4* kt = kg.ktab + (size_t)kg.ptab[idx] * (G::SLOTS * 8);
-    {
-      fe29 lx, ly;
-      ke_load_xy(kt + (size_t)(neg1 == neg2 ? G::LEAD : G::LEAD + 1) * 8, false, lx, ly);
-      acc.x = lx;
-      acc.y = fe29_cond_negate1(ly, neg1);
-      acc.z = fe29_one();
-    }
-    // tooth t of a half: bits 19 t .. 19 t + 18 of a = k >> 1 (tooth 6: 14 bits and zeros); bit j of it is a shift and a mask.
-    // The 19 columns of both halves (7 + 7 bits) are cut once and wait in LDS, one word per round and lane ([round][lane]: no
-    // two lanes of a wave share a bank, no lane reads another's): 19 KiB per block, and no register held across the ladder.
-    __shared__ uint32_t cols[G::SPACING][256];
-    {
-      uint32_t t1[G::TEETH], t2[G::TEETH];
-#pragma unroll
-      for (int t = 0; t < G::TEETH; ++t) {
-        const int bit = G::SPACING * t + 1, limb = bit >> 5, sh = bit & 31;      // (+ 1: a = k >> 1)
-        uint32_t v1 = k1.v[limb] >> sh, v2 = k2.v[limb] >> sh;
-        if (sh > 32 - G::SPACING) {
-          v1 |= k1.v[limb + 1] << (32 - sh);
-          v2 |= k2.v[limb + 1] << (32 - sh);
-        }
-        t1[t] = v1 & ((1u << G::SPACING) - 1u);
-        t2[t] = v2 & ((1u << G::SPACING) - 1u);
-      }
-#pragma unroll
-      for (int j = 0; j < G::SPACING; ++j) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int t = 0; t < G::TEETH; ++t) w |= (((t1[t] >> j) & 1u) << t) | (((t2[t] >> j) & 1u) << (8 + t));
-        cols[j][threadIdx.x] = w;
-      }
-    }
-#pragma unroll 1
-    for (int j = G::SPACING - 1;; --j) {
-      // the column: E1 of the first half and phi(E2) of the second (the beta * x column) are affine over the same Z, so
-      // they are added to each other first (jacobian29.h: coz29_pair_sum, E2 with its sign relative to E1's) and their
-      // sum, over Z h, goes to the accumulator moved onto that curve: 15 M + 5 S against the 16 M + 6 S of two mixed
-      // additions, and both lookups of the column in flight together
-      const uint32_t w12 = cols[j][threadIdx.x], w1 = w12 & 127u, w2 = w12 >> 8;
-      const bool top1 = (w1 & 64u) != 0, top2 = (w2 & 64u) != 0;
-      const bool n1 = neg1 != !top1, n2 = neg2 != !top2;
-      fe29 x1, y1, x2, y2;
-      ke_load_xy(kt + (size_t)((top1 ? w1 : ~w1) & 63u) * 8, false, x1, y1);
-      ke_load_xy(kt + (size_t)((top2 ? w2 : ~w2) & 63u) * 8, true, x2, y2);
-      const coz29_sum t = coz29_pair_sum(x1, y1, x2, fe29_cond_negate1(y2, n1 != n2));
-      acc = jpt29_rescale(acc, t.hh, t.hhh);
-      acc = jpt29_add_affine(acc, t.x, fe29_cond_negate1(t.ny, !n1));   // (ny = -Y_T)
-      acc.z = fe29_mul(acc.z, t.h);
-      if (j == 0) break;
-      acc = jpt29_double(acc);
-    }
-    // the table's points are affine on the curve isomorphic by W (keyed.hip): back on secp256k1 itself
-    // (W is asked for here and not in front of the ladder: nothing is held across it but the accumulator - neither W's nine
-    // registers nor the teeth, which wait in LDS.  The column's four coordinates and its pair sum are 145 VGPRs, three waves
-    // per SIMD; bounded to four, S2K_COMB_WAVES=4, the kernel spills 23 and loses what the column saves.)
-    acc.z = fe29_mul(acc.z, ke_load(kt + (size_t)G::WENT * 8, G::W));
-  } else if constexpr (KEYED) {
-    // k = 16^32 + sum_i d_i 16^i with d_i = 2 nib_i - 15, i = 4c + j: round j (3 down to 0) adds
-    // d_(4c+j) * 2^(16c) Q for the eight chunks c, with four doublings between rounds; the leading
-    // 16^32 Q = 16^3 * 2^116 Q goes in first (for both halves at once: one table point, see below).
-    using G = kt_geom<KEYSET ? KS_CHUNKS : KT_CHUNKS>;
-    const uint4* kt = kg.ktab + (size_t)kg.ptab[idx] * (G::SLOTS * 8);
-    const fe29 kw = ke_load(kt + (size_t)(G::SCR + G::W_SLOT / 3) * 8, G::W_SLOT % 3);   // wanted at the very end: asked for early
-    // The 64 additions of this ladder run in XYZZ coordinates (xyzz29.h: 8 M + 2 S in 9 reductions against 8 M + 3 S in
-    // 10 for the Jacobian mixed addition: 1 441 instead of 1 578 instructions); the 12 doublings stay Jacobian (7 products
-    // against 9), so the accumulator changes form at the three round borders (3 M + 1 S each way together).  The
-    // exceptional-case rule carries over: equal x makes ZZ = 0, ZZ = 0 is sticky through additions, conversions and
-    // doublings, and ends as Z = 0 -> worklist.
-    xyzz29 xa;
-    {
-      // +-L +- phi(L): the table holds L + phi(L) and L - phi(L) (keyed.hip), the other two are their negatives
-      // (wide joint tables: L = 2^(W POS) Q, the pair behind the positions of the key's joint table)
-      fe29 lx, ly;
-      if constexpr (JOINTW)
-        jw_load(kg.jtab + (size_t)kg.ptab[idx] * kjw_geom<JW>::KEY_QUADS + (kjw_geom<JW>::LEAD + (neg1 == neg2 ? 0 : 1)) * kjw_geom<JW>::EQ, lx, ly);
-      else
-        ke_load_xy(kt + (size_t)(neg1 == neg2 ? G::LEAD : G::LEAD + 1) * 8, false, lx, ly);
-      xa = xyzz29_from_affine(lx, fe29_cond_negate1(ly, neg1));
-    }
-    if constexpr (KEYSET) {
-      // Key sets: one chunk per digit, {1,3,..,15} * 16^i Q for i < 32 and L = 16^32 Q: k = 16^32 + sum d_i 16^i is 64
-      // table additions, in any order - bottom up, nibble i = bits 4i+1 .. 4i+4 of the odd half scalar (k >> 1, 128 bits).
-      // JOINT tables hold, per position, E_a + s phi(E_b) for all pairs of odd multiples and both signs: the two halves'
-      // digits d1 = +-(2a+1), d2 = +-(2b+1) are ONE addition of +-(E_a + s phi(E_b)), s = the product of their signs.
-      uint32_t a[4], b[4];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        a[w] = (k1.v[w] >> 1) | (k1.v[w + 1] << 31);
-        b[w] = (k2.v[w] >> 1) | (k2.v[w + 1] << 31);
-      }
-      [[maybe_unused]] const uint4* jt = JOINT ? kg.jtab + (size_t)kg.ptab[idx] * KJ_KEY_QUADS
-                                        : JOINTW ? kg.jtab + (size_t)kg.ptab[idx] * kjw_geom<JW>::KEY_QUADS : nullptr;
-      if constexpr (JOINTW) {
-        // W-bit digits: w_i = bits W i .. W i + W - 1 of (k - 1) / 2, d_i = 2 w_i - (2^W - 1): below 2^(W-1) negative with
-        // magnitude 2 (NE - 1 - w) + 1, else positive with magnitude 2 (w - NE) + 1
-        using J = kjw_geom<JW>;
-        constexpr uint32_t WM = (1u << JW) - 1u, NE = (uint32_t)J::NE;
-        // The entry of position c + 1 is asked for BEFORE the addition of position c (measured both ways, profiles/r06_keyset_wait.json): a joint
-        // table is 0.8 / 2.75 MiB per key and a lookup is a 64-byte read from HBM more often than not - issued behind the
-        // addition, its latency stood between every two additions of a wave.
-        auto next_entry = [&](int c, bool& n1_out) -> uint32_t {
-          const uint32_t w1 = a[0] & WM, w2 = b[0] & WM;
-#pragma unroll
-          for (int w = 0; w < 3; ++w) {
-            a[w] = (a[w] >> JW) | (a[w + 1] << (32 - JW));
-            b[w] = (b[w] >> JW) | (b[w + 1] << (32 - JW));
-          }
-          a[3] >>= JW;
-          b[3] >>= JW;
-          const bool n1 = neg1 != (w1 < NE), n2 = neg2 != (w2 < NE);
-          const uint32_t ea = (w1 < NE) ? (NE - 1u - w1) : (w1 - NE), eb = (w2 < NE) ? (NE - 1u - w2) : (w2 - NE);
-          n1_out = n1;
-          return (((uint32_t)c * NE + ea) * NE + eb) * 2u + (n1 != n2 ? 1u : 0u);
-        };
-        bool n1_cur;
-        jw_raw raw = jw_fetch(jt + (size_t)next_entry(0, n1_cur) * J::EQ);
-#pragma unroll 1
-        for (int c = 0; c < J::POS; ++c) {
-          const jw_raw cur = raw;
-          const bool n1 = n1_cur;
-          if (c + 1 < J::POS) raw = jw_fetch(jt + (size_t)next_entry(c + 1, n1_cur) * J::EQ);
-          fe29 x, y;
-          jw_point(cur, x, y);
-          xa = xyzz29_add_affine(xa, x, fe29_cond_negate1(y, n1));
-        }
-      } else if constexpr (JOINT) {
-        // the 4-bit joint ladder with the same lead: the 80-byte entry of position c + 1 (18 limbs) asked for before the addition
-        // of position c
-        auto next_entry4 = [&](int c, bool& n1_out) -> uint32_t {
-          const uint32_t w1 = a[0] & 15u, w2 = b[0] & 15u;
-#pragma unroll
-          for (int w = 0; w < 3; ++w) {
-            a[w] = (a[w] >> 4) | (a[w + 1] << 28);
-            b[w] = (b[w] >> 4) | (b[w + 1] << 28);
-          }
-          a[3] >>= 4;
-          b[3] >>= 4;
-          const bool n1 = neg1 != (w1 < 8u), n2 = neg2 != (w2 < 8u);
-          const uint32_t ea = (w1 < 8u) ? (7u - w1) : (w1 - 8u), eb = (w2 < 8u) ? (7u - w2) : (w2 - 8u);
-          n1_out = n1;
-          return (((uint32_t)c * 8u + ea) * 8u + eb) * 2u + (n1 != n2 ? 1u : 0u);
-        };
-        bool n1_nxt;
-        fe29 nx, ny;
-        je_load(jt + (size_t)next_entry4(0, n1_nxt) * KJ_ENTRY_QUADS, nx, ny);
-#pragma unroll 1
-        for (int c = 0; c < KS_CHUNKS; ++c) {
-          const fe29 x = nx, y = ny;
-          const bool n1 = n1_nxt;
-          if (c + 1 < KS_CHUNKS) je_load(jt + (size_t)next_entry4(c + 1, n1_nxt) * KJ_ENTRY_QUADS, nx, ny);
-          xa = xyzz29_add_affine(xa, x, fe29_cond_negate1(y, n1));
-        }
-      } else {
-#pragma unroll 1
-        for (int c = 0; c < KS_CHUNKS; ++c) {
-          const uint32_t w1 = a[0] & 15u, w2 = b[0] & 15u;
-#pragma unroll
-          for (int w = 0; w < 3; ++w) {
-            a[w] = (a[w] >> 4) | (a[w + 1] << 28);
-            b[w] = (b[w] >> 4) | (b[w + 1] << 28);
-          }
-          a[3] >>= 4;
-          b[3] >>= 4;
-#pragma unroll 1
-          for (int t = 0; t < 2; ++t) {
-            uint32_t w = t ? w2 : w1;
-            bool neg = (t ? neg2 : neg1) != (w < 8u);
-            uint32_t entry = (w < 8u) ? (7u - w) : (w - 8u);
-            fe29 x, y;
-            ke_load_xy(kt + (size_t)(c * 8 + entry) * 8, t != 0, x, y);
-            xa = xyzz29_add_affine(xa, x, fe29_cond_negate1(y, neg));
-          }
-        }
-      }
-    } else {
-      digit_stream4 d1 = ds4_init_chunked(k1), d2 = ds4_init_chunked(k2);
-#pragma unroll 1
-      for (int round = 0; round < 4; ++round) {
-        if (round) {
-          jpt29 j4 = xyzz29_to_jacobian(xa);
-#pragma unroll 1
-          for (int j = 0; j < 4; ++j) j4 = jpt29_double(j4);
-          xa = xyzz29_from_jacobian(j4);
-        }
-#pragma unroll 1
-        for (int c = 0; c < KT_CHUNKS; ++c) {
-          uint32_t w1 = ds4_next(d1), w2 = ds4_next(d2);
-#pragma unroll 1
-          for (int t = 0; t < 2; ++t) {
-            uint32_t w = t ? w2 : w1;
-            bool neg = (t ? neg2 : neg1) != (w < 8u);
-            uint32_t entry = (w < 8u) ? (7u - w) : (w - 8u);
-            fe29 x, y;
-            ke_load_xy(kt + (size_t)(c * 8 + entry) * 8, t != 0, x, y);
-            xa = xyzz29_add_affine(xa, x, fe29_cond_negate1(y, neg));
-          }
-        }
-      }
-      // (the next entry asked for before the current addition - what the key-set ladders do - costs this ladder its fourth wave
-      // per SIMD: 145-147 VGPRs against 126.  Measured in both forms, four alternating pairs: the step 4.89 against 4.91 ms,
-      // the kernel 58.2 M against 57.8 M cycles under the counters - nothing, and not kept; profiles/r06_wait_shares.txt)
-    }
-    acc = xyzz29_to_jacobian(xa);
-    // the table's points are affine on the curve isomorphic by W (keyed.hip): back on secp256k1 itself
-    acc.z = fe29_mul(acc.z, kw);
-  } else {
-    digit_stream d1 = ds_init(k1), d2 = ds_init(k2);
-    {
-      fe29 t0x = tb_load(qt, stride, idx, 0, TB_X), t0y = tb_load(qt, stride, idx, 0, TB_Y), t0bx = tb_load(qt, stride, idx, 0, TB_BX);
-      acc.x = t0x;
-      acc.y = fe29_cond_negate1(t0y, neg1);
-      acc.z = fe29_one();
-      acc = jpt29_add_affine(acc, t0bx, fe29_cond_negate1(t0y, neg2));
-    }
-#pragma unroll 1
-    for (int i = 31; i >= 0; --i) {
-#pragma unroll 1
-      for (int j = 0; j < 4; ++j) acc = jpt29_double(acc);
-      uint32_t w1 = ds_next(d1), w2 = ds_next(d2);
-#pragma unroll 1
-      for (int t = 0; t < 2; ++t) {
-        uint32_t w = t ? w2 : w1;
-        bool neg = (t ? neg2 : neg1) != (w < 8u);
-        uint32_t entry = (w < 8u) ? (7u - w) : (w - 8u);
-        fe29 x, y;
-        tb_load_xy(qt, stride, idx, entry, t != 0, x, y);
-        acc = jpt29_add_affine(acc, x, fe29_cond_negate1(y, neg));
-      }
-    }
-    acc.z = fe29_mul(acc.z, fq_load(fin, stride, idx, TB_ZC_ELEM));   // times Z_7 * C: back on secp256k1 itself
-  }
-
-  // ---- generator part: u1*G from the resident tables ----
-  // (final_only: Z was not 0 BEFORE the last addition and the addend is finite - then a zero after it arose in that addition,
-  // and the verdict code below decides it instead of queueing the lane for the complete-formula kernel)
-  bool final_only = false;
-  if constexpr (GROUPED) {
-    jpt29 q;                                            // computed by k_generator_part
-    q.x = fq_load(kg.gp, stride, sig, 0);
-    q.y = fq_load(kg.gp, stride, sig, 1);
-    q.z = fq_load(kg.gp, stride, sig, 2);
-    if constexpr (ECDSA) final_only = !fe29_is_zero(acc.z) && !fe29_is_zero(q.z);
-    acc = jpt29_add(acc, q);
-  } else {
-    uint32_t u[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) u[w] = prep[(size_t)w * stride + sig];
-#pragma unroll 1
-    for (uint32_t w = 0; w + 1 < gt.windows; ++w) {
-      apt g = gt_load(gt, w, gt_next_digit(u, gt.bits));
-      acc = jpt29_add_affine(acc, fe29_from_words(g.x.v), fe29_from_words(g.y.v));
-    }
-    {   // the last addition apart: whether Z was 0 before it is what the verdict code needs to know
-      apt g = gt_load(gt, gt.windows - 1, gt_next_digit(u, gt.bits));
-      if constexpr (ECDSA) final_only = !fe29_is_zero(acc.z);
-      acc = jpt29_add_affine(acc, fe29_from_words(g.x.v), fe29_from_words(g.y.v));
-    }
-  }
-
-  // ---- verdict ----
-  uint8_t verdict = 0;
-  // (MODE_RECOVER / MODE_POINT: the 65-byte records start as zeros - one fill of the output array by the caller; the loop of
-  // 65 single-byte stores per lane that used to stand here cost the recovery ladder a tenth of its time)
-  // Z = 0: infinity, or an exceptional case of the incomplete formulas somewhere on the way.  Where the zero first appears
-  // in the FINAL addition of two finite points (Z3 = Z1 Z2 H = 0: equal x) the answer is at hand.  With H = 0 the mixed
-  // addition leaves X3 = I^2, I = Y1 - S2 (jacobian29.h), so X3 != 0 says OPPOSITE points: R is the identity and verify
-  // rejects it (ecdsa.go:450).  That is what anyone who owns a key gets with r = -e/d in every lane, whatever the digests
-  // (the signature need not be valid), and it used to send the whole batch through the complete-formula kernel: 3.4 x a
-  // normal step; now the lane is done.  X3 = 0 says EQUAL points (r = e/d): R is twice the last addend - left to the
-  // worklist kernel with a tag (WL_DOUBLE_GEN: 2 u1 G in the grouped flows, WL_DOUBLE_LAST: twice the last generator-table
-  // entry in the plain one; a twelfth of a full verification or less), since the keyed ladder has no registers to spare.
-  // Zeros from INSIDE the ladder or the generator part (and u1 = 0: a digest that is 0 mod n) go to the worklist as before.
-  bool undecided = ok && fe29_is_zero(acc.z), is_identity = false;
-  uint32_t wl_tag = 0;
-  if constexpr (ECDSA) {
-    if (force_wl && ok) {                                // S2K_ECDSA_FORCE_WORKLIST (diagnostic)
-      undecided = true;
-      final_only = false;
-    }
-  }
-  if constexpr (ECDSA) {
-    if (undecided && final_only) {
-      if (!fe29_is_zero(acc.x)) {
-        undecided = false;
-        is_identity = true;                              // P - P
-      } else if (n < WL_TAG_LIMIT) {
-        wl_tag = GROUPED ? WL_DOUBLE_GEN : WL_DOUBLE_LAST;   // P + P: R = 2 u1 G, or twice the last table entry
-      }
-    }
-  }
-  if (ok) {
-    if (undecided) {
-      // infinity or an exceptional case inside the ladder: the complete kernel decides
-      uint32_t pos = atomicAdd(wl_count, 1u);
-      wl[pos] = (uint32_t)sig | wl_tag;
-    } else if (is_identity) {
-      verdict = 0;                                      // R = infinity (ecdsa.go:450)
-    } else if constexpr (!ECDSA) {
-      // affine epilogue (key bytes / even-y test) needs 1/Z: leave (X, Y, Z) in the SIGNATURE's fin
-      // column (its own lane's when not grouped) and let k_affine_finish share one inversion between 16
-      fq_store(fin, stride, sig, 0, acc.x);
-      fq_store(fin, stride, sig, 1, acc.y);
-      fq_store(fin, stride, sig, 2, acc.z);
-      verdict = VERDICT_PENDING;
-    } else {
-      // x(R) mod n == r  (ecdsa.go:450-465)
-      uint32_t rw[8];
-      load_be32(rw, rsig + sig * 32);
-      fe29 zz = fe29_sqr(acc.z);
-      bool match = fe29_eq(acc.x, fe29_mul(fe29_from_words(rw), zz));
-      if (u256_lt(rw, FE_P_MINUS_N)) {
-        uint32_t r2[8];
-        u256_add(r2, rw, SC_N);
-        match = match || fe29_eq(acc.x, fe29_mul(fe29_from_words(r2), zz));
-      }
-      verdict = match ? 1 : 0;
-    }
-  }
-  out[sig] = verdict;
-  if (stamp && threadIdx.x == 0) {
-    uint64_t* c = clk + (blockIdx.x == 0 ? 0 : 4);
-    c[0] = t0c;
-    c[1] = __builtin_readcyclecounter();
-    c[2] = t0w;
-    c[3] = __builtin_amdgcn_s_memrealtime();
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Affine epilogue of the BIP-340 and recovery paths.  Both need x/Z^2, y/Z^3 of the ladder's
-// result (the reference inverts per point: XBytes / IsYOdd, point_s11n.go:119-134); here one
-// thread takes FIN_M pending lanes (strided, so loads coalesce), multiplies their Z together,
-// inverts once and walks back (Montgomery's trick): 1 inversion per 16 results.
-//   MODE_SCHNORR: valid iff y even and x == r (verifySchnorrSignatureR, schnorr.go:451-478)
-//   MODE_RECOVER: writes the 65-byte key record (RecoverPublicKey, ecdsa.go:244-282)
-// Lanes that are not pending (already rejected, or queued for the complete kernel) ride along
-// with Z = 1.  Scratch: element 3 of the lane's fin region takes the prefix product.
-// ---------------------------------------------------------------------------------------
-
-template <int MODE>
-__global__ void __launch_bounds__(64)
-k_affine_finish(uint32_t n, uint32_t T, const uint8_t* __restrict__ rsig, uint32_t* __restrict__ fin,
-                uint8_t* __restrict__ out, size_t stride, uint8_t* __restrict__ out_pts) {
-  uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= T) return;
-  fe29 acc = fe29_one();
-#pragma unroll 1
-  for (int j = 0; j < FIN_M; ++j) {
-    size_t i = (size_t)t + (size_t)j * T;
-    if (i >= n) break;
-    if (out[i] == VERDICT_PENDING) acc = fe29_mul(acc, fq_load(fin, stride, i, 2));
-    fq_store(fin, stride, i, 3, acc);
-  }
-  fe29 inv = fe29_inv_gcd(acc);   // safegcd mod p (fe29_inv.h): a quarter of the Fermat chain's instructions, and this kernel is latency bound
-#pragma unroll 1
-  for (int j = FIN_M - 1; j >= 0; --j) {
-    size_t i = (size_t)t + (size_t)j * T;
-    if (i >= n || out[i] != VERDICT_PENDING) continue;
-    fe29 prev = j > 0 ? fq_load(fin, stride, i - T, 3) : fe29_one();
-    fe29 zi = fe29_mul(inv, prev);                     // 1 / Z_i
-    inv = fe29_mul(inv, fq_load(fin, stride, i, 2));
-    fe29 zi2 = fe29_sqr(zi);
-    fe29 x = fe29_mul(fq_load(fin, stride, i, 0), zi2);
-    fe29 y = fe29_normalize(fe29_mul(fe29_mul(fq_load(fin, stride, i, 1), zi2), zi));
-    if constexpr (MODE == MODE_RECOVER) {
-      uint32_t xw[8], yw[8];
-      fe29_to_words(xw, fe29_normalize(x));
-      fe29_to_words(yw, y);
-      uint8_t* rec = out_pts + i * 65;
-      rec[0] = 0x04;
-      store_be32_unaligned(rec + 1, xw);
-      store_be32_unaligned(rec + 33, yw);
-      out[i] = 1;
-    } else {
-      uint32_t rw[8];
-      load_be32(rw, rsig + i * 64);
-      out[i] = ((y.n[0] & 1u) == 0 && fe29_eq(x, fe29_from_words(rw))) ? 1 : 0;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// BIP-340: scalar preparation (no inversion needed: R = s*G + (-e)*P) and complete fallback
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_schnorr_prep(uint32_t n, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
-               const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-               uint32_t* __restrict__ prep, size_t stride) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  sc s, e;
-  bool ok = schnorr_parse(i, pk, sig, msgs, offs, msg_len, s, e);
-  sc u2 = sc_neg(e);                                   // schnorr.go:244
-  sc k1, k2;
-  bool neg1, neg2;
-  sc_split_glv_odd(u2, k1, neg1, k2, neg2);
-  uint32_t f = (ok ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) |
-               (k1.v[4] ? PF_K1_B128 : 0) | (k2.v[4] ? PF_K2_B128 : 0);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) prep[(size_t)w * stride + i] = s.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) prep[(size_t)(8 + w) * stride + i] = k1.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) prep[(size_t)(12 + w) * stride + i] = k2.v[w];
-  prep[(size_t)16 * stride + i] = f;
-}
-
-// SchnorrPublicKey.Verify (schnorr.go:221-253) with complete formulas
-S2K_DEV uint8_t schnorr_verify_complete(size_t idx, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
-                                        const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs,
-                                        uint32_t msg_len, gt_view gt, uint32_t* __restrict__ qt,
-                                        size_t stride) {
-  sc s, e;
-  bool ok = schnorr_parse(idx, pk, sig, msgs, offs, msg_len, s, e);
-  apt P;
-  load_be32(P.x.v, pk + idx * 32);
-  ok = ok && fe_is_canonical_raw(P.x.v);
-  fe y;
-  bool has = fe_sqrt(y, fe_curve_rhs(P.x));
-  ok = ok && has;
-  if (!ok) {
-    P.x = fe_from_limbs(FE_GX);
-    y = fe_from_limbs(FE_GY);
-  }
-  y = fe_normalize(y);
-  P.y = fe_normalize(fe_select((y.v[0] & 1u) != 0, y, fe_neg(y)));
-  pt R = pt_add_complete(pt_base_mul(gt, s.v), pt_mul_glv(sc_neg(e), P, qt, stride, idx));
-  apt a;
-  bool finite = pt_to_affine(a, R);
-  uint32_t r_le[8];
-  load_be32(r_le, sig + idx * 64);
-  return (ok && finite && (a.y.v[0] & 1u) == 0 && u256_eq(a.x.v, r_le)) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(256)
-k_schnorr_fallback(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, uint32_t all_n,
-                   const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msgs,
-                   const uint64_t* __restrict__ offs, uint32_t msg_len, uint8_t* __restrict__ out,
-                   gt_view gt, uint32_t* __restrict__ qt, size_t stride) {
-  // all_n != 0: diagnostic mode, every signature through the complete path
-  uint32_t count = all_n ? all_n : *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    size_t idx = all_n ? w : wl[w];
-    out[idx] = schnorr_verify_complete(idx, pk, sig, msgs, offs, msg_len, gt, qt, stride);
-  }
-}
-
-// RecoverPublicKey (ecdsa.go:244-282) for one item with complete formulas
-S2K_DEV uint8_t recover_complete(size_t idx, const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig,
-                                 const uint8_t* __restrict__ ssig, const uint8_t* __restrict__ recid,
-                                 uint8_t* __restrict__ out_pts, gt_view gt,
-                                 uint32_t* __restrict__ qt, size_t stride) {
-  sc r, s;
-  uint32_t e_raw[8];
-  load_be32(r.v, rsig + idx * 32);
-  load_be32(s.v, ssig + idx * 32);
-  load_be32(e_raw, dig + idx * 32);
-  uint32_t rid = recid[idx];
-  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s) && rid < 4 &&
-            (!(rid & 2u) || u256_lt(r.v, FE_P_MINUS_N));
-  apt R;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) R.x.v[i] = r.v[i];
-  if (ok && (rid & 2u)) u256_add(R.x.v, R.x.v, SC_N);
-  fe y;
-  bool has = fe_sqrt(y, fe_curve_rhs(R.x));
-  ok = ok && has;
-  if (!ok) {
-    R.x = fe_from_limbs(FE_GX);
-    y = fe_from_limbs(FE_GY);
-  }
-  y = fe_normalize(y);
-  R.y = fe_normalize(fe_select(((y.v[0] & 1u) != 0) != ((rid & 1u) != 0), y, fe_neg(y)));
-  sc e = sc_reduce_once(e_raw);
-  sc r_inv_m = sc_mont_inv(sc_to_mont(r));
-  sc u1 = sc_montmul(sc_neg(e), r_inv_m), u2 = sc_montmul(s, r_inv_m);
-  pt Q = pt_add_complete(pt_base_mul(gt, u1.v), pt_mul_glv(u2, R, qt, stride, idx));
-  uint8_t* rec = out_pts + idx * 65;
-  apt a;
-  bool finite = pt_to_affine(a, Q);              // identity: NewPublicKeyFromPoint fails (secec.go:206-209)
-  if (!(ok && finite)) {
-    for (int i = 0; i < 65; ++i) rec[i] = 0;
-    return 0;
-  }
-  rec[0] = 0x04;
-  store_be32_unaligned(rec + 1, a.x.v);
-  store_be32_unaligned(rec + 33, a.y.v);
-  return 1;
-}
-
-__global__ void __launch_bounds__(256)
-k_recover_fallback(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, uint32_t all_n,
-                   const uint8_t* __restrict__ dig, const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig,
-                   const uint8_t* __restrict__ recid, uint8_t* __restrict__ ok_out, uint8_t* __restrict__ out_pts,
-                   gt_view gt, uint32_t* __restrict__ qt, size_t stride) {
-  uint32_t count = all_n ? all_n : *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    size_t idx = all_n ? w : wl[w];
-    ok_out[idx] = recover_complete(idx, dig, rsig, ssig, recid, out_pts, gt, qt, stride);
-  }
-}
-
-// x/Z, y/Z of a projective 9x29 point (canonical words); false for the identity
-S2K_DEV bool p29_to_affine_words(uint32_t xw[8], uint32_t yw[8], const pt29& p) {
-  if (fe29_is_zero(p.z)) return false;
-  fe29 zi = fe29_inv_gcd(fe29_normalize_weak(p.z));
-  fe29_to_words(xw, fe29_normalize(fe29_mul(p.x, zi)));
-  fe29_to_words(yw, fe29_normalize(fe29_mul(p.y, zi)));
-  return true;
-}
-// lift_x on the 9x29 field: y with the wanted parity for a canonical x (words), or false
-S2K_DEV bool lift_x29(fe29& x, fe29& y, const uint32_t xw[8], bool want_odd) {
-  x = fe29_from_words(xw);
-  fe29 rhs = fe29_mul(fe29_sqr(x), x);
-  rhs.n[0] += 7;
-  if (!fe29_sqrt(y, rhs)) return false;
-  y = fe29_normalize(y);
-  y = fe29_select(((y.n[0] & 1u) != 0) != want_odd, y, fe29_normalize_weak(fe29_negate(y, 1)));
-  return true;
-}
-
-// The worklists of the BIP-340 and recovery paths, same verifier core (9x29 complete formulas) as
-// the ECDSA worklist; the reference-shaped 8x32 versions above stay for S2K_ECDSA_FORCE_COMPLETE.
-__global__ void __launch_bounds__(256)
-k_schnorr_worklist(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, const uint8_t* __restrict__ pk,
-                   const uint8_t* __restrict__ sig, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs,
-                   uint32_t msg_len, uint8_t* __restrict__ out, gt_view gt, uint32_t* __restrict__ qt,
-                   size_t stride) {
-  const uint32_t count = *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    const size_t idx = wl[w];
-    sc s, e;
-    bool ok = schnorr_parse(idx, pk, sig, msgs, offs, msg_len, s, e);
-    uint32_t xw[8];
-    load_be32(xw, pk + idx * 32);
-    ok = ok && fe_is_canonical_raw(xw);
-    if (!ok) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) xw[i] = FE_GX[i];
-    }
-    fe29 px, py;
-    if (!lift_x29(px, py, xw, false)) {   // not an x-coordinate of the curve (NewSchnorrPublicKey, schnorr.go:257-275)
-      ok = false;
-      px = fe29_from_words(FE_GX);
-      py = fe29_from_words(FE_GY);
-    }
-    pt29 R = dsm_complete29(s, sc_neg(e), px, py, gt, qt, stride, w);   // s*G - e*P (schnorr.go:244); table column = worklist position
-    uint32_t rx[8], ry[8], r_le[8];
-    bool finite = p29_to_affine_words(rx, ry, R);
-    load_be32(r_le, sig + idx * 64);
-    out[idx] = (ok && finite && (ry[0] & 1u) == 0 && u256_eq(rx, r_le)) ? 1 : 0;   // verifySchnorrSignatureR (:451-478)
-  }
-}
-
-__global__ void __launch_bounds__(256)
-k_recover_worklist(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, const uint8_t* __restrict__ dig,
-                   const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, const uint8_t* __restrict__ recid,
-                   uint8_t* __restrict__ ok_out, uint8_t* __restrict__ out_pts, gt_view gt,
-                   uint32_t* __restrict__ qt, size_t stride) {
-  const uint32_t count = *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    const size_t idx = wl[w];
-    sc r, s;
-    uint32_t e_raw[8], xw[8];
-    load_be32(r.v, rsig + idx * 32);
-    load_be32(s.v, ssig + idx * 32);
-    load_be32(e_raw, dig + idx * 32);
-    const uint32_t rid = recid[idx];
-    bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && sc_is_canonical_raw(s.v) && !sc_is_zero(s) && rid < 4 &&
-              (!(rid & 2u) || u256_lt(r.v, FE_P_MINUS_N));   // RecoverPoint (point_s11n.go:245-282)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xw[i] = r.v[i];
-    if (ok && (rid & 2u)) u256_add(xw, xw, SC_N);
-    if (!ok) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) xw[i] = FE_GX[i];
-      r = sc_zero();
-      r.v[0] = 1;
-    }
-    fe29 px, py;
-    if (!lift_x29(px, py, xw, (rid & 1u) != 0)) {
-      ok = false;
-      px = fe29_from_words(FE_GX);
-      py = fe29_from_words(FE_GY);
-    }
-    sc e = sc_reduce_once(e_raw);
-    sc26 r_inv_m = sc26_mont_inv(sc26_to_mont(sc26_from_sc(r)));
-    sc u1 = sc26_to_sc(sc26_mm(sc26_from_sc(sc_neg(e)), r_inv_m)), u2 = sc26_to_sc(sc26_mm(sc26_from_sc(s), r_inv_m));
-    pt29 Q = dsm_complete29(u1, u2, px, py, gt, qt, stride, idx);   // (-e/r) G + (s/r) R (ecdsa.go:244-282)
-    uint32_t qxw[8], qyw[8];
-    bool finite = p29_to_affine_words(qxw, qyw, Q);   // identity: NewPublicKeyFromPoint fails (secec.go:206-209)
-    uint8_t* rec = out_pts + idx * 65;
-    if (!(ok && finite)) {
-      for (int i = 0; i < 65; ++i) rec[i] = 0;
-      ok_out[idx] = 0;
-    } else {
-      rec[0] = 0x04;
-      store_be32_unaligned(rec + 1, qxw);
-      store_be32_unaligned(rec + 33, qyw);
-      ok_out[idx] = 1;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// u1*G + u2*P for arbitrary (u1, u2, P) through the verification ladder (S2K_IMPL_FAST of
-// s2k_double_scalar_mult_basepoint_batch_ex): the same table, signed-digit ladder and generator
-// additions as a verification, with the affine result written as a 65-byte record.
-//   k_hot_prep          65-byte records -> 64-byte affine points + prep planes (u1, odd GLV
-//                       halves of u2); identity / malformed records go straight to the worklist
-//   k_verify_fast<MODE_POINT>, k_affine_finish<MODE_RECOVER>
-//   k_point_fallback    worklist lanes by the complete path (pt_base_mul + pt_mul_glv)
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_hot_prep(uint32_t n, const uint8_t* __restrict__ u1, const uint8_t* __restrict__ u2, const uint8_t* __restrict__ pts65,
-           uint8_t* __restrict__ pub64, uint32_t* __restrict__ prep, size_t stride, uint32_t* __restrict__ wl_count,
-           uint32_t* __restrict__ wl, uint32_t* __restrict__ status) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t* rec = pts65 + i * 65;
-  apt a;
-  load_be32_unaligned(a.x.v, rec + 1);
-  load_be32_unaligned(a.y.v, rec + 33);
-  bool finite = rec[0] == 0x04 && fe_is_canonical_raw(a.x.v) && fe_is_canonical_raw(a.y.v) && apt_on_curve(a);
-  if (!finite && rec[0] != 0x00) atomicOr(status, 1u);   // not a Point the reference could have built
-  if (!finite) {                                          // identity: the complete kernel returns u1*G
-    a.x = fe_from_limbs(FE_GX);
-    a.y = fe_from_limbs(FE_GY);
-    uint32_t pos = atomicAdd(wl_count, 1u);
-    wl[pos] = (uint32_t)i;
-  }
-  store_be32(pub64 + i * 64, a.x.v);
-  store_be32(pub64 + i * 64 + 32, a.y.v);
-  uint32_t raw[8];
-  sc k1, k2;
-  bool neg1, neg2;
-  load_be32(raw, u1 + i * 32);        // zeros for a plain scalar multiplication
-  sc v1 = sc_reduce_once(raw);
-  load_be32(raw, u2 + i * 32);
-  sc_split_glv_odd(sc_reduce_once(raw), k1, neg1, k2, neg2);
-  uint32_t f = (finite ? PF_OK : 0) | (neg1 ? PF_NEG1 : 0) | (neg2 ? PF_NEG2 : 0) | (k1.v[4] ? PF_K1_B128 : 0) |
-               (k2.v[4] ? PF_K2_B128 : 0);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) prep[(size_t)w * stride + i] = v1.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) prep[(size_t)(8 + w) * stride + i] = k1.v[w];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) prep[(size_t)(12 + w) * stride + i] = k2.v[w];
-  prep[(size_t)16 * stride + i] = f;
-}
-
-// ALL: every item (S2K_IMPL_COMPLETE); otherwise the worklist.  u1 is always present (the host
-// passes zeros for a plain scalar multiplication): the conditional form of this kernel
-// (`if (u1)` around the generator part, `all_n ? w : wl[w]` for the index) was miscompiled by
-// hipcc 7.2 -- per-lane garbage for half of the inputs, reproduced standalone in tools/dbg/ --
-// so the kernel keeps to the shape of k_recover_fallback, which is not.
-template <bool ALL>
-__global__ void __launch_bounds__(256)
-k_point_fallback(const uint32_t* __restrict__ wl_count, const uint32_t* __restrict__ wl, uint32_t n,
-                 const uint8_t* __restrict__ u1, const uint8_t* __restrict__ u2, const uint8_t* __restrict__ pts65,
-                 uint8_t* __restrict__ out65, gt_view gt, uint32_t* __restrict__ qt, size_t stride,
-                 uint32_t* __restrict__ status) {
-  uint32_t count;
-  if constexpr (ALL) count = n; else count = *wl_count;
-  for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < count; w += gridDim.x * 256) {
-    size_t idx;
-    if constexpr (ALL) idx = w; else idx = wl[w];
-    const uint8_t* rec = pts65 + idx * 65;
-    apt a;
-    load_be32_unaligned(a.x.v, rec + 1);
-    load_be32_unaligned(a.y.v, rec + 33);
-    bool finite = rec[0] == 0x04 && fe_is_canonical_raw(a.x.v) && fe_is_canonical_raw(a.y.v) && apt_on_curve(a);
-    if (!finite && rec[0] != 0x00) atomicOr(status, 1u);
-    if (!finite) {   // keep the arithmetic on the curve; the term is masked below
-      a.x = fe_from_limbs(FE_GX);
-      a.y = fe_from_limbs(FE_GY);
-    }
-    uint32_t raw1[8], raw2[8];
-    load_be32(raw1, u1 + idx * 32);
-    load_be32(raw2, u2 + idx * 32);
-    sc v1 = sc_reduce_once(raw1), v2 = sc_reduce_once(raw2);
-    pt rq = pt_mul_glv(v2, a, qt, stride, idx);
-    rq = pt_select(!finite, rq, pt_identity());
-    pt res = pt_add_complete(pt_base_mul(gt, v1.v), rq);   // point_mul_glv.go:316
-    uint8_t* o = out65 + idx * 65;
-    apt r;
-    if (!pt_to_affine(r, res)) {
-      for (int j = 0; j < 65; ++j) o[j] = 0;
-    } else {
-      o[0] = 0x04;
-      store_be32_unaligned(o + 1, r.x.v);
-      store_be32_unaligned(o + 33, r.y.v);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
@@ -1434,124 +57,6 @@ __attribute__((visibility("hidden"))) void prof_mark(s2k_ctx* ctx, hipStream_t s
   if (!ctx->prof_on || ctx->prof_used + PROF_EV > ctx->prof_cap) return;
   (void)hipEventRecord(ctx->prof_ev[ctx->prof_used + slot], st);
   if (slot == PROF_EV - 1) ctx->prof_used += PROF_EV;
-}
-
-// One launcher per kernel: it enqueues on the stream it is given and does nothing else (error checks, events and profiling
-// marks stay with the flows).  `ctx` gives the call's generator table (gt_call) and the worklist kernels' grid.
-// launch_scalar_prep: signatures [first, first + count) on `lanes` lanes (the planes are linear in the signature index: a piece
-// is the same kernel on shifted pointers); launch_ladder: the only place that names an instantiation of k_verify_fast.
-// The launchers of the wave-per-signature and four-lanes-per-signature kernels: small_call.hip.
-__attribute__((visibility("hidden"))) void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t count, uint32_t lanes, const uint8_t* dig, const uint8_t* r,
-                               const uint8_t* s, const uint8_t* recid, uint32_t flags) {
-  k_scalar_prep<<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)count, lanes, dig + first * 32, r + first * 32, s + first * 32,
-                                                  recid ? recid + first : nullptr, flags, w.prep + first, w.pref + first, w.smont + first,
-                                                  w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_generator_part(const s2k_ctx* ctx, hipStream_t st, const lane_ws& w, uint32_t first, uint32_t end) {
-  k_generator_part<<<blocks_for(end - first), 256, 0, st>>>(first, end, w.prep, ctx->gt_call, w.gp, w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_ladder(const s2k_ctx* ctx, hipStream_t st, int mode, size_t n, uint32_t kvf, const uint8_t* pub, const uint8_t* rsig,
-                          const lane_ws& w, uint8_t* out, uint8_t* out_pts, uint64_t* clk, const key_groups& kg) {
-#define S2K_LADDER(M)                                                                                                              \
-  case M:                                                                                                                          \
-    k_verify_fast<M><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count, \
-                                                    w.wl, w.stride, out_pts, clk, kg);                                             \
-    break;
-  // The comb ladders run in a kernel of their own that needs no lead point (comb_ladder.hip: k_verify_comb, same arguments);
-  // S2K_COMB_LEAD=1 brings back k_verify_fast<MODE_.._COMB>, =0 the new kernel where the build's default is the old one -
-  // read at every call, as S2K_KEY_FINISH_COMB is, so that a process can switch for A/B runs and for the tests that compare
-  // the two.  profiles/r20_comb_nolead_ab.txt.
-  if (mode == MODE_ECDSA_COMB || mode == MODE_SCHNORR_COMB) {
-    const char* lead = getenv("S2K_COMB_LEAD");
-    if (!(lead && *lead ? atoi(lead) != 0 : S2K_COMB_LEAD_DEFAULT != 0)) {
-      if (mode == MODE_ECDSA_COMB)
-        k_verify_comb<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count,
-                                                            w.wl, w.stride, out_pts, clk, kg);
-      else
-        k_verify_comb<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n | kvf, pub, rsig, w.prep, w.qt, w.fin, ctx->gt_call, out, w.wl_count,
-                                                           w.wl, w.stride, out_pts, clk, kg);
-      return;
-    }
-  }
-  switch (mode) {
-    S2K_LADDER(MODE_ECDSA)
-    S2K_LADDER(MODE_SCHNORR)
-    S2K_LADDER(MODE_RECOVER)
-    S2K_LADDER(MODE_POINT)
-    S2K_LADDER(MODE_ECDSA_KEYED)
-    S2K_LADDER(MODE_ECDSA_LEFT)
-    S2K_LADDER(MODE_SCHNORR_KEYED)
-    S2K_LADDER(MODE_SCHNORR_LEFT)
-    S2K_LADDER(MODE_ECDSA_KEYSET)
-    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT)
-    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT5)
-    S2K_LADDER(MODE_ECDSA_KEYSET_JOINT6)
-    S2K_LADDER(MODE_SCHNORR_KEYSET)
-    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT)
-    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT5)
-    S2K_LADDER(MODE_SCHNORR_KEYSET_JOINT6)
-    S2K_LADDER(MODE_ECDSA_COMB)
-    S2K_LADDER(MODE_SCHNORR_COMB)
-    default:   // (a launch of nothing would leave the verdicts as they were and report success)
-      fprintf(stderr, "secp256k1_voi_amd: launch_ladder: no ladder of mode %d\n", mode);
-      abort();
-  }
-#undef S2K_LADDER
-}
-__attribute__((visibility("hidden"))) void launch_affine_finish(hipStream_t st, int mode, size_t n, uint32_t T, const uint8_t* rsig, const lane_ws& w, uint8_t* out,
-                                 uint8_t* out_pts) {
-  if (mode == MODE_RECOVER)
-    k_affine_finish<MODE_RECOVER><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, rsig, w.fin, out, w.stride, out_pts);
-  else
-    k_affine_finish<MODE_SCHNORR><<<(T + 63) / 64, 64, 0, st>>>((uint32_t)n, T, rsig, w.fin, out, w.stride, out_pts);
-}
-static void launch_ecdsa_verify(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig,
-                                const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
-  k_ecdsa_verify<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pub, dig, r, s, flags, out, ctx->gt_call, w.qt, w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_verify_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig,
-                                   const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
-  k_verify_fallback<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, pub, dig, r, s, flags, out, ctx->gt_call, w.qt, w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_verify_fallback_keyset(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* keys, const uint32_t* kidx,
-                                          const uint8_t* dig, const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out) {
-  k_verify_fallback_keyset<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, keys, kidx, dig, r, s, flags, out, ctx->gt_call, w.qt,
-                                                                    w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_schnorr_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs,
-                                const uint64_t* offs, uint32_t msg_len) {
-  k_schnorr_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, pk, sig, msgs, offs, msg_len, w.prep, w.stride);
-}
-static void launch_schnorr_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
-                                    const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out) {
-  k_schnorr_fallback<<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, pk, sig, msgs, offs, msg_len, out, ctx->gt_call, w.qt,
-                                                    w.stride);
-}
-__attribute__((visibility("hidden"))) void launch_schnorr_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
-                                    const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out) {
-  k_schnorr_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, pk, sig, msgs, offs, msg_len, out, ctx->gt_call, w.qt,
-                                                              w.stride);
-}
-static void launch_recover_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
-                                    const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
-  k_recover_fallback<<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, dig, r, s, recid, ok, pub65, ctx->gt_call, w.qt, w.stride);
-}
-static void launch_recover_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
-                                    const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65) {
-  k_recover_worklist<<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, dig, r, s, recid, ok, pub65, ctx->gt_call, w.qt, w.stride);
-}
-static void launch_hot_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2, const uint8_t* pts65, uint8_t* pub64,
-                            uint32_t* status) {
-  k_hot_prep<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, u1, u2, pts65, pub64, w.prep, w.stride, w.wl_count, w.wl, status);
-}
-static void launch_point_fallback(const s2k_ctx* ctx, hipStream_t st, bool all, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2,
-                                  const uint8_t* pts65, uint8_t* out65, uint32_t* status) {
-  if (all)
-    k_point_fallback<true><<<blocks_for(n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, u1, u2, pts65, out65, ctx->gt_call, w.qt, w.stride,
-                                                          status);
-  else
-    k_point_fallback<false><<<fallback_blocks(ctx, n), 256, 0, st>>>(w.wl_count, w.wl, (uint32_t)n, u1, u2, pts65, out65, ctx->gt_call, w.qt,
-                                                                     w.stride, status);
 }
 
 // Front end of the grouped flows (ECDSA and BIP-340 verification): everything up to the ladders.

@@ -43,7 +43,7 @@ inline constexpr size_t gt_bytes_of(int bits) { return gt_entries_of(bits) * 64;
 
 // what a kernel gets: the table and its geometry, by value.  A CALL uses one view for all its launches (s2k_ctx::gt_call,
 // loaded by ctx_enter): the ladder kernels leave lanes for the worklist kernel whose tags name an entry of the table they ran
-// on (WL_DOUBLE_LAST, engine.hip), so the background build may publish the wide table between two calls, never inside one.
+// on (WL_DOUBLE_LAST, verify_fast.h and worklist.hip), so the background build may publish the wide table between two calls, never inside one.
 struct gt_view {
   const uint32_t* p;
   uint32_t bits, windows;
@@ -249,7 +249,7 @@ struct s2k_ctx {
 };
 
 // Most items one call takes: the worklist entries of the ladder kernels carry a 2-bit tag above a 30-bit index (WL_TAG_LIMIT,
-// engine.hip), so an index with bit 30 set must never reach them.
+// engine_internal.h), so an index with bit 30 set must never reach them.
 constexpr size_t S2K_MAX_BATCH = (size_t)1 << 30;
 
 #include <atomic>
@@ -469,7 +469,7 @@ inline int ctx_stage(s2k_ctx* ctx, const size_t* sizes, int count, uint8_t** ptr
   return S2K_OK;
 }
 
-// ---- repeated-key path (keyed.hip; the ladder itself is k_verify_fast<MODE_ECDSA_KEYED>, engine.hip) ----
+// ---- repeated-key path (keyed.hip; the ladder itself is k_verify_fast<MODE_ECDSA_KEYED>, verify_fast.h) ----
 // A key that signs several signatures of a batch gets ONE table, built once: for each of the eight
 // 16-bit chunks c of a 128-bit half scalar the odd multiples {1,3,..,15} * 2^(16c) Q, and 2^116 Q for
 // the recoding's leading digit, all affine (one shared inversion per key) with their beta*x column.
@@ -525,7 +525,7 @@ struct kjw_geom {
 };
 static_assert(KT_SLOTS == 72 && KT_W_SLOT == 9 && kt_geom<32>::SLOTS == 288, "table geometry");
 // The per-call tables of the ECDSA and BIP-340 flows, and the tables of a comb key set, as a signed Lim-Lee COMB (keyed.hip:
-// k_key_chain<XONLY, 7> / k_key_finish_comb; the ladder is k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>, engine.hip).  An odd half scalar k < 2^129 is k = 2^L + sum_{i<L} b_i 2^i with
+// k_key_chain<XONLY, 7> / k_key_finish_comb; the ladder is k_verify_fast<MODE_ECDSA_COMB> / <MODE_SCHNORR_COMB>, verify_fast.h).  An odd half scalar k < 2^129 is k = 2^L + sum_{i<L} b_i 2^i with
 // b_i = 2 a_i - 1, a = (k - 1) / 2, for any L >= 128.  With L = TEETH * SPACING = 133 and i = 19 t + j the bits of column j
 // select +-E[idx], E[idx] = B_6 + sum_{t<6} (2 idx_t - 1) B_t, B_t = 2^(19 t) Q (the sign is the top tooth's; a negative top
 // tooth complements idx): 19 additions and 18 doublings per half, the doublings shared by the two halves - 38 additions and
@@ -674,7 +674,7 @@ bool s2k_internal_bykey_delegates(const s2k_ctx* ctx, size_t n, uint32_t flags);
 int s2k_internal_bykey_device(s2k_ctx* ctx, const s2k_keyset* ks, size_t n, const void* d_pub_xy, const void* d_dig, const void* d_r,
                               const void* d_s, uint32_t flags, void* d_valid, hipStream_t st, const uint32_t* d_found);
 
-// ---- engine.hip and small_call.hip, for each other and for the key-set flows (keyset.hip): ladder modes, the lane workspace,
+// ---- engine.hip, lane_kernels.hip, fallback.hip, worklist.hip and small_call.hip, for each other and for the key-set flows (keyset.hip): ladder modes, the lane workspace,
 // stage-timing marks and launchers ----
 enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_ECDSA_KEYED = 4, MODE_ECDSA_LEFT = 5,
        MODE_SCHNORR_KEYED = 6, MODE_SCHNORR_LEFT = 7, MODE_ECDSA_KEYSET = 8, MODE_ECDSA_KEYSET_JOINT = 9,
@@ -687,7 +687,7 @@ enum { MODE_ECDSA = 0, MODE_SCHNORR = 1, MODE_RECOVER = 2, MODE_POINT = 3, MODE_
        // MODE_SCHNORR_KEYED over the comb table (the lifted x-only keys of a call, or the X || Y keys of a comb key set)
        MODE_SCHNORR_COMB = 17 };
 constexpr uint32_t KVF_FORCE_WORKLIST = 0x80000000u;   // top bit of k_verify_fast's first argument (batches are below 2^31)
-// what the ladder kernels of engine.hip and comb_ladder.hip share:
+// what the ladder kernels of verify_fast.h and comb_ladder.hip share:
 // the flag word of a signature's prepared scalars (k_scalar_prep, plane 16)
 enum { PF_OK = 1, PF_NEG1 = 2, PF_NEG2 = 4, PF_K1_B128 = 8, PF_K2_B128 = 16 };   // bit 128 of the odd half-scalars
 // A worklist entry of the ECDSA flows is the signature's index, plus (batches below 2^30) a tag in the top bits:
@@ -700,8 +700,20 @@ constexpr uint32_t WL_TAG_LIMIT = 1u << 30, WL_INDEX_MASK = WL_TAG_LIMIT - 1u, W
 #ifndef S2K_COMB_WAVES
 #define S2K_COMB_WAVES 3
 #endif
+// The bounds of the other ladders of k_verify_fast (measured: verify_fast.h) and the signatures that share an inversion in
+// k_scalar_prep (measured: lane_kernels.hip).  Here because s2k_build_config (engine.hip) names them too.
+#ifndef S2K_FAST_WAVES
+#define S2K_FAST_WAVES 3
+#endif
+#ifndef S2K_JOINT_WAVES
+#define S2K_JOINT_WAVES 3
+#endif
+#ifndef S2K_PREP_M
+#define S2K_PREP_M 6
+#endif
+constexpr int PREP_WORDS = 17;                         // planes of a signature's prepared scalars (k_scalar_prep: u1, |k1|, |k2|, flags)
 // Which kernel runs the comb ladders when S2K_COMB_LEAD is not set: 0 = k_verify_comb (comb_ladder.hip: no lead point, the
-// first round is one pair sum), 1 = k_verify_fast<MODE_.._COMB> (engine.hip).  s2k_build_config() names it.
+// first round is one pair sum), 1 = k_verify_fast<MODE_.._COMB> (verify_fast.h).  s2k_build_config() names it.
 #ifndef S2K_COMB_LEAD_DEFAULT
 #define S2K_COMB_LEAD_DEFAULT 0
 #endif
@@ -721,6 +733,13 @@ void launch_scalar_prep(hipStream_t st, const lane_ws& w, size_t first, size_t c
 void launch_generator_part(const s2k_ctx* ctx, hipStream_t st, const lane_ws& w, uint32_t first, uint32_t end);
 void launch_ladder(const s2k_ctx* ctx, hipStream_t st, int mode, size_t n, uint32_t kvf, const uint8_t* pub, const uint8_t* rsig, const lane_ws& w,
                    uint8_t* out, uint8_t* out_pts, uint64_t* clk, const key_groups& kg);
+// verify_fast.h: the ladder kernel, one instantiation per MODE_*, each in one of the ladder_*.hip units; launched by
+// launch_ladder alone
+template <int MODE>
+__global__ void k_verify_fast(uint32_t n_and_flags, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ rsig,
+                              const uint32_t* __restrict__ prep, uint32_t* __restrict__ qt, uint32_t* __restrict__ fin, gt_view gt,
+                              uint8_t* __restrict__ out, uint32_t* __restrict__ wl_count, uint32_t* __restrict__ wl, size_t stride,
+                              uint8_t* __restrict__ out_pts, uint64_t* __restrict__ clk, key_groups kg);
 // comb_ladder.hip: the comb ladders without the lead point (the arguments of k_verify_fast); instantiated there for
 // false (ECDSA) and true (BIP-340), launched by launch_ladder alone
 template <bool SCHNORR>
@@ -737,6 +756,20 @@ void launch_schnorr_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8
                          uint32_t msg_len);
 void launch_schnorr_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
                              const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out);
+void launch_hot_prep(hipStream_t st, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2, const uint8_t* pts65, uint8_t* pub64,
+                     uint32_t* status);
+// fallback.hip (with the three launch_*_fallback* / launch_schnorr_worklist above): the kernels that take every item through the
+// complete formulas, and the recovery and point worklists
+void launch_ecdsa_verify(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pub, const uint8_t* dig,
+                         const uint8_t* r, const uint8_t* s, uint32_t flags, uint8_t* out);
+void launch_schnorr_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* pk, const uint8_t* sig,
+                             const uint8_t* msgs, const uint64_t* offs, uint32_t msg_len, uint8_t* out);
+void launch_recover_fallback(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
+                             const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65);
+void launch_recover_worklist(const s2k_ctx* ctx, hipStream_t st, size_t n, const lane_ws& w, const uint8_t* dig, const uint8_t* r,
+                             const uint8_t* s, const uint8_t* recid, uint8_t* ok, uint8_t* pub65);
+void launch_point_fallback(const s2k_ctx* ctx, hipStream_t st, bool all, size_t n, const lane_ws& w, const uint8_t* u1, const uint8_t* u2,
+                           const uint8_t* pts65, uint8_t* out65, uint32_t* status);
 // small_call.hip: the wave-per-signature kernels (launch_schnorr_row: prep == nullptr is k_schnorr_row<true>, whose fifth wave
 // prepares; else the planes of launch_schnorr_prep) and the four-lanes-per-signature kernels, behind the preparation kernels
 void launch_verify_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,

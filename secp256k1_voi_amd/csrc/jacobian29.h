@@ -75,7 +75,7 @@ S2K_DEV jpt29 jpt29_add(const jpt29& p, const jpt29& q) {
   return r;
 }
 
-// The comb ladder's column (engine.hip, k_verify_fast<.._COMB>): two table entries E1 = (x1, y1) and E2 = (x2, y2), affine
+// The comb ladder's column (verify_fast.h, k_verify_fast<.._COMB>): two table entries E1 = (x1, y1) and E2 = (x2, y2), affine
 // over one Z, are added to each other first and their sum T to the accumulator, 20 products in 18 reductions against
 // the 22 in 20 of two mixed additions.  T comes out over Z h, h = x2 - x1, and its h^2 and h^3 fall out of the co-Z
 // addition (keyed.hip: coz29_conj, the sum half), which a Jacobian + Jacobian addition spends 1 S + 1 M on.

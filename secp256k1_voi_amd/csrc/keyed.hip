@@ -5,7 +5,7 @@
 // doublings interleaved with the table additions.  When a batch holds several signatures of one
 // key, the doublings can be done once per KEY instead: with 2^(16c) Q (c = 0..7) at hand, the 32
 // signed 4-bit digits of a half scalar are consumed four rounds of eight, 12 doublings in all.
-// This file does what has to happen before that ladder (k_verify_fast<MODE_ECDSA_KEYED>, engine.hip):
+// This file does what has to happen before that ladder (k_verify_fast<MODE_ECDSA_KEYED>, verify_fast.h):
 //
 //   k_key_insert   one lane per signature: its key goes into an open-addressing hash table whose
 //                  slots hold the index of the first signature seen with that key; a hit compares
@@ -422,7 +422,7 @@ k_key_chain(const uint32_t* __restrict__ counters, uint32_t max_tables, const ui
     ke_store(e, TB_Y, cur.y);
     ke_store(e, TB_BX, cur.z);
   }
-  // The ladder starts from +-L +- phi(L), L = 2^116 Q (the recoding's leading digit, engine.hip): instead of L and one
+  // The ladder starts from +-L +- phi(L), L = 2^116 Q (the recoding's leading digit, verify_fast.h): instead of L and one
   // addition per SIGNATURE, the table holds L + phi(L) and L - phi(L) (the other two combinations are their negatives).
   // L = (X, Y, Z) and phi(L) = (beta X, Y, Z) share their Z, so both sums come from one co-Z addition (Meloni):
   // with A = (X2 - X1)^2, B = X1 A, C = X2 A:  X3 = (Y2 - Y1)^2 - B - C,  Y3 = (Y2 - Y1)(B - X3) - Y1 (C - B),

@@ -1,5 +1,5 @@
 // lane_tables.h — storage of the fast path's per-lane scratch elements and point tables (shared by
-// engine.hip and keyed.hip).
+// verify_fast.h, lane_kernels.hip, comb_ladder.hip and keyed.hip).
 #pragma once
 #include "fe29.h"
 

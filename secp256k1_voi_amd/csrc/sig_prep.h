@@ -1,6 +1,6 @@
 // sig_prep.h — one signature's scalars prepared by ONE lane: the ECDSA / recovery scalars with their own inversion
 // (scalar_prep_one: the preparation waves of small_call.hip's wave-per-signature kernels) and the BIP-340 parse with its challenge
-// hash (schnorr_parse*: those waves again, and k_schnorr_prep and the complete-formula BIP-340 kernels of engine.hip).
+// hash (schnorr_parse*: those waves again, and k_schnorr_prep and the complete-formula BIP-340 kernels of fallback.hip and worklist.hip).
 #pragma once
 #include "engine_internal.h"
 #include "complete_path.h"
@@ -8,7 +8,7 @@
 #include "sc26.h"
 #include "sha256.h"
 
-// What k_scalar_prep (engine.hip) does for the signatures of a lane,
+// What k_scalar_prep (lane_kernels.hip) does for the signatures of a lane,
 // for ONE signature, its own inversion, the result in 17 words (u1 | k1 | k2 | flags: the planes' layout): the
 // preparation wave of the wave-per-signature kernels (k_verify_row, k_recover_row).  FLAT: the scalar products and the
 // inversion are expanded in place (sc26.h), which leaves the kernel without a private segment.

@@ -1034,7 +1034,7 @@ k_recover_row(uint32_t n, const uint8_t* __restrict__ dig, const uint8_t* __rest
   }
 }
 
-// The launchers (engine_internal.h; the rule they follow: engine.hip).  launch_schnorr_row is the only place that names an
+// The launchers (engine_internal.h; the rule they follow: lane_kernels.hip).  launch_schnorr_row is the only place that names an
 // instantiation of k_schnorr_row: prep == nullptr is k_schnorr_row<true>, whose fifth wave prepares.
 __attribute__((visibility("hidden"))) void launch_verify_row(const s2k_ctx* ctx, hipStream_t st, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
                               uint32_t flags, uint8_t* out) {

@@ -1,6 +1,6 @@
 """The corpus of tests/accept_corpus.py, checked on the CPU: what tests/test_gpu_accept_rule.py expects of every kernel is what
 the C oracle says, every near miss really keeps the parent's R (so only the final comparison can reject it), every claimed bit
-position occurs - and a Python model of the accept rule (engine.hip: X == r Z^k, then X == (r + n) Z^k under r < p - n) with one
+position occurs - and a Python model of the accept rule (verify_fast.h: X == r Z^k, then X == (r + n) Z^k under r < p - n) with one
 limb masked, one limb left out of the comparison, or the guard dropped changes the verdict of named items."""
 import collections
 import hashlib

@@ -1,5 +1,5 @@
 """Model of the comb tables of the ECDSA flow and of the ladder over them (engine_internal.h: kc_geom; keyed.hip:
-coz29_conj, kc_sets, k_key_finish_comb; engine.hip: k_verify_fast<MODE_ECDSA_COMB>), without a GPU:
+coz29_conj, kc_sets, k_key_finish_comb; verify_fast.h: k_verify_fast<MODE_ECDSA_COMB>), without a GPU:
 
   * the recoding: an odd half scalar k < 2^129 as 2^133 + sum b_i 2^i, b_i = 2 a_i - 1, a = k >> 1, read column by column
     through seven teeth 19 bits apart - the digits exactly as the kernel forms them, their sum, the operation counts;
@@ -512,7 +512,7 @@ def test_mutation_is_rejected(mu):
 
 
 def test_the_ladder_runs_19_rounds_of_two_additions():
-    body = fm.body_of("engine.hip", "k_verify_fast")
+    body = fm.body_of("verify_fast.h", "k_verify_fast")
     comb = body[body.index("if constexpr (COMB) {"):body.index("} else if constexpr (KEYED) {")]
     assert comb.count("jpt29_add_affine(") == 1 and comb.count("jpt29_double(") == 1
     assert "for (int j = G::SPACING - 1;; --j)" in comb and "if (j == 0) break;" in comb

@@ -1,4 +1,4 @@
-"""The comb ladder without the lead point (comb_ladder.hip: k_verify_comb) against the ladder with it (engine.hip:
+"""The comb ladder without the lead point (comb_ladder.hip: k_verify_comb) against the ladder with it (verify_fast.h:
 k_verify_fast<MODE_ECDSA_COMB>), both in the BUILT library (tools/isa_count.py on the shipped code object).  No GPU needed.
 
 The first round of the new kernel is the pair sum of its column alone: the lead lookup, jpt29_rescale (2 M),

@@ -271,10 +271,11 @@ def test_products_of_the_ladder():
 
 
 def test_routing_in_launch_ladder():
-    body = fm.body_of("engine.hip", "launch_ladder")
+    body = fm.body_of("lane_kernels.hip", "launch_ladder")
     assert body.count("k_verify_comb<false><<<") == 1 and body.count("k_verify_comb<true><<<") == 1
     assert 'getenv("S2K_COMB_LEAD")' in body and "static" not in body[:body.index("switch (mode)")]      # read at every call
     assert "S2K_LADDER(MODE_ECDSA_COMB)" in body and "S2K_LADDER(MODE_SCHNORR_COMB)" in body             # the old instantiations stay
     # the only launches of the new kernel in the library
-    for f in ("engine.hip", "keyed.hip", "keyset.hip", "comb_ladder.hip"):
-        assert fm.source(f).count("k_verify_comb<") == (2 if f == "engine.hip" else 2 if f == "comb_ladder.hip" else 0), f
+    for f in ("engine.hip", "lane_kernels.hip", "fallback.hip", "worklist.hip", "verify_fast.h", "ladder_ecdsa.hip", "ladder_schnorr.hip",
+              "keyed.hip", "keyset.hip", "comb_ladder.hip"):
+        assert fm.source(f).count("k_verify_comb<") == (2 if f == "lane_kernels.hip" else 2 if f == "comb_ladder.hip" else 0), f

@@ -1,4 +1,4 @@
-"""Model of the comb ladder's column (jacobian29.h: coz29_pair_sum, jpt29_rescale; engine.hip: the COMB block of
+"""Model of the comb ladder's column (jacobian29.h: coz29_pair_sum, jpt29_rescale; verify_fast.h: the COMB block of
 k_verify_fast), without a GPU.  A column adds the round's two table entries to each other first - E1 of the first half
 scalar, phi(E2) of the second, affine over one Z - and their sum to the accumulator: 15 M + 5 S instead of the 16 M + 6 S
 of two mixed additions.
@@ -292,7 +292,7 @@ def test_column_on_extremal_limbs():
 
 # ==== drift guard and mutations ============================================================================================
 def comb_block_text():
-    body = fm.body_of("engine.hip", "k_verify_fast")
+    body = fm.body_of("verify_fast.h", "k_verify_fast")
     return body[body.index("if constexpr (COMB) {"):body.index("} else if constexpr (KEYED) {")]
 
 

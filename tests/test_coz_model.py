@@ -157,7 +157,7 @@ def test_drift_guard(g, tracked):
 
 
 def test_generator_part_uses_the_first_addition_once():
-    body = fm.body_of("engine.hip", "k_generator_part")
+    body = fm.body_of("lane_kernels.hip", "k_generator_part")
     assert body.count("xyzz29_add_affine_first(") == 1 and body.count("xyzz29_add_affine(") == 1
 
 

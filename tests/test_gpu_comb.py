@@ -1,4 +1,4 @@
-"""The comb tables and their ladder on the device (keyed.hip: k_key_chain on the comb's geometry with kc_sets, k_key_finish_comb; engine.hip:
+"""The comb tables and their ladder on the device (keyed.hip: k_key_chain on the comb's geometry with kc_sets, k_key_finish_comb; verify_fast.h:
 k_verify_fast<MODE_ECDSA_COMB>): what an ECDSA verification call builds for its repeated keys by default.
 
 Every case is one call of 4096 signatures with the grouping set by name (KEYS_ALWAYS / KEYS_AUTO: calls this small

@@ -1,4 +1,4 @@
-"""The comb ladder's column on the device (jacobian29.h: coz29_pair_sum, jpt29_rescale; engine.hip: the COMB block of
+"""The comb ladder's column on the device (jacobian29.h: coz29_pair_sum, jpt29_rescale; verify_fast.h: the COMB block of
 k_verify_fast): a round's two table entries added to each other first, their sum to the accumulator.
 
   (a) S2K_HP_JADD_PAIR (ops.hip: k_pair_op, the block's four lines) at exactly the lazy budgets of the interval model

@@ -1,4 +1,4 @@
-"""Every ladder launch_ladder (engine.hip) can choose, at the smallest shape that can still go wrong: 257 signatures - one
+"""Every ladder launch_ladder (lane_kernels.hip) can choose, at the smallest shape that can still go wrong: 257 signatures - one
 full workgroup of k_verify_fast and one lane -, 250 of them under three keys (one stored with odd Y) and 7 under keys that
 occur once, every fourth one damaged.  The wave- and quad-per-signature ladders are switched off, so each call runs the lane
 kernels: the plain modes (ECDSA, BIP-340, recovery, the point entry), the keyed / comb / "left" modes of the grouped flows

@@ -1,7 +1,7 @@
 """Round 6 on the GPU.  One generator-table view per call: a call whose ladder kernel ran on one table
 and whose worklist kernel is launched after the background build has published another must give the verdicts of the
 reference's pure function (secec/ecdsa.go:436-465) — the lanes that show a difference are the ones the ladder leaves for
-the worklist kernel with the tag "twice the last generator-table entry" (engine.hip: WL_DOUBLE_LAST)."""
+the worklist kernel with the tag "twice the last generator-table entry" (verify_fast.h, worklist.hip: WL_DOUBLE_LAST)."""
 import random
 
 import numpy as np

@@ -1,5 +1,5 @@
 """BIP-340 per-signature verification on comb tables (keyed.hip: k_key_chain<true, KC_TEETH> - x-only keys validated and lifted,
-then the comb's chain -, k_key_finish_comb_once; engine.hip: k_verify_fast<MODE_SCHNORR_COMB>): what s2k_schnorr_verify_batch
+then the comb's chain -, k_key_finish_comb_once; verify_fast.h: k_verify_fast<MODE_SCHNORR_COMB>): what s2k_schnorr_verify_batch
 builds for its repeated keys by default.
 
 Every case is one call of 4096 signatures (the padded official vectors: 266) with the grouping set by name (KEYS_ALWAYS /

@@ -1,4 +1,4 @@
-"""Integer model of the recoding behind the per-key tables (engine.hip: ds4_init_chunked and the keyed branch
+"""Integer model of the recoding behind the per-key tables (verify_fast.h: ds4_init_chunked and the keyed branch
 of k_verify_fast; keyed.hip: table contents).  No GPU: it pins down the identities the device code relies on.
 
   * an odd k < 2^129 is  16^32 + sum_{i<32} d_i 16^i  with d_i = 2 nib_i - 15, nib_i = bits 4i+1 .. 4i+4 of k

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction mix of k_verify_fast<ECDSA>, weighted by loop trip counts.
 
-    hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only secp256k1_voi_amd/csrc/engine.hip -o /tmp/engine.s
-    python tools/isa_mix.py /tmp/engine.s
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only secp256k1_voi_amd/csrc/ladder_ecdsa.hip -o /tmp/ladder_ecdsa.s
+    python tools/isa_mix.py /tmp/ladder_ecdsa.s
 
 Regions are cut at the kernel's loop headers (the compiler's "Loop Header" comments); trip counts are
 those of the source: table forward loop 7, table backward loop 7, ladder 32 x (4 doublings, 2 additions),

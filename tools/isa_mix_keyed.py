@@ -4,8 +4,8 @@ of the source: prologue once (lead point and its XYZZ addition), between rounds 
 XYZZ -> Jacobian, four doublings (the doubling loop 3 x 4 = 12 times) and back, the table-addition loop 4 rounds x 8 chunks x
 2 halves = 64 times, its chunk-loop tail 32 times, the epilogue (XYZZ -> Jacobian, generator part, verdict) once.
 
-    hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only secp256k1_voi_amd/csrc/engine.hip -o /tmp/engine.s
-    python tools/isa_mix_keyed.py /tmp/engine.s
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -S --cuda-device-only secp256k1_voi_amd/csrc/ladder_ecdsa.hip -o /tmp/ladder_ecdsa.s
+    python tools/isa_mix_keyed.py /tmp/ladder_ecdsa.s
 
 The regions are found from the compiler's loop comments: the depth-1 inner loop laid out before the main loop header is
 the doubling loop (the block before it and the block after it are the two conversions), the depth-3 loop the addition.
