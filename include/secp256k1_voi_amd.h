@@ -1281,21 +1281,25 @@ int s2k_fp_op_batch_ex8(s2k_ctx *ctx, uint32_t impl, int op, uint32_t lazy, uint
 int s2k_fn_split_glv_batch_ex(s2k_ctx *ctx, uint32_t impl, size_t n, const uint8_t *k, uint8_t *k1, uint8_t *k2,
                               uint8_t *signs);
 
-/* ---- SHA-2 message digests on the device, and ECDSA verification from messages -------- */
+/* ---- SHA-2 and Keccak message digests on the device, and ECDSA verification from messages -------- */
 /* The reference's ECDSA callers start from a message and a hash: h := sha256.Sum256(m); pk.Verify(h[:], sig, opts).  The
  * calls above take h; these take m and hash on the device (one lane per message), so no per-item work is left on the host.
  *   S2K_HASH_SHA256   SHA-256(m)
  *   S2K_HASH_SHA256D  SHA-256(SHA-256(m)), Bitcoin's message hash: one more compression
  *   S2K_HASH_SHA512   SHA-512(m); a verification call uses its leftmost 32 bytes, which is what the reference's hashToScalar
  *                     does with a hash longer than the order (secec/ecdsa.go:477-486)
+ *   S2K_HASH_KECCAK256  Keccak-256(m) as submitted (padding 0x01 .. 0x80): Ethereum's message and address hash
+ *   S2K_HASH_SHA3_256   SHA3-256(m) of FIPS 202: the same permutation and rate (136 bytes), domain byte 0x06
+ * The two Keccak ids run in a kernel of their own (k_digest_keccak); out_len is 32 for them.
  * Messages follow the convention of s2k_schnorr_verify_batch: n strings of msg_len bytes each (msg_offsets == NULL), or one
  * blob with msg_offsets[n + 1] byte offsets (any lengths, zero included; msg_offsets[0] need not be 0).  Every message is
  * shorter than 2^31 bytes.
  *
  * s2k_digest_batch: out[i * out_len .. + out_len) = the digest of message i.  out_len is 32 - the whole SHA-256 / SHA-256d
  * digest, or the leftmost 32 bytes of SHA-512 - or 64 with S2K_HASH_SHA512, the whole digest.  This is the digest the
- * verification calls take: the encoded, recovery, whole-batch and group calls have no messages form of their own and are
- * reached as s2k_digest_batch_device followed by the existing call on the same stream, without a host round trip.
+ * verification calls take: the encoded, whole-batch and group calls have no messages form of their own and are
+ * reached as s2k_digest_batch_device followed by the existing call on the same stream, without a host round trip (recovery
+ * has one where it returns addresses: s2k_ecdsa_recover_address_messages_batch below).
  * _device: device pointers, chained on the caller's stream like the other *_device forms; does not synchronise.
  *
  * s2k_ecdsa_verify_messages_batch[_device/_submit], ..._keyset[_device], ..._keyset_bykey[_device]: the arguments of
@@ -1314,9 +1318,9 @@ int s2k_fn_split_glv_batch_ex(s2k_ctx *ctx, uint32_t impl, size_t n, const uint8
  * not: a decreasing offset makes the device read outside the blob.
  *
  * Cost: lanes of a wavefront with different block counts run to the longest of them, so a batch with one very long message
- * is slow, not wrong; there is no second kernel for it.  Out of scope here: messages forms of the encoded, recovery,
- * whole-batch and group calls (see above), other hash functions, tagged hashes (BIP-340's challenge is computed by the
- * Schnorr calls), and a cooperative kernel for single huge messages.
+ * is slow, not wrong; there is no second kernel for it.  Out of scope here: messages forms of the encoded,
+ * whole-batch and group calls (see above), SHA3-512 and SHAKE, Keccak for the BIP-340 or whole-batch calls, tagged hashes
+ * (BIP-340's challenge is computed by the Schnorr calls), and a cooperative kernel for single huge messages.
  * s2k_ctx_device_bytes does not count the 32 n bytes of the digest buffer.
  *
  * Test hooks.  s2k_debug_digest_caps: out[0] = the bytes of LDS a workgroup stages the stretch of its 256 messages in; a
@@ -1326,6 +1330,8 @@ int s2k_fn_split_glv_batch_ex(s2k_ctx *ctx, uint32_t impl, size_t n, const uint8
 #define S2K_HASH_SHA256 0
 #define S2K_HASH_SHA256D 1
 #define S2K_HASH_SHA512 2
+#define S2K_HASH_KECCAK256 3   /* Keccak-256, original padding (0x01 .. 0x80), rate 136 */
+#define S2K_HASH_SHA3_256  4   /* FIPS 202 SHA3-256: same permutation and rate, domain byte 0x06 */
 int s2k_digest_batch(s2k_ctx *ctx, int alg, size_t n, const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
                      uint8_t *out /* n*out_len */, size_t out_len);
 int s2k_digest_batch_device(s2k_ctx *ctx, int alg, size_t n, const void *d_msgs, const void *d_msg_offsets, size_t msg_len,
@@ -1356,6 +1362,50 @@ int s2k_ecdsa_verify_messages_batch_keyset_bykey_device(s2k_ctx *ctx, const s2k_
 int s2k_debug_digest_caps(uint32_t out[1]);
 int s2k_debug_digest_strided(s2k_ctx *ctx, int alg, size_t n, const uint8_t *msgs, const uint64_t *msg_offsets, size_t msg_len,
                              uint8_t *out /* n*out_stride */, size_t out_len, size_t out_stride);
+
+/* ---- Keccak-256 addresses: of key records, and of the keys recovered from signatures -------- */
+/* Callers who recover keys in bulk want the 20-byte address Keccak-256(X || Y)[12..32), and started from a message whose
+ * digest is Keccak-256 too.  These calls leave neither hash on the host and move 20 bytes per item back instead of 65.
+ *
+ * s2k_keccak_address_batch[_device]: addr20[i] = Keccak-256(pub65[i][1..65))[12..32) when pub65[i][0] == 0x04 and (ok == NULL or
+ * ok[i] != 0); else 20 zero bytes.  The record is hashed as given: no curve check (these are records this library produced,
+ * or keys the caller vouches for).  One kernel, k_keccak_address, one lane per record; records and rows may lie at any
+ * alignment, exactly 20 n bytes are written.
+ *
+ * s2k_ecdsa_recover_address_batch[_device]: s2k_ecdsa_recover_batch, then the address of each recovered key: ok[i] is bit for
+ * bit that call's ok[i], addr20[i] the address of its pub65[i], 20 zero bytes where ok[i] == 0.  flags as
+ * s2k_ecdsa_recover_batch.  The recovery runs unchanged, on whatever ladder its dispatch picks, into a buffer of the context
+ * (65 bytes per item, allocated on the first such call and kept; s2k_ctx_device_bytes does not count it), and
+ * k_keccak_address runs behind it on the same stream: one launch more than the plain recovery.
+ *
+ * s2k_ecdsa_recover_address_messages_batch[_device]: the same with digest32 replaced by (alg, msgs, msg_offsets, msg_len),
+ * conventions of s2k_digest_batch, any S2K_HASH_* id; the digest kernel runs in front, into the context's digest buffer.
+ *
+ * S2K_ERR_ARG before anything is launched, outputs untouched: a NULL ctx, a NULL buffer with n > 0 (the ok of
+ * s2k_keccak_address_batch[_device] may be NULL), n >= 2^30, an unknown alg, msg_len >= 2^31, and on the host forms offsets
+ * that decrease or items of 2^31 bytes or more.  n == 0 succeeds and writes nothing.  The _device forms carry the digest
+ * calls' PRECONDITION on the offsets.
+ *
+ * Out of scope here: a match form (valid[i] = recovered address == expected), ticket (_submit) forms of the recovery calls,
+ * Keccak for the BIP-340 or whole-batch calls, SHA3-512 / SHAKE, RIPEMD-160 addresses, and fusing the hash into the kernels
+ * that write key records. */
+int s2k_keccak_address_batch(s2k_ctx *ctx, size_t n, const uint8_t *pub65 /* n*65 */, const uint8_t *ok /* n, or NULL */,
+                             uint8_t *addr20 /* n*20 */);
+int s2k_keccak_address_batch_device(s2k_ctx *ctx, size_t n, const void *d_pub65, const void *d_ok, void *d_addr20,
+                                    void *hip_stream);
+int s2k_ecdsa_recover_address_batch(s2k_ctx *ctx, size_t n, const uint8_t *digest32 /* n*32 */, const uint8_t *r /* n*32 */,
+                                    const uint8_t *s /* n*32 */, const uint8_t *recovery_id /* n */, uint32_t flags,
+                                    uint8_t *addr20 /* n*20 */, uint8_t *ok /* n */);
+int s2k_ecdsa_recover_address_batch_device(s2k_ctx *ctx, size_t n, const void *d_digest32, const void *d_r, const void *d_s,
+                                           const void *d_recovery_id, uint32_t flags, void *d_addr20, void *d_ok,
+                                           void *hip_stream);
+int s2k_ecdsa_recover_address_messages_batch(s2k_ctx *ctx, size_t n, int alg, const uint8_t *msgs, const uint64_t *msg_offsets,
+                                             size_t msg_len, const uint8_t *r, const uint8_t *s, const uint8_t *recovery_id,
+                                             uint32_t flags, uint8_t *addr20, uint8_t *ok);
+int s2k_ecdsa_recover_address_messages_batch_device(s2k_ctx *ctx, size_t n, int alg, const void *d_msgs,
+                                                    const void *d_msg_offsets, size_t msg_len, const void *d_r, const void *d_s,
+                                                    const void *d_recovery_id, uint32_t flags, void *d_addr20, void *d_ok,
+                                                    void *hip_stream);
 
 /* ---- introspection used by the tests ------------------------------------------------ */
 /* Copies generator-table entry T_i[d] (X‖Y big-endian) to out64.  Layout: DESIGN.md §3. */

@@ -43,6 +43,7 @@ FORCE_COMPLETE = 0x80000000
 FORCE_WORKLIST = 0x40000000
 ENCODING_ASN1, ENCODING_COMPACT, ENCODING_COMPACT_RECOVERABLE = 0, 1, 2
 HASH_SHA256, HASH_SHA256D, HASH_SHA512 = 0, 1, 2    # S2K_HASH_*: the digest of the calls that take messages
+HASH_KECCAK256, HASH_SHA3_256 = 3, 4                # ... Keccak-256 (original padding) and FIPS 202 SHA3-256
 
 OP_MUL, OP_SQR, OP_ADD, OP_SUB, OP_NEG, OP_INV, OP_SQRT = range(7)
 IMPL_COMPLETE, IMPL_FAST = 0, 1
@@ -299,6 +300,12 @@ def load_library() -> C.CDLL:
     lib.s2k_digest_batch_device.argtypes = [vp, ci, sz, vp, vp, sz, vp, sz, vp]
     lib.s2k_debug_digest_caps.argtypes = [vp]
     lib.s2k_debug_digest_strided.argtypes = [vp, ci, sz, vp, vp, sz, vp, sz, sz]
+    lib.s2k_keccak_address_batch.argtypes = [vp, sz, vp, vp, vp]
+    lib.s2k_keccak_address_batch_device.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.s2k_ecdsa_recover_address_batch.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, vp]
+    lib.s2k_ecdsa_recover_address_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, u32, vp, vp, vp]
+    lib.s2k_ecdsa_recover_address_messages_batch.argtypes = [vp, sz, ci, vp, vp, sz, vp, vp, vp, u32, vp, vp]
+    lib.s2k_ecdsa_recover_address_messages_batch_device.argtypes = [vp, sz, ci, vp, vp, sz, vp, vp, vp, u32, vp, vp, vp]
     lib.s2k_ecdsa_verify_messages_batch.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp]
     lib.s2k_ecdsa_verify_messages_batch_device.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, vp]
     lib.s2k_ecdsa_verify_messages_batch_submit.argtypes = [vp, sz, vp, ci, vp, vp, sz, vp, vp, u32, vp, C.POINTER(u64)]
@@ -483,6 +490,8 @@ EXPORTED_SYMBOLS = [
     "s2k_ecdsa_verify_messages_batch", "s2k_ecdsa_verify_messages_batch_device", "s2k_ecdsa_verify_messages_batch_submit",
     "s2k_ecdsa_verify_messages_batch_keyset", "s2k_ecdsa_verify_messages_batch_keyset_device",
     "s2k_ecdsa_verify_messages_batch_keyset_bykey", "s2k_ecdsa_verify_messages_batch_keyset_bykey_device",
+    "s2k_keccak_address_batch", "s2k_keccak_address_batch_device", "s2k_ecdsa_recover_address_batch", "s2k_ecdsa_recover_address_batch_device",
+    "s2k_ecdsa_recover_address_messages_batch", "s2k_ecdsa_recover_address_messages_batch_device",
     "s2k_ecdsa_verify_batch_submit", "s2k_ecdsa_verify_encoded_batch_submit", "s2k_wait", "s2k_poll", "s2k_wait_all",
     "s2k_device_count", "s2k_group_create", "s2k_group_destroy", "s2k_group_size", "s2k_group_last_error",
     "s2k_group_set_key_grouping", "s2k_group_set_small_batch_max", "s2k_group_set_mid_batch_max", "s2k_group_ecdsa_verify_batch", "s2k_group_ecdsa_verify_batch_submit", "s2k_group_wait",
@@ -1222,7 +1231,8 @@ class Engine(_TicketOwner):
     # ---- SHA-2 digests on the device, and ECDSA verification from messages (digest.hip) ----------
     def digest_batch(self, msgs, alg: int = HASH_SHA256, out_len: int = 32, out_stride: int = 0, out=None) -> np.ndarray:
         """s2k_digest_batch: (n, out_len) digests of the messages (`msgs`: a list of byte strings, a (blob, offsets) pair or an
-        (n, L) uint8 array); alg HASH_SHA256 / HASH_SHA256D / HASH_SHA512, out_len 32 or, with HASH_SHA512, 64.
+        (n, L) uint8 array); alg HASH_SHA256 / HASH_SHA256D / HASH_SHA512 / HASH_KECCAK256 / HASH_SHA3_256, out_len 32 or,
+        with HASH_SHA512, 64.
         out_stride (test hook s2k_debug_digest_strided): rows that far apart in `out`, an (n, out_stride) uint8 array that
         goes to the device as it is and comes back with only the first out_len bytes of each row written."""
         n, blob, offs, mlen, keep = _messages(msgs)
@@ -1574,6 +1584,66 @@ class Engine(_TicketOwner):
                                                       rid.ctypes.data, FORCE_COMPLETE if force_complete else 0,
                                                       pub.ctypes.data, ok.ctypes.data))
         return pub, ok
+
+    # ---- Keccak-256 addresses: of key records, and of recovered keys (address.hip) ----------
+    def keccak_address_batch(self, pub65, ok=None) -> np.ndarray:
+        """s2k_keccak_address_batch: (n, 20) addresses Keccak-256(X || Y)[12:] of the 65-byte records; 20 zero bytes for a
+        record whose first byte is not 0x04 or whose ok (an optional (n,) uint8 array) is 0."""
+        pub65 = _arr(pub65, 65)
+        n = pub65.shape[0]
+        okp = None
+        if ok is not None:
+            ok = np.ascontiguousarray(ok, dtype=np.uint8).reshape(-1)
+            if ok.shape[0] != n:
+                raise ValueError("length mismatch")
+            okp = ok.ctypes.data
+        addr = np.zeros((n, 20), dtype=np.uint8)
+        self._check(self._lib.s2k_keccak_address_batch(self._h, n, pub65.ctypes.data, okp, addr.ctypes.data))
+        return addr
+
+    def keccak_address_batch_device(self, n, d_pub65, d_ok, d_addr20, stream=0):
+        """Device-pointer form: integer device addresses (d_ok None: every record counts), enqueued on `stream`."""
+        self._check(self._lib.s2k_keccak_address_batch_device(self._h, int(n), d_pub65, d_ok, d_addr20, stream))
+
+    def ecdsa_recover_address_batch(self, digest32, r, s, recovery_id, force_complete: bool = False):
+        """ecdsa_recover_batch, then the address of each recovered key: returns (addr20 (n,20) uint8, ok (n,) uint8);
+        20 zero bytes where ok is 0."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        digest32, s = _arr(digest32, 32, n), _arr(s, 32, n)
+        rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
+        if rid.shape[0] != n:
+            raise ValueError("length mismatch")
+        addr, ok = np.zeros((n, 20), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_recover_address_batch(self._h, n, digest32.ctypes.data, r.ctypes.data, s.ctypes.data,
+                                                              rid.ctypes.data, FORCE_COMPLETE if force_complete else 0,
+                                                              addr.ctypes.data, ok.ctypes.data))
+        return addr, ok
+
+    def ecdsa_recover_address_batch_device(self, n, d_digest32, d_r, d_s, d_recovery_id, d_addr20, d_ok, flags=0, stream=0):
+        self._check(self._lib.s2k_ecdsa_recover_address_batch_device(self._h, int(n), d_digest32, d_r, d_s, d_recovery_id, int(flags),
+                                                                     d_addr20, d_ok, stream))
+
+    def ecdsa_recover_address_messages_batch(self, msgs, r, s, recovery_id, alg: int = HASH_KECCAK256, force_complete: bool = False):
+        """ecdsa_recover_address_batch on the digests of `msgs`, hashed on the device with `alg`; host buffers."""
+        r = _arr(r, 32)
+        n = r.shape[0]
+        s = _arr(s, 32, n)
+        rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
+        if rid.shape[0] != n:
+            raise ValueError("length mismatch")
+        _, blob, offs, mlen, keep = _messages(msgs, n)
+        addr, ok = np.zeros((n, 20), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.s2k_ecdsa_recover_address_messages_batch(self._h, n, int(alg), blob, offs, mlen, r.ctypes.data, s.ctypes.data,
+                                                                       rid.ctypes.data, FORCE_COMPLETE if force_complete else 0,
+                                                                       addr.ctypes.data, ok.ctypes.data))
+        return addr, ok
+
+    def ecdsa_recover_address_messages_batch_device(self, n, alg, d_msgs, d_msg_offsets, msg_len, d_r, d_s, d_recovery_id, d_addr20, d_ok,
+                                                    flags=0, stream=0):
+        """Device-pointer form: d_msg_offsets None for n messages of msg_len bytes."""
+        self._check(self._lib.s2k_ecdsa_recover_address_messages_batch_device(self._h, int(n), int(alg), d_msgs, d_msg_offsets, int(msg_len),
+                                                                              d_r, d_s, d_recovery_id, int(flags), d_addr20, d_ok, stream))
 
     def pack_valid_device(self, n, d_valid, d_bitmap, d_count, stream=0):
         """valid bytes -> bitmap + uint64 count, all device pointers."""

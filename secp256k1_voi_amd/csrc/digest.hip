@@ -1,4 +1,4 @@
-// digest.hip — SHA-2 message digests on the device, batched, and the ECDSA verification calls that take messages.
+// digest.hip — SHA-2 and Keccak message digests on the device, batched, and the ECDSA verification calls that take messages.
 // The reference's ECDSA callers start from (message, hash): h := sha256.Sum256(m); pk.Verify(h[:], sig, opts)
 // (secec/ecdsa.go:171-228; a hash longer than 32 bytes gives its leftmost 32 bytes to the scalar, hashToScalar, :477-486).
 // Every other ECDSA entry point here takes the digest; these hash first, on the device: k_digest_messages writes the
@@ -11,12 +11,17 @@
 // ingest.hip; the twin here aligns the ADDRESS, not the offset, so a caller's device blob may start anywhere - an aligned
 // 16-byte load that holds one byte of the stretch never leaves that byte's page).  Lanes of a wave with different block
 // counts run to the longest of them: a batch with one very long message is slow, not wrong.  Public data only.
+//
+// Two kernels over the same staging, item addressing and output rows (dg_locate): k_digest_messages for the SHA-2 ids and
+// k_digest_keccak for S2K_HASH_KECCAK256 / S2K_HASH_SHA3_256 (keccak.h).  digest_launch picks by alg.  They are not one kernel
+// with a branch: its register allocation would be the larger of the two, and the sponge's 25-lane state is the larger.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 
 #include "engine_internal.h"
+#include "keccak.h"
 #include "sha2.h"
 
 namespace {
@@ -53,26 +58,58 @@ __device__ __forceinline__ void dg_store(uint8_t* o, const uint32_t (&w)[NW], bo
   }
 }
 
+// four little-endian lanes to o (a Keccak digest): the same choice of stores, no byte swap
+__device__ __forceinline__ void dg_store_le(uint8_t* o, const uint64_t (&d)[4], bool aligned) {
+  if (aligned) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      reinterpret_cast<uint4*>(o)[k] = make_uint4((uint32_t)d[2 * k], (uint32_t)(d[2 * k] >> 32), (uint32_t)d[2 * k + 1], (uint32_t)(d[2 * k + 1] >> 32));
+  } else {
+#pragma unroll
+    for (int k = 0; k < 32; ++k) o[k] = (uint8_t)(d[k / 8] >> (8 * (k % 8)));
+  }
+}
+
+// What a lane of either digest kernel works on: its message (in LDS when the workgroup's stretch was staged, else in place),
+// its output row, and whether the rows take 16-byte stores.  false: the lane has no item.  Every lane of the workgroup calls
+// it (the staging ends in a barrier).
+struct dg_item {
+  const uint8_t* m;
+  uint32_t len;
+  uint8_t* o;
+  bool aligned;
+};
+__device__ __forceinline__ bool dg_locate(dg_item& it, uint4* lds, uint32_t n, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs,
+                                          uint32_t msg_len, uint8_t* __restrict__ out, uint32_t out_stride) {
+  const uint32_t b0 = blockIdx.x * 256;
+  if (b0 >= n) return false;
+  const uint32_t cnt = n - b0 < 256u ? n - b0 : 256u;
+  const uint64_t lo = offs ? offs[b0] : (uint64_t)b0 * msg_len, hi = offs ? offs[b0 + cnt] : (uint64_t)(b0 + cnt) * msg_len;
+  uintptr_t base = 0;
+  const bool staged = dg_stage(msgs, lo, hi, reinterpret_cast<uint8_t*>(lds), base);
+  __syncthreads();
+  if (threadIdx.x >= cnt) return false;
+  const uint32_t i = b0 + threadIdx.x;
+  const uint64_t mo = offs ? offs[i] : (uint64_t)i * msg_len;
+  it.len = offs ? (uint32_t)(offs[i + 1] - mo) : msg_len;
+  it.m = staged ? reinterpret_cast<const uint8_t*>(lds) + ((uintptr_t)(msgs + mo) - base) : msgs + mo;
+  it.o = out + (size_t)i * out_stride;
+  it.aligned = (((uintptr_t)out | out_stride) & 15u) == 0;
+  return true;
+}
+
 // out[i * out_stride .. + out_len) = the digest of message i: msgs[offs[i], offs[i + 1]), or msgs[i * msg_len, (i + 1) * msg_len)
 // with offs null.  out_len is 32, or 64 (S2K_HASH_SHA512 only); bytes of a row behind out_len are not written.
 __global__ void __launch_bounds__(256, 4)
 k_digest_messages(uint32_t alg, uint32_t n, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
                   uint8_t* __restrict__ out, uint32_t out_stride, uint32_t out_len) {
   __shared__ uint4 lds[DG_CAP / 16];
-  const uint32_t b0 = blockIdx.x * 256;
-  if (b0 >= n) return;
-  const uint32_t cnt = n - b0 < 256u ? n - b0 : 256u;
-  const uint64_t lo = offs ? offs[b0] : (uint64_t)b0 * msg_len, hi = offs ? offs[b0 + cnt] : (uint64_t)(b0 + cnt) * msg_len;
-  uintptr_t base = 0;
-  const bool staged = dg_stage(msgs, lo, hi, reinterpret_cast<uint8_t*>(lds), base);
-  __syncthreads();
-  if (threadIdx.x >= cnt) return;
-  const uint32_t i = b0 + threadIdx.x;
-  const uint64_t mo = offs ? offs[i] : (uint64_t)i * msg_len;
-  const uint32_t len = offs ? (uint32_t)(offs[i + 1] - mo) : msg_len;
-  const uint8_t* m = staged ? reinterpret_cast<const uint8_t*>(lds) + ((uintptr_t)(msgs + mo) - base) : msgs + mo;
-  uint8_t* o = out + (size_t)i * out_stride;
-  const bool aligned = (((uintptr_t)out | out_stride) & 15u) == 0;
+  dg_item it;
+  if (!dg_locate(it, lds, n, msgs, offs, msg_len, out, out_stride)) return;
+  const uint8_t* m = it.m;
+  const uint32_t len = it.len;
+  uint8_t* o = it.o;
+  const bool aligned = it.aligned;
   if (alg == S2K_HASH_SHA512) {
     uint64_t st[8];
     s2k_sha2::sha512_message(st, m, len);
@@ -101,8 +138,28 @@ k_digest_messages(uint32_t alg, uint32_t n, const uint8_t* __restrict__ msgs, co
   }
 }
 
+// The same for S2K_HASH_KECCAK256 and S2K_HASH_SHA3_256 (out_len 32): the first four lanes of the sponge's state, little-endian.
+__global__ void __launch_bounds__(256, 4)
+k_digest_keccak(uint32_t alg, uint32_t n, const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
+                uint8_t* __restrict__ out, uint32_t out_stride) {
+  __shared__ uint4 lds[DG_CAP / 16];
+  dg_item it;
+  if (!dg_locate(it, lds, n, msgs, offs, msg_len, out, out_stride)) return;
+  uint64_t d[4];
+  s2k_keccak::keccak256_message(d, it.m, it.len, alg == S2K_HASH_SHA3_256 ? s2k_keccak::DOMAIN_SHA3 : s2k_keccak::DOMAIN_KECCAK);
+  dg_store_le(it.o, d, it.aligned);
+}
+
+inline bool alg_keccak(int alg) { return alg == S2K_HASH_KECCAK256 || alg == S2K_HASH_SHA3_256; }
+
 int digest_launch(s2k_ctx* ctx, hipStream_t st, int alg, size_t n, const void* d_msgs, const void* d_offs, size_t msg_len, void* d_out,
                   size_t out_stride, size_t out_len) {
+  if (alg_keccak(alg)) {
+    k_digest_keccak<<<blocks_for(n), 256, 0, st>>>((uint32_t)alg, (uint32_t)n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, (uint32_t)msg_len,
+                                                   (uint8_t*)d_out, (uint32_t)out_stride);
+    HIP_TRY(ctx, hipGetLastError());
+    return S2K_OK;
+  }
   k_digest_messages<<<blocks_for(n), 256, 0, st>>>((uint32_t)alg, (uint32_t)n, (const uint8_t*)d_msgs, (const uint64_t*)d_offs, (uint32_t)msg_len,
                                                    (uint8_t*)d_out, (uint32_t)out_stride, (uint32_t)out_len);
   HIP_TRY(ctx, hipGetLastError());
@@ -112,7 +169,7 @@ int digest_launch(s2k_ctx* ctx, hipStream_t st, int alg, size_t n, const void* d
 // What every form checks before anything is launched.  host: msgs / msg_offsets are the caller's host arrays - the offsets
 // are scanned (a device form cannot: its precondition is s2k_schnorr_verify_batch_device's) and *total = the bytes to upload.
 int msg_args(s2k_ctx* ctx, int alg, size_t n, const void* msgs, const uint64_t* msg_offsets, size_t msg_len, bool host, size_t* total) {
-  if (alg != S2K_HASH_SHA256 && alg != S2K_HASH_SHA256D && alg != S2K_HASH_SHA512) return fail(ctx, S2K_ERR_ARG, "unknown hash algorithm");
+  if (alg != S2K_HASH_SHA256 && alg != S2K_HASH_SHA256D && alg != S2K_HASH_SHA512 && !alg_keccak(alg)) return fail(ctx, S2K_ERR_ARG, "unknown hash algorithm");
   if (msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "msg_len must be below 2^31");
   if (n >= S2K_MAX_BATCH) return fail(ctx, S2K_ERR_ARG, "batch too large (at most 2^30 - 1 items per call)");
   *total = 0;
@@ -147,12 +204,17 @@ int digest_to_ctx(s2k_ctx* ctx, hipStream_t st, int alg, size_t n, const void* d
   return digest_launch(ctx, st, alg, n, d_msgs, d_offs, msg_len, ctx->msg_digest, 32, 32);
 }
 
-// the parts of a host form's messages: the blob (16 bytes of slack behind it, as the other message calls keep) and the offsets
-inline stage_part part_msgs(const uint8_t* msgs, size_t total) { return stage_in(msgs, total, total + 16); }
-inline stage_part part_offs(const uint64_t* offs, size_t n) { return stage_in(offs, offs ? (n + 1) * 8 : 0, offs ? (n + 1) * 8 : 8); }
-constexpr size_t DG_SMALL_BYTES = (size_t)1 << 20;   // most message bytes a small call moves through the page-locked block
-
 }  // namespace
+
+// for the recovery calls that take messages (address.hip)
+__attribute__((visibility("hidden"))) int s2k_internal_msg_args(s2k_ctx* ctx, int alg, size_t n, const void* msgs, const uint64_t* msg_offsets,
+                                                                size_t msg_len, bool host, size_t* total) {
+  return msg_args(ctx, alg, n, msgs, msg_offsets, msg_len, host, total);
+}
+__attribute__((visibility("hidden"))) int s2k_internal_digest_to_ctx(s2k_ctx* ctx, hipStream_t st, int alg, size_t n, const void* d_msgs,
+                                                                     const void* d_offs, size_t msg_len, const uint8_t** dig) {
+  return digest_to_ctx(ctx, st, alg, n, d_msgs, d_offs, msg_len, dig);
+}
 
 extern "C" {
 

@@ -409,6 +409,7 @@ void s2k_ctx_destroy(s2k_ctx* ctx) {
   if (ctx->h2c_host) (void)hipHostFree(ctx->h2c_host);
   if (ctx->rlc_save) (void)hipFree(ctx->rlc_save);
   if (ctx->msg_digest) (void)hipFree(ctx->msg_digest);
+  if (ctx->rec_keys) (void)hipFree(ctx->rec_keys);
   if (ctx->io) (void)hipFree(ctx->io);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
   if (ctx->clk) (void)hipFree(ctx->clk);

@@ -127,6 +127,8 @@ struct s2k_ctx {
   void* h2c_host = nullptr;     // ... and the pinned host block both travel through
   void* msg_digest = nullptr;   // the verification calls that take messages (digest.hip): 32 bytes per item, what k_digest_messages
   size_t msg_digest_bytes = 0;  // writes and the digest call behind it reads; allocated on the first such call
+  void* rec_keys = nullptr;     // the recovery calls that return addresses (address.hip): 65 bytes per item, the key records
+  size_t rec_keys_bytes = 0;    // s2k_ecdsa_recover_batch_device writes and k_keccak_address reads; allocated on the first such call
   void* rlc_save = nullptr;     // kept terms of a rejected whole-batch check (BIP-340, recoverable ECDSA) while its failing
                                 // signatures are located; the ECDSA leaf verifier's recovered keys
   size_t rlc_save_bytes = 0;
@@ -396,7 +398,7 @@ struct stage_part {
 inline stage_part stage_in(const void* src, size_t bytes) { return {src, nullptr, bytes, bytes}; }
 inline stage_part stage_in(const void* src, size_t bytes, size_t reserve) { return {src, nullptr, bytes, reserve}; }
 inline stage_part stage_out(void* dst, size_t bytes) { return {nullptr, dst, bytes, bytes}; }
-constexpr int STAGE_MAX_PARTS = 6;
+constexpr int STAGE_MAX_PARTS = 7;   // (s2k_ecdsa_recover_address_messages_batch: messages, offsets, r, s, ids, addresses, ok)
 class stage_run {      // a reference to the caller's lambda int(s2k_ctx* c, uint8_t* const* d, hipStream_t st), good for the call it is passed to
   const void* f_;
   int (*call_)(const void*, s2k_ctx*, uint8_t* const*, hipStream_t);
@@ -409,6 +411,15 @@ class stage_run {      // a reference to the caller's lambda int(s2k_ctx* c, uin
 int s2k_internal_staged_call(s2k_ctx* ctx, const stage_part* parts, int count, size_t phase_bytes, bool small, const stage_run& run);
 int s2k_internal_staged_submit(s2k_ctx* ctx, size_t n, uint8_t* valid, const stage_part* parts, int count, const stage_run& run,
                                s2k_ticket* ticket);
+// the parts of a host form's messages: the blob (16 bytes of slack behind it, as the other message calls keep) and the offsets
+inline stage_part part_msgs(const uint8_t* msgs, size_t total) { return stage_in(msgs, total, total + 16); }
+inline stage_part part_offs(const uint64_t* offs, size_t n) { return stage_in(offs, offs ? (n + 1) * 8 : 0, offs ? (n + 1) * 8 : 8); }
+constexpr size_t DG_SMALL_BYTES = (size_t)1 << 20;   // most message bytes a small call moves through the page-locked block
+// digest.hip, for address.hip: what every messages form checks before anything is launched (host: the offsets are scanned,
+// *total = the bytes to upload), and the digests of a call's messages into the context's buffer on `st`
+int s2k_internal_msg_args(s2k_ctx* ctx, int alg, size_t n, const void* msgs, const uint64_t* msg_offsets, size_t msg_len, bool host, size_t* total);
+int s2k_internal_digest_to_ctx(s2k_ctx* ctx, hipStream_t st, int alg, size_t n, const void* d_msgs, const void* d_offs, size_t msg_len,
+                               const uint8_t** dig);
 
 // Synchronous host-pointer entry points are transfer, kernels, answer in series.  Two verifiers (two contexts on two host
 // threads) that take whole batches alternately could hide one's transfer behind the other's kernels, but left alone they fall
