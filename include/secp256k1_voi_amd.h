@@ -938,7 +938,8 @@ int s2k_multi_scalar_mult(s2k_ctx *ctx, size_t n, const uint8_t *k /* n*32 */, c
                           uint8_t *out /* 65 */);
 int s2k_multi_scalar_mult_device(s2k_ctx *ctx, size_t n, const void *d_k, const void *d_points, void *d_out65,
                                  void *hip_stream);
-/* Test hook for the bucket method behind the call above and both whole-batch verifiers (msm.hip): out = sum_i +-mag[i] * P[i]
+/* Test hook for the bucket method (the core of msm.hip) behind the call above, the segmented sums and both whole-batch
+ * verifiers (rlc.hip): out = sum_i +-mag[i] * P[i]
  * over nterms TERMS as the parse and split kernels would have left them - mags: 16 bytes each, big-endian, the whole range
  * 0 .. 2^128 - 1 (the halves of the endomorphism split stay below 0xA2A9 * 2^112; only the raw coefficients of the whole-batch
  * checks go beyond); points: 65-byte records 0x04 || X || Y of points on the curve, or all zero for an identity term (flag 0:
@@ -946,8 +947,9 @@ int s2k_multi_scalar_mult_device(s2k_ctx *ctx, size_t n, const void *d_k, const 
  * nterms terms; 8, 12 or 16: that width at any size.  A small kernel of the hook fills the term arrays (msm_store_term), then
  * the sort, the bucket pass, the reduction and the tail run as in the product.  geom[10] = {c, nw, nb, nslot, nkeys, L_A,
  * nlanes, fold16, big, list_len}: window bits, windows, keys per slot, slots, keys (padded to a multiple of 256), list
- * entries per range of the bucket pass and ranges (restated from the core's formulas for the one-part flow, not read back:
- * S2K_MSM_SPLIT_WINDOW must be unset), 1 when the 16-bit reduction by row and column sums ran, the count of buckets spread over more than 8 ranges (k_msm_stitch's counter:
+ * entries per range of the bucket pass and ranges, and 1 when the 16-bit reduction by row and column sums ran (these three are
+ * the core's own values, as the call ran them, not a restatement; in the two-part flow of S2K_MSM_SPLIT_WINDOW L_A is the
+ * upper part's and nlanes counts the ranges of both parts), the count of buckets spread over more than 8 ranges (k_msm_stitch's counter:
  * it goes beyond the 4096 the queue holds) and the length of the sorted list.  offsets / list: both NULL, or offsets[nkeys_cap]
  * with nkeys_cap >= nkeys + 1 and list[list_cap] with list_cap >= list_len: the sort's offset[0 .. nkeys] and list[0 ..
  * list_len) (term index | 0x80000000 for a negative digit; key = window * nb + |digit| - 1; the order inside a key is not

@@ -660,7 +660,7 @@ inline u64 fe_from_be_canonical(fe& r, const uint8_t* b) {               // mask
 
 extern "C" {
 
-// out = a - b on 65-byte records (public data: the error points of the batch bisection, msm.hip)
+// out = a - b on 65-byte records (public data: the error points of the batch bisection, rlc.hip)
 __attribute__((visibility("hidden"))) int s2k_internal_point_sub65(const uint8_t* a, const uint8_t* b, uint8_t* out) {
   pt pa, pb, r;
   if (!pt_from_record(pa, a) || !pt_from_record(pb, b)) return 1;

@@ -353,23 +353,7 @@ inline void ctx_aux_join(s2k_ctx* ctx, hipStream_t st) {
   (void)hipStreamWaitEvent(st, ctx->ev_join, 0);
 }
 
-// stage timing of the multi-scalar path (s2k_ctx_profile_msm): events before the front end (parsing, or the BIP-340
-// preparation with grouping and key terms) | the sort | the bucket pass | stitching, reduction and tree | the Horner
-// tail | the end
-constexpr int MSM_PROF_EV = 6;
-inline void msm_prof_mark(s2k_ctx* ctx, hipStream_t st, int slot) {
-  if (!ctx->msm_prof_on || ctx->msm_prof_used + MSM_PROF_EV > ctx->msm_prof_cap) return;
-  (void)hipEventRecord(ctx->msm_prof_ev[ctx->msm_prof_used + slot], st);
-  if (slot == MSM_PROF_EV - 1) ctx->msm_prof_used += MSM_PROF_EV;
-}
-
-// msm.hip, for msm_seg.hip: one bucket-method sum enqueued on `st` without a synchronisation.  *d_status receives the address
-// of the call's status word (non-zero after the launches: a malformed record), valid until the next multiscalar call of the
-// context.  s2k_internal_msm_reserve grows the workspace to what a sum of n inputs needs, so that no later enqueue has to with
-// work in flight (the carve is not monotonic in n - the window width changes it - so a caller reserves for every size it will run).
-int s2k_internal_msm_enqueue(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_scalars, const void* d_points, void* d_out65,
-                             uint32_t** d_status);
-int s2k_internal_msm_reserve(s2k_ctx* ctx, size_t n);
+// (the multiscalar core's host interface, its stage timing included: msm_internal.h)
 
 // submit / wait plumbing (pipeline.hip), shared by the entry points that issue tickets (engine.hip, keyset.hip, digest.hip, ingest.hip)
 int s2k_internal_pipe_slot(s2k_ctx* ctx, size_t n, uint8_t* valid, s2k_ctx::pipe_slot** out);   // free slot for the next ticket
@@ -604,7 +588,7 @@ int s2k_internal_key_chains(s2k_ctx* ctx, const uint8_t* d_pub, hipStream_t st, 
 int s2k_internal_key_tables(s2k_ctx* ctx, hipStream_t st, const key_groups* g, uint32_t part, uint32_t nparts,
                             hipEvent_t ev_mid);
 
-// grouping of x-only keys for the BIP-340 whole-batch check (msm.hip): every key a group, long groups cut
+// grouping of x-only keys for the BIP-340 whole-batch check (rlc.hip): every key a group, long groups cut
 // into virtual groups of KG_VGROUP signatures
 constexpr uint32_t KG_VGROUP = 1024;
 struct key_groups32 {
@@ -736,6 +720,8 @@ struct lane_ws {
   size_t stride;
 };
 extern "C" int s2k_internal_ensure_ws(s2k_ctx* ctx, size_t n);
+// ct_cpu.cpp: out = a - b on 65-byte records (host; public data)
+extern "C" __attribute__((visibility("hidden"))) int s2k_internal_point_sub65(const uint8_t* a, const uint8_t* b, uint8_t* out);
 lane_ws lane_ws_of(const s2k_ctx* ctx, size_t n);
 void prof_mark(s2k_ctx* ctx, hipStream_t st, int slot);       // s2k_ctx_profile: event `slot` of the call's six, on st
 uint32_t prep_lanes(size_t n);                                // lanes of k_scalar_prep for n signatures

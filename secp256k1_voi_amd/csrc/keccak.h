@@ -1,9 +1,9 @@
 // keccak.h — Keccak-f[1600] and the two 256-bit sponges over it, one message per caller: Keccak-256 (the original padding,
 // domain byte 0x01: the hash of Ethereum's addresses and message digests) and SHA3-256 (FIPS 202, domain byte 0x06).  The
 // hash cores of k_digest_keccak (digest.hip: one message per lane) and k_keccak_address (address.hip: one key record per
-// lane).  One text for both sides, as sha2.h is: hipcc compiles it for the device and the host, and it compiles as plain C++
-// (tests/c/keccak_sanitize_main.cpp builds it host-only under AddressSanitizer + UBSan, because the driver takes a
-// caller-supplied length).
+// lane).  As sha2.h: under hipcc it is device code only (the round constants are __constant__; a host call there returns a
+// wrong digest), and it runs on the host only as plain C++ (tests/c/keccak_sanitize_main.cpp builds it so under
+// AddressSanitizer + UBSan, because the driver takes a caller-supplied length).
 //
 // The state is 25 lanes of 64 bits, a[x + 5 y].  Every index into it is a compile-time constant, so on the device it is 50
 // registers and never memory; a round produces the next state row by row (keccak_row), so that little more than one state

@@ -110,7 +110,7 @@ S2K_DEV uint32_t kg_take_rank(uint32_t found, uint32_t* __restrict__ cnt) {
 // slot_of[i]: the hash slot = group of signature i (KG_NONE: probe chain too long, general kernel);
 // pos_of[i]: its rank in the group.  rep[] starts as KG_NONE, cnt[] as 0.
 // KEYBYTES: 64 (X || Y, ECDSA) or 32 (x-only BIP-340 keys: the whole-batch check sums the coefficients of
-// each distinct key, msm.hip)
+// each distinct key, rlc.hip)
 template <int KEYBYTES>
 __global__ void __launch_bounds__(256)
 k_key_insert(uint32_t n, const uint8_t* __restrict__ pub, uint32_t hmask, uint64_t seed, uint32_t* __restrict__ rep,
@@ -1703,7 +1703,7 @@ __attribute__((visibility("hidden"))) int s2k_internal_key_reserve32(s2k_ctx* ct
   return ctx_reserve(ctx, &ctx->kg, &ctx->kg_bytes, words * sizeof(uint32_t));
 }
 
-// Whole-batch checks (msm.hip): all n keys grouped - x-only keys of 32 bytes (BIP-340) or X || Y of 64 (recoverable ECDSA) -,
+// Whole-batch checks (rlc.hip): all n keys grouped - x-only keys of 32 bytes (BIP-340) or X || Y of 64 (recoverable ECDSA) -,
 // every group gets (virtual) group indices.
 // Synchronises the stream to hand the counts to the host (they size the multiscalar multiplication).
 __attribute__((visibility("hidden"))) int s2k_internal_key_group32(s2k_ctx* ctx, size_t n, const uint8_t* d_pk32,

@@ -24,20 +24,21 @@
 // with the curve endomorphism into two 128-bit terms (below); the digits are signed (half the buckets).  Window width
 // c is 8 bits for small inputs and 16 bits for large ones (2^20 inputs: 2^21 terms, 9 slots x 32768 buckets, ~57
 // points per bucket).
-#include <sys/random.h>
-
+//
+// This unit is the core (term arrays in, one point out: msm_setup, msm_core), the plain call in front of it and the test hook
+// s2k_debug_msm_terms.  The term format is msm_terms.h; the core's host interface, for the units that feed it (rlc.hip,
+// msm_seg.hip, pointset.hip), is msm_internal.h.  k_msm_parse judges its records with msm_classify_record; the hook's
+// k_msm_debug_fill keeps a copy of that check of its own (see there).
 #include <cstdlib>
 
-#include <vector>
-
-#include "engine_internal.h"
+#include "msm_internal.h"
+#include "msm_terms.h"
 #include "fe29_inv.h"
 #include "pt29.h"
 #include "pt29q.h"
 #include "fe29r.h"
 #include "xyzz29.h"
 #include "sc.h"
-#include "sha256.h"
 
 namespace {
 
@@ -54,16 +55,7 @@ namespace {
 // |k1| * (+-P) + |k2| * (+-lambda P), |k1|, |k2| < 2^128: twice the terms, half the windows.  The
 // bucket additions stay the same (2n * 8 instead of n * 16 at c = 16) but the serial tail -
 // Horner over the windows, 256 - c doublings on one lane - and the bucket reductions halve.
-constexpr int SCW_WORDS = 5;      // scalar planes per term: 128-bit magnitude + one zero word
 constexpr uint32_t SCALAR_BITS = 128;
-
-struct msm_geom {
-  uint32_t c;        // window bits
-  uint32_t nw;       // windows = ceil(128 / c)
-  uint32_t nb;       // keys per slot = 2^(c-1): the magnitudes 1 .. 2^(c-1) of a signed digit (key = magnitude - 1)
-  uint32_t nslot;    // nw + 1 slots of nb keys: one per window, the top window (unsigned, up to 2^c) takes two
-  uint32_t chunk_log2, nchunk;   // buckets per reduction chunk (log2), chunks per slot = nb >> chunk_log2
-};
 
 // window w (c bits) of a 128-bit magnitude held in k[0..3] (k[4] = 0)
 S2K_DEV uint32_t msm_digit(const uint32_t k[SCW_WORDS], uint32_t w, uint32_t c) {
@@ -141,46 +133,8 @@ S2K_DEV void ptq_store(uint32_t* __restrict__ base, size_t stride, size_t slot, 
   for (int w = 0; w < 9; ++w) base[(size_t)(9 * cc + w) * stride + slot] = v.n[w];
 }
 
-// term `t` of a term array with plane stride N: magnitude k (< 2^128), point (x, +-y)
-S2K_DEV void msm_store_term(uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, size_t N, size_t t, const sc& k,
-                            const uint32_t x[8], const uint32_t y[8], bool neg) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) scw[(size_t)w * N + t] = k.v[w];
-  scw[(size_t)4 * N + t] = 0;
-  uint32_t ny[8];
-  u256_sub(ny, FE_P, y);                                   // y != 0 on this curve
-  // points as 64-byte records [t][16 words]: the bucket pass gathers them by index, one
-  // contiguous record per lane (planes would cost 16 sparse sectors per gathered point)
-  uint4* rec4 = reinterpret_cast<uint4*>(ptw + t * 16);
-  rec4[0] = make_uint4(x[0], x[1], x[2], x[3]);
-  rec4[1] = make_uint4(x[4], x[5], x[6], x[7]);
-  rec4[2] = neg ? make_uint4(ny[0], ny[1], ny[2], ny[3]) : make_uint4(y[0], y[1], y[2], y[3]);
-  rec4[3] = neg ? make_uint4(ny[4], ny[5], ny[6], ny[7]) : make_uint4(y[4], y[5], y[6], y[7]);
-}
-// k * (x, y) -> terms t1, t2:  |k1| * (x, +-y) and |k2| * (beta x, +-y)   (mulBeta, point_mul_glv.go:191)
-S2K_DEV void msm_store_split(uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, size_t N, size_t t1, size_t t2,
-                             const sc& k, const uint32_t x[8], const uint32_t y[8]) {
-  sc k1, k2;
-  bool neg1, neg2;
-  sc_split_glv(k, k1, neg1, k2, neg2);
-  msm_store_term(scw, ptw, N, t1, k1, x, y, neg1);
-  uint32_t bx[8];
-  fe29_to_words(bx, fe29_normalize(fe29_mul(fe29_from_words(x), fe29_from_words(FE_BETA))));
-  msm_store_term(scw, ptw, N, t2, k2, bx, y, neg2);
-}
-
-// (x, y) canonical and y^2 == x^3 + 7 on the 9x29 field (a third of the instructions of the 8x32 form): the point check of
-// a record (xyOnCurve, point_s11n.go:298-307) and NewPublicKey's validation of an X || Y key (secec.go:188-216)
-S2K_DEV bool xy_on_curve_words(const uint32_t xw[8], const uint32_t yw[8]) {
-  if (!fe_is_canonical_raw(xw) || !fe_is_canonical_raw(yw)) return false;
-  const fe29 x = fe29_from_words(xw), y = fe29_from_words(yw);
-  fe29 rhs = fe29_mul(fe29_sqr(x), x);
-  rhs.n[0] += 7;
-  return fe29_eq(fe29_sqr(y), rhs);
-}
-
 // bytes -> terms: scalar reduced mod n and split, affine point words; flag per term
-// (0 identity, 1 finite, 2 malformed).  Input i becomes terms i and n + i.
+// (msm_terms.h).  Input i becomes terms i and n + i.
 __global__ void __launch_bounds__(256)
 k_msm_parse(uint32_t n, const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points,
             uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag,
@@ -191,21 +145,12 @@ k_msm_parse(uint32_t n, const uint8_t* __restrict__ scalars, const uint8_t* __re
   load_be32(raw, scalars + i * 32);
   sc k = sc_reduce_once(raw);                     // SetBytes semantics (scalar.go:123)
   const uint8_t* rec = points + i * 65;
-  uint8_t f = 0;
   apt a;
-  a.x = fe_zero();
-  a.y = fe_zero();
-  if (rec[0] == 0x04) {
-    load_be32_unaligned(a.x.v, rec + 1);
-    load_be32_unaligned(a.y.v, rec + 33);
-    f = xy_on_curve_words(a.x.v, a.y.v) ? 1 : 2;
-  } else if (rec[0] != 0x00) {
-    f = 2;
-  }
-  if (f == 2) atomicOr(status, 1u);
+  const uint8_t f = msm_classify_record(rec, a.x.v, a.y.v);
+  if (f == TERM_MALFORMED) atomicOr(status, 1u);
   flag[i] = f;
   flag[(size_t)n + i] = f;
-  if (f == 1) msm_store_split(scw, ptw, 2 * (size_t)n, i, (size_t)n + i, k, a.x.v, a.y.v);
+  if (f == TERM_FINITE) msm_store_split(scw, ptw, 2 * (size_t)n, i, (size_t)n + i, k, a.x.v, a.y.v);
 }
 
 // exclusive scan of `total` counters (total a multiple of 1024), three small launches:
@@ -499,7 +444,7 @@ struct msm_rec {
   uint4 a, b, c, d;
 };
 S2K_DEV msm_rec msm_load_rec(const uint32_t* __restrict__ ptw, uint32_t entry) {
-  const uint4* rec4 = reinterpret_cast<const uint4*>(ptw + (size_t)(entry & ~TERM_NEG) * 16);
+  const uint4* rec4 = reinterpret_cast<const uint4*>(ptw + (size_t)(entry & ~TERM_NEG) * TERM_REC_WORDS);
   msm_rec r;
   r.a = rec4[0]; r.b = rec4[1]; r.c = rec4[2]; r.d = rec4[3];
   return r;
@@ -803,7 +748,7 @@ __global__ void __launch_bounds__(256) k_msm_tree(uint32_t nslots_total, uint32_
 __global__ void __launch_bounds__(64) k_msm_final(msm_geom g, uint32_t* __restrict__ partial, uint8_t* __restrict__ out65, int affine,
                                                   uint32_t w_from, uint32_t w_to) {
   // out65: the 65-byte record of the sum (all zero for the identity); affine == 0: only identity or not is wanted
-  // (first byte 0x00 / 0x04, coordinates left zero): the whole-batch BIP-340 verdict skips the inversion.
+  // (first byte 0x00 / 0x04, coordinates left zero): the whole-batch verdicts (rlc.hip) skip the inversion.
   // The recurrence runs over the windows w_from - 1 down to w_to.  w_from == nw: from the top (the top window's two slots
   // first); otherwise it continues from the point an earlier launch has left in the carry slot.  w_to > 0: the point goes
   // to the carry slot for the launch that continues (two-part flow, msm_core); w_to == 0: it is the result.
@@ -1043,21 +988,6 @@ k_msm_final16(uint32_t* __restrict__ lvl, size_t lstride, uint8_t* __restrict__ 
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-struct msm_ws {
-  msm_geom g;
-  size_t nkeys, nslots;
-  uint32_t *status, *matrix, *offset, *bsum, *scw, *ptw, *list, *sums, *xsum, *partial, *big, *lanekey;
-  size_t cap;          // term capacity the workspace was carved for = plane stride of scw (a call may run on fewer terms)
-  uint32_t lanes_cap;  // bucket pass: most ranges any term count up to cap can make
-  size_t sum_stride;   // slots of `sums`: nkeys buckets, then the left and the right edge piece of every range
-  void* pairs;
-  bool wide;           // two-word pairs (term indices beyond 23 bits)
-  uint32_t ncoarse, nsortblk, nblk_pad, sort_terms;
-  uint8_t* flag;
-  size_t zero_bytes;   // status + size bins + coarse matrix, contiguous from the start
-  uint8_t* aux;        // extra caller-requested scratch
-};
-
 static uint32_t msm_lanes_target() {   // tuning hook: S2K_MSM_LANES overrides the lanes that fill the chip once
   static const uint32_t v = [] {
     const char* e = getenv("S2K_MSM_LANES");
@@ -1065,9 +995,12 @@ static uint32_t msm_lanes_target() {   // tuning hook: S2K_MSM_LANES overrides t
   }();
   return v;
 }
+
+}  // namespace
+
 // carve the MSM workspace for up to n terms (+ aux_bytes of scratch for the caller)
 // (force_c: 0, or the window width a test asks for at any size - s2k_debug_msm_terms)
-int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m, uint32_t force_c = 0) {
+int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m, uint32_t force_c) {
   msm_geom& g = m.g;
   // window width: measured (tools/msm_sweep.py, MI355X, ms for 2^11 .. 2^20 inputs = twice as many terms):
   // 16-bit windows from 2^13 terms on: 0.83 0.75 0.75 0.76 0.78 0.80 0.89 1.01 1.31 1.95; 12-bit windows up to
@@ -1106,7 +1039,7 @@ int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m, uint32_t forc
   const size_t mat_words = (size_t)m.ncoarse * m.nblk_pad;
   size_t o_status = carve(256), o_big = carve(2 * (STITCH_BIG_CAP + 1) * 4), o_matrix = carve((mat_words + 1) * 4),
          o_offset = carve((m.nkeys + 1) * 4), o_bsum = carve((mat_words / 1024 + 1) * 4),
-         o_pairs = carve(n * (size_t)g.nw * 8), o_scw = carve(n * SCW_WORDS * 4), o_ptw = carve(n * 16 * 4), o_flag = carve(n),
+         o_pairs = carve(n * (size_t)g.nw * 8), o_scw = carve(n * SCW_WORDS * 4), o_ptw = carve(n * TERM_REC_WORDS * 4), o_flag = carve(n),
          o_list = carve(n * (size_t)g.nw * 4), o_sums = carve(m.sum_stride * PT_WORDS * 4),
          o_partial = carve((m.nslots + 1) * PT_WORDS * 4), o_lanekey = carve((size_t)m.lanes_cap * 4),
          o_xsum = carve(m.sum_stride * XZ_WORDS * 4), o_aux = carve(aux_bytes);
@@ -1133,8 +1066,8 @@ int msm_setup(s2k_ctx* ctx, size_t n, size_t aux_bytes, msm_ws& m, uint32_t forc
   m.zero_bytes = o_offset;   // status, the queue of oversized buckets and the coarse matrix
   return S2K_OK;
 }
+hipError_t msm_clear(s2k_ctx* ctx, hipStream_t st, const msm_ws& m) { return hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st); }
 
-// buckets -> result, given scw / ptw / flag already filled and status/count/cursor zeroed
 // the second stream of a multi-scalar call (the point half of the front end; the upper part's tail in the two-part flow)
 static int msm_second_stream(s2k_ctx* ctx, hipStream_t* out) {
   if (!ctx->s_msm_tail) {
@@ -1145,10 +1078,16 @@ static int msm_second_stream(s2k_ctx* ctx, hipStream_t* out) {
   *out = ctx->s_msm_tail;
   return S2K_OK;
 }
-int msm_core(s2k_ctx* ctx, hipStream_t st, size_t n, msm_ws& m, uint8_t* d_out65, bool affine = true) {
+namespace {
+// How msm_core runs n terms of the workspace m: the reduction, the windows of the lower part and the ranges of either part.
+// The one place these are computed.
+struct msm_cut {
+  msm_parts P;
+  uint32_t wsplit, b_wgs_per_cu;   // windows in the lower part (0: one part); workgroups per CU of its bucket pass
+  bool fold16;                     // 16-bit windows: row / column sums and bit planes instead of chunks of buckets
+};
+msm_cut msm_cut_for(size_t n, const msm_ws& m) {
   const msm_geom& g = m.g;
-  if (n > m.cap) return fail(ctx, S2K_ERR_ARG, "internal: more terms than the multiscalar workspace was carved for");
-  const uint32_t nsortblk = (uint32_t)((n + m.sort_terms - 1) / m.sort_terms);  // <= m.nsortblk: the matrix columns beyond stay zero
   static const bool fold_off = getenv("S2K_MSM_OLD_REDUCE") != nullptr;      // A/B hook: the round-3 reduction (chunks of 8 buckets, quads)
   const bool fold16 = g.c == 16 && !fold_off && m.nslots + 1 > FOLD_END;
   // Two parts, top-down (16-bit windows, large inputs): the bucket pass of the windows from `wsplit` up
@@ -1171,19 +1110,33 @@ int msm_core(s2k_ctx* ctx, hipStream_t st, size_t n, msm_ws& m, uint8_t* d_out65
   const uint32_t wsplit = (fold16 && n >= ((size_t)1 << 17) && split_env > 0 && split_env < (int)g.nw) ? (uint32_t)split_env : 0u;
   // ranges of the bucket pass: as long as it takes for the lanes of a part to fill the chip once
   msm_parts P;
-  {
-    const size_t pairs_a = n * (size_t)(g.nw - wsplit), pairs_b = n * (size_t)wsplit;
-    const size_t target_a = msm_lanes_target(), target_b = (size_t)msm_lanes_target() * b_wgs_per_cu / 4;
-    size_t la = (pairs_a + target_a - 1) / target_a, lb = wsplit ? (pairs_b + target_b - 1) / target_b : MSM_L_MIN;
-    if (la < MSM_L_MIN) la = MSM_L_MIN;
-    if (lb < MSM_L_MIN) lb = MSM_L_MIN;
-    P.split_key = wsplit * g.nb;
-    P.L_A = (uint32_t)la;
-    P.L_B = (uint32_t)lb;
-    P.nlanesB = wsplit ? (uint32_t)((pairs_b + lb - 1) / lb) : 0u;
-    P.nlanes = P.nlanesB + (uint32_t)((pairs_a + la - 1) / la);                  // <= m.lanes_cap
-  }
+  const size_t pairs_a = n * (size_t)(g.nw - wsplit), pairs_b = n * (size_t)wsplit;
+  const size_t target_a = msm_lanes_target(), target_b = (size_t)msm_lanes_target() * b_wgs_per_cu / 4;
+  size_t la = (pairs_a + target_a - 1) / target_a, lb = wsplit ? (pairs_b + target_b - 1) / target_b : MSM_L_MIN;
+  if (la < MSM_L_MIN) la = MSM_L_MIN;
+  if (lb < MSM_L_MIN) lb = MSM_L_MIN;
+  P.split_key = wsplit * g.nb;
+  P.L_A = (uint32_t)la;
+  P.L_B = (uint32_t)lb;
+  P.nlanesB = wsplit ? (uint32_t)((pairs_b + lb - 1) / lb) : 0u;
+  P.nlanes = P.nlanesB + (uint32_t)((pairs_a + la - 1) / la);                  // <= m.lanes_cap
+  return {P, wsplit, b_wgs_per_cu, fold16};
+}
+}  // namespace
+
+// buckets -> result, given scw / ptw / flag already filled and status/count/cursor zeroed (msm_clear)
+int msm_core(s2k_ctx* ctx, hipStream_t st, size_t n, msm_ws& m, uint8_t* d_out65, bool affine) {
+  const msm_geom& g = m.g;
+  if (n > m.cap) return fail(ctx, S2K_ERR_ARG, "internal: more terms than the multiscalar workspace was carved for");
+  const uint32_t nsortblk = (uint32_t)((n + m.sort_terms - 1) / m.sort_terms);  // <= m.nsortblk: the matrix columns beyond stay zero
+  const msm_cut cut = msm_cut_for(n, m);
+  const msm_parts& P = cut.P;
+  const uint32_t wsplit = cut.wsplit, b_wgs_per_cu = cut.b_wgs_per_cu;
+  const bool fold16 = cut.fold16;
   if (P.nlanes > m.lanes_cap) return fail(ctx, S2K_ERR_ARG, "internal: more ranges than the multiscalar workspace was carved for");
+  m.ran_L_A = P.L_A;
+  m.ran_nlanes = P.nlanes;
+  m.ran_fold16 = fold16;
   const uint32_t nlanes_a = P.nlanes - P.nlanesB;
   // sort: coarse partition (counts -> scan -> scatter), then one workgroup per coarse bucket
   msm_prof_mark(ctx, st, 1);
@@ -1290,442 +1243,30 @@ int msm_core(s2k_ctx* ctx, hipStream_t st, size_t n, msm_ws& m, uint8_t* d_out65
   return S2K_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// BIP-340 batch verification as ONE multi-scalar multiplication (BIP-340 "Batch Verification"):
-//   (sum a_i s_i) * G  -  sum a_i * R_i  -  sum (a_i e_i) * P_i  ==  infinity,
-// R_i = lift_x(r_i), P_i = lift_x(pk_i), a_0 = 1 and a_i 128-bit values from a keyed PRF
-// (SHA-256(seed || i)); the seed is caller-supplied secret randomness.  The reference has
-// only the single-signature Verify (schnorr.go:221-253); the contract is
-// "batch accepts <=> every single Verify accepts", up to 2^-128.
-// Terms, plain form: [0, n) = a_i * (-R_i); [n, 2n) and [2n, 3n) = the two halves of (a_i e_i) * (-P_i);
-// 3n, 3n + 1 = the two halves of (sum a_i s_i) * G.
-// Aggregated form (the whole-batch verdict; keys repeat in real batches): the signatures are grouped by key
-// (keyed.hip) and each distinct key P contributes ONE term pair (sum over its signatures of a_i e_i) * (-P):
-// [0, n) as before, n + 2t, n + 2t + 1 for group t, then the generator's pair.  One square root per distinct
-// key instead of one per signature, n + 2 K + 2 terms instead of 3 n + 2.  The sum is the same group
-// element, so the error point of a rejected batch can seed the bisection, which works on the plain form.
-// ---------------------------------------------------------------------------------------
-S2K_DEV bool lift_x_words(uint32_t yw[8], const uint32_t xw[8]) {
-  if (!fe_is_canonical_raw(xw)) return false;
-  fe29 x = fe29_from_words(xw);
-  fe29 rhs = fe29_mul(fe29_sqr(x), x);
-  rhs.n[0] += 7;
-  fe29 y;
-  if (!fe29_sqrt(y, rhs)) return false;
-  y = fe29_normalize(y);
-  y = fe29_normalize(fe29_select((y.n[0] & 1u) != 0, y, fe29_negate(y, 1)));   // even root
-  fe29_to_words(yw, y);
-  return true;
-}
-// the root whose parity is `odd` (0 / 1): the even root, or p minus it (p is odd and y != 0 on this curve)
-S2K_DEV bool lift_x_parity_words(uint32_t yw[8], const uint32_t xw[8], uint32_t odd) {
-  uint32_t even[8], other[8];
-  if (!lift_x_words(even, xw)) return false;
-  u256_sub(other, FE_P, even);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) yw[w] = odd ? other[w] : even[w];
-  return true;
-}
-// a_i = low 128 bits of SHA-256(key || i), a_0 = 1: the coefficients of the whole-batch checks
-S2K_DEV sc rlc_coefficient(const uint32_t key_be[8], size_t i) {
-  sc a = sc_zero();
-  if (i == 0) {
-    a.v[0] = 1;
-    return a;
-  }
-  uint32_t st[8], w[16];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    st[j] = SHA256_IV[j];
-    w[j] = key_be[j];
-  }
-  w[8] = (uint32_t)(i >> 32);
-  w[9] = (uint32_t)i;
-  w[10] = 0x80000000u;
-  w[11] = w[12] = w[13] = w[14] = 0;
-  w[15] = 40 * 8;
-  sha256_compress(st, w);
-  a.v[0] = st[7]; a.v[1] = st[6]; a.v[2] = st[5]; a.v[3] = st[4];
-  return a;
-}
-
-struct rlc_key {   // PRF key of the coefficients, passed by value as a kernel argument
-  uint32_t w[8];
-};
-// AGG: the key terms are left to k_rlc_key_terms (one term pair per DISTINCT key, its coefficient the sum of
-// a_i e_i over the key's signatures): this kernel stores a_i e_i in ae_out instead, and neither lifts nor
-// judges the key.  N: plane stride of the term arrays (3n + 2 plain, n + 2 (groups) + 2 aggregated).
-template <bool AGG>
-__global__ void __launch_bounds__(256)
-k_schnorr_rlc_prep(uint32_t n, size_t N, const uint8_t* __restrict__ pk, const uint8_t* __restrict__ sig,
-                   const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ offs, uint32_t msg_len,
-                   rlc_key seed_be, uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw,
-                   uint8_t* __restrict__ flag, uint32_t* __restrict__ as_out, uint32_t* __restrict__ ae_out,
-                   uint32_t* __restrict__ status) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint32_t r_le[8], pk_le[8];
-  sc s;
-  load_be32(r_le, sig + i * 64);
-  load_be32(s.v, sig + i * 64 + 32);
-  load_be32(pk_le, pk + i * 32);
-  bool ok = sc_is_canonical_raw(s.v);
-  uint32_t ry[8], py[8];
-  ok = lift_x_words(ry, r_le) && ok;      // r < p and on the curve (BIP-340 batch: fail if lift fails)
-  if constexpr (!AGG) ok = lift_x_words(py, pk_le) && ok;
-  if (!ok) atomicOr(status, 2u);
-  // e_i
-  uint32_t r_be[8], pk_be[8], dg[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    r_be[w] = r_le[7 - w];
-    pk_be[w] = pk_le[7 - w];
-  }
-  const uint8_t* m = offs ? msgs + offs[i] : msgs + i * (size_t)msg_len;
-  uint32_t len = offs ? (uint32_t)(offs[i + 1] - offs[i]) : msg_len;
-  bip340_challenge(dg, r_be, pk_be, m, len);
-  uint32_t e_raw[8];
-#pragma unroll
-  for (int w = 0; w < 8; ++w) e_raw[w] = dg[7 - w];
-  sc e = sc_reduce_once(e_raw);
-  const sc a = rlc_coefficient(seed_be.w, i);
-  sc a_m = sc_to_mont(a);
-  sc ae = sc_montmul(e, a_m), as = sc_montmul(s, a_m);
-  // -a_i * R_i and -(a_i e_i) * P_i are entered as a_i * (-R_i) and (a_i e_i) * (-P_i): negating the
-  // point is free, whereas n - a_i (a_i < 2^128) would put every R term into the same 0xFFFF
-  // buckets of the upper windows and serialise them on single lanes.
-  if (ok) msm_store_term(scw, ptw, N, i, a, r_le, ry, true);                          // a_i < 2^128 already
-  if constexpr (AGG) {
-    // (a 32-byte record per signature, not planes: k_rlc_key_terms gathers them by key, from all over the array - eight
-    // 4-byte reads per member, each a memory transaction of its own, were most of that kernel's 0.070 ms; now 0.035)
-    uint4* rec = reinterpret_cast<uint4*>(ae_out + (size_t)i * 8);
-    rec[0] = make_uint4(ae.v[0], ae.v[1], ae.v[2], ae.v[3]);
-    rec[1] = make_uint4(ae.v[4], ae.v[5], ae.v[6], ae.v[7]);
-  } else {
-    uint32_t npy[8];
-    u256_sub(npy, FE_P, py);
-    if (ok) msm_store_split(scw, ptw, N, (size_t)n + i, 2 * (size_t)n + i, ae, pk_le, npy);
-    flag[(size_t)n + i] = ok ? 1 : 0;
-    flag[2 * (size_t)n + i] = ok ? 1 : 0;
-  }
-  // a signature whose r or key does not lift is invalid on its own; it takes no part in the combination
-#pragma unroll
-  for (int w = 0; w < 8; ++w) as_out[(size_t)w * n + i] = ok ? as.v[w] : 0u;
-  flag[i] = ok ? 1 : 0;
-}
-
-// Recoverable ECDSA signatures as the same kind of sum (header: s2k_ecdsa_batch_verify_rlc):
-//   sum a_i * R_i  -  (sum a_i u1_i) * G  -  sum (a_i u2_i) * Q_i  ==  infinity,   u1 = e / s, u2 = r / s, R_i = RecoverPoint(r_i, v_i),
-// in the layouts of the BIP-340 forms above.  Terms [0, n) = a_i * R_i (a 128-bit coefficient, never negated); the key terms
-// are (a_i u2_i) * (-Q_i), negated on the point as there - per signature at [n, 2n) and [2n, 3n) in the plain form, per
-// distinct key behind n in the aggregated one (ae_out gets a_i u2_i; k_ecdsa_key_check judges the keys, k_rlc_key_terms sums);
-// as_out gets a_i u1_i, whose sum k_schnorr_rlc_sum enters negated with G.  An item that fails one of its own checks
-// (ranges of r and s, low s under the flag, v, x = r + n below p, x on the curve; plain form: its key) leaves the combination.
-// One lane per signature with an inversion of its own (sc_modinv: safegcd): no lane shares a product with another, so an s
-// that has no inverse cannot spoil a neighbour's (the simpler of the two ways; k_scalar_prep's shared inversion would save most of it).
-template <bool AGG>
-__global__ void __launch_bounds__(256)
-k_ecdsa_rlc_prep(uint32_t n, size_t N, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ dig,
-                 const uint8_t* __restrict__ rsig, const uint8_t* __restrict__ ssig, const uint8_t* __restrict__ recid,
-                 uint32_t flags, rlc_key seed_be, uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw,
-                 uint8_t* __restrict__ flag, uint32_t* __restrict__ as_out, uint32_t* __restrict__ ae_out,
-                 uint32_t* __restrict__ status) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  sc r, s;
-  uint32_t e_raw[8];
-  load_be32(r.v, rsig + i * 32);
-  load_be32(s.v, ssig + i * 32);
-  load_be32(e_raw, dig + i * 32);
-  const uint32_t v = recid[i];
-  const bool s_ok = sc_is_canonical_raw(s.v) && !sc_is_zero(s);
-  bool ok = sc_is_canonical_raw(r.v) && !sc_is_zero(r) && s_ok && v <= 3u;
-  if (flags & S2K_ECDSA_REJECT_MALLEABLE) ok = ok && !sc_is_gt_half_n(s);
-  // RecoverPoint (point_s11n.go:245-282): bit 1 of v means x = r + n, which must stay below p; bit 0 is the parity of y
-  uint32_t xw[8], ry[8];
-  {
-    uint32_t rn[8];
-    const uint32_t carry = u256_add(rn, r.v, SC_N);
-    const bool high = (v & 2u) != 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) xw[w] = high ? rn[w] : r.v[w];
-    ok = ok && !(high && carry != 0);
-  }
-  ok = lift_x_parity_words(ry, xw, v & 1u) && ok;          // (refuses x >= p)
-  uint32_t qx[8], qy[8];
-  if constexpr (!AGG) {
-    load_be32(qx, pub + i * 64);
-    load_be32(qy, pub + i * 64 + 32);
-    ok = xy_on_curve_words(qx, qy) && ok;
-  }
-  if (!ok) atomicOr(status, 2u);
-  sc s_inv = s;
-  if (!s_ok) {            // (rejected above; the inversion wants a canonical value)
-    s_inv = sc_zero();
-    s_inv.v[0] = 1;
-  }
-  const sc s_inv_m = sc_to_mont(sc_modinv(s_inv));
-  const sc e = sc_reduce_once(e_raw);
-  const sc a = rlc_coefficient(seed_be.w, i);
-  const sc a_m = sc_to_mont(a);
-  const sc au1 = sc_montmul(sc_montmul(e, s_inv_m), a_m), au2 = sc_montmul(sc_montmul(r, s_inv_m), a_m);
-  if (ok) msm_store_term(scw, ptw, N, i, a, xw, ry, false);                           // a_i < 2^128 already
-  if constexpr (AGG) {
-    uint4* rec = reinterpret_cast<uint4*>(ae_out + (size_t)i * 8);
-    rec[0] = make_uint4(au2.v[0], au2.v[1], au2.v[2], au2.v[3]);
-    rec[1] = make_uint4(au2.v[4], au2.v[5], au2.v[6], au2.v[7]);
-  } else {
-    uint32_t nqy[8];
-    u256_sub(nqy, FE_P, qy);
-    if (ok) msm_store_split(scw, ptw, N, (size_t)n + i, 2 * (size_t)n + i, au2, qx, nqy);
-    flag[(size_t)n + i] = ok ? 1 : 0;
-    flag[2 * (size_t)n + i] = ok ? 1 : 0;
-  }
-#pragma unroll
-  for (int w = 0; w < 8; ++w) as_out[(size_t)w * n + i] = ok ? au1.v[w] : 0u;
-  flag[i] = ok ? 1 : 0;
-}
-// The aggregated form's keys are X || Y: no square root per key, only NewPublicKey's validation, once per group
-// (ky[w][t] = Y, kok[t] = 1 if the key is a point of the curve: what k_rlc_key_lift leaves for x-only keys).
-__global__ void __launch_bounds__(64)
-k_ecdsa_key_check(uint32_t ngroups, uint32_t nleft, size_t kstride, const uint32_t* __restrict__ vslot, const uint32_t* __restrict__ rep,
-                  const uint32_t* __restrict__ left, const uint8_t* __restrict__ pub, uint32_t* __restrict__ ky, uint8_t* __restrict__ kok) {
-  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= ngroups + nleft) return;
-  const uint32_t key_sig = t < ngroups ? rep[vslot[t]] : left[t - ngroups];
-  uint32_t qx[8], qy[8];
-  load_be32(qx, pub + (size_t)key_sig * 64);
-  load_be32(qy, pub + (size_t)key_sig * 64 + 32);
-  const bool key_ok = xy_on_curve_words(qx, qy);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) ky[(size_t)w * kstride + t] = key_ok ? qy[w] : 0u;
-  kok[t] = key_ok ? 1 : 0;
-}
-// The leaf of the ECDSA bisection, behind s2k_ecdsa_recover_batch_device: valid[i] = RecoverPublicKey succeeded and returned
-// exactly the supplied key (k.Equal(q) compares the serialised points, secec.go:121-129; a recovered key is a canonical point
-// of the curve, so a supplied key that NewPublicKey refuses equals none), and s <= n/2 under the flag.
-__global__ void __launch_bounds__(256)
-k_ecdsa_rlc_leaf(uint32_t n, const uint8_t* __restrict__ pub, const uint8_t* __restrict__ ssig, uint32_t flags,
-                 const uint8_t* __restrict__ rec65, const uint8_t* __restrict__ ok, uint8_t* __restrict__ valid) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t* a = pub + i * 64;
-  const uint8_t* b = rec65 + i * 65;
-  uint32_t diff = b[0] ^ 0x04u;
-  for (int j = 0; j < 64; ++j) diff |= (uint32_t)(a[j] ^ b[1 + j]);
-  bool good = ok[i] == 1 && diff == 0;
-  if (flags & S2K_ECDSA_REJECT_MALLEABLE) {
-    sc s;
-    load_be32(s.v, ssig + i * 32);
-    good = good && !sc_is_gt_half_n(s);
-  }
-  valid[i] = good ? 1 : 0;
-}
-
-// Aggregated key terms, in two kernels.  Lane t < ngroups: virtual group t (the signatures perm[first .. first + count)
-// of one key); lane ngroups + q: the signature left[q] on its own.
-// k_rlc_key_lift lifts the group's key ONCE (a square root: the expensive part; it needs the grouping only, so it runs on
-// the second stream beside k_schnorr_rlc_prep): ky[w][t] = the even y, kok[t] = 1 if the key lifts.
-__global__ void __launch_bounds__(64)
-k_rlc_key_lift(uint32_t ngroups, uint32_t nleft, size_t kstride, const uint32_t* __restrict__ vslot, const uint32_t* __restrict__ rep,
-               const uint32_t* __restrict__ left, const uint8_t* __restrict__ pk, uint32_t* __restrict__ ky, uint8_t* __restrict__ kok) {
-  const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= ngroups + nleft) return;
-  const uint32_t key_sig = t < ngroups ? rep[vslot[t]] : left[t - ngroups];
-  uint32_t pk_le[8], py[8];
-  load_be32(pk_le, pk + (size_t)key_sig * 32);
-  const bool key_ok = lift_x_words(py, pk_le);
-#pragma unroll
-  for (int w = 0; w < 8; ++w) ky[(size_t)w * kstride + t] = key_ok ? py[w] : 0u;
-  kok[t] = key_ok ? 1 : 0;
-}
-// k_rlc_key_terms: the group's coefficient is the sum of a_i e_i over its members that are still in the combination
-// (flag).  A key that does not lift takes its signatures out of the combination (flag, a_i s_i) and fails the batch
-// (status).  Terms n + 2t, n + 2t + 1 (N: plane stride of the term arrays).  KEYBYTES: 32 (x-only, BIP-340) or 64 (X || Y, ECDSA);
-// either way the term's point is the key's (x, -y), y from ky.
-template <int KEYBYTES>
-__global__ void __launch_bounds__(64)
-k_rlc_key_terms(uint32_t n, size_t N, uint32_t ngroups, uint32_t nleft, const uint32_t* __restrict__ vslot,
-                const uint32_t* __restrict__ rep, const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ base,
-                const uint32_t* __restrict__ tix, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ left,
-                const uint8_t* __restrict__ pk, size_t kstride, const uint32_t* __restrict__ ky, const uint8_t* __restrict__ kok,
-                const uint32_t* __restrict__ ae, uint32_t* __restrict__ as_io,
-                uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag,
-                uint32_t* __restrict__ status) {
-  uint32_t t = blockIdx.x * 64 + threadIdx.x;
-  if (t >= ngroups + nleft) return;
-  uint32_t first = 0, count = 1, key_sig;
-  const uint32_t* members;
-  if (t < ngroups) {
-    const uint32_t s = vslot[t], v = t - tix[s];
-    first = base[s] + v * KG_VGROUP;
-    const uint32_t rest = cnt[s] - v * KG_VGROUP;
-    count = rest < KG_VGROUP ? rest : KG_VGROUP;
-    key_sig = rep[s];
-    members = perm;
-  } else {
-    first = t - ngroups;
-    key_sig = left[first];
-    members = left;
-  }
-  const bool key_ok = kok[t] != 0;
-  sc sum = sc_zero();
-  bool any = false;
-#pragma unroll 1
-  for (uint32_t j = 0; j < count; ++j) {
-    const size_t i = members[first + j];
-    if (!flag[i]) continue;
-    if (!key_ok) {   // out of the combination
-      flag[i] = 0;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) as_io[(size_t)w * n + i] = 0u;
-      continue;
-    }
-    const uint4* rec = reinterpret_cast<const uint4*>(ae + i * 8);
-    const uint4 lo4 = rec[0], hi4 = rec[1];
-    sc v;
-    v.v[0] = lo4.x; v.v[1] = lo4.y; v.v[2] = lo4.z; v.v[3] = lo4.w;
-    v.v[4] = hi4.x; v.v[5] = hi4.y; v.v[6] = hi4.z; v.v[7] = hi4.w;
-    sum = sc_add(sum, v);
-    any = true;
-  }
-  if (!key_ok) atomicOr(status, 2u);
-  const size_t t1 = (size_t)n + 2 * (size_t)t, t2 = t1 + 1;
-  if (key_ok && any) {
-    uint32_t pk_le[8], py[8], npy[8];
-    load_be32(pk_le, pk + (size_t)key_sig * KEYBYTES);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) py[w] = ky[(size_t)w * kstride + t];
-    u256_sub(npy, FE_P, py);
-    msm_store_split(scw, ptw, N, t1, t2, sum, pk_le, npy);
-    flag[t1] = 1;
-    flag[t2] = 1;
-  }
-}
-
-// sum of n scalars mod n in two launches: RLC_SUM_BLOCKS workgroups leave one partial sum each in
-// `part` (8 words each), then one workgroup folds those and writes the result as terms 3n, 3n + 1
-// with the point G (as == nullptr selects the second stage) - with -G when `negate` (the ECDSA form subtracts the generator's
-// term; the full-width coefficient is negated, it is split anyway); N terms in arrays of plane stride tstride
-constexpr uint32_t RLC_SUM_BLOCKS = 256;
-// (`as` has plane stride `stride`; a sub-range of a saved batch passes as + lo with the batch's stride)
-__global__ void __launch_bounds__(256)
-k_schnorr_rlc_sum(uint32_t n, size_t stride, const uint32_t* __restrict__ as, uint32_t* __restrict__ part,
-                  uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag, size_t N, size_t tstride,
-                  uint32_t negate) {
-  __shared__ uint32_t sh[256][8];
-  sc acc = sc_zero();
-  if (as) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)RLC_SUM_BLOCKS * 256) {
-      sc v;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v.v[w] = as[(size_t)w * stride + i];
-      acc = sc_add(acc, v);
-    }
-  } else if (threadIdx.x < RLC_SUM_BLOCKS) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) acc.v[w] = part[threadIdx.x * 8 + w];
-  }
-#pragma unroll
-  for (int w = 0; w < 8; ++w) sh[threadIdx.x][w] = acc.v[w];
-  __syncthreads();
-  for (uint32_t half = 128; half >= 1; half >>= 1) {
-    if (threadIdx.x < half) {
-      sc a, b;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) {
-        a.v[w] = sh[threadIdx.x][w];
-        b.v[w] = sh[threadIdx.x + half][w];
-      }
-      a = sc_add(a, b);
-#pragma unroll
-      for (int w = 0; w < 8; ++w) sh[threadIdx.x][w] = a.v[w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x != 0) return;
-  if (as) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) part[blockIdx.x * 8 + w] = sh[0][w];
-  } else {
-    sc tot;                                   // the generator's terms are the last two of the N
-#pragma unroll
-    for (int w = 0; w < 8; ++w) tot.v[w] = sh[0][w];
-    if (negate) tot = sc_neg(tot);
-    msm_store_split(scw, ptw, tstride, N - 2, N - 1, tot, FE_GX, FE_GY);
-    flag[N - 2] = 1;
-    flag[N - 1] = 1;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Locating the failing signatures of a rejected batch.  The terms of the whole
-// batch (coefficients, challenges times coefficients, lifted points: the expensive part of the
-// preparation) are kept; a sub-range [lo, lo + m) of the signatures is re-checked by gathering its
-// 3m terms into a fresh term array, summing its a_i s_i for the generator term and running the
-// multiscalar core on 3m + 2 terms.  The result is the range's error point E = sum of the
-// coefficients times the individual errors; E_right = E_parent - E_left, so every level costs one
-// multiscalar multiplication of half its parent's size.
-// Saved layout: s_scw [4][3n] (magnitudes), s_ptw [3n][16], s_flag [n], s_as [8][n].
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-k_rlc_gather(uint32_t lo, uint32_t m, uint32_t n, const uint32_t* __restrict__ s_scw, const uint32_t* __restrict__ s_ptw,
-             const uint8_t* __restrict__ s_flag, uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw,
-             uint8_t* __restrict__ flag) {
-  size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;     // destination term among the 3m
-  if (j >= 3 * (size_t)m) return;
-  const size_t part = j / m, i = j - part * m;            // 0: R terms, 1 and 2: the halves of the P terms
-  const size_t src = part * n + lo + i, N = 3 * (size_t)m + 2, NS = 3 * (size_t)n;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) scw[(size_t)w * N + j] = s_scw[(size_t)w * NS + src];
-  scw[(size_t)4 * N + j] = 0;
-  const uint4* a = reinterpret_cast<const uint4*>(s_ptw + src * 16);
-  uint4* b = reinterpret_cast<uint4*>(ptw + j * 16);
-  b[0] = a[0]; b[1] = a[1]; b[2] = a[2]; b[3] = a[3];
-  flag[j] = s_flag[lo + i];
-}
-// terms of the whole batch -> saved arrays (3n + 2 -> 3n: the generator terms are rebuilt per range)
-__global__ void __launch_bounds__(256)
-k_rlc_save(uint32_t n, const uint32_t* __restrict__ scw, const uint32_t* __restrict__ ptw, const uint8_t* __restrict__ flag,
-           uint32_t* __restrict__ s_scw, uint32_t* __restrict__ s_ptw, uint8_t* __restrict__ s_flag) {
-  size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= 3 * (size_t)n) return;
-  const size_t N = 3 * (size_t)n + 2, NS = 3 * (size_t)n;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) s_scw[(size_t)w * NS + j] = scw[(size_t)w * N + j];
-  const uint4* a = reinterpret_cast<const uint4*>(ptw + j * 16);
-  uint4* b = reinterpret_cast<uint4*>(s_ptw + j * 16);
-  b[0] = a[0]; b[1] = a[1]; b[2] = a[2]; b[3] = a[3];
-  if (j < n) s_flag[j] = flag[j];
-}
-// valid[lo + i] = ok-to-lift flag of signature lo + i (a range the combination has cleared)
-__global__ void __launch_bounds__(256)
-k_rlc_mark_valid(uint32_t lo, uint32_t m, const uint8_t* __restrict__ s_flag, uint8_t* __restrict__ valid) {
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < m) valid[lo + i] = s_flag[lo + i];
-}
-
+namespace {
 // Test hook (s2k_debug_msm_terms): given magnitudes, points and signs -> terms, as k_msm_parse and the whole-batch front ends
-// leave them.  flag 1: a point on the curve, 0: an all-zero record (the term is skipped), 2: anything else (status).
+// leave them.  The flags of msm_classify_record, but stricter about the identity: only an all-zero record is skipped, any other
+// that is no point is malformed (status).  It keeps its OWN COPY of the record rule for that difference: with the shared
+// function in front of the all-zero test its machine code came out different (882 instructions for 842).
 __global__ void __launch_bounds__(256)
 k_msm_debug_fill(uint32_t n, const uint8_t* __restrict__ mags, const uint8_t* __restrict__ points, const uint8_t* __restrict__ signs,
                  uint32_t* __restrict__ scw, uint32_t* __restrict__ ptw, uint8_t* __restrict__ flag, uint32_t* __restrict__ status) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint8_t* rec = points + i * 65;
-  uint8_t f = 0;
+  uint8_t f = TERM_SKIP;
   uint32_t x[8], y[8];
   if (rec[0] == 0x04) {
     load_be32_unaligned(x, rec + 1);
     load_be32_unaligned(y, rec + 33);
-    f = xy_on_curve_words(x, y) ? 1 : 2;
+    f = xy_on_curve_words(x, y) ? TERM_FINITE : TERM_MALFORMED;
   } else {
     for (int j = 0; j < 65; ++j)
-      if (rec[j]) f = 2;
+      if (rec[j]) f = TERM_MALFORMED;
   }
-  if (f == 2) atomicOr(status, 1u);
+  if (f == TERM_MALFORMED) atomicOr(status, 1u);
   flag[i] = f;
-  if (f != 1) return;
+  if (f != TERM_FINITE) return;
   sc k = sc_zero();
   const uint8_t* mg = mags + i * 16;
 #pragma unroll
@@ -1733,18 +1274,16 @@ k_msm_debug_fill(uint32_t n, const uint8_t* __restrict__ mags, const uint8_t* __
     k.v[w] = (uint32_t)mg[12 - 4 * w] << 24 | (uint32_t)mg[13 - 4 * w] << 16 | (uint32_t)mg[14 - 4 * w] << 8 | mg[15 - 4 * w];
   msm_store_term(scw, ptw, n, i, k, x, y, signs && signs[i]);
 }
-constexpr size_t MSM_DEBUG_TERMS_MAX = (size_t)1 << 22;     // what the hook lays out: 64 MiB of magnitudes, 272 MiB of records
-
 }  // namespace
 
-// (engine_internal.h) the launches of one sum, n > 0 inputs; the caller has entered the context and synchronises
+// (msm_internal.h) the launches of one sum, n > 0 inputs; the caller has entered the context and synchronises
 __attribute__((visibility("hidden"))) int s2k_internal_msm_enqueue(s2k_ctx* ctx, hipStream_t st, size_t n, const void* d_scalars, const void* d_points, void* d_out65,
                              uint32_t** d_status) {
   msm_ws m;
   int rc = msm_setup(ctx, 2 * n, 0, m);   // every input is two terms (endomorphism split)
   if (rc) return rc;
   msm_prof_mark(ctx, st, 0);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
+  HIP_TRY(ctx, msm_clear(ctx, st, m));
   // (the front end moves 275 MB in 0.075 ms - it is bound by that, not by its arithmetic: splitting it into a scalar kernel in
   // front of the sort and a point kernel beside it on a second stream was measured 0.03 ms SLOWER, profiles/r06_msm_attempts.txt)
   k_msm_parse<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, (const uint8_t*)d_scalars, (const uint8_t*)d_points, m.scw,
@@ -1880,7 +1419,7 @@ int s2k_debug_msm_terms(s2k_ctx* ctx, size_t nterms, const uint8_t* mags, const 
   HIP_TRY(ctx, hipMemcpyAsync(d[0], mags, n * 16, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d[1], points, n * 65, hipMemcpyHostToDevice, st));
   if (signs) HIP_TRY(ctx, hipMemcpyAsync(d[2], signs, n, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
+  HIP_TRY(ctx, msm_clear(ctx, st, m));
   k_msm_debug_fill<<<blocks_for(n), 256, 0, st>>>((uint32_t)n, d[0], d[1], signs ? d[2] : nullptr, m.scw, m.ptw, m.flag, m.status);
   HIP_TRY(ctx, hipGetLastError());
   rc = msm_core(ctx, st, n, m, d[3]);
@@ -1896,21 +1435,15 @@ int s2k_debug_msm_terms(s2k_ctx* ctx, size_t nterms, const uint8_t* mags, const 
   HIP_TRY(ctx, hipStreamSynchronize(st));
   ctx->have_last = false;   // the stream has been synchronised: nothing of this context is in flight
   if (h_status) return fail(ctx, S2K_ERR_ARG, "a point record is neither a point on the curve nor all zero");
-  // the geometry as msm_setup chose it.  L_A, nlanes and fold16 are NOT observed: they restate msm_core's formulas for the
-  // one-part flow (S2K_MSM_SPLIT_WINDOW unset) and read S2K_MSM_OLD_REDUCE afresh where the core caches it, so a change of
-  // msm_core has to be repeated here - the tests use them to know where range borders fall, the sums and the sort's arrays
-  // are what they check the core by
-  const size_t pairs = n * (size_t)g.nw, target = msm_lanes_target();
-  size_t la = (pairs + target - 1) / target;
-  if (la < MSM_L_MIN) la = MSM_L_MIN;
+  // the geometry as msm_setup chose it, and the cut as msm_core ran it
   geom[0] = g.c;
   geom[1] = g.nw;
   geom[2] = g.nb;
   geom[3] = g.nslot;
   geom[4] = (uint32_t)m.nkeys;
-  geom[5] = (uint32_t)la;
-  geom[6] = (uint32_t)((pairs + la - 1) / la);
-  geom[7] = g.c == 16 && !getenv("S2K_MSM_OLD_REDUCE") && m.nslots + 1 > FOLD_END ? 1u : 0u;
+  geom[5] = m.ran_L_A;
+  geom[6] = m.ran_nlanes;
+  geom[7] = m.ran_fold16 ? 1u : 0u;
   geom[8] = h_big;
   geom[9] = h_total;
   if (offsets) {
@@ -1919,670 +1452,6 @@ int s2k_debug_msm_terms(s2k_ctx* ctx, size_t nterms, const uint8_t* mags, const 
     if (h_total) HIP_TRY(ctx, hipMemcpy(list, m.list, (size_t)h_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
   return S2K_OK;
-}
-
-// SHA-256 on the host (FIPS 180-4), for mixing the caller's seed with operating-system randomness
-static void host_sha256(uint8_t out[32], const uint8_t* msg, size_t len) {
-  static const uint32_t K[64] = {
-      0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
-      0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc,
-      0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147,
-      0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-      0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08,
-      0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208,
-      0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  uint8_t buf[128];
-  size_t full = len / 64, rem = len % 64;
-  auto block = [&](const uint8_t* b) {
-    uint32_t w[64];
-    for (int i = 0; i < 16; ++i) w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
-    for (int i = 16; i < 64; ++i) {
-      uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-      w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-    }
-    uint32_t a = st[0], bb = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], hh = st[7];
-    for (int i = 0; i < 64; ++i) {
-      uint32_t S1 = rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25), ch = (e & f) ^ (~e & g), t1 = hh + S1 + ch + K[i] + w[i];
-      uint32_t S0 = rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22), mj = (a & bb) ^ (a & c) ^ (bb & c), t2 = S0 + mj;
-      hh = g; g = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + t2;
-    }
-    st[0] += a; st[1] += bb; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += hh;
-  };
-  for (size_t i = 0; i < full; ++i) block(msg + 64 * i);
-  memset(buf, 0, sizeof buf);
-  memcpy(buf, msg + 64 * full, rem);
-  buf[rem] = 0x80;
-  size_t padded = rem + 9 <= 64 ? 64 : 128;
-  uint64_t bits = (uint64_t)len * 8;
-  for (int i = 0; i < 8; ++i) buf[padded - 1 - i] = (uint8_t)(bits >> (8 * i));
-  block(buf);
-  if (padded == 128) block(buf + 64);
-  for (int i = 0; i < 8; ++i) {
-    out[4 * i] = (uint8_t)(st[i] >> 24); out[4 * i + 1] = (uint8_t)(st[i] >> 16); out[4 * i + 2] = (uint8_t)(st[i] >> 8); out[4 * i + 3] = (uint8_t)st[i];
-  }
-}
-
-// ct_cpu.cpp: out = a - b on 65-byte records (host; public data)
-extern "C" __attribute__((visibility("hidden"))) int s2k_internal_point_sub65(const uint8_t* a, const uint8_t* b, uint8_t* out);
-
-static int stage_schnorr(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets, size_t msg_len,
-                         const uint8_t* sig, uint8_t* d[5], hipStream_t* st_out);
-
-// whole-batch combination: preparation, generator term, multiscalar core; leaves the 129 bytes
-// [status word .. 64: error point record] in h.  The caller's seed is mixed with 32 bytes from the
-// operating system's CSPRNG, so a reused or predictable seed does not weaken the check (the
-// coefficients have to be unpredictable to whoever chose the signatures).
-enum rlc_mode {
-  RLC_AGGREGATED,        // one term pair per distinct key; combination evaluated
-  RLC_PLAIN_TERMS_ONLY   // one term pair per signature (the layout the bisection gathers from); terms only
-};
-// The two signature schemes that are checked this way share everything behind their front end: the term arrays and
-// their two layouts, the grouping of the keys, the key terms, the generator's term, the multiscalar core, the bisection.
-enum rlc_scheme { RLC_BIP340, RLC_ECDSA };
-struct rlc_batch {        // the device pointers of one batch
-  rlc_scheme scheme;
-  const uint8_t* key;     // BIP-340: x-only keys, 32 bytes each; ECDSA: X || Y, 64 bytes each
-  // BIP-340
-  const uint8_t* msgs;
-  const uint64_t* msg_offsets;
-  size_t msg_len;
-  const uint8_t* sig;
-  // ECDSA, recoverable signatures
-  const uint8_t *dig, *r, *s, *recid;
-  uint32_t flags;         // S2K_ECDSA_REJECT_MALLEABLE
-};
-static rlc_batch rlc_batch_bip340(const void* d_pk, const void* d_msgs, const void* d_msg_offsets, size_t msg_len, const void* d_sig) {
-  rlc_batch b{};
-  b.scheme = RLC_BIP340;
-  b.key = (const uint8_t*)d_pk;
-  b.msgs = (const uint8_t*)d_msgs;
-  b.msg_offsets = (const uint64_t*)d_msg_offsets;
-  b.msg_len = msg_len;
-  b.sig = (const uint8_t*)d_sig;
-  return b;
-}
-static rlc_batch rlc_batch_ecdsa(const void* d_pub, const void* d_dig, const void* d_r, const void* d_s, const void* d_recid, uint32_t flags) {
-  rlc_batch b{};
-  b.scheme = RLC_ECDSA;
-  b.key = (const uint8_t*)d_pub;
-  b.dig = (const uint8_t*)d_dig;
-  b.r = (const uint8_t*)d_r;
-  b.s = (const uint8_t*)d_s;
-  b.recid = (const uint8_t*)d_recid;
-  b.flags = flags;
-  return b;
-}
-// `seed_be`: the coefficient key; derived here from seed32 and OS randomness when `fresh`, otherwise taken
-// as it is (a second pass over the same batch must use the coefficients of the first).
-static int rlc_run_full(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, msm_ws& m,
-                        uint32_t** as_out, uint8_t h[192], rlc_mode mode, rlc_key& seed_be, bool fresh) {
-  const bool ecdsa = in.scheme == RLC_ECDSA;
-  if (fresh) {
-    uint8_t mix[64], key[32];
-    memcpy(mix, seed32, 32);
-    if (getrandom(mix + 32, 32, 0) != 32) return fail(ctx, S2K_ERR_HIP, "getrandom failed: no randomness for the batch coefficients");
-    host_sha256(key, mix, 64);
-    for (int j = 0; j < 8; ++j)
-      seed_be.w[j] = ((uint32_t)key[4 * j] << 24) | ((uint32_t)key[4 * j + 1] << 16) | ((uint32_t)key[4 * j + 2] << 8) | key[4 * j + 3];
-  }
-  // The workspace is carved for the plain form's 3n + 2 terms in both modes (the aggregated form has fewer, but how many
-  // is known only once the keys are grouped, and the preparation must not wait for that): `cap` is the plane stride.
-  const size_t cap = 3 * n + 2;
-  size_t N = cap;
-  // aux: 256 bytes | partial sums of the generator's coefficient | a_i s_i planes | a_i e_i records, lifted keys (aggregated)
-  // (ECDSA: a_i u1_i planes, a_i u2_i records, the keys' Y)
-  const size_t as_bytes = n * 8 * 4, kstride = (n + 63) & ~(size_t)63;
-  int rc = msm_setup(ctx, cap, 256 + RLC_SUM_BLOCKS * 32 + as_bytes + (mode == RLC_AGGREGATED ? as_bytes + kstride * 36 : 0), m);
-  if (rc) return rc;
-  uint32_t* sum_part = (uint32_t*)(m.aux + 256);
-  uint32_t* as = (uint32_t*)(m.aux + 256 + RLC_SUM_BLOCKS * 32);
-  uint32_t* ae = as + n * 8;
-  uint32_t* ky = ae + n * 8;
-  uint8_t* kok = (uint8_t*)(ky + kstride * 8);
-  msm_prof_mark(ctx, st, 0);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, m.zero_bytes, st));
-  if (mode == RLC_AGGREGATED) {
-    // Two streams.  Caller's: the per-signature preparation (challenge hash, square root of r, coefficients: 1.2 ms of
-    // multiplier time for 2^20 signatures).  Second: the grouping of the keys (hash table, latency bound; it ends with
-    // the one host read of the call, the group count) and one square root per DISTINCT key.  They meet at the key terms.
-    rc = ctx_aux_streams(ctx);
-    if (rc) return rc;
-    rc = s2k_internal_key_reserve32(ctx, n);   // the grouping arrays are grown before the fork (growing synchronises the device)
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(m.flag, 0, cap, st));     // the key terms set their own flags
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, st));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, ctx->ev_fork, 0));
-    if (ecdsa)
-      k_ecdsa_rlc_prep<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.dig, in.r, in.s, in.recid, in.flags, seed_be,
-                                                            m.scw, m.ptw, m.flag, as, ae, m.status);
-    else
-      k_schnorr_rlc_prep<true><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.sig, in.msgs, in.msg_offsets,
-                                                              (uint32_t)in.msg_len, seed_be, m.scw, m.ptw, m.flag, as, ae, m.status);
-    key_groups32 kg;
-    rc = hipGetLastError() == hipSuccess ? S2K_OK : fail(ctx, S2K_ERR_HIP, "whole-batch preparation: launch failed");
-    if (rc == S2K_OK) rc = s2k_internal_key_group_all(ctx, n, in.key, ecdsa ? 64 : 32, ctx->s_aux, &kg);   // (synchronises the second stream)
-    uint32_t lanes = 0;
-    if (rc == S2K_OK) {
-      lanes = kg.ngroups + kg.nleft;
-      N = n + 2 * (size_t)lanes + 2;
-      if (ecdsa)
-        k_ecdsa_key_check<<<(lanes + 63) / 64, 64, 0, ctx->s_aux>>>(kg.ngroups, kg.nleft, kstride, kg.vslot, kg.rep, kg.left, in.key, ky, kok);
-      else
-        k_rlc_key_lift<<<(lanes + 63) / 64, 64, 0, ctx->s_aux>>>(kg.ngroups, kg.nleft, kstride, kg.vslot, kg.rep, kg.left, in.key, ky, kok);
-      if (hipGetLastError() != hipSuccess) rc = fail(ctx, S2K_ERR_HIP, "whole-batch key check: launch failed");
-    }
-    ctx_aux_join(ctx, st);            // error or not: nothing stays in flight on the second stream alone
-    if (rc) {
-      (void)ctx_leave(ctx, st);
-      return rc;
-    }
-    if (ecdsa)
-      k_rlc_key_terms<64><<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)n, cap, kg.ngroups, kg.nleft, kg.vslot, kg.rep, kg.cnt, kg.base, kg.tix,
-                                                            kg.perm, kg.left, in.key, kstride, ky, kok, ae, as, m.scw, m.ptw, m.flag, m.status);
-    else
-      k_rlc_key_terms<32><<<(lanes + 63) / 64, 64, 0, st>>>((uint32_t)n, cap, kg.ngroups, kg.nleft, kg.vslot, kg.rep, kg.cnt, kg.base, kg.tix,
-                                                            kg.perm, kg.left, in.key, kstride, ky, kok, ae, as, m.scw, m.ptw, m.flag, m.status);
-    HIP_TRY(ctx, hipGetLastError());
-  } else {
-    if (ecdsa)
-      k_ecdsa_rlc_prep<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.dig, in.r, in.s, in.recid, in.flags, seed_be,
-                                                             m.scw, m.ptw, m.flag, as, nullptr, m.status);
-    else
-      k_schnorr_rlc_prep<false><<<blocks_for(n), 256, 0, st>>>((uint32_t)n, cap, in.key, in.sig, in.msgs, in.msg_offsets,
-                                                               (uint32_t)in.msg_len, seed_be, m.scw, m.ptw, m.flag, as, nullptr, m.status);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  if (as_out) *as_out = as;
-  if (mode == RLC_PLAIN_TERMS_ONLY) return S2K_OK;
-  k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>((uint32_t)n, n, as, sum_part, m.scw, m.ptw, m.flag, N, cap, 0u);
-  k_schnorr_rlc_sum<<<1, 256, 0, st>>>((uint32_t)n, n, nullptr, sum_part, m.scw, m.ptw, m.flag, N, cap, ecdsa ? 1u : 0u);
-  HIP_TRY(ctx, hipGetLastError());
-  uint8_t* d_out = (uint8_t*)m.status + 64;   // 65-byte record inside the 256-byte status slot
-  rc = msm_core(ctx, st, N, m, d_out, /*affine=*/as_out != nullptr);   // the verdict alone needs no coordinates; the bisection does
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(h, m.status, 64 + 65, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  ctx->have_last = false;
-  return S2K_OK;
-}
-
-// the whole-batch verdict of a checked, non-empty batch (the context entered)
-static int rlc_verdict(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, int* all_valid) {
-  msm_ws m;
-  uint8_t h[192];
-  rlc_key coeff;
-  int rc = rlc_run_full(ctx, st, n, in, seed32, m, nullptr, h, RLC_AGGREGATED, coeff, true);
-  if (rc) return rc;
-  uint32_t h_status;
-  memcpy(&h_status, h, 4);
-  *all_valid = (h_status == 0 && h[64] == 0x00) ? 1 : 0;
-  return S2K_OK;
-}
-
-int s2k_schnorr_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pk, const void* d_msgs,
-                                        const void* d_msg_offsets, size_t msg_len, const void* d_sig,
-                                        const uint8_t* seed32, int* all_valid, void* hip_stream) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  *all_valid = 0;
-  if (n == 0) {
-    *all_valid = 1;   // an empty batch has no failing signature
-    return S2K_OK;
-  }
-  if (!d_pk || !d_sig || (!d_msgs && (d_msg_offsets || msg_len))) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  int rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  return rlc_verdict(ctx, st, n, rlc_batch_bip340(d_pk, d_msgs, d_msg_offsets, msg_len, d_sig), seed32, all_valid);
-}
-
-// The kept terms of a batch in the plain form (the context's rlc_save): what a sub-range is gathered from, since the
-// sub-range runs re-carve the multiscalar workspace.  `leaf`: leaf_bytes of scratch behind them (the ECDSA leaf verifier's).
-struct rlc_saved {
-  size_t n;
-  uint32_t *scw, *ptw, *as;
-  uint8_t *flag, *leaf;
-};
-static size_t rlc_pad(size_t b) { return (b + 255) & ~(size_t)255; }
-// terms, flags and a_i s_i planes of the plain form as rlc_run_full left them in `m` / `as` -> sv
-static int rlc_keep_terms(s2k_ctx* ctx, hipStream_t st, size_t n, const msm_ws& m, const uint32_t* as, size_t leaf_bytes, rlc_saved& sv) {
-  const size_t NS = 3 * n;
-  const size_t o_scw = 0, o_ptw = rlc_pad(NS * 4 * 4), o_flag = o_ptw + rlc_pad(NS * 16 * 4), o_as = o_flag + rlc_pad(n),
-               o_leaf = o_as + rlc_pad(n * 8 * 4), total = o_leaf + leaf_bytes;
-  int rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, total);
-  if (rc) return rc;
-  uint8_t* base = (uint8_t*)ctx->rlc_save;
-  sv.n = n;
-  sv.scw = (uint32_t*)(base + o_scw);
-  sv.ptw = (uint32_t*)(base + o_ptw);
-  sv.as = (uint32_t*)(base + o_as);
-  sv.flag = base + o_flag;
-  sv.leaf = base + o_leaf;
-  k_rlc_save<<<blocks_for(NS), 256, 0, st>>>((uint32_t)n, m.scw, m.ptw, m.flag, sv.scw, sv.ptw, sv.flag);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(sv.as, as, n * 8 * 4, hipMemcpyDeviceToDevice, st));
-  return S2K_OK;
-}
-// error point of the sub-range [lo, lo + cnt) of the kept batch: its 3 cnt terms gathered, its generator term summed, the
-// multiscalar core on 3 cnt + 2 terms; E on the host, the stream synchronised
-static int rlc_sub_range(s2k_ctx* ctx, hipStream_t st, const rlc_saved& sv, bool ecdsa, uint32_t lo, uint32_t cnt, uint8_t E[65]) {
-  msm_ws w;
-  const size_t N = 3 * (size_t)cnt + 2;
-  int r = msm_setup(ctx, N, 256 + RLC_SUM_BLOCKS * 32, w);
-  if (r) return r;
-  uint32_t* sum_part = (uint32_t*)w.aux;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->msm_ws, 0, w.zero_bytes, st));
-  k_rlc_gather<<<blocks_for(3 * (size_t)cnt), 256, 0, st>>>(lo, cnt, (uint32_t)sv.n, sv.scw, sv.ptw, sv.flag, w.scw, w.ptw, w.flag);
-  k_schnorr_rlc_sum<<<RLC_SUM_BLOCKS, 256, 0, st>>>(cnt, sv.n, sv.as + lo, sum_part, w.scw, w.ptw, w.flag, N, N, 0u);
-  k_schnorr_rlc_sum<<<1, 256, 0, st>>>(cnt, sv.n, nullptr, sum_part, w.scw, w.ptw, w.flag, N, N, ecdsa ? 1u : 0u);
-  HIP_TRY(ctx, hipGetLastError());
-  uint8_t* d_out = (uint8_t*)w.status + 64;
-  r = msm_core(ctx, st, N, w, d_out);
-  if (r) return r;
-  HIP_TRY(ctx, hipMemcpyAsync(E, d_out, 65, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return S2K_OK;
-}
-
-// Per-signature verdicts at the price of the whole-batch check when (as usual) everything verifies:
-// one combination over the batch; if it is rejected, the failing signatures are located by
-// bisection on the kept terms (header).  stats (host, optional): [0] sub-range multiscalar
-// multiplications, [1] signatures verified one by one, [2] levels descended, [3] 1 = gave up
-// bisecting (many failing ranges) and verified the rest one by one.
-// The driver behind both schemes' bisect calls (a checked, non-empty batch; the context entered).
-static int rlc_bisect(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* seed32, uint8_t* valid, uint32_t* stats) {
-  const bool ecdsa = in.scheme == RLC_ECDSA;
-  int rc;
-  // Below LEAF signatures a range is verified signature by signature: a combination costs at least the
-  // multiscalar floor (0.75 ms + preparation), per-signature verification 0.56 ms per 2^16 signatures.
-  constexpr uint32_t LEAF = 1u << 17;
-  constexpr size_t MAX_FAILING = 8;        // more failing ranges than this on one level: stop bisecting
-  // The leaf verifier is the ground truth the combination is allowed to skip.  BIP-340: s2k_schnorr_verify_batch.  ECDSA: the
-  // keys recovered by s2k_ecdsa_recover_batch_device into `leaf` (65-byte records, then the ok bytes; it lies behind the kept
-  // terms in rlc_save, sized for the whole batch: once bisecting is abandoned a range can be any size) and k_ecdsa_rlc_leaf.
-  const size_t leaf_bytes = ecdsa ? rlc_pad(n * 65) + rlc_pad(n) : 0;
-  uint8_t* leaf = nullptr;
-  auto verify_each = [&](uint32_t lo, uint32_t cnt) -> int {
-    if (stats) stats[1] += cnt;
-    if (!ecdsa)
-      return s2k_schnorr_verify_batch_device(ctx, cnt, in.key + (size_t)lo * 32,
-                                             in.msg_offsets ? in.msgs : (in.msgs ? in.msgs + (size_t)lo * in.msg_len : nullptr),
-                                             in.msg_offsets ? in.msg_offsets + lo : nullptr, in.msg_len, in.sig + (size_t)lo * 64, 0, valid + lo, st);
-    uint8_t *rec = leaf, *okb = leaf + rlc_pad(n * 65);
-    int r = s2k_ecdsa_recover_batch_device(ctx, cnt, in.dig + (size_t)lo * 32, in.r + (size_t)lo * 32, in.s + (size_t)lo * 32, in.recid + lo,
-                                           0u, rec, okb, st);
-    if (r) return r;
-    k_ecdsa_rlc_leaf<<<blocks_for(cnt), 256, 0, st>>>(cnt, in.key + (size_t)lo * 64, in.s + (size_t)lo * 32, in.flags, rec, okb, valid + lo);
-    HIP_TRY(ctx, hipGetLastError());
-    return ctx_leave(ctx, st);
-  };
-  if (n <= LEAF) {
-    if (ecdsa) {
-      rc = ctx_reserve(ctx, &ctx->rlc_save, &ctx->rlc_save_bytes, leaf_bytes);
-      if (rc) return rc;
-      leaf = (uint8_t*)ctx->rlc_save;
-    }
-    return verify_each(0, (uint32_t)n);
-  }
-
-  msm_ws m;
-  uint32_t* as = nullptr;
-  uint8_t h[192];
-  rlc_key coeff;
-  rc = rlc_run_full(ctx, st, n, in, seed32, m, &as, h, RLC_AGGREGATED, coeff, true);
-  if (rc) return rc;
-  if (h[64] == 0x00) {   // the combination of every liftable signature vanishes: those are all valid
-    k_rlc_mark_valid<<<blocks_for(n), 256, 0, st>>>(0u, (uint32_t)n, m.flag, valid);
-    HIP_TRY(ctx, hipGetLastError());
-    return ctx_leave(ctx, st);
-  }
-  // Rejected.  The bisection gathers per-signature terms, so the plain form is prepared now, with the
-  // coefficients of the pass that has just failed: its error point h + 64 is the plain form's as well.
-  {
-    uint8_t h2[192];
-    rc = rlc_run_full(ctx, st, n, in, seed32, m, &as, h2, RLC_PLAIN_TERMS_ONLY, coeff, false);
-    if (rc) return rc;
-  }
-  // keep the terms: the sub-range runs re-carve the multiscalar workspace
-  rlc_saved sv;
-  rc = rlc_keep_terms(ctx, st, n, m, as, leaf_bytes, sv);
-  if (rc) return rc;
-  leaf = sv.leaf;
-  const uint8_t* s_flag = sv.flag;
-
-  // error point of a sub-range
-  auto sub = [&](uint32_t lo, uint32_t cnt, uint8_t E[65]) -> int {
-    int r = rlc_sub_range(ctx, st, sv, ecdsa, lo, cnt, E);
-    if (r == S2K_OK && stats) stats[0] += 1;
-    return r;
-  };
-  struct range {
-    uint32_t lo, cnt;
-    uint8_t E[65];
-  };
-  std::vector<range> cur(1), next;
-  cur[0].lo = 0;
-  cur[0].cnt = (uint32_t)n;
-  memcpy(cur[0].E, h + 64, 65);
-  while (!cur.empty()) {
-    if (cur.size() > MAX_FAILING) {   // errors everywhere: bisection would cost more than it saves
-      if (stats) stats[3] = 1;
-      for (const range& r : cur) {
-        rc = verify_each(r.lo, r.cnt);
-        if (rc) return rc;
-      }
-      break;
-    }
-    next.clear();
-    for (const range& r : cur) {
-      if (r.cnt <= LEAF) {
-        rc = verify_each(r.lo, r.cnt);
-        if (rc) return rc;
-        continue;
-      }
-      range left, right;
-      left.lo = r.lo;
-      left.cnt = r.cnt / 2;
-      right.lo = r.lo + left.cnt;
-      right.cnt = r.cnt - left.cnt;
-      rc = sub(left.lo, left.cnt, left.E);
-      if (rc) return rc;
-      if (s2k_internal_point_sub65(r.E, left.E, right.E) != 0) return fail(ctx, S2K_ERR_HIP, "internal: bad error point");
-      for (const range* h2 : {&left, &right}) {
-        if (h2->E[0] == 0x00) {
-          k_rlc_mark_valid<<<blocks_for(h2->cnt), 256, 0, st>>>(h2->lo, h2->cnt, s_flag, valid);
-          HIP_TRY(ctx, hipGetLastError());
-        } else {
-          next.push_back(*h2);
-        }
-      }
-    }
-    if (stats && !next.empty()) stats[2] += 1;
-    cur.swap(next);
-  }
-  return ctx_leave(ctx, st);
-}
-
-int s2k_schnorr_verify_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d_pk, const void* d_msgs,
-                                           const void* d_msg_offsets, size_t msg_len, const void* d_sig,
-                                           const uint8_t* seed32, void* d_valid, uint32_t* stats, void* hip_stream) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (n == 0) return S2K_OK;
-  if (!d_pk || !d_sig || !d_valid || (!d_msgs && (d_msg_offsets || msg_len))) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  int rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  return rlc_bisect(ctx, st, n, rlc_batch_bip340(d_pk, d_msgs, d_msg_offsets, msg_len, d_sig), seed32, (uint8_t*)d_valid, stats);
-}
-
-int s2k_schnorr_verify_batch_bisect(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets,
-                                    size_t msg_len, const uint8_t* sig, const uint8_t* seed32, uint8_t* valid, uint32_t* stats) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (n == 0) return S2K_OK;
-  if (!pk || !sig || !valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  // before anything is staged: n * msg_len bytes would be reserved and copied from `msgs`
-  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  uint8_t* d[5];
-  hipStream_t st;
-  s2k_phase_guard phase(ctx->device, n * 128);           // (two verifiers on two threads: engine_internal.h)
-  int rc = stage_schnorr(ctx, n, pk, msgs, msg_offsets, msg_len, sig, d, &st);
-  if (rc) return rc;
-  HIP_TRY(ctx, phase.landed(st));
-  rc = s2k_schnorr_verify_batch_bisect_device(ctx, n, d[0], d[1], msg_offsets ? d[2] : nullptr, msg_len, d[3], seed32, d[4], stats, st);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(valid, d[4], n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  ctx->have_last = false;
-  return S2K_OK;
-}
-
-// stage (pk, msgs, offsets, sig [, valid]) of a BIP-340 batch in the context's buffers on its compute stream
-static int stage_schnorr(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets, size_t msg_len,
-                         const uint8_t* sig, uint8_t* d[5], hipStream_t* st_out) {
-  size_t total = msg_offsets ? (size_t)msg_offsets[n] : n * msg_len;
-  if (total && !msgs) return fail(ctx, S2K_ERR_ARG, "null message buffer");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ctx_streams(ctx);
-  if (rc) return rc;
-  const size_t sizes[5] = {n * 32, total ? total : 16, (n + 1) * sizeof(uint64_t), n * 64, n};
-  rc = ctx_stage(ctx, sizes, 5, d);
-  if (rc) return rc;
-  hipStream_t st = ctx->s_comp;
-  HIP_TRY(ctx, hipMemcpyAsync(d[0], pk, n * 32, hipMemcpyHostToDevice, st));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(d[1], msgs, total, hipMemcpyHostToDevice, st));
-  if (msg_offsets) HIP_TRY(ctx, hipMemcpyAsync(d[2], msg_offsets, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d[3], sig, n * 64, hipMemcpyHostToDevice, st));
-  *st_out = st;
-  return S2K_OK;
-}
-
-int s2k_schnorr_batch_verify_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs,
-                                 const uint64_t* msg_offsets, size_t msg_len, const uint8_t* sig,
-                                 const uint8_t* seed32, int* all_valid) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  *all_valid = 0;       // (a refusal below leaves no verdict of an earlier call behind)
-  if (n == 0) {
-    *all_valid = 1;
-    return S2K_OK;
-  }
-  if (!pk || !sig) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  // before anything is staged: n * msg_len bytes would be reserved and copied from `msgs`
-  if (n > 0x0fffffffu || msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  uint8_t* d[5];
-  hipStream_t st;
-  s2k_phase_guard phase(ctx->device, n * 128);           // (two verifiers on two threads: engine_internal.h)
-  int rc = stage_schnorr(ctx, n, pk, msgs, msg_offsets, msg_len, sig, d, &st);
-  if (rc) return rc;
-  HIP_TRY(ctx, phase.landed(st));
-  return s2k_schnorr_batch_verify_rlc_device(ctx, n, d[0], d[1], msg_offsets ? d[2] : nullptr, msg_len, d[3], seed32, all_valid, st);
-}
-
-// ---- recoverable ECDSA signatures (header: the contract; above: k_ecdsa_rlc_prep) ----
-// refusals shared by the four entry points: S2K_ERR_ARG before any launch
-static int ecdsa_rlc_check_args(s2k_ctx* ctx, size_t n, const void* pub, const void* dig, const void* r, const void* s, const void* recid,
-                                uint32_t flags) {
-  if (!pub || !dig || !r || !s || !recid) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  if (n > 0x0fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  if (flags & ~S2K_ECDSA_REJECT_MALLEABLE) return fail(ctx, S2K_ERR_ARG, "unknown flag bits (S2K_ECDSA_REJECT_MALLEABLE only)");
-  return S2K_OK;
-}
-
-int s2k_ecdsa_batch_verify_rlc_device(s2k_ctx* ctx, size_t n, const void* d_pub, const void* d_dig, const void* d_r, const void* d_s,
-                                      const void* d_recid, uint32_t flags, const uint8_t* seed32, int* all_valid, void* hip_stream) {
-  if (all_valid) *all_valid = 0;
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  int rc = ecdsa_rlc_check_args(ctx, n, d_pub, d_dig, d_r, d_s, d_recid, flags);
-  if (rc) return rc;
-  if (n == 0) {
-    *all_valid = 1;   // an empty batch has no failing item
-    return S2K_OK;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  return rlc_verdict(ctx, st, n, rlc_batch_ecdsa(d_pub, d_dig, d_r, d_s, d_recid, flags), seed32, all_valid);
-}
-
-int s2k_ecdsa_verify_recoverable_batch_bisect_device(s2k_ctx* ctx, size_t n, const void* d_pub, const void* d_dig, const void* d_r,
-                                                     const void* d_s, const void* d_recid, uint32_t flags, const uint8_t* seed32,
-                                                     void* d_valid, uint32_t* stats, void* hip_stream) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!seed32 || !d_valid) return fail(ctx, S2K_ERR_ARG, "null argument");
-  int rc = ecdsa_rlc_check_args(ctx, n, d_pub, d_dig, d_r, d_s, d_recid, flags);
-  if (rc) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (n == 0) return S2K_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)hip_stream;
-  rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  return rlc_bisect(ctx, st, n, rlc_batch_ecdsa(d_pub, d_dig, d_r, d_s, d_recid, flags), seed32, (uint8_t*)d_valid, stats);
-}
-
-// stage (pub, digest, r, s, recovery id [, valid]) of a batch in the context's buffers on its compute stream
-static int stage_ecdsa_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
-                           const uint8_t* recid, uint8_t* d[6], hipStream_t* st_out) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ctx_streams(ctx);
-  if (rc) return rc;
-  const size_t sizes[6] = {n * 64, n * 32, n * 32, n * 32, n, n};
-  rc = ctx_stage(ctx, sizes, 6, d);
-  if (rc) return rc;
-  hipStream_t st = ctx->s_comp;
-  const uint8_t* src[5] = {pub, dig, r, s, recid};
-  for (int k = 0; k < 5; ++k) HIP_TRY(ctx, hipMemcpyAsync(d[k], src[k], sizes[k], hipMemcpyHostToDevice, st));
-  *st_out = st;
-  return S2K_OK;
-}
-
-int s2k_ecdsa_batch_verify_rlc(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
-                               const uint8_t* recid, uint32_t flags, const uint8_t* seed32, int* all_valid) {
-  if (all_valid) *all_valid = 0;
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!all_valid || !seed32) return fail(ctx, S2K_ERR_ARG, "null argument");
-  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
-  if (rc) return rc;
-  if (n == 0) {
-    *all_valid = 1;
-    return S2K_OK;
-  }
-  uint8_t* d[6];
-  hipStream_t st;
-  s2k_phase_guard phase(ctx->device, n * 161);           // (two verifiers on two threads: engine_internal.h)
-  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
-  if (rc) return rc;
-  HIP_TRY(ctx, phase.landed(st));
-  return s2k_ecdsa_batch_verify_rlc_device(ctx, n, d[0], d[1], d[2], d[3], d[4], flags, seed32, all_valid, st);
-}
-
-int s2k_ecdsa_verify_recoverable_batch_bisect(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r,
-                                              const uint8_t* s, const uint8_t* recid, uint32_t flags, const uint8_t* seed32,
-                                              uint8_t* valid, uint32_t* stats) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!seed32 || !valid) return fail(ctx, S2K_ERR_ARG, "null argument");
-  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
-  if (rc) return rc;
-  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  if (n == 0) return S2K_OK;
-  uint8_t* d[6];
-  hipStream_t st;
-  s2k_phase_guard phase(ctx->device, n * 161);           // (two verifiers on two threads: engine_internal.h)
-  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
-  if (rc) return rc;
-  HIP_TRY(ctx, phase.landed(st));
-  rc = s2k_ecdsa_verify_recoverable_batch_bisect_device(ctx, n, d[0], d[1], d[2], d[3], d[4], flags, seed32, d[5], stats, st);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(valid, d[5], n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  ctx->have_last = false;
-  return S2K_OK;
-}
-
-// ---- test hooks: the error point of a whole-batch check under a GIVEN coefficient key (see the header) ----
-// (a staged, checked batch; the context entered).  form 0: what rlc_verdict runs, with the affine record of the bisect call's
-// first pass; form 1: the plain-form terms kept and the sub-range [lo, lo + cnt) summed, by the functions rlc_bisect runs.
-static int rlc_debug_point(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* key32, int form, size_t lo,
-                           size_t cnt, uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
-  rlc_key coeff;
-  for (int j = 0; j < 8; ++j)
-    coeff.w[j] = ((uint32_t)key32[4 * j] << 24) | ((uint32_t)key32[4 * j + 1] << 16) | ((uint32_t)key32[4 * j + 2] << 8) | key32[4 * j + 3];
-  msm_ws m;
-  uint32_t* as = nullptr;
-  uint8_t h[192];
-  const uint8_t* d_flag;
-  if (form == 0) {
-    int rc = rlc_run_full(ctx, st, n, in, key32, m, &as, h, RLC_AGGREGATED, coeff, false);
-    if (rc) return rc;
-    memcpy(status, h, 4);
-    memcpy(out65, h + 64, 65);
-    d_flag = m.flag;
-  } else {
-    int rc = rlc_run_full(ctx, st, n, in, key32, m, &as, h, RLC_PLAIN_TERMS_ONLY, coeff, false);
-    if (rc) return rc;
-    // the preparation's word, over the whole batch: the sub-range step re-carves the workspace and zeroes it
-    HIP_TRY(ctx, hipMemcpyAsync(status, m.status, 4, hipMemcpyDeviceToHost, st));
-    rlc_saved sv;
-    rc = rlc_keep_terms(ctx, st, n, m, as, 0, sv);
-    if (rc) return rc;
-    rc = rlc_sub_range(ctx, st, sv, in.scheme == RLC_ECDSA, (uint32_t)lo, (uint32_t)cnt, out65);
-    if (rc) return rc;
-    d_flag = sv.flag;
-  }
-  if (in_comb) HIP_TRY(ctx, hipMemcpyAsync(in_comb, d_flag, n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return S2K_OK;
-}
-static int rlc_debug_check_args(s2k_ctx* ctx, size_t n, const void* key32, int form, size_t lo, size_t cnt, const void* out65,
-                                const void* status) {
-  if (!key32 || !out65 || !status) return fail(ctx, S2K_ERR_ARG, "null argument");
-  if (n == 0 || n > MSM_DEBUG_TERMS_MAX) return fail(ctx, S2K_ERR_ARG, "batch size outside 1 .. 2^22");
-  if (form != 0 && form != 1) return fail(ctx, S2K_ERR_ARG, "form must be 0 (aggregated) or 1 (plain, sub-range)");
-  if (form == 0 ? (lo != 0 || cnt != n) : (cnt == 0 || lo >= n || cnt > n - lo))
-    return fail(ctx, S2K_ERR_ARG, "range outside the batch (the aggregated form takes the whole batch only)");
-  return S2K_OK;
-}
-// enter, run, leave: every path behind ctx_enter goes through ctx_leave, a failed one with nothing left in flight
-static int rlc_debug_run(s2k_ctx* ctx, hipStream_t st, size_t n, const rlc_batch& in, const uint8_t* key32, int form, size_t lo,
-                         size_t cnt, uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
-  int rc = ctx_enter(ctx, st);
-  if (rc) return rc;
-  rc = rlc_debug_point(ctx, st, n, in, key32, form, lo, cnt, out65, status, in_comb);
-  if (rc) s2k_internal_drain(ctx);
-  const int left = ctx_leave(ctx, st);
-  if (rc == S2K_OK && left == S2K_OK) ctx->have_last = false;   // the stream has been synchronised
-  return rc ? rc : left;
-}
-
-int s2k_debug_schnorr_rlc_point(s2k_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* msgs, const uint64_t* msg_offsets, size_t msg_len,
-                                const uint8_t* sig, const uint8_t* key32, int form, size_t lo, size_t cnt, uint8_t* out65,
-                                uint32_t* status, uint8_t* in_comb) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  if (!pk || !sig) return fail(ctx, S2K_ERR_ARG, "null buffer");
-  int rc = rlc_debug_check_args(ctx, n, key32, form, lo, cnt, out65, status);
-  if (rc) return rc;
-  if (msg_len > 0x7fffffffu) return fail(ctx, S2K_ERR_ARG, "batch too large");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
-  uint8_t* d[5];
-  hipStream_t st;
-  rc = stage_schnorr(ctx, n, pk, msgs, msg_offsets, msg_len, sig, d, &st);
-  if (rc) {
-    s2k_internal_drain(ctx);
-    return rc;
-  }
-  return rlc_debug_run(ctx, st, n, rlc_batch_bip340(d[0], d[1], msg_offsets ? d[2] : nullptr, msg_len, d[3]), key32, form, lo, cnt,
-                       out65, status, in_comb);
-}
-
-int s2k_debug_ecdsa_rlc_point(s2k_ctx* ctx, size_t n, const uint8_t* pub, const uint8_t* dig, const uint8_t* r, const uint8_t* s,
-                              const uint8_t* recid, uint32_t flags, const uint8_t* key32, int form, size_t lo, size_t cnt,
-                              uint8_t* out65, uint32_t* status, uint8_t* in_comb) {
-  if (!ctx) return fail(nullptr, S2K_ERR_ARG, "ctx is NULL");
-  int rc = ecdsa_rlc_check_args(ctx, n, pub, dig, r, s, recid, flags);
-  if (rc) return rc;
-  rc = rlc_debug_check_args(ctx, n, key32, form, lo, cnt, out65, status);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipDeviceSynchronize());               // nothing in flight reads the buffers below
-  uint8_t* d[6];
-  hipStream_t st;
-  rc = stage_ecdsa_rlc(ctx, n, pub, dig, r, s, recid, d, &st);
-  if (rc) {
-    s2k_internal_drain(ctx);
-    return rc;
-  }
-  return rlc_debug_run(ctx, st, n, rlc_batch_ecdsa(d[0], d[1], d[2], d[3], d[4], flags), key32, form, lo, cnt, out65, status, in_comb);
 }
 
 }  // extern "C"

@@ -9,8 +9,8 @@
 //   host plan      (seg_plan_build, a pure function: s2k_debug_msm_segments_plan exposes it to the tests) every segment of at
 //                  most `crossover` terms is cut into PIECES of at most T consecutive terms; the pieces are ordered by length,
 //                  longest first, so that the lanes of a wave run the same number of additions.  Longer segments go to msm.hip.
-//   k_seg_front    one lane per term (of the short segments): scalar reduced as SetBytes, record parsed and checked as
-//                  k_msm_parse does, endomorphism split (two 128-bit magnitudes with signs), both recoded into 33 signed 4-bit
+//   k_seg_front    one lane per term (of the short segments): scalar reduced as SetBytes, record judged by
+//                  msm_classify_record29 (msm_terms.h), endomorphism split (two 128-bit magnitudes with signs), both recoded into 33 signed 4-bit
 //                  digits (-8 .. 7, by adding 0x88..8: no carry chain), one byte per digit in position-major planes; and the
 //                  table {1 .. 8} * P: a Jacobian chain (one doubling, six mixed additions: jacobian29.h, the chain k_key_odd
 //                  runs), brought to TRUE affine with one safegcd inversion per term (the Z of entry j is the Z of entry
@@ -31,7 +31,8 @@
 
 #include <vector>
 
-#include "engine_internal.h"
+#include "msm_internal.h"
+#include "msm_terms.h"
 #include "fe29_inv.h"
 #include "jacobian29.h"
 #include "pt29.h"
@@ -192,25 +193,9 @@ k_seg_front(uint32_t lo, uint32_t clo, uint32_t count, uint32_t NS, const uint8_
   load_be32(raw, scalars + i * 32);
   const sc k = sc_reduce_once(raw);                     // SetBytes semantics (scalar.go:123)
   const uint8_t* rec = points + i * 65;
-  uint32_t f = 0;                                       // 0 identity, 1 finite, 2 malformed (as k_msm_parse)
-  uint32_t xw[8], yw[8];
-  fe29 px = fe29_zero(), py = fe29_zero();
-  if (rec[0] == 0x04) {
-    load_be32_unaligned(xw, rec + 1);
-    load_be32_unaligned(yw, rec + 33);
-    bool on = fe_is_canonical_raw(xw) && fe_is_canonical_raw(yw);
-    if (on) {                                           // y^2 == x^3 + 7 (xyOnCurve, point_s11n.go:298-307)
-      px = fe29_from_words(xw);
-      py = fe29_from_words(yw);
-      fe29 rhs = fe29_mul(fe29_sqr(px), px);
-      rhs.n[0] += 7;
-      on = fe29_eq(fe29_sqr(py), rhs);
-    }
-    f = on ? 1 : 2;
-  } else if (rec[0] != 0x00) {
-    f = 2;
-  }
-  if (f == 2) atomicOr(status, 1u);
+  fe29 px, py;
+  const uint32_t f = msm_classify_record29(rec, px, py);
+  if (f == TERM_MALFORMED) atomicOr(status, 1u);
   sc k1, k2;
   bool neg1, neg2;
   sc_split_glv(k, k1, neg1, k2, neg2);

@@ -13,7 +13,7 @@
 // order of the additions is free), which makes the device as a whole sweep the tables slab by slab: one position of a 64-point
 // set is 512 KiB at C = 8, where the whole set (8.5 MiB) is larger than an XCD's L2.
 //
-//   build          k_ps_chain      one lane per point: the record parsed and checked as k_msm_parse / k_seg_front do, the chain
+//   build          k_ps_chain      one lane per point: the record judged by msm_classify_record29 (msm_terms.h), the chain
 //                                  B_pos = 2^(C pos) * P by Jacobian doublings, made affine with one inversion per point
 //                                  (prefix products of the Z) and stored as entry (pos, 1).
 //                  k_ps_multiples  one lane per (point, position): 2 B by a Jacobian doubling, 3 B .. 2^(C-1) B by Jacobian mixed
@@ -44,7 +44,8 @@
 
 #include <vector>
 
-#include "engine_internal.h"
+#include "msm_internal.h"
+#include "msm_terms.h"
 #include "fe29_inv.h"
 #include "jacobian29.h"
 #include "pt29.h"
@@ -83,7 +84,7 @@ struct ps_geom {
   static constexpr uint32_t ADDC = C == 4 ? 0x88888888u : 0x80808080u;   // bit C-1 of every digit
   static constexpr size_t POINT_BYTES = (size_t)POS * E * PS_ENTRY_BYTES;
 };
-constexpr uint32_t PS_FINITE = 1, PS_MALFORMED = 2;         // per-point flag (0: the identity record), as k_msm_parse
+constexpr uint32_t PS_FINITE = TERM_FINITE, PS_MALFORMED = TERM_MALFORMED;   // per-point flag (0: the identity record): msm_terms.h
 constexpr uint32_t PS_ST_RECORD = 1, PS_ST_INDEX = 2;       // status word of a call
 constexpr uint32_t PS_NEG = 0x8000u, PS_MAG = 0x1ffu;       // digit word
 
@@ -145,24 +146,8 @@ k_ps_chain(uint32_t m, const uint8_t* __restrict__ recs, uint8_t* __restrict__ f
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= m) return;
   const uint8_t* rec = recs + (size_t)i * 65;
-  uint32_t f = 0;
-  fe29 px = fe29_zero(), py = fe29_zero();
-  if (rec[0] == 0x04) {
-    uint32_t xw[8], yw[8];
-    load_be32_unaligned(xw, rec + 1);
-    load_be32_unaligned(yw, rec + 33);
-    bool on = fe_is_canonical_raw(xw) && fe_is_canonical_raw(yw);
-    if (on) {                                           // y^2 == x^3 + 7 (xyOnCurve, point_s11n.go:298-307)
-      px = fe29_from_words(xw);
-      py = fe29_from_words(yw);
-      fe29 rhs = fe29_mul(fe29_sqr(px), px);
-      rhs.n[0] += 7;
-      on = fe29_eq(fe29_sqr(py), rhs);
-    }
-    f = on ? PS_FINITE : PS_MALFORMED;
-  } else if (rec[0] != 0x00) {
-    f = PS_MALFORMED;
-  }
+  fe29 px, py;
+  const uint32_t f = msm_classify_record29(rec, px, py);
   flags[i] = (uint8_t)f;
   if (f == PS_MALFORMED) atomicOr(status, PS_ST_RECORD);
   if (f != PS_FINITE) return;                           // (an identity record has no table: its terms' digits are zero)

@@ -1,8 +1,10 @@
 // sha2.h — SHA-256 and SHA-512 (FIPS 180-4) over (bytes, len), one message per caller: the hash cores of the message
-// digests (digest.hip: k_digest_messages hashes one message per lane).  One text for both sides: hipcc compiles it for the
-// device and the host, and it compiles as plain C++ too (no HIP header is needed then), the way der.h and h2c_host.h do -
-// tests/c/sha2_sanitize_main.cpp builds it host-only under AddressSanitizer + UBSan, because both drivers take a
-// caller-supplied length.  sha256.h (the BIP-340 challenge) is left as it is; the compression here is the same 16-word
+// digests (digest.hip: k_digest_messages hashes one message per lane).  Under hipcc this is DEVICE code only: the functions are
+// marked __host__ __device__ so that they compile, but the round constants are __constant__, whose host shadow is never
+// filled, and a host call returns a wrong digest (sha256_hash("abc") gives the initial state 6a09e667...5be0cd19 at -O3) - the
+// library's host code has a SHA-256 of its own (rlc.hip).  It RUNS on the host only as plain C++ (no HIP header is needed then),
+// the way der.h and h2c_host.h do: tests/c/sha2_sanitize_main.cpp builds it so under AddressSanitizer + UBSan, because both
+// drivers take a caller-supplied length.  sha256.h (the BIP-340 challenge) is left as it is; the compression here is the same 16-word
 // rolling schedule under a name of its own.
 //
 // Lengths are below 2^31 bytes.  A driver reads msg[0 .. len) and nothing else: the padding (0x80, zeros, the bit length in

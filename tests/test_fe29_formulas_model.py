@@ -5,7 +5,7 @@ test_fe29_model.py.
   * bounds: every formula is run on upper bounds of its operands' limbs at their stated invariants; no 32-bit limb,
     64-bit column sum or negate() bias may overflow, and the invariants are closed under the formulas' own chaining;
   * call sites: every fe29_eq / fe29_is_zero / fe29_normalize / fe29_inv_gcd of verify_fast.h, lane_kernels.hip, worklist.hip,
-    small_call.hip, keyed.hip and msm.hip has a row with its modelled operand bound (fe29_normalize_weak's input contract:
+    small_call.hip, keyed.hip, msm.hip, msm_terms.h and rlc.hip has a row with its modelled operand bound (fe29_normalize_weak's input contract:
     limbs < 2^32 - 2^18);
   * drift guard: the calls each model makes are compared with the calls of the C++ body it restates;
   * non-vacuity: one-token mutations of the source that the bounds must reject;
@@ -630,15 +630,15 @@ CALL_SITES = [
     ("aff29.h", "fe29_inv_gcd(fe29_add(y, y))", 1, lambda: inv_gcd(add.body(TWO_P, TWO_P))),
     ("aff29.h", "fe29_inv_gcd(fe29_add(x2, fe29_negate(x1, 1)))", 1,
      lambda: inv_gcd(add.body(B([3 * p // 2 for p in P_LIMBS]), negate.body(TWO_P, 1)))),
-    ("msm.hip", "fe29_normalize(fe29_mul(fe29_from_words(x), fe29_from_words(FE_BETA)))", 1, lambda: normalize(PROD)),
-    ("msm.hip", "fe29_eq(fe29_sqr(y), rhs)", 1, lambda: eq(PROD, RHS)),
+    ("msm_terms.h", "fe29_normalize(fe29_mul(fe29_from_words(x), fe29_from_words(FE_BETA)))", 1, lambda: normalize(PROD)),
+    ("msm_terms.h", "fe29_eq(fe29_sqr(y), rhs)", 1, lambda: eq(PROD, RHS)),
     ("msm.hip", "fe29_is_zero(x.zz)", 1, lambda: is_zero(COORD)),
     ("msm.hip", "fe29_is_zero(acc.z)", 2, lambda: is_zero(COORD)),
     ("msm.hip", "fe29_inv_gcd(fe29_normalize_weak(acc.z))", 2, lambda: inv_gcd(NW)),
     ("msm.hip", "fe29_normalize(fe29_mul(acc.x, zi))", 2, lambda: normalize(PROD)),
     ("msm.hip", "fe29_normalize(fe29_mul(acc.y, zi))", 2, lambda: normalize(PROD)),
-    ("msm.hip", "y = fe29_normalize(y)", 1, lambda: normalize(PROD)),
-    ("msm.hip", "fe29_normalize(fe29_select((y.n[0] & 1u) != 0, y, fe29_negate(y, 1)))", 1, lambda: normalize(SEL_RAW)),
+    ("rlc.hip", "y = fe29_normalize(y)", 1, lambda: normalize(PROD)),
+    ("rlc.hip", "fe29_normalize(fe29_select((y.n[0] & 1u) != 0, y, fe29_negate(y, 1)))", 1, lambda: normalize(SEL_RAW)),
 ]
 ROOTS = re.compile(r"\bfe29_(?:eq|is_zero|normalize|inv_gcd)\s*\(")
 
@@ -654,7 +654,7 @@ def test_call_site_table_is_complete():
     # (engine.hip's kernels moved to verify_fast.h, lane_kernels.hip, fallback.hip and worklist.hip: 10 + 4 + 0 + 9 call sites, the
     # 23 engine.hip had; engine.hip and the ladder units stay in the list so that a call that turns up there needs a row)
     for f in ("engine.hip", "verify_fast.h", "lane_kernels.hip", "fallback.hip", "worklist.hip", "ladder_ecdsa.hip", "ladder_schnorr.hip",
-              "small_call.hip", "gtable.hip", "keyed.hip", "msm.hip", "aff29.h"):
+              "small_call.hip", "gtable.hip", "keyed.hip", "msm.hip", "msm_terms.h", "msm_internal.h", "rlc.hip", "aff29.h"):
         rows = [r for r in CALL_SITES if r[0] == f]
         s = source(f)
         assert len(ROOTS.findall(s)) == sum(r[2] for r in rows), f"{f}: a call of fe29_eq / is_zero / normalize / inv_gcd has no row"

@@ -92,8 +92,8 @@ def check_dump(res, mags, present, c):
 def check_geometry(res, nterms, force_c):
     g = M.geometry(nterms, force_c)
     assert {k: res[k] for k in g} == g
-    # the hook's restatement of msm_core's cut (one-part flow, no tuning variable set) against the constants read out of msm.hip:
-    # the tests use L_A to know where range borders fall; the core itself is checked by the sums and the sort's arrays
+    # msm_core's own cut, as the call ran it (one-part flow, no tuning variable set), against the constants read out of msm.hip:
+    # the tests use L_A to know where range borders fall; the sums and the sort's arrays check the rest of the core
     assert res["fold16"] == (1 if g["c"] == 16 else 0)
     assert res["L_A"] == max(L_MIN, -(-nterms * g["nw"] // K["LANES"]))
     assert res["nlanes"] == -(-nterms * g["nw"] // res["L_A"])
